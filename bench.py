@@ -467,6 +467,46 @@ def octant_stats(kernel_ms, idx_of_launch, n_proj):
     return out
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: what all ranks of one run write together (the files stay under 64 MB)
+DUMP_SEED = 20241015   # the voxels of volume_sample: the same for every run of a workload, so that two builds compare value for value
+
+
+def dump_outputs(path, vol, proj, rank_tag, world):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as .npy files under `path` -- the rank's slab
+    of the volume (every timed step and every warmup step added to it) and the last projection the step processed (weighted and
+    filtered in place; the detector rows the slab reads, as float32). A slab is up to 32 GiB, so it is written as
+      volume_z_sums     float64 sum of every z slice of the slab (each voxel counts)
+      volume_sample     float32 values at voxels drawn by numpy's default_rng(DUMP_SEED) from the flattened (z, y, x) slab, sorted
+      volume_mid_slice  float32 slice z = depth // 2, every s-th row and column for the least s that fits
+      projection        float32, every s-th row and column likewise
+    With N > 1 ranks each file name carries _rank<r> and the ranks share the budget."""
+    import numpy as np
+    import torch
+    budget = DUMP_BYTES // world
+    tag = "" if world == 1 else "_rank%d" % rank_tag
+
+    def fit(t, max_bytes):
+        s = 1
+        while -(-t.shape[0] // s) * -(-t.shape[1] // s) * 4 > max_bytes:
+            s += 1
+        return t[::s, ::s]
+
+    flat = vol.reshape(-1)
+    n = min(flat.numel(), budget // 16)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), n, dtype=np.int64))
+    # a float64 sum converts its whole input to float64 first: a few slices at a time, not a 64 GiB copy of the slab
+    chunk = max(1, (128 << 20) // (vol.shape[1] * vol.shape[2]))
+    arrays = {
+        "volume_z_sums": torch.cat([torch.sum(vol[z:z + chunk], dim=(1, 2), dtype=torch.float64) for z in range(0, vol.shape[0], chunk)]),
+        "volume_sample": flat[torch.from_numpy(idx).to(vol.device)],
+        "volume_mid_slice": fit(vol[vol.shape[0] // 2], budget * 3 // 8),
+        "projection": fit(proj, budget * 3 // 8).float(),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + tag + ".npy"), a.cpu().numpy())
+
+
 def launch_ranks(args, argv, grace=120.0, _cmd=None):
     """`python3 bench.py --gpus N` with N > 1 and no RANK in the environment: the job starts itself. One rank per GPU is started
     through torch.distributed.run as an ordinary CHILD process (this process never touches the GPU: counting devices does not
@@ -605,7 +645,11 @@ def main():
                     "before it gives up: one dead rank ends the run instead of hanging the others until the caller's limit")
     ap.add_argument("--paris-loop", type=int, default=1, help="1 (default; N = 1, the whole config-3 job only): PARIS's own per-projection "
                     "loop through the C++ mirror (paris_hip_demo, child processes) is timed for four jobs and reported as `paris_loop`")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path computed (the "
+                    "volume, as a fixed sample, and the last filtered projection) as DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # called the way the N = 1 line is (`python3 bench.py --gpus N ...`): this process becomes the launcher
@@ -737,6 +781,7 @@ def main():
     band = slice(band_first, band_first + band_count)
 
     launched = []  # projection index of every single-projection backprojection call, in call order
+    last = {}  # "slot": the buffer of the last projection a step backprojected (--dump-outputs)
 
     shard = bool(args.filter_shard) and world > 1
     if shard:
@@ -767,6 +812,7 @@ def main():
                     rp.idx = (first_idx + j0 + q) % n_proj
                     B.backproject(be, rp, d_vol, z_first, det, vol_geo, False, roi is not None, roi)
                     launched.append(rp.idx)
+                    last["slot"] = q
 
     def step(first_idx, count=None, indices=None):
         """one pass of the hot path over `count` consecutive projections from first_idx, or over the given projection indices"""
@@ -788,6 +834,7 @@ def main():
                 B.filter_rows(be, p, det, band_first, band_count)             # :103 (weights in its load)
                 B.backproject(be, p, d_vol, z_first, det, vol_geo, False, roi is not None, roi)  # :104
             launched.append(p.idx)
+            last["slot"] = b
 
     def barrier():
         if dist is not None:
@@ -855,6 +902,10 @@ def main():
         kernel_idx = launched[-len(kernel_ms):] if kernel_ms else []
     else:
         be.backproject_timing_arm(1)
+    if args.dump_outputs:  # before the legs below add more projections to the volume
+        proj = shard_recv[last["slot"]] if shard else half if f16 else work[last["slot"]]
+        dump_outputs(args.dump_outputs, vol, proj[band], vrank, world)
+        mark("dump_outputs")
 
     # ---- one more step with paris_hip_set_backproject_skip_invalid(0): every tile is read and written, also those no ray
     # reaches -- the kernel's rate on exactly the algorithmic bytes. Its projections are spread over the whole circle.

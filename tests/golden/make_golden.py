@@ -5,6 +5,8 @@ Fixtures are data only (inputs are regenerated from the LCG; expected outputs ar
   kat.npz     KAT geometry of SURVEY.md 8c: weighted projection 0, the 8 filtered projections, the full
               67x67x61 volume, the ramp filter K for N in {128, 1024, 2048, 4096}
   cube64.npz  64^3 / 8 projections: three central slices, sum and abs-sum
+  mkl_fft.npz MKL's FFTW transforms (libmkl_rt.so) of the KAT geometry's filter and 8 weighted projections, keyed by the
+              sha256 of their inputs (tests/mkl_fftw.py: Recorded); written only where libmkl_rt.so exists
 """
 import os
 import sys
@@ -14,6 +16,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from oracle import oracle as O  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(HERE))
+import mkl_fftw  # noqa: E402
 
 
 def main():
@@ -31,8 +36,26 @@ def main():
     v = O.reconstruct(d, g, 8)
     np.savez_compressed(os.path.join(HERE, "cube64.npz"), slices=v[31:34].copy(),
                         sum=np.float64(v.sum(dtype=np.float64)), abssum=np.float64(np.abs(v).sum(dtype=np.float64)))
-    for f in ("kat.npz", "cube64.npz"):
+    files = ["kat.npz", "cube64.npz"]
+    if mkl_fftw.available():
+        record_mkl()
+        files.append("mkl_fft.npz")
+    for f in files:
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
+
+
+def record_mkl():
+    """What tests/test_oracle_kat.py's bit-exact checksum test hands MKL: the KAT filter and the 8 weighted projections."""
+    det = O.DetectorGeometry(64, 48, 0.2, 0.25, 1.5, -0.75, 100, 200, 45)
+    fs = O.filter_size(det.n_row)
+    log = []
+    k = mkl_fftw.make_filter(O, fs, det.l_px_row, log=log)
+    rf = mkl_fftw.RowFilter(fs, det.n_col, log=log)
+    for i in range(8):
+        p = O.lcg_projection(det.n_row, det.n_col, i)
+        O.weight(p, det)
+        rf.apply(p, k)
+    mkl_fftw.save_log(log, os.path.join(HERE, "mkl_fft.npz"))
 
 
 if __name__ == "__main__":

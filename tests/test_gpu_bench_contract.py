@@ -61,6 +61,37 @@ def test_single_gpu_line():
     assert abs(sum(v for k, v in legs.items() if k != "total") - legs["total"]) < 0.2
 
 
+def test_dump_outputs_are_the_timed_paths_and_repeat(tmp_path):
+    """--dump-outputs DIR: after the timed steps the volume (z-slice sums, a seeded sample, the middle slice) and the last filtered
+    projection are written as float32 / float64 .npy files, under 64 MB in all. Two runs with the same arguments write the same
+    bits, also when the legs after the timed region differ (they add to the volume only after the dump)."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "4", "--warmup", "1", "--cpu-budget", "0",
+            "--cpu-c1", "0"]
+    a = subprocess.run(base + ["--fused-steps", "0", "--noskip-step", "0", "--dump-outputs", str(tmp_path / "a")], capture_output=True,
+                       text=True, timeout=600, cwd=ROOT)
+    assert a.returncode == 0, a.stderr[-2000:]
+    d = last_json_line(a.stdout)
+    assert d["steps"] == 4 and d["config"]["projections_per_step"] == 90
+    assert abs(d["ms_per_step"] * 4 / 1e3 - d["legs_seconds"]["timed_region"]) < 0.01
+    b = subprocess.run(base + ["--fused-steps", "2", "--dump-outputs", str(tmp_path / "b")], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+    assert b.returncode == 0, b.stderr[-2000:]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["projection.npy", "volume_mid_slice.npy", "volume_sample.npy",
+                                                         "volume_z_sums.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64e6
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert got["volume_z_sums"].dtype == np.float64 and got["volume_z_sums"].shape == (256,)
+    assert got["volume_mid_slice"].dtype == got["volume_sample"].dtype == got["projection"].dtype == np.float32
+    assert got["volume_mid_slice"].shape == (256, 256) and got["projection"].shape == (512, 512)
+    assert np.all(np.isfinite(got["volume_z_sums"])) and np.count_nonzero(got["volume_mid_slice"]) > 0.5 * 256 * 256
+    # the slice is the volume's: its sum is its z entry
+    assert abs(got["volume_mid_slice"].sum(dtype=np.float64) - got["volume_z_sums"][128]) <= 1e-9 * np.abs(got["volume_mid_slice"]).sum()
+
+
 def test_two_rank_rehearsal():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

@@ -153,11 +153,21 @@ def test_bit_exact_checksums_with_the_surveys_fft(oracle, kat):
     """With the same third-party FFT the survey's reference run linked, the oracle reproduces the reference's
     volume checksums bit for bit: full volume and the v_offset=30 slab. This pins weighting,
     filter generation, expand/multiply/shrink/normalise and backprojection exactly."""
+    _checksums_with_the_surveys_fft(oracle, kat, None)
+
+
+def test_bit_exact_checksums_with_the_surveys_fft_recorded(oracle, kat, golden_dir):
+    """The same with MKL's transforms replayed from tests/golden/mkl_fft.npz: every input the oracle hands the FFT must be
+    the one MKL was given when it was recorded, so the check holds where libmkl_rt.so is absent."""
+    _checksums_with_the_surveys_fft(oracle, kat, mkl_fftw.Recorded(os.path.join(golden_dir, "mkl_fft.npz")))
+
+
+def _checksums_with_the_surveys_fft(oracle, kat, recorded):
     det = kat_det(oracle, kat)
     vg = oracle.calculate_volume_geometry(det)
     fs = oracle.filter_size(det.n_row)
-    k = mkl_fftw.make_filter(oracle, fs, det.l_px_row)
-    rf = mkl_fftw.RowFilter(fs, det.n_col)
+    k = mkl_fftw.make_filter(oracle, fs, det.l_px_row, recorded)
+    rf = mkl_fftw.RowFilter(fs, det.n_col, recorded)
 
     def recon(v_dims, off):
         vol = np.zeros(v_dims, np.float32)
