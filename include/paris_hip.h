@@ -144,6 +144,19 @@ int paris_hip_memcpy_projection_h2d(paris_hip_ctx* ctx, float* d_dst, size_t d_p
  * before the upload -- the library sees only its own entry points. */
 int paris_hip_upload_projection(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const float* h_src, size_t h_pitch,
                                 uint32_t dim_x, uint32_t dim_y);
+/* Extension: paris_hip_upload_projection for frames in the detector's stored pixel type: the copy carries s bytes per pixel
+ * (1, 2 or 4) instead of 4, and in stream order the dim_x floats of every row of d_dst then hold exactly static_cast<float>(v) of the
+ * stored pixels -- bit for bit what the fp32 upload leaves after the host's conversion (u32: round to nearest even; f32: a bit copy,
+ * NaN payloads, -0 and denormals included). No staging memory: each stored row goes into the tail of its own float row (bytes
+ * [(4 - s) * dim_x, 4 * dim_x)) and a kernel on the ctx stream widens it in place; bytes past 4 * dim_x of a row are not written.
+ * h_pitch is in bytes. PARIS_HIP_ERROR_INVALID_ARGUMENT for an unknown pixel type (f64 included: convert it on the host), d_pitch <
+ * 4 * dim_x or not a multiple of 4, h_pitch < s * dim_x, or null pointers. Same ordering rules as paris_hip_upload_projection. */
+#define PARIS_HIP_PIXEL_U8 1
+#define PARIS_HIP_PIXEL_U16 2
+#define PARIS_HIP_PIXEL_U32 3
+#define PARIS_HIP_PIXEL_F32 4
+int paris_hip_upload_projection_raw(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch,
+                                    uint32_t dim_x, uint32_t dim_y, int pixel_type);
 int paris_hip_memcpy_projection_d2h(paris_hip_ctx* ctx, float* h_dst, size_t h_pitch, const float* d_src,
                                     size_t d_pitch, uint32_t dim_x, uint32_t dim_y);
 int paris_hip_memcpy_volume_h2d(paris_hip_ctx* ctx, float* d_dst, const float* h_src, uint32_t dim_x,

@@ -19,6 +19,11 @@ CTX_DEFAULT = 0
 CTX_SYNCHRONOUS = 1
 CTX_LEGACY_STREAM = 2
 CTX_WARM = 4
+# pixel types of paris_hip_upload_projection_raw
+PIXEL_U8 = 1
+PIXEL_U16 = 2
+PIXEL_U32 = 3
+PIXEL_F32 = 4
 
 
 class DetectorGeometry(C.Structure):
@@ -77,6 +82,7 @@ SIGNATURES = {
     "paris_hip_free_host": (C.c_int, [_vp, _vp]),
     "paris_hip_memcpy_projection_h2d": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_upload_projection": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
+    "paris_hip_upload_projection_raw": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, C.c_int]),
     "paris_hip_memcpy_projection_d2h": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_memcpy_volume_h2d": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "paris_hip_memcpy_volume_d2h": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),

@@ -228,6 +228,26 @@ class Backend:
                                                   h.dim_x, h.dim_y), "paris_hip_upload_projection")
         d.idx, d.phi = h.idx, h.phi
 
+    _PIXEL_TYPES = {np.dtype(np.uint8): _lib.PIXEL_U8, np.dtype(np.uint16): _lib.PIXEL_U16, np.dtype(np.uint32): _lib.PIXEL_U32,
+                    np.dtype(np.float32): _lib.PIXEL_F32}
+
+    def upload_raw(self, h, d):
+        """upload() of a frame in its stored pixel type (paris_hip_upload_projection_raw): h is a 2-D uint8, uint16, uint32 or float32
+        ndarray (rows may be padded: h.strides[0] is the host pitch); the copy carries its bytes as they are and the device widens
+        them to fp32 in place -- bit for bit h.astype(np.float32). Returns without waiting, like upload()."""
+        if not isinstance(h, np.ndarray) or h.ndim != 2:
+            raise TypeError("upload_raw: h must be a 2-D ndarray")
+        if h.dtype == np.float64:
+            raise TypeError("upload_raw: float64 frames are not uploaded raw -- convert them on the host (h.astype(np.float32))")
+        pixel = self._PIXEL_TYPES.get(h.dtype)
+        if pixel is None:
+            raise TypeError("upload_raw: unsupported dtype %s (uint8, uint16, uint32 or float32)" % h.dtype)
+        if h.strides[1] != h.itemsize or h.strides[0] < h.shape[1] * h.itemsize:
+            raise ValueError("upload_raw: the rows of h must be contiguous")
+        assert h.shape == (d.dim_y, d.dim_x)
+        check(self._L.paris_hip_upload_projection_raw(self._ctx, d.ptr, d.pitch, h.ctypes.data, h.strides[0], d.dim_x, d.dim_y, pixel),
+              "paris_hip_upload_projection_raw")
+
     def copy_d2h(self, d, h):
         if isinstance(d, Projection):
             assert h.buf.dtype == np.float32 and h.dim_x == d.dim_x and h.dim_y == d.dim_y

@@ -105,6 +105,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_filter_fused();
             paris_hip_warm_weight();
             paris_hip_warm_validate();
+            paris_hip_warm_widen();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -1125,42 +1126,33 @@ extern "C" int paris_hip_free_host(paris_hip_ctx* ctx, void* h_ptr)
     return PARIS_HIP_SUCCESS;
 }
 
-extern "C" int paris_hip_memcpy_projection_h2d(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const float* h_src,
-                                               size_t h_pitch, uint32_t dim_x, uint32_t dim_y)
+// The host -> device copy of rows of `px` bytes per pixel into d_dst (px < 4: into the tail of each float row, see
+// paris_hip_upload_projection_raw) on the compute stream. The caller has bound the ctx and flushed a held-back weighting.
+static int copy_rows_on_compute(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch, uint32_t dim_x,
+                                uint32_t dim_y, size_t px)
 {
-    if(int rc = paris_hip_bind(ctx))
-        return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx))
-        return rc;
-    if(d_dst == nullptr || h_src == nullptr)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     if(int rc = paris_hip_projection_guard(ctx, d_dst, d_pitch * dim_y, ctx->stream, true))
         return rc;
+    char* d_rows = reinterpret_cast<char*>(d_dst) + (sizeof(float) - px) * dim_x;
     // rows as far apart on both sides as they are long: one linear copy (the 2-D form costs the runtime more per call)
-    if(d_pitch == h_pitch && d_pitch == static_cast<size_t>(dim_x) * sizeof(float))
-        PARIS_HIP_TRY(hipMemcpyAsync(d_dst, h_src, d_pitch * dim_y, hipMemcpyHostToDevice, ctx->stream));
+    if(d_pitch == h_pitch && d_pitch == static_cast<size_t>(dim_x) * px)
+        PARIS_HIP_TRY(hipMemcpyAsync(d_rows, h_src, d_pitch * dim_y, hipMemcpyHostToDevice, ctx->stream));
     else
-        PARIS_HIP_TRY(hipMemcpy2DAsync(d_dst, d_pitch, h_src, h_pitch, static_cast<size_t>(dim_x) * sizeof(float), dim_y,
-                                       hipMemcpyHostToDevice, ctx->stream));
+        PARIS_HIP_TRY(hipMemcpy2DAsync(d_rows, d_pitch, h_src, h_pitch, static_cast<size_t>(dim_x) * px, dim_y, hipMemcpyHostToDevice,
+                                       ctx->stream));
     paris_hip_note_host_use(ctx, h_src, paris_hip_ctx::USED_COMPUTE);
-    if(int rc = paris_hip_note_projection_use(ctx, d_dst, d_pitch * dim_y)) // a later upload into the buffer must not overtake this copy
-        return rc;
-    return paris_hip_finish(ctx);
+    return paris_hip_note_projection_use(ctx, d_dst, d_pitch * dim_y); // a later upload into the buffer must not overtake this copy
 }
 
-extern "C" int paris_hip_upload_projection(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const float* h_src, size_t h_pitch,
-                                           uint32_t dim_x, uint32_t dim_y)
+// The same copy on the ctx's upload stream, the compute stream made to wait for it (paris_hip_upload_projection): both upload entry
+// points, which differ only in the bytes per pixel.
+static int copy_rows_on_upload_stream(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch, uint32_t dim_x,
+                                      uint32_t dim_y, size_t px)
 {
-    if(int rc = paris_hip_bind(ctx))
-        return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx))
-        return rc;
-    if(d_dst == nullptr || h_src == nullptr)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
 #ifdef PARIS_HIP_EXPERIMENTS
     static const bool serial = [] { const char* e = std::getenv("PARIS_HIP_UPLOAD_STREAM"); return e != nullptr && e[0] == '0'; }();
     if(serial) // diagnostic: PARIS_HIP_UPLOAD_STREAM=0 keeps the copy on the compute stream (A/B of the overlap)
-        return paris_hip_memcpy_projection_h2d(ctx, d_dst, d_pitch, h_src, h_pitch, dim_x, dim_y);
+        return copy_rows_on_compute(ctx, d_dst, d_pitch, h_src, h_pitch, dim_x, dim_y, px);
 #endif
     if(int rc = paris_hip_ensure_upload_stream(ctx))
         return rc;
@@ -1199,16 +1191,78 @@ extern "C" int paris_hip_upload_projection(paris_hip_ctx* ctx, float* d_dst, siz
         target->second.bytes = std::max(target->second.bytes, d_pitch * dim_y);
     }
     hipEvent_t done = ctx->upload_events[ctx->uploads++ % ctx->upload_events.size()];
+    char* d_rows = reinterpret_cast<char*>(d_dst) + (sizeof(float) - px) * dim_x;
     // rows as far apart on both sides as they are long: one linear copy (the 2-D form costs the runtime more per call)
-    if(d_pitch == h_pitch && d_pitch == static_cast<size_t>(dim_x) * sizeof(float))
-        PARIS_HIP_TRY(hipMemcpyAsync(d_dst, h_src, d_pitch * dim_y, hipMemcpyHostToDevice, ctx->upload_stream));
+    if(d_pitch == h_pitch && d_pitch == static_cast<size_t>(dim_x) * px)
+        PARIS_HIP_TRY(hipMemcpyAsync(d_rows, h_src, d_pitch * dim_y, hipMemcpyHostToDevice, ctx->upload_stream));
     else
-        PARIS_HIP_TRY(hipMemcpy2DAsync(d_dst, d_pitch, h_src, h_pitch, static_cast<size_t>(dim_x) * sizeof(float), dim_y,
-                                       hipMemcpyHostToDevice, ctx->upload_stream));
+        PARIS_HIP_TRY(hipMemcpy2DAsync(d_rows, d_pitch, h_src, h_pitch, static_cast<size_t>(dim_x) * px, dim_y, hipMemcpyHostToDevice,
+                                       ctx->upload_stream));
     paris_hip_note_host_use(ctx, h_src, paris_hip_ctx::USED_UPLOAD);
     paris_hip_mark_touched(ctx, d_dst);
     PARIS_HIP_TRY(hipEventRecord(done, ctx->upload_stream));
     PARIS_HIP_TRY(hipStreamWaitEvent(ctx->stream, done, 0)); // kernels enqueued from now on see the uploaded frame
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_memcpy_projection_h2d(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const float* h_src,
+                                               size_t h_pitch, uint32_t dim_x, uint32_t dim_y)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_flush_pending_weight(ctx))
+        return rc;
+    if(d_dst == nullptr || h_src == nullptr)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(int rc = copy_rows_on_compute(ctx, d_dst, d_pitch, h_src, h_pitch, dim_x, dim_y, sizeof(float)))
+        return rc;
+    return paris_hip_finish(ctx);
+}
+
+extern "C" int paris_hip_upload_projection(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const float* h_src, size_t h_pitch,
+                                           uint32_t dim_x, uint32_t dim_y)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_flush_pending_weight(ctx))
+        return rc;
+    if(d_dst == nullptr || h_src == nullptr)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(int rc = copy_rows_on_upload_stream(ctx, d_dst, d_pitch, h_src, h_pitch, dim_x, dim_y, sizeof(float)))
+        return rc;
+    return paris_hip_finish(ctx);
+}
+
+extern "C" int paris_hip_upload_projection_raw(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch,
+                                               uint32_t dim_x, uint32_t dim_y, int pixel_type)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    size_t px = 0;
+    switch(pixel_type)
+    {
+        case PARIS_HIP_PIXEL_U8: px = 1; break;
+        case PARIS_HIP_PIXEL_U16: px = 2; break;
+        case PARIS_HIP_PIXEL_U32: px = 4; break;
+        case PARIS_HIP_PIXEL_F32: px = 4; break;
+        default: return PARIS_HIP_ERROR_INVALID_ARGUMENT; // (f64 included: a host conversion)
+    }
+    if(d_dst == nullptr || h_src == nullptr || d_pitch < static_cast<size_t>(dim_x) * sizeof(float) || d_pitch % sizeof(float) != 0
+       || h_pitch < static_cast<size_t>(dim_x) * px)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(int rc = paris_hip_flush_pending_weight(ctx))
+        return rc;
+    if(int rc = copy_rows_on_upload_stream(ctx, d_dst, d_pitch, h_src, h_pitch, dim_x, dim_y, px))
+        return rc;
+    if(pixel_type != PARIS_HIP_PIXEL_F32) // f32: the copy was the whole job
+    {
+        // on the compute stream, behind its wait for the copy; a compute-stream write of d_dst like any stage: a later upload into
+        // the buffer waits for it
+        if(int rc = paris_hip_widen_rows(ctx, d_dst, d_pitch, dim_x, dim_y, pixel_type))
+            return rc;
+        if(int rc = paris_hip_note_projection_use(ctx, d_dst, d_pitch * dim_y))
+            return rc;
+    }
     return paris_hip_finish(ctx);
 }
 

@@ -345,6 +345,11 @@ void paris_hip_warm_filter();
 void paris_hip_warm_filter_fused();
 void paris_hip_warm_weight();
 void paris_hip_warm_validate();
+void paris_hip_warm_widen();
+
+// widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
+// tail of their float rows (paris_hip_upload_projection_raw)
+int paris_hip_widen_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, int pixel_type);
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events
 int paris_hip_take_event(paris_hip_ctx* ctx, hipEvent_t* out);

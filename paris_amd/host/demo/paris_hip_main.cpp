@@ -146,6 +146,7 @@ int main(int argc, char** argv)
                         d.enqueue_s, d.drain_wait_s, d.two_volumes ? "two volume buffers" : "one volume buffer", d.drain_s, d.save_s);
             for(const auto& s : d.skipped)
                 std::printf("  skipped invalid file %s\n", s.c_str());
+            std::printf("  H2D of device %d: %llu bytes of projection rows, as stored\n", d.device, static_cast<unsigned long long>(d.h2d_bytes));
         }
         return 0;
     }

@@ -110,21 +110,24 @@ int paris_io_source_scan(const char* dir, int enable_angles, const char* angle_f
     }
     catch(const std::exception&) { return 1; }
 }
-// the same scan through frame_stream: frame i is written into data + i * dim_x * dim_y (caller-filled with a sentinel),
-// only rows [row_first, row_first + row_count). Frames of another size end the scan with return code 3.
-int paris_io_stream_scan(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
-                         uint32_t row_first, uint32_t row_count, uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out,
-                         float* data, uint32_t* n_skipped)
+// the same scan through frame_stream: frame i is written into data + i * dim_x * dim_y * size (caller-filled with a sentinel),
+// only rows [row_first, row_first + row_count); size = 4 (floats), raw: the frame's pixels as stored, at most 4 bytes each, their
+// type (his::pixel_type) in type_out. Frames of another size end the scan with return code 3.
+static int stream_scan(bool raw, const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                       uint32_t row_first, uint32_t row_count, uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out,
+                       void* data, int32_t* type_out, uint32_t* n_skipped)
 {
     try
     {
         paris::frame_stream src{dir, enable_angles != 0, angle_file ? angle_file : "", quality};
-        auto scratch = std::vector<float>(static_cast<size_t>(dim_x) * dim_y);
+        const auto frame = static_cast<size_t>(dim_x) * dim_y * sizeof(float);
+        auto scratch = std::vector<uint8_t>(frame);
         uint32_t n = 0;
         for(;;)
         {
-            float* dst = n < cap ? data + static_cast<size_t>(n) * dim_x * dim_y : scratch.data();
-            const auto info = src.next(dst, dim_x, dim_y, row_first, row_count);
+            void* dst = n < cap ? static_cast<uint8_t*>(data) + static_cast<size_t>(n) * frame : scratch.data();
+            const auto info = raw ? src.next_raw(dst, dim_x, dim_y, row_first, row_count)
+                                  : src.next(static_cast<float*>(dst), dim_x, dim_y, row_first, row_count);
             if(!info.valid())
                 break;
             if(info.dim_x != dim_x || info.dim_y != dim_y)
@@ -133,6 +136,8 @@ int paris_io_stream_scan(const char* dir, int enable_angles, const char* angle_f
             {
                 idx_out[n] = info.idx;
                 phi_out[n] = info.phi;
+                if(type_out)
+                    type_out[n] = info.pixel;
             }
             ++n;
         }
@@ -143,36 +148,56 @@ int paris_io_stream_scan(const char* dir, int enable_angles, const char* angle_f
     catch(const std::exception&) { return 1; }
 }
 
+int paris_io_stream_scan(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                         uint32_t row_first, uint32_t row_count, uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out,
+                         float* data, uint32_t* n_skipped)
+{
+    return stream_scan(false, dir, enable_angles, angle_file, quality, dim_x, dim_y, row_first, row_count, cap, n_frames, idx_out, phi_out,
+                       data, nullptr, n_skipped);
+}
+
+int paris_io_stream_scan_raw(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                             uint32_t row_first, uint32_t row_count, uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out,
+                             void* data, int32_t* type_out, uint32_t* n_skipped)
+{
+    return stream_scan(true, dir, enable_angles, angle_file, quality, dim_x, dim_y, row_first, row_count, cap, n_frames, idx_out, phi_out,
+                       data, type_out, n_skipped);
+}
+
 // shared_frames under `n_threads` consumers: thread i reads rows [row_first[i], row_first[i] + row_count[i]) of every frame into
-// data + i * cap * dim_x * dim_y (caller-filled with a sentinel); thread i sleeps delay_us[i] microseconds per frame, so a
-// slow consumer falls out of the ring (capacity) and takes its own fallback stream. counters: produced, served, reread.
-int paris_io_shared_scan(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
-                         uint32_t n_threads, const uint32_t* row_first, const uint32_t* row_count, const uint32_t* delay_us, uint32_t capacity,
-                         uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out, float* data, uint64_t* counters)
+// data + (i * cap + n) * dim_x * dim_y * 4 bytes (caller-filled with a sentinel): floats, or raw: the pixels as stored, their type in
+// type_out[i * cap + n]; thread i sleeps delay_us[i] microseconds per frame, so a slow consumer falls out of the ring (capacity) and
+// takes its own fallback stream. counters: produced, served, reread.
+static int shared_scan(bool raw, const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                       uint32_t n_threads, const uint32_t* row_first, const uint32_t* row_count, const uint32_t* delay_us, uint32_t capacity,
+                       uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out, void* data, int32_t* type_out, uint64_t* counters)
 {
     try
     {
         paris::shared_frames shared{dir, enable_angles != 0, angle_file ? angle_file : "", quality, dim_x, dim_y, capacity};
         auto failed = std::vector<int>(n_threads, 0);
         auto workers = std::vector<std::thread>{};
-        const auto frame = static_cast<size_t>(dim_x) * dim_y;
+        const auto frame = static_cast<size_t>(dim_x) * dim_y * sizeof(float);
         for(uint32_t i = 0; i < n_threads; ++i)
             workers.emplace_back([&, i] {
                 try
                 {
                     auto cur = paris::shared_frames::cursor{};
-                    auto scratch = std::vector<float>(frame);
+                    auto scratch = std::vector<uint8_t>(frame);
                     uint32_t n = 0;
                     for(;;)
                     {
-                        float* dst = n < cap ? data + (static_cast<size_t>(i) * cap + n) * frame : scratch.data();
-                        const auto info = shared.next(cur, dst, dim_x, dim_y, row_first[i], row_count[i]);
+                        void* dst = n < cap ? static_cast<uint8_t*>(data) + (static_cast<size_t>(i) * cap + n) * frame : scratch.data();
+                        const auto info = raw ? shared.next_raw(cur, dst, dim_x, dim_y, row_first[i], row_count[i])
+                                              : shared.next(cur, static_cast<float*>(dst), dim_x, dim_y, row_first[i], row_count[i]);
                         if(!info.valid())
                             break;
                         if(n < cap)
                         {
                             idx_out[static_cast<size_t>(i) * cap + n] = info.idx;
                             phi_out[static_cast<size_t>(i) * cap + n] = info.phi;
+                            if(type_out)
+                                type_out[static_cast<size_t>(i) * cap + n] = info.pixel;
                         }
                         ++n;
                         if(delay_us[i])
@@ -194,5 +219,21 @@ int paris_io_shared_scan(const char* dir, int enable_angles, const char* angle_f
         return 0;
     }
     catch(const std::exception&) { return 1; }
+}
+
+int paris_io_shared_scan(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                         uint32_t n_threads, const uint32_t* row_first, const uint32_t* row_count, const uint32_t* delay_us, uint32_t capacity,
+                         uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out, float* data, uint64_t* counters)
+{
+    return shared_scan(false, dir, enable_angles, angle_file, quality, dim_x, dim_y, n_threads, row_first, row_count, delay_us, capacity, cap,
+                       n_frames, idx_out, phi_out, data, nullptr, counters);
+}
+
+int paris_io_shared_scan_raw(const char* dir, int enable_angles, const char* angle_file, uint16_t quality, uint32_t dim_x, uint32_t dim_y,
+                             uint32_t n_threads, const uint32_t* row_first, const uint32_t* row_count, const uint32_t* delay_us, uint32_t capacity,
+                             uint32_t cap, uint32_t* n_frames, uint32_t* idx_out, float* phi_out, void* data, int32_t* type_out, uint64_t* counters)
+{
+    return shared_scan(true, dir, enable_angles, angle_file, quality, dim_x, dim_y, n_threads, row_first, row_count, delay_us, capacity, cap,
+                       n_frames, idx_out, phi_out, data, type_out, counters);
 }
 }

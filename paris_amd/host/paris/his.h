@@ -2,7 +2,8 @@
 //
 // Reader semantics follow src/his.cpp:105-198: 68-byte little-endian file header read field by field, frames of
 // (brx-ulx+1) x (bry-uly+1) pixels in one of five number types converted to float, and -- quirk Q14 -- the
-// `image_header_size` bytes are skipped before EVERY frame. A file that is not HIS (wrong id / header size /
+// `image_header_size` bytes are skipped before EVERY frame. read_rows_raw hands the pixels out as stored (f64 as f32) for
+// paris_hip_upload_projection_raw; read_rows converts them to float on the host, as the reference does. A file that is not HIS (wrong id / header size /
 // number type) yields no frames (the caller logs and skips it: src/source.cpp:96-100); an unopenable file throws.
 #ifndef PARIS_AMD_HOST_HIS_H_
 #define PARIS_AMD_HOST_HIS_H_
@@ -46,6 +47,39 @@ namespace paris
             std::uint16_t number_type = type_float;
         };
 
+        // The pixel types a frame is handed out in by read_rows_raw (the values of PARIS_HIP_PIXEL_* in include/paris_hip.h): the
+        // stored type, except that f64 frames are converted to f32 on the way in (the device path takes no f64)
+        enum pixel_type : int
+        {
+            pixel_u8 = 1,
+            pixel_u16 = 2,
+            pixel_u32 = 3,
+            pixel_f32 = 4
+        };
+        inline auto pixel_size(int type) noexcept -> std::size_t { return type == pixel_u8 ? 1u : type == pixel_u16 ? 2u : 4u; }
+
+        // count pixels of `type` at src -> floats: the implicit conversion of the reference's std::copy (src/his.cpp:99)
+        inline void widen(float* dst, const void* src, std::size_t count, int type)
+        {
+            const auto* p = static_cast<const std::uint8_t*>(src);
+            const auto each = [&](auto zero) {
+                using T = decltype(zero);
+                for(std::size_t i = 0; i < count; ++i)
+                {
+                    T v;
+                    std::memcpy(&v, p + i * sizeof(T), sizeof(T));
+                    dst[i] = static_cast<float>(v);
+                }
+            };
+            switch(type)
+            {
+                case pixel_u8: each(std::uint8_t{}); break;
+                case pixel_u16: each(std::uint16_t{}); break;
+                case pixel_u32: each(std::uint32_t{}); break;
+                default: std::memcpy(dst, src, count * sizeof(float)); break;
+            }
+        }
+
         struct frame
         {
             std::vector<float> pixels; // dim_x fastest
@@ -74,7 +108,7 @@ namespace paris
         }
 
         // Frame-at-a-time reader with the acceptance rules of src/his.cpp:105-198. load() below is built on it; the
-        // pipelined driver uses it directly to convert a frame (or only a band of its rows) straight into its pinned
+        // pipelined driver uses it directly to read a frame (or only a band of its rows), as stored, straight into its pinned
         // upload buffer, without the intermediate copy the reference's reader makes.
         class reader
         {
@@ -131,52 +165,84 @@ namespace paris
                 return true;
             }
 
-            // Converts rows [row_first, row_first + row_count) of the current frame into dst (dim_x * dim_y floats, row
-            // stride dim_x); other rows of dst are left untouched. Elements the file no longer holds read as 0.
-            void read_rows(float* dst, std::uint32_t row_first, std::uint32_t row_count)
+            // the type read_rows_raw hands the frames of this file out in (f64 is converted to f32); meaningless for a file without frames
+            auto pixel() const noexcept -> int
             {
-                if(!in_frame_)
-                    return;
-                const auto total = static_cast<std::size_t>(dim_x_) * dim_y_;
-                auto a = static_cast<std::size_t>(row_first) * dim_x_;
-                auto b = a + static_cast<std::size_t>(row_count) * dim_x_;
-                a = a < total ? a : total;
-                b = b < total ? b : total;
-                const auto stored_b = b < n_ ? b : n_; // elements beyond n_ are not in the file: they stay 0
-                const auto stored_a = a < stored_b ? a : stored_b;
-                const auto count = stored_b - stored_a;
-                raw_.resize(count * px_);
-                std::size_t got = 0;
-                if(count && std::fseek(f_.get(), static_cast<long>(stored_a * px_), SEEK_CUR) == 0)
-                    got = std::fread(raw_.data(), px_, count, f_.get());
-                consumed_ = stored_a * px_ + got * px_;
-                if(got < count)
-                    std::memset(raw_.data() + got * px_, 0, (count - got) * px_); // a short read leaves zeros (:99)
-                float* out = dst + stored_a;
                 switch(h_.number_type)
                 {
-                    case type_uchar: convert<std::uint8_t>(out, count); break;
-                    case type_ushort: convert<std::uint16_t>(out, count); break;
-                    case type_dword: convert<std::uint32_t>(out, count); break;
-                    case type_double: convert<double>(out, count); break;
-                    default: convert<float>(out, count); break;
+                    case type_uchar: return pixel_u8;
+                    case type_ushort: return pixel_u16;
+                    case type_dword: return pixel_u32;
+                    default: return pixel_f32;
                 }
-                for(auto i = stored_b; i < b; ++i)
-                    dst[i] = 0.f;
-                skip_payload();
+            }
+
+            // Rows [row_first, row_first + row_count) of the current frame, as stored, into dst (dim_x * dim_y pixels of
+            // pixel_size(pixel()) bytes, row stride dim_x pixels); other rows of dst are left untouched. Elements the file no
+            // longer holds read as 0. f64 frames arrive as their f32 cast.
+            void read_rows_raw(void* dst, std::uint32_t row_first, std::uint32_t row_count)
+            {
+                std::size_t a = 0, b = 0;
+                band(row_first, row_count, a, b);
+                read_stored(static_cast<std::uint8_t*>(dst) + a * pixel_size(pixel()), a, b);
+            }
+
+            // The same rows converted to float into dst (dim_x * dim_y floats, row stride dim_x): read_rows_raw, then widened here.
+            void read_rows(float* dst, std::uint32_t row_first, std::uint32_t row_count)
+            {
+                std::size_t a = 0, b = 0;
+                band(row_first, row_count, a, b);
+                if(!in_frame_)
+                    return;
+                band_.resize((b - a) * pixel_size(pixel()));
+                read_stored(band_.data(), a, b);
+                widen(dst + a, band_.data(), b - a, pixel());
             }
 
         private:
-            template <typename T>
-            void convert(float* out, std::size_t count) const
+            // elements [a, b) of the frame that rows [row_first, row_first + row_count) cover, clipped to the frame
+            void band(std::uint32_t row_first, std::uint32_t row_count, std::size_t& a, std::size_t& b) const
             {
-                const auto* src = raw_.data();
-                for(std::size_t i = 0; i < count; ++i)
+                const auto total = static_cast<std::size_t>(dim_x_) * dim_y_;
+                a = static_cast<std::size_t>(row_first) * dim_x_;
+                b = a + static_cast<std::size_t>(row_count) * dim_x_;
+                a = a < total ? a : total;
+                b = b < total ? b : total;
+            }
+
+            // elements [a, b) of the current frame into out (pixel_size(pixel()) bytes each); the one reading path
+            void read_stored(std::uint8_t* out, std::size_t a, std::size_t b)
+            {
+                if(!in_frame_)
+                    return;
+                const auto ps = pixel_size(pixel());
+                const auto stored_b = b < n_ ? b : n_; // elements beyond n_ are not in the file: they stay 0
+                const auto stored_a = a < stored_b ? a : stored_b;
+                const auto count = stored_b - stored_a;
+                const bool f64 = h_.number_type == type_double;
+                std::uint8_t* in = out + (stored_a - a) * ps;
+                if(f64)
                 {
-                    T v;
-                    std::memcpy(&v, src + i * sizeof(T), sizeof(T));
-                    out[i] = static_cast<float>(v); // std::copy's implicit conversion: src/his.cpp:99
+                    raw_.resize(count * px_);
+                    in = raw_.data();
                 }
+                std::size_t got = 0;
+                if(count && std::fseek(f_.get(), static_cast<long>(stored_a * px_), SEEK_CUR) == 0)
+                    got = std::fread(in, px_, count, f_.get());
+                consumed_ = stored_a * px_ + got * px_;
+                if(got < count)
+                    std::memset(in + got * px_, 0, (count - got) * px_); // a short read leaves zeros (:99)
+                if(f64)
+                    for(std::size_t i = 0; i < count; ++i)
+                    {
+                        double v;
+                        std::memcpy(&v, raw_.data() + i * sizeof(double), sizeof(double));
+                        const auto f = static_cast<float>(v);
+                        std::memcpy(out + (stored_a - a + i) * sizeof(float), &f, sizeof(float));
+                    }
+                if(b > stored_b)
+                    std::memset(out + (stored_b - a) * ps, 0, (b - stored_b) * ps);
+                skip_payload();
             }
 
             void skip_payload() // leaves the file position behind the current frame's pixels
@@ -193,7 +259,7 @@ namespace paris
             bool accepted_ = false, in_frame_ = false;
             std::uint32_t dim_x_ = 0, dim_y_ = 0, next_ = 0;
             std::size_t n_ = 0, px_ = 0, consumed_ = 0;
-            std::vector<std::uint8_t> skip_, raw_;
+            std::vector<std::uint8_t> skip_, raw_, band_;
         };
 
         // src/his.cpp:105-198. `out_header` (optional) receives the parsed file header.

@@ -4,9 +4,10 @@
 // (src/main.cpp:157-167), the stage order load -> weight -> filter -> backproject per projection (:98-105), one
 // sink shared by all threads.
 // What is rebuilt for the GPU:
-//   - the per-projection chain is enqueued asynchronously on the device's stream; the host thread meanwhile reads and
-//     converts the next HIS frame into a pinned upload slot (slot = pinned host + device frame); the upload runs on a
+//   - the per-projection chain is enqueued asynchronously on the device's stream; the host thread meanwhile reads the
+//     next HIS frame, as stored, into a pinned upload slot (slot = pinned host + device frame); the upload runs on a
 //     second stream and the compute stream waits for it by event, so file I/O, PCIe upload and GPU work all overlap;
+//     the device widens the stored pixels to fp32 (paris_hip_upload_projection_raw): a u16 frame crosses PCIe at 2 B per pixel;
 //   - slots form two groups of `batch` frames; a full group is backprojected by one fused launch and guarded by a
 //     stream fence, the host fills the other group meanwhile;
 //   - per slab only the detector rows it can read are converted, uploaded, weighted and filtered (8f-4,
@@ -42,6 +43,10 @@
 
 namespace paris
 {
+    static_assert(his::pixel_u8 == PARIS_HIP_PIXEL_U8 && his::pixel_u16 == PARIS_HIP_PIXEL_U16 && his::pixel_u32 == PARIS_HIP_PIXEL_U32
+                      && his::pixel_f32 == PARIS_HIP_PIXEL_F32,
+                  "his::pixel_type names the pixel types of paris_hip_upload_projection_raw");
+
     // src/program_options.h:34-50 (the parts the hot path needs)
     struct program_options
     {
@@ -185,6 +190,7 @@ namespace paris
         double setup_s = 0;       // ctx, pinned slots, device frames: before the first task is popped
         double source_wait_s = 0; // the device thread waiting for the feed thread's next frame (read_ahead)
         double drain_wait_s = 0; // the device thread waiting for the drain thread (a volume buffer to come free; the end of the run)
+        std::uint64_t h2d_bytes = 0; // projection rows uploaded, in their stored pixel type (paris_hip_upload_projection_raw)
         bool two_volumes = false; // a second slab buffer was in use: slab k went to the file while slab k + 1 was reconstructed
         std::vector<std::string> skipped;
     };
@@ -645,7 +651,6 @@ namespace paris
                     rt(paris_hip_slab_row_band(&t.det_geo, &t.vol_geo, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, t.enable_roi,
                                                &t.roi, &band_first, &band_count), "slab_row_band()");
                 rep.band_rows += band_count;
-                const auto row_bytes = static_cast<std::size_t>(n_row) * sizeof(float);
 
                 t0 = clock::now();
                 // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
@@ -689,9 +694,11 @@ namespace paris
                 };
                 // f4: only the detector rows this slab can read are converted, uploaded, weighted and filtered; the
                 // buffers keep their full size, rows outside the band are never read for a voxel of the slab
+                // The rows arrive as stored (u8 / u16 / u32 / f32; f64 as f32): the upload carries those bytes and the device widens them
+                // (paris_hip_upload_projection_raw, bit for bit the host's conversion). A slot keeps room for 4 bytes per pixel.
                 const auto next_frame = [&](float* dst) {
-                    return shared ? shared->next(cur, dst, n_row, n_col, band_first, band_count)
-                                  : own->next(dst, n_row, n_col, band_first, band_count); // :100, straight into pinned memory
+                    return shared ? shared->next_raw(cur, dst, n_row, n_col, band_first, band_count)
+                                  : own->next_raw(dst, n_row, n_col, band_first, band_count); // :100, straight into pinned memory
                 };
                 if(po.read_ahead)
                     feed.reset(new frame_feed{ctx, next_frame, h_buf, batch, fence});
@@ -720,12 +727,15 @@ namespace paris
                     if(p.dim_x != n_row || p.dim_y != n_col)
                         throw stage_runtime_error{"projection size does not match the detector geometry"};
                     t0 = clock::now();
-                    const auto band_off = static_cast<std::size_t>(band_first) * n_row;
+                    const auto px = his::pixel_size(p.pixel);
+                    const auto band_off = static_cast<std::size_t>(band_first) * n_row * px; // bytes
                     auto* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_buf[slot]) + static_cast<std::size_t>(band_first) * d_pitch);
                     if(band_count != 0)
                     {
                         // :101 -- on the upload stream, overlapping the kernels of the previous projections
-                        rt(paris_hip_upload_projection(ctx, d_band, d_pitch, h_buf[slot] + band_off, row_bytes, n_row, band_count), "load()");
+                        rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px, n_row,
+                                                           band_count, p.pixel), "load()");
+                        rep.h2d_bytes += static_cast<std::uint64_t>(band_count) * n_row * px;
                         // :102-103 in one launch: the weight rides along in the row filter's load; with --f16 (BASELINE config 5) the
                         // filtered band is stored as IEEE half straight into the slot's half frame
                         // (small frames: the whole group by one launch when it is flushed -- a launch per 512^2 frame is mostly latency)

@@ -178,6 +178,7 @@ namespace paris
         std::uint32_t dim_x = 0, dim_y = 0;
         std::uint32_t idx = 0;
         float phi = 0.f;
+        int pixel = his::pixel_f32; // what next_raw() wrote: his::pixel_type of this frame (a directory may mix number types)
         bool valid() const noexcept { return dim_x != 0 && dim_y != 0; }
     };
 
@@ -203,6 +204,19 @@ namespace paris
         // stride dim_x) and returns its metadata; !valid() when the directory is exhausted. A frame whose size is not
         // dim_x x dim_y is reported with its own size and nothing is written.
         auto next(float* dst, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
+        {
+            return next_frame(dst, false, dim_x, dim_y, row_first, row_count);
+        }
+
+        // The same with the rows as stored (his::reader::read_rows_raw): dst holds dim_x * dim_y pixels of
+        // his::pixel_size(info.pixel) bytes, room for 4 bytes per pixel covers every type.
+        auto next_raw(void* dst, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
+        {
+            return next_frame(dst, true, dim_x, dim_y, row_first, row_count);
+        }
+
+    private:
+        auto next_frame(void* dst, bool raw, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
         {
             for(;;)
             {
@@ -235,15 +249,20 @@ namespace paris
                 info.dim_x = reader_->dim_x();
                 info.dim_y = reader_->dim_y();
                 info.idx = counter;
+                info.pixel = reader_->pixel();
                 if(enable_angles_ && !angles_.empty())
                     info.phi = angles_.at(counter);
                 if(info.dim_x == dim_x && info.dim_y == dim_y)
-                    reader_->read_rows(dst, row_first, row_count);
+                {
+                    if(raw)
+                        reader_->read_rows_raw(dst, row_first, row_count);
+                    else
+                        reader_->read_rows(static_cast<float*>(dst), row_first, row_count);
+                }
                 return info;
             }
         }
 
-    private:
         std::vector<std::string> paths_;
         std::size_t next_path_ = 0;
         std::unique_ptr<his::reader> reader_;
@@ -257,8 +276,9 @@ namespace paris
 
     // Read-once frame source shared by the device threads of one run. Every device needs every projection for its slab;
     // the reference lets each device thread read the whole set again (src/main.cpp:93: a source per task). Here every kept
-    // frame is read and converted once, into a buffer of a small ring, by whichever thread gets to it first; the other
-    // threads copy the rows they need (their slab's detector band) from that buffer. Frames are claimed in order, one
+    // frame is read once, as stored, into a buffer of a small ring, by whichever thread gets to it first; the other
+    // threads copy the rows they need (their slab's detector band) from that buffer, as stored (next_raw) or widened to float
+    // (next). Frames are claimed in order, one
     // thread each, and several are in production at a time: a thread whose own frame is still being read by another one
     // does not sleep, it claims and reads the next unclaimed frame ahead (up to half a ring ahead of its own position), so
     // N device threads convert N frames side by side instead of queueing behind one reader. Every producing thread reads
@@ -299,11 +319,37 @@ namespace paris
         // frame_stream::next for the consumer behind `c`
         auto next(cursor& c, float* dst, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
         {
+            return next_frame(c, dst, false, dim_x, dim_y, row_first, row_count);
+        }
+
+        // frame_stream::next_raw for the consumer behind `c`
+        auto next_raw(cursor& c, void* dst, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
+        {
+            return next_frame(c, dst, true, dim_x, dim_y, row_first, row_count);
+        }
+
+        // the files the shared streams skipped (complete once a consumer has reached the end of the set)
+        auto skipped_files() const -> std::vector<std::string>
+        {
+            std::lock_guard<std::mutex> lock{m_};
+            return skipped_;
+        }
+
+        auto stats() const -> counters
+        {
+            std::lock_guard<std::mutex> lock{m_};
+            return stats_;
+        }
+
+    private:
+        auto next_frame(cursor& c, void* dst, bool raw, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t row_first,
+                        std::uint32_t row_count) -> frame_info
+        {
             if(dim_x != dim_x_ || dim_y != dim_y_)
                 throw std::runtime_error{"shared_frames::next(): frame size differs from the one the cache was built for"};
             const auto k = c.next_++;
             if(c.own_) // once behind, stay on the private stream: it is already positioned
-                return from_own(c, k, dst, row_first, row_count);
+                return from_own(c, k, dst, raw, row_first, row_count);
             const std::uint64_t ahead = ring_.size() / 2u; // how far beyond its own frame a waiting thread may produce
             std::shared_ptr<const entry> e;
             {
@@ -364,32 +410,24 @@ namespace paris
                 }
             }
             if(!e)
-                return from_own(c, k, dst, row_first, row_count);
+                return from_own(c, k, dst, raw, row_first, row_count);
             if(e->info.dim_x == dim_x && e->info.dim_y == dim_y && row_count != 0)
-                std::memcpy(dst + static_cast<std::size_t>(row_first) * dim_x, e->pixels.data() + static_cast<std::size_t>(row_first) * dim_x,
-                            static_cast<std::size_t>(row_count) * dim_x * sizeof(float));
+            {
+                const auto first = static_cast<std::size_t>(row_first) * dim_x, count = static_cast<std::size_t>(row_count) * dim_x;
+                const auto ps = his::pixel_size(e->info.pixel);
+                if(raw)
+                    std::memcpy(static_cast<std::uint8_t*>(dst) + first * ps, e->pixels.data() + first * ps, count * ps);
+                else
+                    his::widen(static_cast<float*>(dst) + first, e->pixels.data() + first * ps, count, e->info.pixel);
+            }
             return e->info;
         }
 
-        // the files the shared streams skipped (complete once a consumer has reached the end of the set)
-        auto skipped_files() const -> std::vector<std::string>
-        {
-            std::lock_guard<std::mutex> lock{m_};
-            return skipped_;
-        }
-
-        auto stats() const -> counters
-        {
-            std::lock_guard<std::mutex> lock{m_};
-            return stats_;
-        }
-
-    private:
         struct entry
         {
             std::uint64_t ordinal = 0;
             frame_info info{};
-            std::vector<float> pixels; // the whole frame (consumers want different bands)
+            std::vector<std::uint8_t> pixels; // the whole frame as stored (consumers want different bands, and raw or float rows)
         };
 
         // reads kept frame j through the cursor's producing stream (frames are claimed in rising order, so the stream only ever
@@ -402,7 +440,7 @@ namespace paris
                 c.prod_pos_ = 0;
             }
             for(; c.prod_pos_ < j; ++c.prod_pos_) // frames other threads produce are stepped over without conversion
-                if(!c.prod_->next(nullptr, dim_x_, dim_y_, 0, 0).valid())
+                if(!c.prod_->next_raw(nullptr, dim_x_, dim_y_, 0, 0).valid())
                     return nullptr;
             // frame buffers are recycled: the deleter of an entry hands its pixel vector back (a fresh 16 MiB vector per
             // frame would cost a page-faulting zero fill each time)
@@ -424,15 +462,15 @@ namespace paris
                 delete d;
             }};
             e->ordinal = j;
-            e->pixels.resize(static_cast<std::size_t>(dim_x_) * dim_y_);
-            e->info = c.prod_->next(e->pixels.data(), dim_x_, dim_y_, 0, dim_y_);
+            e->pixels.resize(static_cast<std::size_t>(dim_x_) * dim_y_ * sizeof(float)); // (room for any pixel type)
+            e->info = c.prod_->next_raw(e->pixels.data(), dim_x_, dim_y_, 0, dim_y_);
             ++c.prod_pos_;
             if(!e->info.valid())
                 return nullptr;
             return e;
         }
 
-        auto from_own(cursor& c, std::uint64_t k, float* dst, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
+        auto from_own(cursor& c, std::uint64_t k, void* dst, bool raw, std::uint32_t row_first, std::uint32_t row_count) -> frame_info
         {
             if(!c.own_)
             {
@@ -440,10 +478,11 @@ namespace paris
                 c.own_pos_ = 0;
             }
             for(; c.own_pos_ < k; ++c.own_pos_) // seek: kept frames before k are stepped over without conversion
-                if(!c.own_->next(dst, dim_x_, dim_y_, 0, 0).valid())
+                if(!c.own_->next_raw(dst, dim_x_, dim_y_, 0, 0).valid())
                     return frame_info{};
             ++c.own_pos_;
-            const auto info = c.own_->next(dst, dim_x_, dim_y_, row_first, row_count);
+            const auto info = raw ? c.own_->next_raw(dst, dim_x_, dim_y_, row_first, row_count)
+                                  : c.own_->next(static_cast<float*>(dst), dim_x_, dim_y_, row_first, row_count);
             if(info.valid())
             {
                 std::lock_guard<std::mutex> lock{m_};
@@ -460,7 +499,7 @@ namespace paris
         mutable std::mutex m_;
         std::condition_variable cv_;
         std::mutex spare_m_;
-        std::vector<std::vector<float>> spare_; // declared before ring_: the entries' deleters use it while ring_ is destroyed
+        std::vector<std::vector<std::uint8_t>> spare_; // declared before ring_: the entries' deleters use it while ring_ is destroyed
         std::vector<std::shared_ptr<const entry>> ring_;
         std::uint64_t claimed_ = 0;             // frames 0 .. claimed_ - 1 have a producer (or are done)
         std::uint64_t end_ = 0, fail_at_ = 0;
