@@ -443,6 +443,29 @@ int paris_hip_slab_row_band(const paris_detector_geometry* det_geo, const paris_
 /* angle of projection idx -> sin/cos on the host in fp32 (src/backprojection.cpp:52-63) */
 int paris_hip_stage_angle(const paris_detector_geometry* det_geo, uint32_t idx, int enable_angles, float phi,
                           float* sin_phi, float* cos_phi);
+
+/* Extension (no reference counterpart): short scans. A scan covers the projection angles [start_deg, start_deg + range_deg]
+ * -- the angle the backprojection uses, idx * delta_phi or phi with angles enabled -- and is valid when
+ * 180 + 2 gamma_m <= range_deg <= 360, gamma_m the largest |fan angle| atan(t / d_sd) over the two outermost pixel centres in the
+ * backprojector's coordinates, t = (i + 1/2) l_px_row - n_row l_px_row / 2 - delta_s l_px_row (delta_s included). */
+typedef struct paris_short_scan {
+    float start_deg;  /* first projection angle [deg] */
+    float range_deg;  /* angle covered from the first to the last projection [deg] */
+} paris_short_scan;
+/* Host only. PARIS_HIP_ERROR_INVALID_ARGUMENT when range_deg < 180 + 2 gamma_m, range_deg > 360, or a value is not finite.
+ * gamma_max_deg (may be NULL) receives gamma_m in degrees, for refused scans too. */
+int paris_hip_short_scan_check(const paris_detector_geometry* det_geo, const paris_short_scan* scan, float* gamma_max_deg);
+/* Parker redundancy weighting: every row in [row_first, row_first + row_count) of n_frames projections frame_stride bytes apart
+ * has column i multiplied by 2 w(beta, gamma_i), beta = (phi_deg[f] - start_deg) mod 360 (DESIGN.md "Short scans"); the 2 cancels
+ * the backprojection's 0.5, so the volume has the full circle's scale. Where w == 1 the pixel becomes exactly 2 p. Call it on the
+ * raw frame, before the cosine weighting; dim_x must equal det_geo->n_row. Runs the check above. */
+int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                     uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
+                                     const paris_detector_geometry* det_geo, const paris_short_scan* scan, const float* phi_deg);
+/* The same for one whole projection, its angle resolved from idx / phi exactly as paris_hip_stage_angle does */
+int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
+                                      const paris_detector_geometry* det_geo, const paris_short_scan* scan, uint32_t idx,
+                                      int enable_angles, float phi);
 /* paris::backproject (src/backprojection.cpp:37-69): p_idx / p_phi are projection::idx / projection::phi */
 int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_pitch, uint32_t p_dim_x,
                                 uint32_t p_dim_y, uint32_t p_idx, float p_phi, float* d_v, uint32_t v_dim_x,

@@ -53,6 +53,11 @@ class RegionOfInterest(C.Structure):
                 ("y2", C.c_uint32), ("z1", C.c_uint32), ("z2", C.c_uint32)]
 
 
+class ShortScan(C.Structure):
+    """paris_short_scan: the projection angles [start_deg, start_deg + range_deg] a short scan covers (extension)"""
+    _fields_ = [("start_deg", C.c_float), ("range_deg", C.c_float)]
+
+
 class SubvolumeInfo(C.Structure):
     """paris::subvolume_info (src/subvolume_information.h:30-34)"""
     _fields_ = [("geo", SubvolumeGeometry), ("num", C.c_int)]
@@ -143,6 +148,11 @@ SIGNATURES = {
     "paris_hip_slab_row_band": (C.c_int, [_P(DetectorGeometry), _P(VolumeGeometry), _u32, _u32, _u32, _u32, C.c_int,
                                           _P(RegionOfInterest), _P(_u32), _P(_u32)]),
     "paris_hip_stage_angle": (C.c_int, [_P(DetectorGeometry), _u32, C.c_int, _f, _P(_f), _P(_f)]),
+    "paris_hip_short_scan_check": (C.c_int, [_P(DetectorGeometry), _P(ShortScan), _P(_f)]),
+    "paris_hip_short_scan_weight_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32, _P(DetectorGeometry), _P(ShortScan),
+                                                   _P(_f)]),
+    "paris_hip_stage_short_scan_weight": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _P(DetectorGeometry), _P(ShortScan), _u32, C.c_int,
+                                                    _f]),
     "paris_hip_stage_backproject": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _u32, _f, _vp, _u32, _u32, _u32, _u32,
                                               _P(DetectorGeometry), _P(VolumeGeometry), C.c_int, C.c_int,
                                               _P(RegionOfInterest)]),

@@ -12,13 +12,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DetectorGeometry, ParisHipError, RegionOfInterest, SubvolumeGeometry, SubvolumeInfo,
+from ._lib import (DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan, SubvolumeGeometry, SubvolumeInfo,
                    VolumeGeometry, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
-           "ParisHipError", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
+           "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
-           "backproject"]
+           "backproject", "short_scan_check"]
 
 
 class Projection:
@@ -274,6 +274,20 @@ class Backend:
         check(self._L.paris_hip_weight(self._ctx, p.ptr, p.pitch, p.dim_x, p.dim_y, h_min, v_min, d_sd,
                                        l_px_row, l_px_col), "paris_hip_weight")
 
+    def short_scan_weight(self, p, det_geo, scan, phi_deg, row_first=0, row_count=None, frame_stride=0):
+        """Parker redundancy weighting of a short scan (paris_hip_short_scan_weight_rows), on the raw frame before weight():
+        rows [row_first, row_first + row_count) of each column i are multiplied by 2 w(beta, gamma_i). scan is a ShortScan or
+        (start_deg, range_deg); phi_deg is the projection angle in degrees as the backprojection resolves it, or a sequence of
+        them for len(phi_deg) frames frame_stride bytes apart starting at p (one launch)."""
+        if not isinstance(scan, ShortScan):
+            scan = ShortScan(*scan)
+        phis = np.atleast_1d(np.asarray(phi_deg, np.float32))
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_short_scan_weight_rows(self._ctx, p.ptr, p.pitch, frame_stride, len(phis), p.dim_x, p.dim_y, row_first,
+                                                       count, C.byref(det_geo), C.byref(scan),
+                                                       phis.ctypes.data_as(C.POINTER(C.c_float))),
+              "paris_hip_short_scan_weight_rows")
+
     def make_filter(self, size, tau, window=0):
         """backend::make_filter (src/openmp/filtering.cpp:139-165); window 1 = Shepp-Logan (extension)"""
         ptr = C.c_void_p()
@@ -516,6 +530,25 @@ def filter(backend, p, det_geo):  # noqa: A001 - the reference's name
     """paris::filter (src/filtering.cpp:32-45)"""
     check(backend._L.paris_hip_stage_filter(backend._ctx, p.ptr, p.pitch, p.dim_x, p.dim_y, C.byref(det_geo)),
           "paris_hip_stage_filter")
+
+
+def short_scan_check(det_geo, start_deg, range_deg):
+    """gamma_m in degrees -- the largest |fan angle| over the outermost pixel centres -- of a valid short scan over
+    [start_deg, start_deg + range_deg] (paris_hip_short_scan_check); raises ParisHipError when range_deg < 180 + 2 gamma_m,
+    range_deg > 360 or a value is not finite"""
+    g = C.c_float()
+    check(_lib.load().paris_hip_short_scan_check(C.byref(det_geo), C.byref(ShortScan(start_deg, range_deg)), C.byref(g)),
+          "paris_hip_short_scan_check")
+    return g.value
+
+
+def stage_short_scan_weight(backend, p, det_geo, scan, enable_angles=False):
+    """The redundancy weight of one whole projection, its angle resolved from p.idx / p.phi as the backprojection does
+    (paris_hip_stage_short_scan_weight)"""
+    if not isinstance(scan, ShortScan):
+        scan = ShortScan(*scan)
+    check(backend._L.paris_hip_stage_short_scan_weight(backend._ctx, p.ptr, p.pitch, p.dim_x, p.dim_y, C.byref(det_geo), C.byref(scan),
+                                                       p.idx, int(bool(enable_angles)), p.phi), "paris_hip_stage_short_scan_weight")
 
 
 def slab_row_band(det_geo, vol_geo, v_dim_x, v_dim_y, v_dim_z, v_offset=0, roi=None):

@@ -4,10 +4,13 @@
 // usage: paris_hip_demo <n_row> <n_col> <l_px_row> <l_px_col> <delta_s> <delta_t> <d_so> <d_od> <delta_phi>
 //                       <n_proj> <in.raw | lcg> <out.raw> [--no-weight] [--no-filter]
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
+//                       [--short-scan start_deg range_deg]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
 // --json: one more line, the same figures as a JSON object (bench.py's paris_loop leg reads it).
+// --short-scan: the projections (angle i * delta_phi) form a short scan over [start_deg, start_deg + range_deg]: set_short_scan() before
+// the loops, so that paris::weight() applies the Parker redundancy weight first.
 // out.raw receives the whole (ROI) volume, slabs written at their slice offsets (fixing SURVEY.md Q4).
 #include <chrono>
 #include <cstdio>
@@ -57,6 +60,8 @@ int main(int argc, char** argv)
         bool do_weight = true, do_filter = true, enable_roi = false, write_out = true, json = false;
         int slabs = 1;
         std::uint32_t cycle = 0;
+        bool short_scan = false;
+        float scan_start = 0.f, scan_range = 0.f;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
         auto vol_geo = paris::calculate_volume_geometry(det);
@@ -69,6 +74,13 @@ int main(int argc, char** argv)
             else if(!std::strcmp(argv[a], "--no-out")) write_out = false;
             else if(!std::strcmp(argv[a], "--json")) json = true;
             else if(!std::strcmp(argv[a], "--order") && a + 1 < argc) order = std::atoi(argv[++a]);
+            else if(!std::strcmp(argv[a], "--short-scan") && a + 2 < argc)
+            {
+                short_scan = true;
+                scan_start = std::strtof(argv[a + 1], nullptr);
+                scan_range = std::strtof(argv[a + 2], nullptr);
+                a += 2;
+            }
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
                 enable_roi = true;
@@ -97,6 +109,8 @@ int main(int argc, char** argv)
         if(devices.empty())
             throw paris::stage_construction_error{"no HIP device"};
         paris::backend::set_device(devices[0]); // src/main.cpp:87
+        if(short_scan)
+            paris::backend::set_short_scan(scan_start, scan_range, false);
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 

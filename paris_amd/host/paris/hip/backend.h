@@ -113,10 +113,17 @@ namespace paris
 
             struct ctx_deleter { void operator()(paris_hip_ctx* c) const noexcept { paris_hip_ctx_destroy(c); } };
 
+            struct short_scan_setting
+            {
+                paris_short_scan scan;
+                bool enable_angles;
+            };
+
             struct thread_state
             {
                 std::map<device_handle, std::unique_ptr<paris_hip_ctx, ctx_deleter>> per_device;
                 paris_hip_ctx* current = nullptr;
+                std::map<const paris_hip_ctx*, short_scan_setting> short_scans; // set_short_scan(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -185,6 +192,34 @@ namespace paris
                 set_device(d);
             }
             return s.current;
+        }
+
+        // Extension (no reference counterpart): the projections of this thread's current device form a short scan over
+        // [start_deg, start_deg + range_deg] (paris_short_scan). Until clear_short_scan(), paris::weight() first applies the Parker
+        // redundancy weight to each projection, its angle taken from p.idx / p.phi as backproject() takes it (enable_angles: the
+        // angle file's phi). The scan is checked against the detector at each weight(): a range below 180 degrees plus twice the fan
+        // angle throws stage_runtime_error.
+        inline auto set_short_scan(float start_deg, float range_deg, bool enable_angles) -> void
+        {
+            detail::state().short_scans[current_ctx()] = detail::short_scan_setting{paris_short_scan{start_deg, range_deg}, enable_angles};
+        }
+
+        inline auto clear_short_scan() -> void
+        {
+            detail::state().short_scans.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            // the short scan set for the calling thread's current device, or nullptr
+            inline auto short_scan_of(const paris_hip_ctx* ctx) -> const short_scan_setting*
+            {
+                const auto& m = state().short_scans;
+                if(m.empty())
+                    return nullptr;
+                const auto it = m.find(ctx);
+                return it == m.end() ? nullptr : &it->second;
+            }
         }
 
         // ---- buffers ------------------------------------------------------------------------------------------

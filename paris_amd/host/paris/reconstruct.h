@@ -22,7 +22,9 @@
 
 #include <chrono>
 #include <condition_variable>
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <exception>
@@ -77,6 +79,10 @@ namespace paris
         // memory-driven split that gives every device one slab of at least 1 GiB: cut each into this many (0: leave it), so that all
         // but the last of a device's slabs go to the file while the next one is reconstructed
         int pipeline_slabs = 4;
+        // Parker redundancy weighting of a short scan (extension): [start, start + range] is derived by run() from the first and last
+        // angle of the frames the run uses, before any device work (detail::derive_short_scan)
+        bool short_scan = false;
+        paris_short_scan scan{};
     };
 
     // src/task.h:33-57
@@ -663,6 +669,7 @@ namespace paris
                 std::uint32_t group = 0, filled = 0; // frames of the current group already enqueued
                 auto feed = std::unique_ptr<frame_feed>{};
                 auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch);
+                auto angles = std::vector<float>(batch); // --short-scan: each frame's angle [deg], resolved as paris_hip_stage_angle does
                 const float delta_s = t.det_geo.delta_s * t.det_geo.l_px_row, delta_t = t.det_geo.delta_t * t.det_geo.l_px_col; // src/backprojection.cpp:49-50
                 // frames of up to 1024 x 1024 are weighted and filtered group by group (one launch for up to `batch` frames when the
                 // group is flushed) instead of frame by frame behind each upload: their launches are mostly latency
@@ -671,6 +678,9 @@ namespace paris
                     if(filled == 0)
                         return;
                     const auto t1 = clock::now();
+                    if(filter_by_group && band_count != 0 && po.short_scan) // the redundancy weight first, one launch for the group
+                        rt(paris_hip_short_scan_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count,
+                                                            &t.det_geo, &po.scan, angles.data()), "short-scan weight()");
                     if(filter_by_group && band_count != 0)
                         rt(paris_hip_stage_weight_filter_batch(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count,
                                                                &t.det_geo,
@@ -736,6 +746,10 @@ namespace paris
                         rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px, n_row,
                                                            band_count, p.pixel), "load()");
                         rep.h2d_bytes += static_cast<std::uint64_t>(band_count) * n_row * px;
+                        angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                        if(po.short_scan && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
+                            rt(paris_hip_short_scan_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count, &t.det_geo,
+                                                                &po.scan, &angles[filled]), "short-scan weight()");
                         // :102-103 in one launch: the weight rides along in the row filter's load; with --f16 (BASELINE config 5) the
                         // filtered band is stored as IEEE half straight into the slot's half frame
                         // (small frames: the whole group by one launch when it is flushed -- a launch per 512^2 frame is mostly latency)
@@ -801,12 +815,46 @@ namespace paris
         std::string output_file;
     };
 
+    namespace detail
+    {
+        // --short-scan: the scan the frames of the run cover, from their first and last angle (after the quality stride). The
+        // angles must be strictly monotonic, and the range must be at least 180 degrees plus twice the fan angle: otherwise some
+        // rays are never measured, and the run is refused here, before any device work.
+        inline auto derive_short_scan(const program_options& po) -> paris_short_scan
+        {
+            const auto a = frame_angles(po.input_path, po.enable_angles, po.angle_path, po.quality, po.det_geo.delta_phi);
+            if(a.size() < 2u)
+                throw stage_construction_error{"--short-scan needs at least two projections"};
+            const bool up = a[1] > a[0];
+            for(std::size_t i = 1; i < a.size(); ++i)
+                if(up ? !(a[i] > a[i - 1]) : !(a[i] < a[i - 1]))
+                    throw stage_construction_error{"--short-scan: the projection angles are not monotonic (frame " + std::to_string(i) + ": "
+                                                   + std::to_string(a[i]) + " degrees after " + std::to_string(a[i - 1]) + ")"};
+            const auto scan = paris_short_scan{up ? a.front() : a.back(), std::abs(a.back() - a.front())};
+            float gamma_m = 0.f;
+            if(paris_hip_short_scan_check(&po.det_geo, &scan, &gamma_m) != PARIS_HIP_SUCCESS)
+            {
+                const double need = 180.0 + 2.0 * gamma_m;
+                char msg[256];
+                if(scan.range_deg > 360.f)
+                    std::snprintf(msg, sizeof msg, "--short-scan: the projections cover %.4f degrees, more than 360", scan.range_deg);
+                else
+                    std::snprintf(msg, sizeof msg, "--short-scan: the projections cover %.4f degrees, a short scan needs at least 180 + 2 * %.4f = %.4f "
+                                  "(%.4f degrees short)", scan.range_deg, gamma_m, need, need - scan.range_deg);
+                throw stage_construction_error{msg};
+            }
+            return scan;
+        }
+    }
+
     // src/main.cpp:120-178
     inline auto run(const program_options& requested) -> run_report
     {
         auto po = requested; // batch may shrink to fit the devices' memory (detail::fit_batch)
         auto r = run_report{};
         const auto start = detail::clock::now();
+        if(po.short_scan)
+            po.scan = detail::derive_short_scan(po);
         r.vol_geo = calculate_volume_geometry(po.det_geo); // :122
         r.roi_geo = r.vol_geo;
         if(po.enable_roi)                                  // :124-130

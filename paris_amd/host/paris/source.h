@@ -274,6 +274,31 @@ namespace paris
         std::uint32_t counter_ = 0;
     };
 
+    // The projection angle [deg] of every frame frame_stream would hand out, in order, resolved as the backprojection resolves it
+    // (paris_hip_stage_angle: phi of the angle file, or idx * delta_phi in fp32). Reads frame headers only, no pixels.
+    inline auto frame_angles(const std::string& proj_dir, bool enable_angles, const std::string& angle_file, std::uint16_t quality,
+                             float delta_phi) -> std::vector<float>
+    {
+        const auto stride = quality == 0 ? std::uint16_t{1} : quality;
+        const auto angles = enable_angles ? read_angles(angle_file) : std::vector<float>{};
+        auto out = std::vector<float>{};
+        std::uint32_t counter = 0;
+        for(const auto& path : read_directory(proj_dir))
+        {
+            auto r = std::unique_ptr<his::reader>{};
+            try { r.reset(new his::reader{path}); }
+            catch(const std::system_error&) { continue; }
+            while(r->advance())
+            {
+                const auto idx = counter++;
+                if(idx % stride != 0u)
+                    continue;
+                out.push_back(enable_angles ? (angles.empty() ? 0.f : angles.at(idx)) : static_cast<float>(idx) * delta_phi);
+            }
+        }
+        return out;
+    }
+
     // Read-once frame source shared by the device threads of one run. Every device needs every projection for its slab;
     // the reference lets each device thread read the whole set again (src/main.cpp:93: a source per task). Here every kept
     // frame is read once, as stored, into a buffer of a small ring, by whichever thread gets to it first; the other

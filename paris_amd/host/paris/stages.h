@@ -28,8 +28,13 @@ namespace paris
         return backend::make_volume_device(subvol_geo.dim_x, subvol_geo.dim_y, dim_z);
     }
 
+    // with a short scan set (backend::set_short_scan), the Parker redundancy weight comes first
     inline auto weight(backend::projection_device_type& p, const detector_geometry& det_geo) -> void
     {
+        if(const auto* s = backend::detail::short_scan_of(backend::current_ctx()))
+            backend::detail::runtime_check(paris_hip_stage_short_scan_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y,
+                                                                             &det_geo, &s->scan, p.idx, s->enable_angles ? 1 : 0, p.phi),
+                                           "weight()");
         backend::detail::runtime_check(paris_hip_stage_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                               p.dim_y, &det_geo), "weight()");
     }
