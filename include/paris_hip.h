@@ -466,6 +466,27 @@ int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitc
 int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
                                       const paris_detector_geometry* det_geo, const paris_short_scan* scan, uint32_t idx,
                                       int enable_angles, float phi);
+/* Extension (no reference counterpart): dark / flat ("offset / gain") correction of intensity frames to line integrals. With I a
+ * pixel as fp32 and D, F the dark and flat reference pixels of the same detector row and column, in double, rounded once:
+ *   p = -ln(max((I - D) / (F - D), t_min))   when I, D and F are finite and F - D > 0,   p = 0 otherwise (dead pixel).
+ * There is no upper clamp: noise may make p negative.
+ * paris_hip_set_flat_field copies the two dim_x x dim_y frames (rows dim_x floats apart; h_dark NULL = zeros) into memory the ctx
+ * owns, replacing an earlier setting; the old frames are freed once the work queued before the call no longer reads them.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL h_flat, a zero dimension, or t_min outside (0, 1]. The frames count towards
+ * paris_hip_projection_reserve_bytes while set; paris_hip_ctx_destroy frees them. Without a setting nothing else changes. */
+int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark, const float* h_flat, uint32_t dim_x, uint32_t dim_y, float t_min);
+int paris_hip_clear_flat_field(paris_hip_ctx* ctx);
+/* In place on float frames: rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes apart, d_p the first
+ * frame's row 0, each pixel corrected with the reference pixel of its own row. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting,
+ * when dim_x / dim_y differ from the setting's, or for a band, pitch or stride the short-scan pass would refuse. */
+int paris_hip_flat_field_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                              uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* paris_hip_upload_projection_raw of rows [row_first, row_first + row_count) -- h_src points at the band's first stored row,
+ * d_frame at the full frame's row 0 -- widened and corrected in one pass on the device: bit for bit the raw upload into those rows
+ * followed by paris_hip_flat_field_rows on them. Any pixel type of the raw upload, PARIS_HIP_PIXEL_F32 included; its ordering rules.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or when dim_x / dim_y differ from the setting's. */
+int paris_hip_upload_projection_raw_corrected(paris_hip_ctx* ctx, float* d_frame, size_t d_pitch, const void* h_src, size_t h_pitch,
+                                              uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count, int pixel_type);
 /* paris::backproject (src/backprojection.cpp:37-69): p_idx / p_phi are projection::idx / projection::phi */
 int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_pitch, uint32_t p_dim_x,
                                 uint32_t p_dim_y, uint32_t p_idx, float p_phi, float* d_v, uint32_t v_dim_x,

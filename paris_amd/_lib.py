@@ -88,6 +88,10 @@ SIGNATURES = {
     "paris_hip_memcpy_projection_h2d": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_upload_projection": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_upload_projection_raw": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, C.c_int]),
+    "paris_hip_upload_projection_raw_corrected": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u32, C.c_int]),
+    "paris_hip_set_flat_field": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _f]),
+    "paris_hip_clear_flat_field": (C.c_int, [_vp]),
+    "paris_hip_flat_field_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_memcpy_projection_d2h": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_memcpy_volume_h2d": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "paris_hip_memcpy_volume_d2h": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),

@@ -231,10 +231,13 @@ class Backend:
     _PIXEL_TYPES = {np.dtype(np.uint8): _lib.PIXEL_U8, np.dtype(np.uint16): _lib.PIXEL_U16, np.dtype(np.uint32): _lib.PIXEL_U32,
                     np.dtype(np.float32): _lib.PIXEL_F32}
 
-    def upload_raw(self, h, d):
+    def upload_raw(self, h, d, row_first=0, corrected=False):
         """upload() of a frame in its stored pixel type (paris_hip_upload_projection_raw): h is a 2-D uint8, uint16, uint32 or float32
         ndarray (rows may be padded: h.strides[0] is the host pitch); the copy carries its bytes as they are and the device widens
-        them to fp32 in place -- bit for bit h.astype(np.float32). Returns without waiting, like upload()."""
+        them to fp32 in place -- bit for bit h.astype(np.float32). Returns without waiting, like upload().
+        h may be a band of rows: they go to rows [row_first, row_first + len(h)) of d. corrected: the same pass also applies the
+        dark / flat correction of set_flat_field() (paris_hip_upload_projection_raw_corrected) -- bit for bit upload_raw()
+        followed by flat_field_rows() on those rows."""
         if not isinstance(h, np.ndarray) or h.ndim != 2:
             raise TypeError("upload_raw: h must be a 2-D ndarray")
         if h.dtype == np.float64:
@@ -244,9 +247,40 @@ class Backend:
             raise TypeError("upload_raw: unsupported dtype %s (uint8, uint16, uint32 or float32)" % h.dtype)
         if h.strides[1] != h.itemsize or h.strides[0] < h.shape[1] * h.itemsize:
             raise ValueError("upload_raw: the rows of h must be contiguous")
-        assert h.shape == (d.dim_y, d.dim_x)
-        check(self._L.paris_hip_upload_projection_raw(self._ctx, d.ptr, d.pitch, h.ctypes.data, h.strides[0], d.dim_x, d.dim_y, pixel),
-              "paris_hip_upload_projection_raw")
+        rows = h.shape[0]
+        assert h.shape[1] == d.dim_x and 0 <= row_first and row_first + rows <= d.dim_y
+        if corrected:
+            check(self._L.paris_hip_upload_projection_raw_corrected(self._ctx, d.ptr, d.pitch, h.ctypes.data, h.strides[0], d.dim_x,
+                                                                    d.dim_y, row_first, rows, pixel),
+                  "paris_hip_upload_projection_raw_corrected")
+            return
+        check(self._L.paris_hip_upload_projection_raw(self._ctx, d.ptr + row_first * d.pitch, d.pitch, h.ctypes.data, h.strides[0],
+                                                      d.dim_x, rows, pixel), "paris_hip_upload_projection_raw")
+
+    def set_flat_field(self, dark, flat, t_min=1e-5):
+        """Dark / flat correction to line integrals (paris_hip_set_flat_field): dark (None = zeros) and flat are 2-D arrays of the
+        detector's size (n_col, n_row), taken as float32. p = -ln(max((I - D) / (F - D), t_min)), in double, rounded once; a pixel
+        whose I, D or F is not finite or whose flat is not above its dark becomes 0. Replaces an earlier setting safely: work already
+        queued keeps the old frames."""
+        f = np.ascontiguousarray(flat, np.float32)
+        if f.ndim != 2:
+            raise ValueError("set_flat_field: flat must be a 2-D array")
+        dk = None if dark is None else np.ascontiguousarray(dark, np.float32)
+        if dk is not None and dk.shape != f.shape:
+            raise ValueError("set_flat_field: dark and flat differ in shape")
+        check(self._L.paris_hip_set_flat_field(self._ctx, None if dk is None else dk.ctypes.data, f.ctypes.data, f.shape[1], f.shape[0],
+                                               t_min), "paris_hip_set_flat_field")
+
+    def clear_flat_field(self):
+        """paris_hip_clear_flat_field: no correction from here on"""
+        check(self._L.paris_hip_clear_flat_field(self._ctx), "paris_hip_clear_flat_field")
+
+    def flat_field_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """The correction of set_flat_field() in place on float frames (paris_hip_flat_field_rows): rows [row_first, row_first +
+        row_count) of n_frames frames frame_stride bytes apart starting at p, each with the reference rows of the same detector rows"""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_flat_field_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_flat_field_rows")
 
     def copy_d2h(self, d, h):
         if isinstance(d, Projection):

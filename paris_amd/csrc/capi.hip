@@ -107,6 +107,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_validate();
             paris_hip_warm_widen();
             paris_hip_warm_short_scan();
+            paris_hip_warm_flat_field();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -317,6 +318,7 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     if(ctx->upload_stream != nullptr)
         (void)hipStreamSynchronize(ctx->upload_stream);
     ctx->pending_weight.active = false; // a weighting nobody filtered or read: dropped with the ctx
+    paris_hip_flat_field_release(ctx, true); // (nothing reads the reference frames but the compute stream, drained above)
     if(ctx->defer_count != 0)
     {
         // Projections still deferred belong to key_v. Every library entry point that reads or frees a volume has flushed them
@@ -1264,6 +1266,40 @@ extern "C" int paris_hip_upload_projection_raw(paris_hip_ctx* ctx, float* d_dst,
         if(int rc = paris_hip_note_projection_use(ctx, d_dst, d_pitch * dim_y))
             return rc;
     }
+    return paris_hip_finish(ctx);
+}
+
+extern "C" int paris_hip_upload_projection_raw_corrected(paris_hip_ctx* ctx, float* d_frame, size_t d_pitch, const void* h_src, size_t h_pitch,
+                                                         uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count, int pixel_type)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    size_t px = 0;
+    switch(pixel_type)
+    {
+        case PARIS_HIP_PIXEL_U8: px = 1; break;
+        case PARIS_HIP_PIXEL_U16: px = 2; break;
+        case PARIS_HIP_PIXEL_U32: px = 4; break;
+        case PARIS_HIP_PIXEL_F32: px = 4; break;
+        default: return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    }
+    const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
+    if(d_frame == nullptr || h_src == nullptr || d_pitch < static_cast<size_t>(dim_x) * sizeof(float) || d_pitch % sizeof(float) != 0
+       || h_pitch < static_cast<size_t>(dim_x) * px || row_first > dim_y || row_count > dim_y - row_first || ff.d_ref == nullptr
+       || dim_x != ff.dim_x || dim_y != ff.dim_y)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(int rc = paris_hip_flush_pending_weight(ctx))
+        return rc;
+    if(row_count == 0)
+        return paris_hip_finish(ctx);
+    // the band as paris_hip_upload_projection_raw puts it there, then ONE pass widens and corrects it (f32 included: tail offset 0)
+    float* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_frame) + static_cast<size_t>(row_first) * d_pitch);
+    if(int rc = copy_rows_on_upload_stream(ctx, d_band, d_pitch, h_src, h_pitch, dim_x, row_count, px))
+        return rc;
+    if(int rc = paris_hip_widen_correct_rows(ctx, d_band, d_pitch, dim_x, row_count, pixel_type, row_first))
+        return rc;
+    if(int rc = paris_hip_note_projection_use(ctx, d_band, d_pitch * row_count))
+        return rc;
     return paris_hip_finish(ctx);
 }
 

@@ -111,6 +111,17 @@ struct paris_hip_ctx
         size_t bytes = 0; // extent of the buffer as uploaded (pitch x rows): stage calls on a row band pass interior pointers
     };
     std::map<const void*, upload_target> upload_targets;
+    // Dark / flat correction (paris_hip_set_flat_field): the reference frames on the device, the dark at d_ref, the flat right behind
+    // it (each dim_x x dim_y, rows dim_x floats apart). Only kernels on the compute stream read them, so a replaced or cleared
+    // setting's buffer is retired behind an event recorded there and freed once that event has completed: at a later set / clear,
+    // or at destroy.
+    struct flat_field_t
+    {
+        float* d_ref = nullptr;
+        uint32_t dim_x = 0, dim_y = 0;
+        double t_min = 1.0;
+    } flat_field;
+    std::vector<std::pair<float*, hipEvent_t>> flat_field_retired;
     // K cached by paris_hip_stage_filter (reference: thread_local static in src/filtering.cpp:42)
     float* stage_k = nullptr;
     uint32_t stage_k_size = 0;
@@ -337,7 +348,8 @@ int paris_hip_run_check(paris_hip_ctx* ctx, const std::array<uint32_t, 4>& key, 
                         const void* arg, bool* ok, bool* known);
 int paris_hip_ensure_upload_stream(paris_hip_ctx* ctx); // upload_stream + its event ring
 int paris_hip_ensure_bp_stream(paris_hip_ctx* ctx);     // bp_stream + its events
-// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip: one cheap query per translation unit that makes the
+// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip: one cheap query per
+// translation unit that makes the
 // runtime load its code object now rather than at the first launch
 void paris_hip_warm_backproject();
 void paris_hip_warm_backproject_fused();
@@ -347,10 +359,18 @@ void paris_hip_warm_weight();
 void paris_hip_warm_validate();
 void paris_hip_warm_widen();
 void paris_hip_warm_short_scan();
+void paris_hip_warm_flat_field();
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
 // tail of their float rows (paris_hip_upload_projection_raw)
 int paris_hip_widen_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, int pixel_type);
+// widen.hip: the same pass for any stored type (PARIS_HIP_PIXEL_F32 included), each pixel then corrected with the ctx's dark and flat
+// frames at detector row row0 + r (paris_hip_upload_projection_raw_corrected). PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, for
+// another dim_x or rows outside the setting's.
+int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, int pixel_type,
+                                 uint32_t row0);
+// flat_field.hip: the ctx's reference frames go, their memory freed as soon as no queued work can read them (ctx destroy: at once)
+void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying);
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events
 int paris_hip_take_event(paris_hip_ctx* ctx, hipEvent_t* out);

@@ -12,6 +12,15 @@
 //
 // Memory bound: s bytes read and 4 written per pixel. Conversions: u8 -> v_cvt_f32_ubyte*, u16 -> zero extension + v_cvt_f32_u32,
 // u32 -> v_cvt_f32_u32 (round to nearest even in the default mode) -- static_cast<float>, exactly what the host's conversion does.
+//
+// CORRECT (paris_hip_upload_projection_raw_corrected): the same pass also turns each widened pixel into its line integral with the
+// ctx's dark and flat frames (flat_field_line_integral, flat_field.h), reading them at the pixel's own index of its ABSOLUTE
+// detector row (band row r is detector row row0 + r). The in-place argument above is unchanged: the correction only adds reads
+// of the reference frames, which are separate buffers, and the values stored are still those of the chunk's own pixels, loaded
+// before the barrier. An f32 instantiation exists for this path only: its tail offset is 0, so each lane reads and writes just
+// its own pixels -- trivially in place -- and every stored type takes exactly one pass over the frame. 8 more bytes read per
+// pixel (the 32 MiB references of a 2048^2 detector may stay in the Infinity Cache from frame to frame).
+#include "flat_field.h"
 #include "paris_hip_internal.h"
 
 namespace
@@ -29,8 +38,18 @@ namespace
 
     // vec (uniform per launch): the stored rows start 16-byte aligned and are a whole number of 16-byte vectors: a lane loads 16
     // bytes (16 / s pixels) and stores 16 / s floats as float4s. Otherwise a lane loads and stores one pixel. Same values either way.
-    template <typename T>
-    __global__ void __launch_bounds__(WIDEN_THREADS) widen_rows_kernel(char* d, size_t pitch, uint32_t dim_x, uint32_t dim_y, bool vec)
+    // the reference frames of a CORRECT launch: rows dim_x floats apart, band row r reads detector row row0 + r
+    struct correction
+    {
+        const float* dark = nullptr;
+        const float* flat = nullptr;
+        uint32_t row0 = 0;
+        double t_min = 1.0;
+    };
+
+    template <typename T, bool CORRECT>
+    __global__ void __launch_bounds__(WIDEN_THREADS) widen_rows_kernel(char* d, size_t pitch, uint32_t dim_x, uint32_t dim_y, bool vec,
+                                                                       correction c)
     {
         constexpr uint32_t S = sizeof(T);
         constexpr uint32_t VEC_PIXELS = 16u / S;
@@ -42,6 +61,7 @@ namespace
             char* row = d + static_cast<size_t>(r) * pitch;
             const T* src = reinterpret_cast<const T*>(row + tail);
             float* dst = reinterpret_cast<float*>(row);
+            const size_t ref_row = CORRECT ? static_cast<size_t>(c.row0 + r) * dim_x : 0u;
             for(uint32_t c0 = 0; c0 < dim_x; c0 += chunk) // (uniform trip count: every lane reaches every barrier)
             {
                 const uint32_t j = c0 + threadIdx.x * per_lane;
@@ -56,9 +76,26 @@ namespace
 #pragma unroll
                         for(uint32_t k = 0; k < VEC_PIXELS; ++k)
                             f[k] = static_cast<float>(v[k]);
+                        if constexpr(CORRECT) // (vec: dim_x is a multiple of 4, so the reference rows start on 16 bytes too)
+                        {
+#pragma unroll
+                            for(uint32_t k = 0; k < VEC_PIXELS; k += 4u)
+                            {
+                                const float4 dk = *reinterpret_cast<const float4*>(c.dark + ref_row + j + k);
+                                const float4 fk = *reinterpret_cast<const float4*>(c.flat + ref_row + j + k);
+                                f[k] = flat_field_line_integral(f[k], dk.x, fk.x, c.t_min);
+                                f[k + 1] = flat_field_line_integral(f[k + 1], dk.y, fk.y, c.t_min);
+                                f[k + 2] = flat_field_line_integral(f[k + 2], dk.z, fk.z, c.t_min);
+                                f[k + 3] = flat_field_line_integral(f[k + 3], dk.w, fk.w, c.t_min);
+                            }
+                        }
                     }
                     else
+                    {
                         f[0] = static_cast<float>(src[j]);
+                        if constexpr(CORRECT)
+                            f[0] = flat_field_line_integral(f[0], c.dark[ref_row + j], c.flat[ref_row + j], c.t_min);
+                    }
                 }
                 loads_done_then_barrier();
                 if(live)
@@ -76,14 +113,14 @@ namespace
         }
     }
 
-    template <typename T>
-    int launch(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y)
+    template <typename T, bool CORRECT>
+    int launch(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, const correction& c)
     {
         const dim3 grid(dim_y < WIDEN_MAX_BLOCKS ? dim_y : WIDEN_MAX_BLOCKS);
         char* d = reinterpret_cast<char*>(d_dst);
         // s * dim_x a multiple of 16 (then 4 * dim_x is one as well) and 16-byte aligned rows: every stored row starts on 16 bytes
         const bool vec = (static_cast<size_t>(sizeof(T)) * dim_x) % 16u == 0 && d_pitch % 16u == 0 && reinterpret_cast<uintptr_t>(d) % 16u == 0;
-        hipLaunchKernelGGL(widen_rows_kernel<T>, grid, dim3(WIDEN_THREADS), 0, ctx->stream, d, d_pitch, dim_x, dim_y, vec);
+        hipLaunchKernelGGL((widen_rows_kernel<T, CORRECT>), grid, dim3(WIDEN_THREADS), 0, ctx->stream, d, d_pitch, dim_x, dim_y, vec, c);
         PARIS_HIP_TRY(hipGetLastError());
         return PARIS_HIP_SUCCESS;
     }
@@ -95,9 +132,32 @@ int paris_hip_widen_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint3
         return PARIS_HIP_SUCCESS;
     switch(pixel_type)
     {
-        case PARIS_HIP_PIXEL_U8: return launch<uint8_t>(ctx, d_dst, d_pitch, dim_x, dim_y);
-        case PARIS_HIP_PIXEL_U16: return launch<uint16_t>(ctx, d_dst, d_pitch, dim_x, dim_y);
-        case PARIS_HIP_PIXEL_U32: return launch<uint32_t>(ctx, d_dst, d_pitch, dim_x, dim_y);
+        case PARIS_HIP_PIXEL_U8: return launch<uint8_t, false>(ctx, d_dst, d_pitch, dim_x, dim_y, correction{});
+        case PARIS_HIP_PIXEL_U16: return launch<uint16_t, false>(ctx, d_dst, d_pitch, dim_x, dim_y, correction{});
+        case PARIS_HIP_PIXEL_U32: return launch<uint32_t, false>(ctx, d_dst, d_pitch, dim_x, dim_y, correction{});
+        default: return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    }
+}
+
+int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, int pixel_type,
+                                 uint32_t row0)
+{
+    const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
+    if(ff.d_ref == nullptr || dim_x != ff.dim_x || row0 > ff.dim_y || dim_y > ff.dim_y - row0)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(dim_x == 0 || dim_y == 0)
+        return PARIS_HIP_SUCCESS;
+    correction c;
+    c.dark = ff.d_ref;
+    c.flat = ff.d_ref + static_cast<size_t>(ff.dim_x) * ff.dim_y;
+    c.row0 = row0;
+    c.t_min = ff.t_min;
+    switch(pixel_type)
+    {
+        case PARIS_HIP_PIXEL_U8: return launch<uint8_t, true>(ctx, d_dst, d_pitch, dim_x, dim_y, c);
+        case PARIS_HIP_PIXEL_U16: return launch<uint16_t, true>(ctx, d_dst, d_pitch, dim_x, dim_y, c);
+        case PARIS_HIP_PIXEL_U32: return launch<uint32_t, true>(ctx, d_dst, d_pitch, dim_x, dim_y, c);
+        case PARIS_HIP_PIXEL_F32: return launch<float, true>(ctx, d_dst, d_pitch, dim_x, dim_y, c);
         default: return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     }
 }
@@ -105,5 +165,5 @@ int paris_hip_widen_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint3
 void paris_hip_warm_widen()
 {
     hipFuncAttributes a{};
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&widen_rows_kernel<uint16_t>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&widen_rows_kernel<uint16_t, false>));
 }

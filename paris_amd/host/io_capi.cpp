@@ -38,6 +38,27 @@ int paris_io_his_load(const char* path, uint32_t* n_frames, uint32_t* dim_x, uin
 
 void paris_io_free(void* p) { std::free(p); }
 
+// his::mean_frame: the mean of all frames of a HIS file (dark / flat references); *data receives dim_x*dim_y floats (free with
+// paris_io_free), NULL for a file without frames. Returns 0, or 1 when the file cannot be opened.
+int paris_io_his_mean_frame(const char* path, uint32_t* n_frames, uint32_t* dim_x, uint32_t* dim_y, float** data)
+{
+    try
+    {
+        const auto m = paris::his::mean_frame(path);
+        *n_frames = m.n_frames;
+        *dim_x = m.dim_x;
+        *dim_y = m.dim_y;
+        *data = nullptr;
+        if(m.n_frames != 0)
+        {
+            *data = static_cast<float*>(std::malloc(m.pixels.size() * sizeof(float)));
+            std::memcpy(*data, m.pixels.data(), m.pixels.size() * sizeof(float));
+        }
+        return 0;
+    }
+    catch(const std::exception&) { return 1; }
+}
+
 int paris_io_his_save(const char* path, const float* frames, uint16_t n_frames, uint16_t dim_x, uint16_t dim_y, uint16_t number_type,
                       uint16_t image_header_size)
 {

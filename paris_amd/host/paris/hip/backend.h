@@ -72,6 +72,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <map>
+#include <set>
 #include <memory>
 #include <string>
 #include <vector>
@@ -124,6 +125,7 @@ namespace paris
                 std::map<device_handle, std::unique_ptr<paris_hip_ctx, ctx_deleter>> per_device;
                 paris_hip_ctx* current = nullptr;
                 std::map<const paris_hip_ctx*, short_scan_setting> short_scans; // set_short_scan(), per device of this thread
+                std::set<const paris_hip_ctx*> flat_fields; // set_flat_field(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -219,6 +221,31 @@ namespace paris
                     return nullptr;
                 const auto it = m.find(ctx);
                 return it == m.end() ? nullptr : &it->second;
+            }
+        }
+
+        // Extension (no reference counterpart): the projections of this thread's current device are intensities. Until
+        // clear_flat_field(), paris::weight() first turns each into line integrals with these dark and flat frames (n_row x n_col
+        // floats each, rows n_row apart; dark nullptr = zeros): p = -ln(max((I - D) / (F - D), t_min)), dead pixels 0
+        // (paris_hip_set_flat_field). The library keeps its own copy of the frames.
+        inline auto set_flat_field(const float* dark, const float* flat, std::uint32_t n_row, std::uint32_t n_col, float t_min = 1e-5f) -> void
+        {
+            detail::runtime_check(paris_hip_set_flat_field(current_ctx(), dark, flat, n_row, n_col, t_min), "set_flat_field()");
+            detail::state().flat_fields.insert(current_ctx());
+        }
+
+        inline auto clear_flat_field() -> void
+        {
+            detail::runtime_check(paris_hip_clear_flat_field(current_ctx()), "clear_flat_field()");
+            detail::state().flat_fields.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_flat_field(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().flat_fields;
+                return !s.empty() && s.count(ctx) != 0u;
             }
         }
 

@@ -9,6 +9,7 @@
 #define PARIS_AMD_HOST_HIS_H_
 
 #include <cerrno>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -279,6 +280,43 @@ namespace paris
                 frames.push_back(std::move(fr));
             }
             return frames;
+        }
+
+        // Extension: the mean of all frames of a HIS file (dark and flat reference files): every frame as load() gives it (f64 as
+        // f32), summed in double in frame order and divided by the count, rounded once to fp32. An unopenable file throws (reader);
+        // a file without frames gives n_frames = 0 and no pixels.
+        struct mean
+        {
+            std::vector<float> pixels; // dim_x fastest
+            std::uint32_t dim_x = 0, dim_y = 0, n_frames = 0;
+        };
+
+        inline auto mean_frame(const std::string& path) -> mean
+        {
+            auto out = mean{};
+            auto r = reader{path};
+            auto sum = std::vector<double>{};
+            auto fr = std::vector<float>{};
+            while(r.advance())
+            {
+                const auto n = static_cast<std::size_t>(r.dim_x()) * r.dim_y();
+                if(out.n_frames == 0)
+                {
+                    out.dim_x = r.dim_x();
+                    out.dim_y = r.dim_y();
+                    sum.assign(n, 0.0);
+                    fr.resize(n);
+                }
+                std::fill(fr.begin(), fr.end(), 0.f);
+                r.read_rows(fr.data(), 0, out.dim_y);
+                for(std::size_t i = 0; i < n; ++i)
+                    sum[i] += static_cast<double>(fr[i]);
+                ++out.n_frames;
+            }
+            out.pixels.resize(sum.size());
+            for(std::size_t i = 0; i < sum.size(); ++i)
+                out.pixels[i] = static_cast<float>(sum[i] / out.n_frames);
+            return out;
         }
 
         // Writer for synthetic projection sets (no reference counterpart; produces what load() accepts).

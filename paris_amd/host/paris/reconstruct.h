@@ -83,6 +83,12 @@ namespace paris
         // angle of the frames the run uses, before any device work (detail::derive_short_scan)
         bool short_scan = false;
         paris_short_scan scan{};
+        // dark / flat correction of intensity frames to line integrals (extension): --flat / --dark name HIS files whose frames are
+        // averaged into one reference frame each by run(), before any device work (detail::load_flat_field); every device ctx gets
+        // them and uploads frames through paris_hip_upload_projection_raw_corrected
+        std::string flat_path, dark_path;
+        float t_min = 1e-5f;
+        std::shared_ptr<const his::mean> flat, dark; // filled by run(); dark may stay empty (a zero dark)
     };
 
     // src/task.h:33-57
@@ -243,7 +249,9 @@ namespace paris
             const auto slots = static_cast<std::size_t>(shape.first) * shape.second;
             const auto row = (static_cast<std::size_t>(po.det_geo.n_row) * sizeof(float) + 255u) / 256u * 256u;
             const auto half_row = (static_cast<std::size_t>(po.det_geo.n_row) * 2u + 255u) / 256u * 256u;
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes;
+            // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
+            const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references;
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -548,6 +556,16 @@ namespace paris
         const auto t_setup = clock::now();
         paris_hip_ctx* ctx = nullptr;
         rt(paris_hip_ctx_create(device, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()"); // :87
+        if(po.flat)
+        {
+            const int rc = paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row,
+                                                    po.det_geo.n_col, po.t_min);
+            if(rc != PARIS_HIP_SUCCESS)
+            {
+                paris_hip_ctx_destroy(ctx);
+                rt(rc, "set_flat_field()");
+            }
+        }
 
         // Projections travel in groups: a group of `batch` frames is converted, uploaded, weighted and filtered one by one,
         // then backprojected with ONE fused launch (paris_hip_backproject_batch[_f16]: bit-identical to the sequence, the slab
@@ -706,6 +724,8 @@ namespace paris
                 // buffers keep their full size, rows outside the band are never read for a voxel of the slab
                 // The rows arrive as stored (u8 / u16 / u32 / f32; f64 as f32): the upload carries those bytes and the device widens them
                 // (paris_hip_upload_projection_raw, bit for bit the host's conversion). A slot keeps room for 4 bytes per pixel.
+                // With --flat the same pass corrects them to line integrals with the reference rows of their absolute detector rows
+                // (paris_hip_upload_projection_raw_corrected): the short-scan weight and the weight + filter see line integrals.
                 const auto next_frame = [&](float* dst) {
                     return shared ? shared->next_raw(cur, dst, n_row, n_col, band_first, band_count)
                                   : own->next_raw(dst, n_row, n_col, band_first, band_count); // :100, straight into pinned memory
@@ -743,8 +763,12 @@ namespace paris
                     if(band_count != 0)
                     {
                         // :101 -- on the upload stream, overlapping the kernels of the previous projections
-                        rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px, n_row,
-                                                           band_count, p.pixel), "load()");
+                        if(po.flat)
+                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_buf[slot], d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off,
+                                                                         n_row * px, n_row, n_col, band_first, band_count, p.pixel), "load()");
+                        else
+                            rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
+                                                               n_row, band_count, p.pixel), "load()");
                         rep.h2d_bytes += static_cast<std::uint64_t>(band_count) * n_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
                         if(po.short_scan && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
@@ -811,6 +835,7 @@ namespace paris
         double rows_per_pass = 0.0;   // several devices: detector rows the slabs of one pass need between them, in detectors
         std::vector<std::string> skipped;                  // several devices: invalid files skipped by the shared source
         int batch = 0; // frames per fused launch actually used (program_options::batch, halved until the slots fit the devices)
+        std::uint32_t flat_frames = 0, dark_frames = 0; // --flat / --dark: frames averaged into the reference frames (0: no correction)
         double wall_s = 0;
         std::string output_file;
     };
@@ -845,6 +870,48 @@ namespace paris
             }
             return scan;
         }
+
+        // --flat / --dark: each file's frames averaged into one reference frame (his::mean_frame), refused here -- before any device
+        // work -- when the file cannot be read or holds no frames, when its frames are not the detector's size, when it lies inside
+        // --input (it would be read as a projection too), or when t_min is outside (0, 1]
+        inline auto load_reference(const std::string& option, const std::string& path, const program_options& po) -> std::shared_ptr<const his::mean>
+        {
+            char in_dir[PATH_MAX], file[PATH_MAX];
+            if(::realpath(path.c_str(), file) == nullptr)
+                throw stage_construction_error{option + " " + path + ": no such file"};
+            if(::realpath(po.input_path.c_str(), in_dir) != nullptr)
+            {
+                const auto dir = std::string{in_dir} + "/";
+                if(std::string{file}.compare(0, dir.size(), dir) == 0)
+                    throw stage_construction_error{option + " " + path + " lies inside --input " + po.input_path
+                                                   + ": it would be read as a projection as well"};
+            }
+            auto m = std::make_shared<his::mean>();
+            try { *m = his::mean_frame(path); }
+            catch(const std::system_error&) { throw stage_construction_error{option + " " + path + ": cannot open the file"}; }
+            if(m->n_frames == 0)
+                throw stage_construction_error{option + " " + path + ": the file holds no frames"};
+            if(m->dim_x != po.det_geo.n_row || m->dim_y != po.det_geo.n_col)
+                throw stage_construction_error{option + " " + path + ": its frames are " + std::to_string(m->dim_x) + " x " + std::to_string(m->dim_y)
+                                               + " pixels, the geometry's detector is " + std::to_string(po.det_geo.n_row) + " x "
+                                               + std::to_string(po.det_geo.n_col)};
+            return m;
+        }
+
+        inline auto load_flat_field(program_options& po) -> void
+        {
+            if(po.flat_path.empty())
+            {
+                if(!po.dark_path.empty())
+                    throw stage_construction_error{"--dark needs --flat: a dark frame alone does not make line integrals"};
+                return;
+            }
+            if(!(po.t_min > 0.f && po.t_min <= 1.f))
+                throw stage_construction_error{"--min-transmission " + std::to_string(po.t_min) + " is outside (0, 1]"};
+            po.flat = load_reference("--flat", po.flat_path, po);
+            if(!po.dark_path.empty())
+                po.dark = load_reference("--dark", po.dark_path, po);
+        }
     }
 
     // src/main.cpp:120-178
@@ -853,6 +920,9 @@ namespace paris
         auto po = requested; // batch may shrink to fit the devices' memory (detail::fit_batch)
         auto r = run_report{};
         const auto start = detail::clock::now();
+        detail::load_flat_field(po);
+        r.flat_frames = po.flat ? po.flat->n_frames : 0u;
+        r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         if(po.short_scan)
             po.scan = detail::derive_short_scan(po);
         r.vol_geo = calculate_volume_geometry(po.det_geo); // :122
