@@ -2,6 +2,12 @@
 """Benchmark of the FDK hot path (weight -> ramp row filter -> backproject) on MI355X.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W --full   ... and every leg beside the headline (FULL_LEGS)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its one JSON line; at N > 1 the job still
+ends with its one collective (--final-gather). Everything else the line can carry -- the live counter passes, the skip-off step,
+the fused and deferred legs, the CPU baselines, the other workloads, PARIS's own loop -- runs with --full, or when its own option
+asks for it.
 
 Metric (BASELINE.json): GVoxel-updates/s = voxels x projections / seconds / 1e9, whole job over all N GPUs.
 A step is one pass of the hot path over one batch of synthetic projections: for each projection a device copy of
@@ -24,7 +30,7 @@ The JSON line also carries
                 one pass over the projection) / average launch duration from HIP events recorded on the launch
                 stream inside the timed region, against the 8 TB/s HBM3E peak;
   cpu_baseline  the CPU oracle (this repo's restatement of the reference's OpenMP path, "port") timed on this
-                host's cores on a bounded sample of the same workload (rank 0, N = 1 only).
+                host's cores on a bounded sample of the same workload (rank 0, N = 1 only; --full).
 """
 import argparse
 import json
@@ -172,7 +178,7 @@ def other_workloads(common_tail):
         t0 = time.perf_counter()
         try:
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + common_tail
-                               + ["--cpu-budget", "0", "--cpu-c1", "0", "--live-traffic", "0", "--workloads", "0", "--paris-loop", "0"],
+                               + ["--full", "--cpu-budget", "0", "--cpu-c1", "0", "--live-traffic", "0", "--workloads", "0", "--paris-loop", "0"],
                                cwd=ROOT, env=env, capture_output=True, text=True, timeout=150)  # (2-10 s each; bounded)
             lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not lines:
@@ -572,6 +578,26 @@ def launch_ranks(args, argv, grace=120.0, _cmd=None):
     return rc
 
 
+# the legs beside the headline: option -> (value with --full, value of a plain run). An option given on the command line wins either way
+FULL_LEGS = {
+    "live_traffic": (1, 0),
+    "noskip_step": (1, 0),
+    "fused_steps": (8, 0),
+    "cpu_budget": (15.0, 0.0),
+    "cpu_c1": (1, 0),
+    "workloads": (1, 0),
+    "paris_loop": (1, 0),
+}
+
+
+def resolve_legs(args):
+    """fills in every FULL_LEGS option the command line left unset (None), from --full"""
+    for name, (full, plain) in FULL_LEGS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
+    return args
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -580,15 +606,15 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--batch", type=int, default=0, help="projections per step; 0 (default) = ceil(n_proj / steps), i.e. the "
                     "timed steps are the whole job")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline (0 disables)")
+    ap.add_argument("--cpu-budget", type=float, default=None, help="seconds of CPU baseline (0 disables; --full: 15)")
     ap.add_argument("--vx", type=int, default=0)
     ap.add_argument("--unroll", type=int, default=0)
     ap.add_argument("--tz", type=int, default=0)
     ap.add_argument("--lds-bytes", type=int, default=0)
     ap.add_argument("--variant", type=int, default=0, help="backprojection kernel variant (0: default; 5: two-pass, column constants precomputed per projection)")
     ap.add_argument("--order", type=int, default=-1, help="workgroup -> tile order of the backprojection kernel (-1: the library's default)")
-    ap.add_argument("--fused-steps", type=int, default=8, help="extra steps with the fused multi-projection kernel, "
-                    "reported as fused_extension next to the headline (0 disables); the steps are spread over the circle")
+    ap.add_argument("--fused-steps", type=int, default=None, help="extra steps with the fused multi-projection kernel, "
+                    "reported as fused_extension next to the headline (0 disables; --full: 8); the steps are spread over the circle")
     ap.add_argument("--fused-batch", type=int, default=48, help="projections per fused launch in fused_extension and "
                     "deferred_boundary (2..64; the headline step keeps single-projection launches)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL; default) or gloo (rehearsal of the N > 1 path "
@@ -606,9 +632,9 @@ def main():
                     "the bench stream: copy + weight/filter + backproject of all its projections, angles baked in) before the timed "
                     "region and replayed inside it -- for the launch-bound small configurations; kernel times then come from a "
                     "separate eager pass (events cannot be read back from a captured stream)")
-    ap.add_argument("--noskip-step", type=int, default=1, help="1 (default): after the timed region, one more step with "
+    ap.add_argument("--noskip-step", type=int, default=None, help="1 (--full): after the timed region, one more step with "
                     "paris_hip_set_backproject_skip_invalid(0), reported as roofline.frac_without_skip")
-    ap.add_argument("--cpu-c1", type=int, default=1, help="1 (default, N = 1 only): also time the oracle on the whole BASELINE "
+    ap.add_argument("--cpu-c1", type=int, default=None, help="1 (--full, N = 1 only): also time the oracle on the whole BASELINE "
                     "config-1 job (cpu_baseline_c1, a few seconds of CPU work plus ~20 s of frame synthesis)")
     ap.add_argument("--filter-batch", type=int, default=1, help="fused_extension leg: 1 (default) = the group's frames are weighted and "
                     "filtered by one launch (paris_hip_stage_weight_filter_batch), 0 = one launch per frame")
@@ -619,7 +645,7 @@ def main():
                     "fused launches of deferred calls on the ctx's second stream beside the next group's copies and filters "
                     "(paris_hip_set_backproject_overlap); 0 (the bare library's default) = on the ctx stream. Config 1: 920 -> 1040-1050 "
                     "GVox/s, configs 2-5 within noise (profiles/r04_ab_overlap_c1.txt, r04_ab_overlap_resident_c2.txt)")
-    ap.add_argument("--live-traffic", type=int, default=1, help="1 (default; N = 1, config 3 only): roofline.traffic is measured in this "
+    ap.add_argument("--live-traffic", type=int, default=None, help="1 (--full; N = 1, config 3 only): roofline.traffic is measured in this "
                     "run -- before the GPU is touched, two child runs of this script under `rocprofv3 --pmc FETCH_SIZE` / `WRITE_SIZE` add 16 "
                     "projections spread over the circle each (about 20 s per pass); 0: the newest matching record under profiles/")
     ap.add_argument("--spread", type=int, default=0, help="1: with a partial job (--batch), the timed projections are spread evenly "
@@ -631,7 +657,7 @@ def main():
     ap.add_argument("--deferred-leg", type=int, default=1, help="0: the fused extension without the deferred_boundary leg -- every "
                     "bp_fused_kernel launch of the run then adds exactly --fused-batch projections (counter passes normalise per launch; "
                     "the deferred leg's first groups are launched early, after 8, 16 and 32 calls)")
-    ap.add_argument("--workloads", type=int, default=1, help="1 (default; N = 1, the whole config-3 job only): after the headline's "
+    ap.add_argument("--workloads", type=int, default=None, help="1 (--full; N = 1, the whole config-3 job only): after the headline's "
                     "measurements the other BASELINE configs are run as child processes and summarised under `workloads` "
                     "(config 1, config 2, config 4's slab shape, config 5 sampled)")
     ap.add_argument("--as-world", type=int, default=0, help="rehearsal of a larger job on fewer processes (the GPU pool allows at "
@@ -643,11 +669,13 @@ def main():
                     "of the volume (the reference's split rule), i.e. the slab checksums an N-rank run of the same projections must reproduce")
     ap.add_argument("--dist-timeout", type=float, default=240.0, help="seconds a rank waits in the rendezvous (init_process_group) "
                     "before it gives up: one dead rank ends the run instead of hanging the others until the caller's limit")
-    ap.add_argument("--paris-loop", type=int, default=1, help="1 (default; N = 1, the whole config-3 job only): PARIS's own per-projection "
+    ap.add_argument("--paris-loop", type=int, default=None, help="1 (--full; N = 1, the whole config-3 job only): PARIS's own per-projection "
                     "loop through the C++ mirror (paris_hip_demo, child processes) is timed for four jobs and reported as `paris_loop`")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path computed (the "
                     "volume, as a fixed sample, and the last filtered projection) as DIR/<name>.npy: see dump_outputs()")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline that its option leaves unset, at the "
+                    "value FULL_LEGS gives it (a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line)")
+    args = resolve_legs(ap.parse_args())
     if args.steps < 1:
         ap.error("--steps must be at least 1")
 

@@ -21,7 +21,7 @@ def last_json_line(text):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1", "--full",
                         "--cpu-budget", "2", "--fused-steps", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr
     d = last_json_line(r.stdout)
@@ -59,6 +59,22 @@ def test_single_gpu_line():
     legs = d["legs_seconds"]
     assert legs["total"] > legs["timed_region"] > 0 and "cpu_baselines" in legs and "setup_and_warmup" in legs
     assert abs(sum(v for k, v in legs.items() if k != "total") - legs["total"]) < 0.2
+
+
+def test_plain_line_is_the_headline_alone():
+    """Without --full a run sets up, warms up, times its steps and prints its line: the headline's keys and the roofline of the
+    timed launches are there, and no leg beside them ran."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    d = last_json_line(r.stdout)
+    for k in REQUIRED:
+        assert k in d, k
+    for k in ("cpu_baseline", "cpu_baseline_c1", "fused_extension", "deferred_boundary", "workloads", "paris_loop", "final_gather"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["config"]["projections_timed"] == 360
+    rf = d["roofline"]
+    assert rf["launches_timed"] == 360 and rf["traffic_measured_in_this_run"] is False and "frac_without_skip" not in rf
 
 
 def test_dump_outputs_are_the_timed_paths_and_repeat(tmp_path):
@@ -253,7 +269,7 @@ def test_plain_command_line_over_rccl_needs_a_gpu_per_rank():
 
 
 def test_config3_line_measures_its_traffic_in_the_run():
-    """The driver's own invocation is config 3 at N = 1: before it touches the GPU, bench.py runs child passes of itself under
+    """With --full, config 3 at N = 1: before it touches the GPU, bench.py runs child passes of itself under
     `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU: one counter per pass) and reports the HBM bytes per launch and the
     fused kernel's instructions per voxel-update measured there. A short job here (4 timed projections); the counter passes are
     the real ones."""
@@ -261,7 +277,8 @@ def test_config3_line_measures_its_traffic_in_the_run():
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--batch", "4", "--spread", "1",
-                        "--cpu-budget", "0", "--cpu-c1", "0", "--fused-steps", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--cpu-budget", "0", "--cpu-c1", "0", "--fused-steps", "1"], capture_output=True, text=True, timeout=900,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json_line(r.stdout)
     rf = d["roofline"]
@@ -334,12 +351,13 @@ def test_eight_slab_partition_at_full_shape(workload, gather):
 
 
 def test_default_run_reports_every_baseline_config():
-    """the driver's invocation (config 3, whole job, N = 1) ends with a `workloads` object -- config 1 and 2 as
+    """the --full run of config 3 (whole job, N = 1) ends with a `workloads` object -- config 1 and 2 as
     whole jobs, config 4's slab shape as a whole job, config 5 sampled over the circle -- each with the headline's figures, from
     fresh child runs -- and with `paris_loop`, PARIS's per-projection loop through paris::hip for four jobs. (CPU legs and the live
     counter passes are switched off here: they have tests of their own.)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--cpu-budget", "0", "--cpu-c1", "0",
-                        "--live-traffic", "0", "--fused-steps", "1", "--noskip-step", "0"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--full", "--cpu-budget", "0",
+                        "--cpu-c1", "0", "--live-traffic", "0", "--fused-steps", "1", "--noskip-step", "0"], capture_output=True, text=True,
+                       timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json_line(r.stdout)
     assert d["config"]["whole_job"] is True and d["config"]["projections_timed"] == 1440

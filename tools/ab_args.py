@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved same-device A/B of bench.py argument sets (and optionally library builds): R rounds over all configurations in
 one GPU call, one line per run. The only comparison that survives the +-3 % spread between the boxes of the pool.
+Every run has --full: the skip-off, fused and deferred figures it prints come from the legs beside the headline.
 
   python tools/ab_args.py [--rounds 2] [--common "--steps 10 --warmup 2"] "<args of config A>" "<args of config B>" ...
 
@@ -39,7 +40,7 @@ try:
                     env[k] = v
                 words = words[1:]
             shutil.copy(lib, LIB)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + shlex.split(args.common) + words,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + shlex.split(args.common) + words,
                                capture_output=True, text=True, cwd=ROOT, env=env)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not line:

@@ -14,7 +14,7 @@ trap 'cp /tmp/ab_lib_keep.so paris_amd/lib/libparis_hip.so' EXIT
 for rep in 1 2; do
   for lib in "${libs[@]}"; do
     cp "$lib" paris_amd/lib/libparis_hip.so
-    python bench.py --steps 8 --warmup 2 --cpu-budget 0 "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 8 --warmup 2 --cpu-budget 0 "$@" 2>/dev/null | python -c "
 import json, sys
 j = json.loads(sys.stdin.readline())
 f = j.get('fused_extension', {})

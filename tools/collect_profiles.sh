@@ -12,8 +12,8 @@ export TMPDIR=/tmp
 run() { echo "== $*" >&2; "$@"; }
 # 1. counters first: bench.py's roofline.traffic and fused_extension.roofline read the newest records under profiles/
 #    (one --pmc pass each, nothing else traced); kernel times for the derived figures come from an unprofiled run
-run python bench.py --steps 8 --warmup 2 --cpu-budget 0 --cpu-c1 0 --live-traffic 0 --workloads 0 --paris-loop 0 > $out/quick.json
-A="--steps 1 --warmup 1 --batch 16 --spread 1 --cpu-budget 0 --cpu-c1 0 --noskip-step 0 --live-traffic 0"  # 16 timed launches that sample the whole circle
+run python bench.py --full --steps 8 --warmup 2 --cpu-budget 0 --cpu-c1 0 --live-traffic 0 --workloads 0 --paris-loop 0 > $out/quick.json
+A="--full --steps 1 --warmup 1 --batch 16 --spread 1 --cpu-budget 0 --cpu-c1 0 --noskip-step 0 --live-traffic 0"  # 16 timed launches that sample the whole circle
 run rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/prof_fetch -- python3 bench.py $A > /dev/null
 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/prof_write -- python3 bench.py $A > /dev/null
 python tools/pmc_traffic.py $out/prof_fetch $out/prof_write "2048^3 volume, 1440 projections @ 2048x2048 fp32" $out/${tag}_pmc_traffic_c3.json
@@ -27,17 +27,17 @@ python tools/pmc_wait.py $out/pmc_w1 $out/pmc_sq_a $out/quick.json > $out/${tag}
 cp $out/${tag}_pmc_traffic_c3.json $out/${tag}_pmc_sq_counters_c3.json $out/${tag}_pmc_wave_states_c3.json profiles/
 echo "counters done" >&2
 # 2. the bench lines
-run python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_c3.json
-run python bench.py --steps 20 --warmup 5 --workload c3 --slices 256 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c4_slab_shape_1gpu.json
-run python bench.py --steps 20 --warmup 5 --workload c2 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c2_1gpu.json
-run python bench.py --steps 20 --warmup 5 --workload c1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c1_1gpu.json
-run python bench.py --steps 20 --warmup 5 --workload c1 --graph 1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c1_graph_1gpu.json
-run python bench.py --steps 20 --warmup 5 --workload c5 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c5_1gpu.json
+run python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_c3.json
+run python bench.py --full --steps 20 --warmup 5 --workload c3 --slices 256 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c4_slab_shape_1gpu.json
+run python bench.py --full --steps 20 --warmup 5 --workload c2 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c2_1gpu.json
+run python bench.py --full --steps 20 --warmup 5 --workload c1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c1_1gpu.json
+run python bench.py --full --steps 20 --warmup 5 --workload c1 --graph 1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c1_graph_1gpu.json
+run python bench.py --full --steps 20 --warmup 5 --workload c5 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c5_1gpu.json
 # config 5 without the ROI crop: rank 3's 4096 x 4096 x 512 slab of the 8-GPU job over the whole 4096^3 grid, 360 launches over the circle
-run python bench.py --steps 10 --warmup 1 --workload c5u --as-world 8 --as-rank-base 3 --batch 36 --spread 1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c5_uncropped_slab.json
+run python bench.py --full --steps 10 --warmup 1 --workload c5u --as-world 8 --as-rank-base 3 --batch 36 --spread 1 --cpu-budget 0 --cpu-c1 0 > $out/${tag}_bench_c5_uncropped_slab.json
 echo "benches done" >&2
 # 3. the same default command under the profiler (kernel trace only)
-run rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 20 --warmup 5 --cpu-budget 0 --cpu-c1 0 --live-traffic 0 > $out/${tag}_bench_under_rocprof_c3.json
+run rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 20 --warmup 5 --cpu-budget 0 --cpu-c1 0 --live-traffic 0 > $out/${tag}_bench_under_rocprof_c3.json
 cp $(ls $out/stats/*/*_kernel_stats.csv | head -1) $out/${tag}_kernel_stats_bench_c3_whole_job.csv
 echo "kernel stats done" >&2
 # 4. PARIS's own per-projection loop through the C++ mirror paris::hip, whole circles (tools/demo_bench.py), and the device timeline
