@@ -466,6 +466,26 @@ int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitc
 int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
                                       const paris_detector_geometry* det_geo, const paris_short_scan* scan, uint32_t idx,
                                       int enable_angles, float phi);
+/* Extension (no reference counterpart): offset detectors (half fan, extended field of view) over a full circle. The detector is
+ * shifted sideways (delta_s) so that it covers the rotation axis and one side further than the other; in the backprojector's
+ * coordinates it spans [-t_half, n_row l - t_half], t_half = n_row l / 2 + delta_s l, l = l_px_row, and the rays within the overlap
+ * |t| < tau = min(t_half, n_row l - t_half) = (n_row / 2 - |delta_s|) l are measured twice per circle, the others once.
+ * Host only. gamma_tau_deg (may be NULL) receives the overlap half-angle atan(tau / d_sd) in degrees, for refused geometries too.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT when tau < 2 l (the central ray misses the detector or lies within 2 pixels of its edge), for
+ * n_row == 0, l_px_row <= 0, d_sd = |d_so| + |d_od| <= 0 or a value that is not finite. A centred detector is accepted: the weight
+ * is valid there, only pointless. */
+int paris_hip_offset_detector_check(const paris_detector_geometry* det_geo, float* gamma_tau_deg);
+/* Wang's redundancy weighting: every row in [row_first, row_first + row_count) of n_frames projections frame_stride bytes apart has
+ * column i multiplied by 2 w(x_i), x_i = sigma gamma_i / gamma_tau, gamma_i = atan(t_i / d_sd), sigma = +1 for delta_s <= 0 and -1
+ * otherwise: 2 w = 2 for x >= 1, 2 sin^2(pi/4 (1 + x)) for -1 < x < 1, 0 for x <= -1 (DESIGN.md "Offset detectors"). Columns at t and
+ * -t add up to 2; beyond the overlap a pixel becomes exactly 2 p. The weight does not depend on the angle. Call it on the raw frame
+ * of a full-circle scan, before the cosine weighting; dim_x must equal det_geo->n_row. Runs the check above. */
+int paris_hip_offset_detector_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                          uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
+                                          const paris_detector_geometry* det_geo);
+/* The same for one whole projection */
+int paris_hip_stage_offset_detector_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
+                                           const paris_detector_geometry* det_geo);
 /* Extension (no reference counterpart): dark / flat ("offset / gain") correction of intensity frames to line integrals. With I a
  * pixel as fp32 and D, F the dark and flat reference pixels of the same detector row and column, in double, rounded once:
  *   p = -ln(max((I - D) / (F - D), t_min))   when I, D and F are finite and F - D > 0,   p = 0 otherwise (dead pixel).

@@ -157,6 +157,9 @@ SIGNATURES = {
                                                    _P(_f)]),
     "paris_hip_stage_short_scan_weight": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _P(DetectorGeometry), _P(ShortScan), _u32, C.c_int,
                                                     _f]),
+    "paris_hip_offset_detector_check": (C.c_int, [_P(DetectorGeometry), _P(_f)]),
+    "paris_hip_offset_detector_weight_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32, _P(DetectorGeometry)]),
+    "paris_hip_stage_offset_detector_weight": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _P(DetectorGeometry)]),
     "paris_hip_stage_backproject": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _u32, _f, _vp, _u32, _u32, _u32, _u32,
                                               _P(DetectorGeometry), _P(VolumeGeometry), C.c_int, C.c_int,
                                               _P(RegionOfInterest)]),

@@ -18,7 +18,7 @@ from ._lib import (DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan,
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
-           "backproject", "short_scan_check"]
+           "backproject", "short_scan_check", "offset_detector_check"]
 
 
 class Projection:
@@ -322,6 +322,14 @@ class Backend:
                                                        phis.ctypes.data_as(C.POINTER(C.c_float))),
               "paris_hip_short_scan_weight_rows")
 
+    def offset_detector_weight(self, p, det_geo, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """Redundancy weighting of an offset-detector (half-fan) full circle (paris_hip_offset_detector_weight_rows), on the raw
+        frame before weight(): rows [row_first, row_first + row_count) of each column i of n_frames frames frame_stride bytes
+        apart, starting at p, are multiplied by 2 w(gamma_i); the weight does not depend on the angle."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_offset_detector_weight_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first,
+                                                            count, C.byref(det_geo)), "paris_hip_offset_detector_weight_rows")
+
     def make_filter(self, size, tau, window=0):
         """backend::make_filter (src/openmp/filtering.cpp:139-165); window 1 = Shepp-Logan (extension)"""
         ptr = C.c_void_p()
@@ -583,6 +591,21 @@ def stage_short_scan_weight(backend, p, det_geo, scan, enable_angles=False):
         scan = ShortScan(*scan)
     check(backend._L.paris_hip_stage_short_scan_weight(backend._ctx, p.ptr, p.pitch, p.dim_x, p.dim_y, C.byref(det_geo), C.byref(scan),
                                                        p.idx, int(bool(enable_angles)), p.phi), "paris_hip_stage_short_scan_weight")
+
+
+def offset_detector_check(det_geo):
+    """gamma_tau in degrees -- the half-angle of the overlap |t| < tau = (n_row / 2 - |delta_s|) l_px_row that an offset detector
+    measures twice per circle (paris_hip_offset_detector_check); raises ParisHipError when tau < 2 l_px_row or the geometry is
+    degenerate or not finite"""
+    g = C.c_float()
+    check(_lib.load().paris_hip_offset_detector_check(C.byref(det_geo), C.byref(g)), "paris_hip_offset_detector_check")
+    return g.value
+
+
+def stage_offset_detector_weight(backend, p, det_geo):
+    """The offset-detector redundancy weight of one whole projection (paris_hip_stage_offset_detector_weight)"""
+    check(backend._L.paris_hip_stage_offset_detector_weight(backend._ctx, p.ptr, p.pitch, p.dim_x, p.dim_y, C.byref(det_geo)),
+          "paris_hip_stage_offset_detector_weight")
 
 
 def slab_row_band(det_geo, vol_geo, v_dim_x, v_dim_y, v_dim_z, v_offset=0, roi=None):

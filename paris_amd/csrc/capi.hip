@@ -106,7 +106,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_weight();
             paris_hip_warm_validate();
             paris_hip_warm_widen();
-            paris_hip_warm_short_scan();
+            paris_hip_warm_redundancy_weights();
             paris_hip_warm_flat_field();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first

@@ -358,7 +358,7 @@ void paris_hip_warm_filter_fused();
 void paris_hip_warm_weight();
 void paris_hip_warm_validate();
 void paris_hip_warm_widen();
-void paris_hip_warm_short_scan();
+void paris_hip_warm_redundancy_weights(); // short_scan.hip: the Parker and offset-detector kernels
 void paris_hip_warm_flat_field();
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the

@@ -1,5 +1,7 @@
-// Parker redundancy weighting of short scans for gfx950.
+// Redundancy weights for gfx950: Parker's for short scans and Wang's for offset detectors. Both multiply each column of a raw
+// frame by twice a weight of that column's ray, before the cosine weighting, and share one launch scaffold (weight_columns).
 //
+// Short scans.
 // A short scan covers [start, start + range] in the projection angle phi (the angle the backprojection uses), with
 // pi + 2 gamma_m <= range <= 2 pi. The ray of column i at phi has fan angle gamma_i = atan(t_i / d_sd) in the
 // backprojector's coordinates, t_i = (i + 1/2) l_px_row - n_row l_px_row / 2 - delta_s l_px_row, and direction angle phi +
@@ -18,6 +20,18 @@
 // rounded once: near the smallest valid range the ramps of the outermost columns are a fraction of a milliradian wide, and
 // the fp32 rounding of gamma or beta would be magnified by (pi / 4) / (delta -+ gamma). In the middle region the factor is
 // exactly 2.0f. Memory bound: 8 B per pixel (one read, one write).
+//
+// Offset detectors (half fan). The detector covers [-t_half, n_row l_px_row - t_half] in t, so the rays within the overlap
+// |t| < tau = min(t_half, n_row l_px_row - t_half) are measured twice per circle and the others once. With gamma_tau =
+// atan(tau / d_sd), sigma = +1 when the detector reaches further to +t (delta_s <= 0, else -1) and x = sigma gamma_i / gamma_tau:
+//
+//   2 w = 2                          x >= 1       (the long side: measured once)
+//   2 w = 2 sin^2(pi/4 (1 + x))      -1 < x < 1   (the overlap)
+//   2 w = 0                          x <= -1
+//
+// The weights of t and -t add up to 2, and the conjugate of (phi, gamma) is (phi + pi + 2 gamma, -gamma), so a full circle
+// counts every ray once; the factor 2 again cancels the backprojection's 0.5. The weight does not depend on the angle. It is
+// formed per column in double and rounded once, like Parker's.
 #include <cmath>
 
 #include "paris_hip_internal.h"
@@ -69,6 +83,32 @@ namespace
             frame[static_cast<size_t>(t) * pitch_f + s] *= w2;
     }
 
+    // 2 w of the offset-detector table above, x = sigma gamma / gamma_tau
+    __device__ inline float twice_offset_weight(double x)
+    {
+        if(x >= 1.0)
+            return 2.f;
+        if(!(x > -1.0))
+            return 0.f;
+        const double s = sin(M_PI_4 * (1.0 + x));
+        return static_cast<float>(2.0 * s * s);
+    }
+
+    // grid: as short_scan_kernel's; one weight per column for every frame
+    __global__ void __launch_bounds__(SS_THREADS)
+        offset_detector_kernel(char* p, size_t frame_stride, uint32_t pitch_f, uint32_t dim_x, uint32_t row_first, uint32_t row_end,
+                               double t_half, double l_px_row, double d_sd, double sigma, double gamma_tau)
+    {
+        const uint32_t s = blockIdx.x * SS_THREADS + threadIdx.x;
+        if(s >= dim_x)
+            return;
+        const double t_s = (static_cast<double>(s) + 0.5) * l_px_row - t_half;
+        const float w2 = twice_offset_weight(sigma * atan(t_s / d_sd) / gamma_tau);
+        float* frame = reinterpret_cast<float*>(p + static_cast<size_t>(blockIdx.z) * frame_stride);
+        for(uint32_t t = row_first + blockIdx.y; t < row_end; t += gridDim.y)
+            frame[static_cast<size_t>(t) * pitch_f + s] *= w2;
+    }
+
     // d_sd and the two terms of t_i that do not depend on i, in double (the same statement as the check and the tests)
     struct column_geometry
     {
@@ -106,6 +146,69 @@ namespace
         *delta = d;
         return PARIS_HIP_SUCCESS;
     }
+
+    // the offset detector's overlap: sigma (+1: the detector reaches further to +t) and gamma_tau, or an error for a geometry
+    // whose central ray misses the detector or lies within 2 pixels of its edge (tau < 2 l_px_row)
+    struct overlap
+    {
+        double tau, gamma_tau, sigma;
+    };
+
+    overlap overlap_of(const paris_detector_geometry& det)
+    {
+        const column_geometry c = columns_of(det);
+        const double tau = std::min(c.t_half, static_cast<double>(det.n_row) * c.l_px_row - c.t_half);
+        return {tau, std::atan(tau / c.d_sd), det.delta_s <= 0.f ? 1.0 : -1.0};
+    }
+
+    int check_offset_detector(const paris_detector_geometry* det, overlap* o)
+    {
+        if(det == nullptr || det->n_row == 0)
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        const column_geometry c = columns_of(*det);
+        const overlap v = overlap_of(*det);
+        if(!(c.d_sd > 0.0) || !(c.l_px_row > 0.0) || !std::isfinite(c.d_sd) || !std::isfinite(c.t_half) || !std::isfinite(v.gamma_tau))
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        if(!(v.tau >= 2.0 * c.l_px_row))
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        *o = v;
+        return PARIS_HIP_SUCCESS;
+    }
+
+    // The scaffold both redundancy weights share: binds the ctx, runs an earlier weighting nobody filtered, checks the launch
+    // arguments of a column pass over rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes apart, then
+    // refuse() -- the weight's own checks -- and around launch(base, grid) the guards that keep by-reference groups sound
+    // (deferral by reference: a buffer the pending group reads must not be weighted again before that group has run).
+    // launch() enqueues on ctx->stream; grid.z is left for it to set.
+    template <typename Refuse, typename Launch>
+    int weight_columns(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                       uint32_t dim_y, uint32_t row_first, uint32_t row_count, const paris_detector_geometry* det_geo, Refuse refuse,
+                       Launch launch)
+    {
+        if(int rc = paris_hip_bind(ctx))
+            return rc;
+        if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
+            return rc;
+        if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
+           || row_count > dim_y - row_first || det_geo == nullptr || dim_x != det_geo->n_row)
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
+        if(int rc = refuse())
+            return rc;
+        if(dim_x == 0 || row_count == 0 || n_frames == 0)
+            return paris_hip_finish(ctx);
+        char* base = reinterpret_cast<char*>(d_p);
+        for(uint32_t f = 0; f < n_frames; ++f)
+            if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
+                return rc;
+        const uint32_t slices = (row_count + SS_ROWS_PER_THREAD - 1u) / SS_ROWS_PER_THREAD;
+        launch(base, dim3((dim_x + SS_THREADS - 1u) / SS_THREADS, slices < 65535u ? slices : 65535u, 1u));
+        for(uint32_t f = 0; f < n_frames; ++f)
+            if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(row_first) * pitch, pitch * row_count))
+                return rc;
+        return paris_hip_finish(ctx);
+    }
 }
 
 extern "C" int paris_hip_short_scan_check(const paris_detector_geometry* det_geo, const paris_short_scan* scan, float* gamma_max_deg)
@@ -121,51 +224,38 @@ extern "C" int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, 
                                                 uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
                                                 const paris_detector_geometry* det_geo, const paris_short_scan* scan, const float* phi_deg)
 {
-    if(int rc = paris_hip_bind(ctx))
-        return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
-        return rc;
-    if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
-       || row_count > dim_y - row_first || det_geo == nullptr || dim_x != det_geo->n_row || (n_frames != 0 && phi_deg == nullptr))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
     double delta = 0.0;
-    if(int rc = check_scan(det_geo, scan, &delta))
-        return rc;
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(!std::isfinite(phi_deg[f]))
+    const auto refuse = [&]() -> int {
+        if(n_frames != 0 && phi_deg == nullptr)
             return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(dim_x == 0 || row_count == 0 || n_frames == 0)
-        return paris_hip_finish(ctx);
-    char* base = reinterpret_cast<char*>(d_p);
-    // (deferral by reference: a buffer the pending group reads must not be weighted again before that group has run)
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
+        if(int rc = check_scan(det_geo, scan, &delta))
             return rc;
-    const column_geometry c = columns_of(*det_geo);
-    const uint32_t slices = (row_count + SS_ROWS_PER_THREAD - 1u) / SS_ROWS_PER_THREAD;
-    for(uint32_t f0 = 0; f0 < n_frames; f0 += SS_MAX_FRAMES)
-    {
-        const uint32_t n = std::min(n_frames - f0, SS_MAX_FRAMES);
-        frame_angles a{};
-        for(uint32_t f = 0; f < n; ++f)
+        for(uint32_t f = 0; f < n_frames; ++f)
+            if(!std::isfinite(phi_deg[f]))
+                return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        return PARIS_HIP_SUCCESS;
+    };
+    const auto launch = [&](char* base, dim3 grid) {
+        const column_geometry c = columns_of(*det_geo);
+        for(uint32_t f0 = 0; f0 < n_frames; f0 += SS_MAX_FRAMES)
         {
-            // (phi - start) mod 360 degrees in double, then radians
-            double b = std::fmod(static_cast<double>(phi_deg[f0 + f]) - static_cast<double>(scan->start_deg), 360.0);
-            if(b < 0.0)
-                b += 360.0;
-            a.beta[f] = b * (M_PI / 180.0);
+            const uint32_t n = std::min(n_frames - f0, SS_MAX_FRAMES);
+            frame_angles a{};
+            for(uint32_t f = 0; f < n; ++f)
+            {
+                // (phi - start) mod 360 degrees in double, then radians
+                double b = std::fmod(static_cast<double>(phi_deg[f0 + f]) - static_cast<double>(scan->start_deg), 360.0);
+                if(b < 0.0)
+                    b += 360.0;
+                a.beta[f] = b * (M_PI / 180.0);
+            }
+            grid.z = n;
+            hipLaunchKernelGGL(short_scan_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
+                               static_cast<uint32_t>(pitch / sizeof(float)), dim_x, row_first, row_first + row_count, c.t_half, c.l_px_row,
+                               c.d_sd, delta, a);
         }
-        const dim3 grid((dim_x + SS_THREADS - 1u) / SS_THREADS, slices < 65535u ? slices : 65535u, n);
-        hipLaunchKernelGGL(short_scan_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
-                           static_cast<uint32_t>(pitch / sizeof(float)), dim_x, row_first, row_first + row_count, c.t_half, c.l_px_row, c.d_sd,
-                           delta, a);
-    }
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(row_first) * pitch, pitch * row_count))
-            return rc;
-    return paris_hip_finish(ctx);
+    };
+    return weight_columns(ctx, d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count, det_geo, refuse, launch);
 }
 
 extern "C" int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
@@ -179,8 +269,44 @@ extern "C" int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p,
     return paris_hip_short_scan_weight_rows(ctx, d_p, pitch, 0u, 1u, dim_x, dim_y, 0u, dim_y, det_geo, scan, &a);
 }
 
-void paris_hip_warm_short_scan()
+extern "C" int paris_hip_offset_detector_check(const paris_detector_geometry* det_geo, float* gamma_tau_deg)
+{
+    overlap o{};
+    const int rc = check_offset_detector(det_geo, &o);
+    if(gamma_tau_deg != nullptr && det_geo != nullptr && det_geo->n_row != 0) // refused geometries too: the caller can name the overlap
+        *gamma_tau_deg = static_cast<float>(overlap_of(*det_geo).gamma_tau * (180.0 / M_PI));
+    return rc;
+}
+
+extern "C" int paris_hip_offset_detector_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                                     uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
+                                                     const paris_detector_geometry* det_geo)
+{
+    overlap o{};
+    const auto refuse = [&]() -> int { return check_offset_detector(det_geo, &o); };
+    const auto launch = [&](char* base, dim3 grid) {
+        const column_geometry c = columns_of(*det_geo);
+        // the weight does not depend on the angle: no per-frame arguments, only the grid-z limit splits a batch
+        for(uint32_t f0 = 0; f0 < n_frames; f0 += 65535u)
+        {
+            grid.z = std::min(n_frames - f0, 65535u);
+            hipLaunchKernelGGL(offset_detector_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
+                               static_cast<uint32_t>(pitch / sizeof(float)), dim_x, row_first, row_first + row_count, c.t_half, c.l_px_row,
+                               c.d_sd, o.sigma, o.gamma_tau);
+        }
+    };
+    return weight_columns(ctx, d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count, det_geo, refuse, launch);
+}
+
+extern "C" int paris_hip_stage_offset_detector_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
+                                                      const paris_detector_geometry* det_geo)
+{
+    return paris_hip_offset_detector_weight_rows(ctx, d_p, pitch, 0u, 1u, dim_x, dim_y, 0u, dim_y, det_geo);
+}
+
+void paris_hip_warm_redundancy_weights()
 {
     hipFuncAttributes a{};
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&short_scan_kernel));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&offset_detector_kernel));
 }

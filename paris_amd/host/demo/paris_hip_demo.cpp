@@ -4,13 +4,15 @@
 // usage: paris_hip_demo <n_row> <n_col> <l_px_row> <l_px_col> <delta_s> <delta_t> <d_so> <d_od> <delta_phi>
 //                       <n_proj> <in.raw | lcg> <out.raw> [--no-weight] [--no-filter]
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
-//                       [--short-scan start_deg range_deg] [--flat dark.raw|none flat.raw t_min]
+//                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
 // --json: one more line, the same figures as a JSON object (bench.py's paris_loop leg reads it).
 // --short-scan: the projections (angle i * delta_phi) form a short scan over [start_deg, start_deg + range_deg]: set_short_scan() before
 // the loops, so that paris::weight() applies the Parker redundancy weight first.
+// --offset-detector: the projections come from an offset detector over a full circle: set_offset_detector() before the loops, so
+// that paris::weight() applies the offset-detector redundancy weight before the cosine weight.
 // --flat: the frames are intensities; dark.raw and flat.raw hold one n_col x n_row float32 frame each ("none": a zero dark).
 // set_flat_field() before the loops, so that paris::weight() turns each frame into line integrals first.
 // out.raw receives the whole (ROI) volume, slabs written at their slice offsets (fixing SURVEY.md Q4).
@@ -64,6 +66,7 @@ int main(int argc, char** argv)
         std::uint32_t cycle = 0;
         bool short_scan = false;
         float scan_start = 0.f, scan_range = 0.f;
+        bool offset_detector = false, offset_first = false; // offset_first: --offset-detector came before --short-scan (setter order)
         std::string dark_path, flat_path;
         float t_min = 1e-5f;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
@@ -84,6 +87,11 @@ int main(int argc, char** argv)
                 scan_start = std::strtof(argv[a + 1], nullptr);
                 scan_range = std::strtof(argv[a + 2], nullptr);
                 a += 2;
+            }
+            else if(!std::strcmp(argv[a], "--offset-detector"))
+            {
+                offset_detector = true;
+                offset_first = !short_scan;
             }
             else if(!std::strcmp(argv[a], "--flat") && a + 3 < argc)
             {
@@ -120,8 +128,12 @@ int main(int argc, char** argv)
         if(devices.empty())
             throw paris::stage_construction_error{"no HIP device"};
         paris::backend::set_device(devices[0]); // src/main.cpp:87
+        if(offset_detector && offset_first)
+            paris::backend::set_offset_detector();
         if(short_scan)
             paris::backend::set_short_scan(scan_start, scan_range, false);
+        if(offset_detector && !offset_first)
+            paris::backend::set_offset_detector();
         if(!flat_path.empty())
         {
             const auto n = std::size_t{det.n_row} * det.n_col;

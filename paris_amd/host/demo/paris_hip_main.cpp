@@ -5,7 +5,7 @@
 //   paris.hip --geometry geo.ini --input <dir> --output <dir> [--name vol] [--angles file] [--quality q]
 //             [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
-//             [--window ramp|shepp-logan] [--short-scan] [--flat file.his [--dark file.his] [--min-transmission t]]
+//             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -78,11 +78,13 @@ int main(int argc, char** argv)
                 std::printf("paris.hip --geometry geo.ini --input <dir of .his files> --output <dir> [--name vol] [--angles file] [--quality q]\n"
                             "          [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]\n"
                             "          [--slabs n] [--devices n] [--f16] [--window ramp|shepp-logan] [--batch n] [--no-row-band] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]\n"
-                            "          [--drain-chunk-kib n] [--short-scan] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
+                            "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
                             "twice the fan angle); each is weighted by Parker's redundancy weight before the cosine weight.\n"
+                            "--offset-detector: the detector is shifted sideways (delta_s) over a full circle (half fan); each projection is\n"
+                            "weighted by the offset-detector redundancy weight before the cosine weight.\n"
                             "--flat / --dark: the projections are detector counts; each is corrected with the mean flat (and dark) frame of\n"
                             "these HIS files to line integrals -ln(max((I - D) / (F - D), t)) on the device, t = --min-transmission (1e-5).\n");
                 return 0;
@@ -104,6 +106,7 @@ int main(int argc, char** argv)
             else if(k == "--devices") po.devices = std::stoi(val());
             else if(k == "--f16") po.f16 = true;
             else if(k == "--short-scan") po.short_scan = true;
+            else if(k == "--offset-detector") po.offset_detector = true;
             else if(k == "--flat") po.flat_path = val();
             else if(k == "--dark") po.dark_path = val();
             else if(k == "--min-transmission") po.t_min = std::stof(val());

@@ -126,6 +126,7 @@ namespace paris
                 paris_hip_ctx* current = nullptr;
                 std::map<const paris_hip_ctx*, short_scan_setting> short_scans; // set_short_scan(), per device of this thread
                 std::set<const paris_hip_ctx*> flat_fields; // set_flat_field(), per device of this thread
+                std::set<const paris_hip_ctx*> offset_detectors; // set_offset_detector(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -203,6 +204,9 @@ namespace paris
         // angle throws stage_runtime_error.
         inline auto set_short_scan(float start_deg, float range_deg, bool enable_angles) -> void
         {
+            if(detail::state().offset_detectors.count(current_ctx()) != 0u)
+                throw stage_runtime_error{"set_short_scan(): an offset detector is set on this device; a short scan with an offset detector needs "
+                                          "a different weight"};
             detail::state().short_scans[current_ctx()] = detail::short_scan_setting{paris_short_scan{start_deg, range_deg}, enable_angles};
         }
 
@@ -221,6 +225,33 @@ namespace paris
                     return nullptr;
                 const auto it = m.find(ctx);
                 return it == m.end() ? nullptr : &it->second;
+            }
+        }
+
+        // Extension (no reference counterpart): the projections of this thread's current device come from an offset detector (half fan)
+        // over a full circle. Until clear_offset_detector(), paris::weight() applies the offset-detector redundancy weight to each
+        // projection, after a dark / flat correction and before the cosine weight (paris_hip_stage_offset_detector_weight). The detector
+        // is checked at each weight(): an overlap tau below 2 pixels throws stage_runtime_error. Set together with a short scan on
+        // the same device, whichever setter comes second throws stage_runtime_error.
+        inline auto set_offset_detector() -> void
+        {
+            if(detail::state().short_scans.count(current_ctx()) != 0u)
+                throw stage_runtime_error{"set_offset_detector(): a short scan is set on this device; a short scan with an offset detector needs "
+                                          "a different weight"};
+            detail::state().offset_detectors.insert(current_ctx());
+        }
+
+        inline auto clear_offset_detector() -> void
+        {
+            detail::state().offset_detectors.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_offset_detector(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().offset_detectors;
+                return !s.empty() && s.count(ctx) != 0u;
             }
         }
 

@@ -83,6 +83,9 @@ namespace paris
         // angle of the frames the run uses, before any device work (detail::derive_short_scan)
         bool short_scan = false;
         paris_short_scan scan{};
+        // redundancy weighting of an offset-detector (half-fan) full circle (extension): run() checks the detector's overlap and that
+        // the frames cover the circle, before any device work (detail::check_offset_detector)
+        bool offset_detector = false;
         // dark / flat correction of intensity frames to line integrals (extension): --flat / --dark name HIS files whose frames are
         // averaged into one reference frame each by run(), before any device work (detail::load_flat_field); every device ctx gets
         // them and uploads frames through paris_hip_upload_projection_raw_corrected
@@ -696,6 +699,9 @@ namespace paris
                     if(filled == 0)
                         return;
                     const auto t1 = clock::now();
+                    if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
+                        rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
+                                                                 band_count, &t.det_geo), "offset-detector weight()");
                     if(filter_by_group && band_count != 0 && po.short_scan) // the redundancy weight first, one launch for the group
                         rt(paris_hip_short_scan_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count,
                                                             &t.det_geo, &po.scan, angles.data()), "short-scan weight()");
@@ -771,6 +777,9 @@ namespace paris
                                                                n_row, band_count, p.pixel), "load()");
                         rep.h2d_bytes += static_cast<std::uint64_t>(band_count) * n_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                        if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
+                            rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
+                                                                     &t.det_geo), "offset-detector weight()");
                         if(po.short_scan && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
                             rt(paris_hip_short_scan_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count, &t.det_geo,
                                                                 &po.scan, &angles[filled]), "short-scan weight()");
@@ -871,6 +880,42 @@ namespace paris
             return scan;
         }
 
+        // --offset-detector: refused here, before any device work, together with --short-scan (that combination needs a different
+        // weight), for a detector whose overlap tau = (n_row / 2 - |delta_s|) l_px_row is below 2 pixels, and unless the frames of the
+        // run (after the quality stride) have monotonic angles whose span plus one mean step reaches 360 degrees within half a step
+        inline auto check_offset_detector(const program_options& po) -> void
+        {
+            if(po.short_scan)
+                throw stage_construction_error{"--offset-detector and --short-scan together: a short scan with an offset detector needs a "
+                                               "different weight"};
+            float gamma_tau = 0.f;
+            if(paris_hip_offset_detector_check(&po.det_geo, &gamma_tau) != PARIS_HIP_SUCCESS)
+            {
+                char msg[256];
+                std::snprintf(msg, sizeof msg, "--offset-detector: the overlap tau = (n_row / 2 - |delta_s|) = %.4f pixels (n_row %u, delta_s %.4f); "
+                              "the weight needs at least 2", static_cast<double>(po.det_geo.n_row) / 2.0 - std::abs(static_cast<double>(po.det_geo.delta_s)),
+                              po.det_geo.n_row, static_cast<double>(po.det_geo.delta_s));
+                throw stage_construction_error{msg};
+            }
+            const auto a = frame_angles(po.input_path, po.enable_angles, po.angle_path, po.quality, po.det_geo.delta_phi);
+            if(a.size() < 2u)
+                throw stage_construction_error{"--offset-detector needs at least two projections"};
+            const bool up = a[1] > a[0];
+            for(std::size_t i = 1; i < a.size(); ++i)
+                if(up ? !(a[i] > a[i - 1]) : !(a[i] < a[i - 1]))
+                    throw stage_construction_error{"--offset-detector: the projection angles are not monotonic (frame " + std::to_string(i) + ": "
+                                                   + std::to_string(a[i]) + " degrees after " + std::to_string(a[i - 1]) + ")"};
+            const double span = std::abs(static_cast<double>(a.back()) - static_cast<double>(a.front()));
+            const double step = span / static_cast<double>(a.size() - 1u);
+            if(360.0 - (span + step) > step / 2.0)
+            {
+                char msg[256];
+                std::snprintf(msg, sizeof msg, "--offset-detector: the projections cover %.4f degrees (%.4f plus one step of %.4f), an offset "
+                              "detector needs a full circle of 360", span + step, span, step);
+                throw stage_construction_error{msg};
+            }
+        }
+
         // --flat / --dark: each file's frames averaged into one reference frame (his::mean_frame), refused here -- before any device
         // work -- when the file cannot be read or holds no frames, when its frames are not the detector's size, when it lies inside
         // --input (it would be read as a projection too), or when t_min is outside (0, 1]
@@ -923,6 +968,8 @@ namespace paris
         detail::load_flat_field(po);
         r.flat_frames = po.flat ? po.flat->n_frames : 0u;
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
+        if(po.offset_detector)
+            detail::check_offset_detector(po);
         if(po.short_scan)
             po.scan = detail::derive_short_scan(po);
         r.vol_geo = calculate_volume_geometry(po.det_geo); // :122
