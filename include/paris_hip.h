@@ -514,6 +514,46 @@ int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_p
                                 const paris_detector_geometry* det_geo, const paris_volume_geometry* vol_geo,
                                 int enable_angles, int enable_roi, const paris_region_of_interest* roi);
 
+/* ---- forward projection (extension, no reference counterpart) -------------------------------------------
+ * The cone-beam projections of a volume on the device, in the backprojector's geometry, by Joseph's method: every detector pixel
+ * casts one ray from the source to its centre, sampled once per voxel plane along the axis (x or y) it runs more nearly parallel
+ * to, bilinearly in that plane. There is no step size: the result is fully defined. For a view with s = sin_phi[f], c = cos_phi[f],
+ * d_sd = |d_so| + |d_od| and delta_s, delta_t in mm as paris_hip_backproject receives them:
+ *   pixel (i, j), column i in [0, n_row), row j in [0, n_col):
+ *     t = (i + 1/2) l_px_row - n_row l_px_row / 2 - delta_s,   z = (j + 1/2) l_px_col - n_col l_px_col / 2 - delta_t
+ *     source S = (-d_so c, -d_so s, 0),   ray direction (dx, dy, dz) = (d_sd c - t s, d_sd s + t c, z)
+ *   x-marching when |dx| >= |dy|, else y-marching (the same statement with x and y exchanged):
+ *     for every plane K in [0, vol_geo->dim_x):  x_K = -(dim_x l_vx_x / 2) + l_vx_x / 2 + K l_vx_x
+ *       a = (x_K - S_x) / dx;  planes with a <= 0 or a > 1 (not between source and detector) add nothing
+ *       y = S_y + a dy,  w = a dz
+ *       fy = (y + dim_y l_vx_y / 2) / l_vx_y - 1/2,  fz = (w + dim_z l_vx_z / 2) / l_vx_z - 1/2   (dim_* of the full grid vol_geo)
+ *       sample = bilinear over the taps (floor fy, floor fz), (+1, .), (., +1), (+1, +1) of plane K; a tap outside the grid, or
+ *                outside the slab [v_offset, v_offset + v_dim_z), counts as 0 on its own
+ *     p(i, j) = (sum_K sample_K) l_vx_x sqrt(dx^2 + dy^2 + dz^2) / |dx|
+ * What is done once per ray (t, z, the direction, the choice of the marching axis with dx and dy exactly as written, the length
+ * factor, the per-plane increments) is formed in double from the fp32 arguments; the per-plane work is fp32.
+ * d_v is a z-slab of the grid vol_geo, as in paris_hip_backproject: v_dim_x, v_dim_y equal vol_geo's, v_dim_z slices from global
+ * slice v_offset. The projections of disjoint slabs add up to the whole volume's (to fp32 rounding). No ROI form.
+ * View f is written at d_p + f * p_stride_bytes (p_pitch bytes per row; only the p_dim_x floats of a row are written). With
+ * accumulate != 0 the finished ray sum is added to the stored pixel in one fp32 addition instead. sin_phi / cos_phi are host
+ * arrays of n_views. PARIS_HIP_ERROR_INVALID_ARGUMENT for null pointers, p_dim_x != n_row or p_dim_y != n_col, p_pitch <
+ * 4 * p_dim_x or not a multiple of 4, overlapping frames (n_views > 1 with p_stride_bytes < p_pitch * p_dim_y), v_dim_x / v_dim_y
+ * other than vol_geo's, v_offset + v_dim_z > vol_geo->dim_z, a pixel or voxel size <= 0, d_so <= 0, or a value that is not finite.
+ * n_views == 0, or v_dim_z == 0 with accumulate, does nothing; v_dim_z == 0 without it writes zeros.
+ * The call reads a volume and writes projection buffers: what is deferred (backprojections into any volume, a held-back
+ * weighting) runs first, and a destination the pending by-reference group refers to has that group launched first. */
+int paris_hip_forward_project(paris_hip_ctx* ctx, const float* d_v, uint32_t v_dim_x, uint32_t v_dim_y, uint32_t v_dim_z,
+                              uint32_t v_offset, const paris_detector_geometry* det_geo, const paris_volume_geometry* vol_geo,
+                              float* d_p, size_t p_pitch, size_t p_stride_bytes, uint32_t n_views, uint32_t p_dim_x,
+                              uint32_t p_dim_y, const float* sin_phi, const float* cos_phi, float delta_s, float delta_t,
+                              int accumulate);
+/* One view, its angle from p_idx / p_phi exactly as paris_hip_stage_angle gives it and delta_s l_px_row, delta_t l_px_col in fp32
+ * as paris_hip_stage_backproject derives them */
+int paris_hip_stage_forward_project(paris_hip_ctx* ctx, const float* d_v, uint32_t v_dim_x, uint32_t v_dim_y, uint32_t v_dim_z,
+                                    uint32_t v_offset, const paris_detector_geometry* det_geo, const paris_volume_geometry* vol_geo,
+                                    float* d_p, size_t p_pitch, uint32_t p_dim_x, uint32_t p_dim_y, uint32_t p_idx, float p_phi,
+                                    int enable_angles, int accumulate);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 const char* paris_hip_strerror(int status);
 /* library version "major.minor.patch" */

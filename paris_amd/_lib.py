@@ -163,6 +163,10 @@ SIGNATURES = {
     "paris_hip_stage_backproject": (C.c_int, [_vp, _vp, _sz, _u32, _u32, _u32, _f, _vp, _u32, _u32, _u32, _u32,
                                               _P(DetectorGeometry), _P(VolumeGeometry), C.c_int, C.c_int,
                                               _P(RegionOfInterest)]),
+    "paris_hip_forward_project": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _P(DetectorGeometry), _P(VolumeGeometry), _vp, _sz, _sz,
+                                            _u32, _u32, _u32, _P(_f), _P(_f), _f, _f, C.c_int]),
+    "paris_hip_stage_forward_project": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _P(DetectorGeometry), _P(VolumeGeometry), _vp, _sz,
+                                                  _u32, _u32, _u32, _f, C.c_int, C.c_int]),
     "paris_hip_strerror": (C.c_char_p, [C.c_int]),
     "paris_hip_version": (C.c_char_p, []),
     "paris_hip_last_backproject_ms": (C.c_int, [_vp, _P(_f)]),

@@ -18,7 +18,7 @@ from ._lib import (DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan,
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
-           "backproject", "short_scan_check", "offset_detector_check"]
+           "backproject", "forward_project", "short_scan_check", "offset_detector_check"]
 
 
 class Projection:
@@ -418,6 +418,21 @@ class Backend:
                                                       C.byref(vol_geo), int(bool(enable_roi)), C.byref(r), s, c,
                                                       delta_s, delta_t), "paris_hip_backproject_batch_f16")
 
+    def forward_project(self, v, v_offset, det_geo, vol_geo, p, sin, cos, delta_s, delta_t, accumulate=False, frame_stride=0):
+        """Cone-beam projections of the slab v (first slice: global slice v_offset of the grid vol_geo) by Joseph's method
+        (paris_hip_forward_project), in the backprojector's geometry. sin / cos are scalars for one view or sequences for n views,
+        written frame_stride bytes apart starting at p; delta_s / delta_t in mm. accumulate: each ray sum is added to the stored
+        pixel instead of replacing it."""
+        sins = np.atleast_1d(np.asarray(sin, np.float32))
+        coss = np.atleast_1d(np.asarray(cos, np.float32))
+        if sins.shape != coss.shape or sins.ndim != 1:
+            raise ValueError("forward_project: sin and cos must be scalars or sequences of one length")
+        fp = C.POINTER(C.c_float)
+        check(self._L.paris_hip_forward_project(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z, v_offset, C.byref(det_geo), C.byref(vol_geo),
+                                                p.ptr, p.pitch, frame_stride, len(sins), p.dim_x, p.dim_y, sins.ctypes.data_as(fp),
+                                                coss.ctypes.data_as(fp), delta_s, delta_t, int(bool(accumulate))),
+              "paris_hip_forward_project")
+
     # ---- diagnostics ------------------------------------------------------------------------------------------
     def last_backproject_ms(self):
         ms = C.c_float()
@@ -654,6 +669,15 @@ def backproject(backend, p, v, v_offset, det_geo, vol_geo, enable_angles, enable
                                                  C.byref(vol_geo), int(bool(enable_angles)),
                                                  int(bool(enable_roi)), C.byref(r)),
           "paris_hip_stage_backproject")
+
+
+def forward_project(backend, v, v_offset, p, det_geo, vol_geo, enable_angles=False, accumulate=False):
+    """The projection of the slab v at the angle of p.idx / p.phi, resolved as backproject() resolves it, written into (or, with
+    accumulate, added to) p (paris_hip_stage_forward_project)"""
+    check(backend._L.paris_hip_stage_forward_project(backend._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z, v_offset, C.byref(det_geo),
+                                                     C.byref(vol_geo), p.ptr, p.pitch, p.dim_x, p.dim_y, p.idx, p.phi,
+                                                     int(bool(enable_angles)), int(bool(accumulate))),
+          "paris_hip_stage_forward_project")
 
 
 def stage_angle(det_geo, idx, enable_angles=False, phi=0.0):

@@ -348,7 +348,7 @@ int paris_hip_run_check(paris_hip_ctx* ctx, const std::array<uint32_t, 4>& key, 
                         const void* arg, bool* ok, bool* known);
 int paris_hip_ensure_upload_stream(paris_hip_ctx* ctx); // upload_stream + its event ring
 int paris_hip_ensure_bp_stream(paris_hip_ctx* ctx);     // bp_stream + its events
-// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip: one cheap query per
+// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip / forward_project.hip: one cheap query per
 // translation unit that makes the
 // runtime load its code object now rather than at the first launch
 void paris_hip_warm_backproject();
@@ -360,6 +360,7 @@ void paris_hip_warm_validate();
 void paris_hip_warm_widen();
 void paris_hip_warm_redundancy_weights(); // short_scan.hip: the Parker and offset-detector kernels
 void paris_hip_warm_flat_field();
+void paris_hip_warm_forward_project();
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
 // tail of their float rows (paris_hip_upload_projection_raw)

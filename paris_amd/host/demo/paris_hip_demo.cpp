@@ -5,6 +5,7 @@
 //                       <n_proj> <in.raw | lcg> <out.raw> [--no-weight] [--no-filter]
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
+//                       [--reproject frames.raw]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -15,6 +16,10 @@
 // that paris::weight() applies the offset-detector redundancy weight before the cosine weight.
 // --flat: the frames are intensities; dark.raw and flat.raw hold one n_col x n_row float32 frame each ("none": a zero dark).
 // set_flat_field() before the loops, so that paris::weight() turns each frame into line integrals first.
+// --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
+// frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
+// host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
+// ascending order. Refused together with --roi (the forward projector has no ROI form).
 // out.raw receives the whole (ROI) volume, slabs written at their slice offsets (fixing SURVEY.md Q4).
 #include <chrono>
 #include <cstdio>
@@ -67,7 +72,7 @@ int main(int argc, char** argv)
         bool short_scan = false;
         float scan_start = 0.f, scan_range = 0.f;
         bool offset_detector = false, offset_first = false; // offset_first: --offset-detector came before --short-scan (setter order)
-        std::string dark_path, flat_path;
+        std::string dark_path, flat_path, reproject_path;
         float t_min = 1e-5f;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
@@ -100,6 +105,7 @@ int main(int argc, char** argv)
                 t_min = std::strtof(argv[a + 3], nullptr);
                 a += 3;
             }
+            else if(!std::strcmp(argv[a], "--reproject") && a + 1 < argc) reproject_path = argv[++a];
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
                 enable_roi = true;
@@ -119,6 +125,11 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "unknown argument %s\n", argv[a]);
                 return 2;
             }
+        }
+        if(!reproject_path.empty() && enable_roi)
+        {
+            std::fprintf(stderr, "--reproject cannot be combined with --roi: the forward projector has no ROI form\n");
+            return 2;
         }
         auto roi_geo = vol_geo;
         if(enable_roi)
@@ -179,6 +190,8 @@ int main(int argc, char** argv)
         if(write_out && out == nullptr)
             throw paris::stage_runtime_error{"cannot open " + out_path};
 
+        auto reprojected = std::vector<float>(reproject_path.empty() ? std::size_t{0} : frame * n_proj); // --reproject: the frames so far
+
         using clock = std::chrono::steady_clock;
         double split_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // make_projection_host, frame fill, load, weight, filter, backproject, free device, free host
         double fill_s = 0.0, tail_s = 0.0; // of loop_s: the host's own frame fill (memcpy into the pinned buffer), the wait for the GPU after the last call
@@ -219,6 +232,25 @@ int main(int argc, char** argv)
             paris::backend::synchronize(); // the timed region ends when the GPU has finished, not when the last call returned
             tail_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tail).count();
             loop_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+            if(!reproject_path.empty()) // this slab's part of every view, while its volume is alive
+            {
+                const float delta_s = det.delta_s * det.l_px_row, delta_t = det.delta_t * det.l_px_col; // src/backprojection.cpp:49-50
+                for(std::uint32_t i = 0; i < n_proj; ++i)
+                {
+                    float sin_phi = 0.f, cos_phi = 0.f;
+                    paris::backend::detail::runtime_check(paris_hip_stage_angle(&det, i, 0, 0.f, &sin_phi, &cos_phi), "--reproject");
+                    auto h_p = paris::backend::make_projection_host(det.n_row, det.n_col);
+                    auto d_p = paris::backend::make_projection_device(det.n_row, det.n_col);
+                    if(id > 0)
+                    {
+                        std::memcpy(h_p.buf.get(), reprojected.data() + frame * i, frame * sizeof(float));
+                        paris::backend::copy_h2d(h_p, d_p);
+                    }
+                    paris::backend::forward_project(v, offset, det, vol_geo, d_p, sin_phi, cos_phi, delta_s, delta_t, id > 0);
+                    paris::backend::copy_d2h(d_p, h_p);
+                    std::memcpy(reprojected.data() + frame * i, h_p.buf.get(), frame * sizeof(float));
+                }
+            }
             if(out == nullptr) // --no-out: a throughput run, the volume is neither read back nor written
                 continue;
             auto h_v = paris::backend::make_volume_host(v.dim_x, v.dim_y, v.dim_z);
@@ -230,6 +262,13 @@ int main(int argc, char** argv)
         }
         if(out != nullptr)
             std::fclose(out);
+        if(!reproject_path.empty())
+        {
+            std::FILE* f = std::fopen(reproject_path.c_str(), "wb");
+            if(f == nullptr || std::fwrite(reprojected.data(), sizeof(float), reprojected.size(), f) != reprojected.size())
+                throw paris::stage_runtime_error{"cannot write " + reproject_path};
+            std::fclose(f);
+        }
         std::printf("ok %u %u %u\n", roi_geo.dim_x, roi_geo.dim_y, roi_geo.dim_z);
         std::printf("projection loops %.3f s: %.1f GVoxel-updates/s through paris::load / weight / filter / backproject (deferral depth %d, %s)\n", loop_s,
                     static_cast<double>(roi_geo.dim_x) * roi_geo.dim_y * roi_geo.dim_z * n_proj / loop_s / 1e9, PARIS_HIP_BACKPROJECT_DEFERRAL,

@@ -444,6 +444,20 @@ namespace paris
                                                         detail::as_c<paris_region_of_interest>(roi), sin, cos, delta_s, delta_t),
                                   "backproject()");
         }
+
+        // Extension (no reference counterpart): the cone-beam projections of the slab v (first slice: global slice v_offset of the
+        // grid vol_geo) by Joseph's method, in backproject()'s geometry and with its arguments (paris_hip_forward_project). One view
+        // into p, or -- accumulate -- added to what p holds: the projections of disjoint slabs add up to the whole volume's.
+        inline auto forward_project(const volume_device_type& v, std::uint32_t v_offset, const detector_geometry& det_geo,
+                                    const volume_geometry& vol_geo, projection_device_type& p, float sin, float cos, float delta_s,
+                                    float delta_t, bool accumulate = false) -> void
+        {
+            detail::runtime_check(paris_hip_forward_project(current_ctx(), v.buf.get(), v.dim_x, v.dim_y, v.dim_z, v_offset,
+                                                            detail::as_c<paris_detector_geometry>(det_geo),
+                                                            detail::as_c<paris_volume_geometry>(vol_geo), p.buf.get(), p.buf.pitch(), 0u, 1u,
+                                                            p.dim_x, p.dim_y, &sin, &cos, delta_s, delta_t, accumulate ? 1 : 0),
+                                  "forward_project()");
+        }
     }
 }
 
