@@ -507,6 +507,63 @@ int paris_hip_flat_field_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size
  * PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or when dim_x / dim_y differ from the setting's. */
 int paris_hip_upload_projection_raw_corrected(paris_hip_ctx* ctx, float* d_frame, size_t d_pitch, const void* h_src, size_t h_pitch,
                                               uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count, int pixel_type);
+/* The pixels of the current flat-field setting that are dead by the rule above whatever the frame holds -- D or F not finite, or
+ * F - D <= 0 -- as dim_x * dim_y bytes (1 = dead), rows dim_x apart. Computed on the host by paris_hip_set_flat_field and kept with the
+ * setting; callers OR it into the defect map they set below. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL mask. */
+int paris_hip_flat_field_dead_pixels(paris_hip_ctx* ctx, uint8_t* mask);
+
+/* Extension (no reference counterpart): repair of defective detector pixels (dead pixels, lines, hot pixels) on the device, after
+ * the dark / flat correction and before every weight.
+ * A defect map is dim_y rows of dim_x bytes at full detector size; a nonzero byte marks a defective pixel, every other pixel is good.
+ * For a defective pixel q = (x, y):
+ *   r_q     = the smallest r in 1 .. PARIS_HIP_DEFECT_R_MAX for which some good pixel inside the detector has Chebyshev distance
+ *             max(|dx|, |dy|) <= r from q;
+ *   sources = all good pixels within that distance -- by the choice of r_q they all lie on ring r_q, at most 8 r_q of them -- in
+ *             row-major order;
+ *   w_k     = (1 / d_k^2) / sum_j (1 / d_j^2), d^2 = dx^2 + dy^2, formed in double on the host when the map is set and rounded once
+ *             to fp32;
+ *   value   = acc = 0; for k in order: acc = fmaf(w_k, p_k, acc), in fp32.
+ * A defective pixel with no good pixel within PARIS_HIP_DEFECT_R_MAX is unrepairable: it is left as it is, and counted.
+ * Sources are good pixels only and only defective pixels are written, so the pass runs in place without races, and running it twice
+ * gives the bits of running it once. A pixel that is bad in one frame only (a NaN in an f32 frame) is no map defect: it stays 0
+ * as the dark / flat correction leaves it. */
+#define PARIS_HIP_DEFECT_R_MAX 8
+typedef struct paris_hip_defect_stats {
+    uint64_t defects;      /* pixels the map marks */
+    uint64_t unrepairable; /* of those, pixels with no good pixel within PARIS_HIP_DEFECT_R_MAX */
+    uint64_t sources;      /* source entries over all repairable defects */
+    uint32_t reach_rows;   /* the largest |dy| any source has */
+    uint32_t reach_cols;   /* the largest |dx| any source has */
+    uint64_t device_bytes; /* what the plan occupies on the device while set (0 for a plan without a repairable defect) */
+} paris_hip_defect_stats;
+/* The plan of a map, on the host alone (no device, no ctx): the only implementation of the rule above. dim_x * dim_y and the number
+ * of sources must each fit 32 bits (PARIS_HIP_ERROR_UNSUPPORTED). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer or a zero
+ * dimension. */
+typedef struct paris_hip_defect_plan paris_hip_defect_plan;
+int paris_hip_defect_plan_create(const uint8_t* mask, uint32_t dim_x, uint32_t dim_y, paris_hip_defect_plan** out);
+int paris_hip_defect_plan_destroy(paris_hip_defect_plan* plan);
+int paris_hip_defect_plan_stats(const paris_hip_defect_plan* plan, paris_hip_defect_stats* out);
+/* The plan as CSR arrays, n = defects - unrepairable, m = sources: defect_index[n] the linear index y * dim_x + x of every repairable
+ * defect, sorted row-major; first_source[n + 1]; source_index[m] and weight[m], defect k's at [first_source[k], first_source[k + 1]).
+ * Any of the four may be NULL (not copied). */
+int paris_hip_defect_plan_copy(const paris_hip_defect_plan* plan, uint32_t* defect_index, uint32_t* first_source, uint32_t* source_index,
+                               float* weight);
+/* paris_hip_set_defect_map builds the plan and copies it into memory the ctx owns, replacing an earlier setting; the old plan is
+ * freed once the work queued before the call no longer reads it. A map without a defect is accepted and makes the repair a no-op.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL mask or a zero dimension. The plan's bytes count towards
+ * paris_hip_projection_reserve_bytes while set; paris_hip_ctx_destroy frees them. Without a setting nothing else changes. */
+int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_defect_map(paris_hip_ctx* ctx);
+/* The stats of the current setting. PARIS_HIP_ERROR_INVALID_ARGUMENT without one. */
+int paris_hip_defect_map_info(paris_hip_ctx* ctx, paris_hip_defect_stats* out);
+/* In place on float frames: the repairable defects whose row lies in [row_first, row_first + row_count) of n_frames frames
+ * frame_stride bytes apart, d_p the first frame's row 0, are replaced by their repaired value. Their sources may lie up to reach_rows
+ * rows OUTSIDE the band (clipped to the detector): the caller guarantees that those rows of every frame hold valid pixels -- a driver
+ * that processes a row band uploads and corrects the band widened by reach_rows on each side, and repairs, weights and filters the
+ * band itself. Call it on line integrals, before the redundancy and cosine weights. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting,
+ * when dim_x / dim_y differ from the setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_defect_repair_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count);
 /* paris::backproject (src/backprojection.cpp:37-69): p_idx / p_phi are projection::idx / projection::phi */
 int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_pitch, uint32_t p_dim_x,
                                 uint32_t p_dim_y, uint32_t p_idx, float p_phi, float* d_v, uint32_t v_dim_x,

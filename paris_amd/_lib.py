@@ -58,6 +58,12 @@ class ShortScan(C.Structure):
     _fields_ = [("start_deg", C.c_float), ("range_deg", C.c_float)]
 
 
+class DefectStats(C.Structure):
+    """paris_hip_defect_stats: what a defect map's repair plan holds (extension)"""
+    _fields_ = [("defects", C.c_uint64), ("unrepairable", C.c_uint64), ("sources", C.c_uint64),
+                ("reach_rows", C.c_uint32), ("reach_cols", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
 class SubvolumeInfo(C.Structure):
     """paris::subvolume_info (src/subvolume_information.h:30-34)"""
     _fields_ = [("geo", SubvolumeGeometry), ("num", C.c_int)]
@@ -92,6 +98,15 @@ SIGNATURES = {
     "paris_hip_set_flat_field": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _f]),
     "paris_hip_clear_flat_field": (C.c_int, [_vp]),
     "paris_hip_flat_field_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_flat_field_dead_pixels": (C.c_int, [_vp, _vp]),
+    "paris_hip_defect_plan_create": (C.c_int, [_vp, _u32, _u32, _P(_vp)]),
+    "paris_hip_defect_plan_destroy": (C.c_int, [_vp]),
+    "paris_hip_defect_plan_stats": (C.c_int, [_vp, _P(DefectStats)]),
+    "paris_hip_defect_plan_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "paris_hip_set_defect_map": (C.c_int, [_vp, _vp, _u32, _u32]),
+    "paris_hip_clear_defect_map": (C.c_int, [_vp]),
+    "paris_hip_defect_map_info": (C.c_int, [_vp, _P(DefectStats)]),
+    "paris_hip_defect_repair_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_memcpy_projection_d2h": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_memcpy_volume_h2d": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "paris_hip_memcpy_volume_d2h": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),

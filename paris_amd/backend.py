@@ -12,13 +12,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan, SubvolumeGeometry, SubvolumeInfo,
+from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan, SubvolumeGeometry, SubvolumeInfo,
                    VolumeGeometry, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
-           "backproject", "forward_project", "short_scan_check", "offset_detector_check"]
+           "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan"]
 
 
 class Projection:
@@ -64,6 +64,51 @@ class FilterBuffer:
         self.ptr = ptr
         self.size = size
         self._backend = backend
+
+
+class DefectPlan:
+    """The repair plan of a defect map (paris_hip_defect_plan_*), as numpy arrays: defect[n] the linear index y * dim_x + x of every
+    repairable defect, sorted row-major; first_source[n + 1]; source[m] and weight[m] (float32), defect k's at
+    [first_source[k], first_source[k + 1]). The counts of paris_hip_defect_stats are attributes."""
+
+    def __init__(self, stats, defect, first_source, source, weight):
+        self.defects = int(stats.defects)
+        self.unrepairable = int(stats.unrepairable)
+        self.sources = int(stats.sources)
+        self.reach_rows = int(stats.reach_rows)
+        self.reach_cols = int(stats.reach_cols)
+        self.device_bytes = int(stats.device_bytes)
+        self.defect = defect
+        self.first_source = first_source
+        self.source = source
+        self.weight = weight
+
+
+def _mask_bytes(mask, what):
+    m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    if m.ndim != 2:
+        raise ValueError("%s: the defect map must be a 2-D array (n_col, n_row)" % what)
+    return m
+
+
+def defect_plan(mask):
+    """Host only, no device: the repair plan of a defect map -- a 2-D array of the detector's size (n_col, n_row), nonzero = defective
+    (paris_hip_defect_plan_create). Returns a DefectPlan."""
+    m = _mask_bytes(mask, "defect_plan")
+    L = _lib.load()
+    plan = C.c_void_p()
+    check(L.paris_hip_defect_plan_create(m.ctypes.data, m.shape[1], m.shape[0], C.byref(plan)), "paris_hip_defect_plan_create")
+    try:
+        st = DefectStats()
+        check(L.paris_hip_defect_plan_stats(plan, C.byref(st)), "paris_hip_defect_plan_stats")
+        n = int(st.defects - st.unrepairable)
+        defect, first = np.empty(n, np.uint32), np.empty(n + 1, np.uint32)
+        source, weight = np.empty(int(st.sources), np.uint32), np.empty(int(st.sources), np.float32)
+        check(L.paris_hip_defect_plan_copy(plan, defect.ctypes.data, first.ctypes.data, source.ctypes.data, weight.ctypes.data),
+              "paris_hip_defect_plan_copy")
+    finally:
+        L.paris_hip_defect_plan_destroy(plan)
+    return DefectPlan(st, defect, first, source, weight)
 
 
 class Backend:
@@ -270,10 +315,12 @@ class Backend:
             raise ValueError("set_flat_field: dark and flat differ in shape")
         check(self._L.paris_hip_set_flat_field(self._ctx, None if dk is None else dk.ctypes.data, f.ctypes.data, f.shape[1], f.shape[0],
                                                t_min), "paris_hip_set_flat_field")
+        self._flat_shape = f.shape
 
     def clear_flat_field(self):
         """paris_hip_clear_flat_field: no correction from here on"""
         check(self._L.paris_hip_clear_flat_field(self._ctx), "paris_hip_clear_flat_field")
+        self._flat_shape = None
 
     def flat_field_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
         """The correction of set_flat_field() in place on float frames (paris_hip_flat_field_rows): rows [row_first, row_first +
@@ -281,6 +328,46 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_flat_field_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_flat_field_rows")
+
+    def flat_field_dead_pixels(self):
+        """The pixels of the current set_flat_field() setting that are dead whatever a frame holds -- dark or flat not finite, or flat
+        not above dark -- as a uint8 array (n_col, n_row) of 0 / 1 (paris_hip_flat_field_dead_pixels); OR it into a defect map"""
+        if getattr(self, "_flat_shape", None) is None:
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_flat_field_dead_pixels")
+        out = np.empty(self._flat_shape, np.uint8)
+        check(self._L.paris_hip_flat_field_dead_pixels(self._ctx, out.ctypes.data), "paris_hip_flat_field_dead_pixels")
+        return out
+
+    # ---- defect map (DESIGN.md section 4.9) ---------------------------------------------------------------
+    defect_plan = staticmethod(defect_plan)
+
+    def set_defect_map(self, mask):
+        """paris_hip_set_defect_map: mask is a 2-D array of the detector's size (n_col, n_row), nonzero = defective. Each defective
+        pixel is then replaced, by defect_repair_rows(), with the inverse-square-distance weighted mean of the good pixels on the
+        nearest ring that holds one (up to 8 pixels away). Replaces an earlier setting safely: work already queued keeps the old
+        plan. Returns defect_map_info()."""
+        m = _mask_bytes(mask, "set_defect_map")
+        check(self._L.paris_hip_set_defect_map(self._ctx, m.ctypes.data, m.shape[1], m.shape[0]), "paris_hip_set_defect_map")
+        return self.defect_map_info()
+
+    def clear_defect_map(self):
+        """paris_hip_clear_defect_map: no repair from here on"""
+        check(self._L.paris_hip_clear_defect_map(self._ctx), "paris_hip_clear_defect_map")
+
+    def defect_map_info(self):
+        """The DefectStats of the current setting (paris_hip_defect_map_info): defects, unrepairable, sources, reach_rows, reach_cols,
+        device_bytes"""
+        st = DefectStats()
+        check(self._L.paris_hip_defect_map_info(self._ctx, C.byref(st)), "paris_hip_defect_map_info")
+        return st
+
+    def defect_repair_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """The repair of set_defect_map() in place on float frames (paris_hip_defect_repair_rows): the defects in rows [row_first,
+        row_first + row_count) of n_frames frames frame_stride bytes apart starting at p. Sources lie up to reach_rows rows outside
+        the band: those rows must hold valid pixels. Call it on line integrals, before every weight."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_defect_repair_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_defect_repair_rows")
 
     def copy_d2h(self, d, h):
         if isinstance(d, Projection):

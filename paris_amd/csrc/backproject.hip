@@ -1024,6 +1024,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += (ctx->defer_refs != 0 ? 1u : 2u) * static_cast<size_t>(ctx->defer_depth) * frame; // the pending group by reference, or the ring's two halves
     if(ctx->flat_field.d_ref != nullptr) // the dark and flat frames of paris_hip_set_flat_field
         total += 2u * sizeof(float) * static_cast<size_t>(ctx->flat_field.dim_x) * ctx->flat_field.dim_y;
+    if(ctx->defect_map.set) // the plan of paris_hip_set_defect_map
+        total += static_cast<size_t>(ctx->defect_map.stats.device_bytes);
     *bytes = total;
     return PARIS_HIP_SUCCESS;
 }

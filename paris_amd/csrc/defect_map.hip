@@ -1,0 +1,219 @@
+// Repair of defective detector pixels for gfx950 (the statement is in include/paris_hip.h).
+//
+// The ctx holds one setting: the plan defect_plan.cpp builds on the host from the map, copied as it is into one device buffer by
+// paris_hip_set_defect_map. The repair (paris_hip_defect_repair_rows) is one sparse launch: one lane per (defect of the band, frame),
+// defects on grid x, frames on grid z; a lane walks its own sources and stores one pixel. Sources are good pixels, destinations are
+// defective ones, so lanes never read what another lane writes: in place, no races, idempotent.
+// The launch moves a few bytes per defect -- a 2048^2 detector with a dead row, a dead column and 0.1 % scattered pixels has about
+// 8 000 defects -- so it is sized by latency, not bandwidth: nothing here is tuned beyond the block size.
+#include <algorithm>
+
+#include "defect_plan.h"
+#include "paris_hip_internal.h"
+
+namespace
+{
+    constexpr uint32_t DM_THREADS = 256u;
+    constexpr uint32_t DM_MAX_FRAMES = 65535u;    // grid z
+    constexpr uint32_t DM_MAX_BLOCKS = 0x7fffffffu; // grid x
+
+    // p: the first frame's base (row 0) of this launch; rows pitch_f floats apart, frames frame_stride bytes apart (grid z).
+    // Defects [k_first, k_end) of the sorted list; a pixel index is y * dim_x + x.
+    __global__ void __launch_bounds__(DM_THREADS)
+        defect_repair_kernel(char* p, size_t frame_stride, size_t pitch_f, uint32_t dim_x, const uint32_t* __restrict__ defect,
+                             const uint32_t* __restrict__ first_source, const uint32_t* __restrict__ source,
+                             const float* __restrict__ weight, uint32_t k_first, uint32_t k_end)
+    {
+        const uint64_t k = static_cast<uint64_t>(k_first) + static_cast<uint64_t>(blockIdx.x) * DM_THREADS + threadIdx.x;
+        if(k >= k_end)
+            return;
+        float* frame = reinterpret_cast<float*>(p + static_cast<size_t>(blockIdx.z) * frame_stride);
+        float acc = 0.f;
+        for(uint32_t s = first_source[k], e = first_source[k + 1u]; s < e; ++s)
+        {
+            const uint32_t i = source[s];
+            const uint32_t sy = i / dim_x, sx = i - sy * dim_x;
+            acc = __builtin_fmaf(weight[s], frame[static_cast<size_t>(sy) * pitch_f + sx], acc);
+        }
+        const uint32_t q = defect[k];
+        const uint32_t y = q / dim_x, x = q - y * dim_x;
+        frame[static_cast<size_t>(y) * pitch_f + x] = acc;
+    }
+
+    // frees the retired plans no queued work can read any more (all of them when the ctx goes)
+    void sweep_retired(paris_hip_ctx* ctx, bool all)
+    {
+        auto& v = ctx->defect_map_retired;
+        for(size_t k = 0; k < v.size();)
+        {
+            if(all || hipEventQuery(v[k].second) == hipSuccess)
+            {
+                (void)hipFree(v[k].first);
+                paris_hip_give_event(ctx, v[k].second);
+                v[k] = v.back();
+                v.pop_back();
+            }
+            else
+                ++k;
+        }
+    }
+}
+
+void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying)
+{
+    paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+    if(dm.d_plan != nullptr)
+    {
+        hipEvent_t e = nullptr;
+        // work already queued on the compute stream may still read the old plan: it goes once that has run
+        if(!destroying && paris_hip_take_event(ctx, &e) == PARIS_HIP_SUCCESS && hipEventRecord(e, ctx->stream) == hipSuccess)
+            ctx->defect_map_retired.emplace_back(dm.d_plan, e);
+        else
+        {
+            if(e != nullptr)
+                paris_hip_give_event(ctx, e);
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(dm.d_plan);
+        }
+    }
+    dm = paris_hip_ctx::defect_map_t{};
+    sweep_retired(ctx, destroying); // (destroy has drained the streams already)
+}
+
+extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(mask == nullptr || dim_x == 0 || dim_y == 0)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    paris_hip_defect_plan* plan = nullptr;
+    if(int rc = paris_hip_defect_plan_create(mask, dim_x, dim_y, &plan))
+        return rc;
+    const size_t n = plan->defect.size(), m = plan->source.size();
+    uint32_t* d = nullptr;
+    int rc = PARIS_HIP_SUCCESS;
+    if(n != 0)
+    {
+        const size_t bytes = static_cast<size_t>(plan->stats.device_bytes);
+        hipError_t err = hipMalloc(reinterpret_cast<void**>(&d), bytes);
+        if(err == hipErrorOutOfMemory)
+        {
+            (void)hipGetLastError();
+            rc = paris_hip_drain_device_pool(ctx);
+            if(rc == PARIS_HIP_SUCCESS)
+                err = hipMalloc(reinterpret_cast<void**>(&d), bytes);
+        }
+        if(rc == PARIS_HIP_SUCCESS)
+            rc = static_cast<int>(err);
+        // The copies run on the ctx's own auxiliary stream and are waited for there: the plan's host arrays go with this call, and
+        // the new plan must be in place before any kernel of the compute stream reads it -- without waiting for the work queued
+        // there, which may still read the old setting.
+        if(rc == PARIS_HIP_SUCCESS)
+            rc = paris_hip_ensure_aux(ctx);
+        if(rc == PARIS_HIP_SUCCESS)
+        {
+            err = hipMemcpyAsync(d, plan->defect.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
+            if(err == hipSuccess)
+                err = hipMemcpyAsync(d + n, plan->first_source.data(), (n + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
+            if(err == hipSuccess)
+                err = hipMemcpyAsync(d + 2u * n + 1u, plan->source.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
+            if(err == hipSuccess)
+                err = hipMemcpyAsync(d + 2u * n + 1u + m, plan->weight.data(), m * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream);
+            // (waited for even after a failed copy: the earlier ones still read the plan's arrays)
+            const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
+            rc = static_cast<int>(err != hipSuccess ? err : waited);
+        }
+        if(rc != PARIS_HIP_SUCCESS)
+        {
+            if(d != nullptr)
+                (void)hipFree(d);
+            paris_hip_defect_plan_destroy(plan);
+            return rc;
+        }
+    }
+    paris_hip_defect_map_release(ctx, false);
+    paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+    dm.set = true;
+    dm.d_plan = d;
+    dm.dim_x = dim_x;
+    dm.dim_y = dim_y;
+    dm.n = static_cast<uint32_t>(n);
+    dm.m = static_cast<uint32_t>(m);
+    dm.stats = plan->stats;
+    dm.row_start.swap(plan->row_start);
+    paris_hip_defect_plan_destroy(plan);
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_clear_defect_map(paris_hip_ctx* ctx)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    paris_hip_defect_map_release(ctx, false);
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_defect_map_info(paris_hip_ctx* ctx, paris_hip_defect_stats* out)
+{
+    if(ctx == nullptr || out == nullptr || !ctx->defect_map.set)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    *out = ctx->defect_map.stats;
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_defect_repair_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                            uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
+        return rc;
+    const paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+    if(!dm.set || dim_x != dm.dim_x || dim_y != dm.dim_y)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
+       || row_count > dim_y - row_first)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
+    if(row_count == 0 || n_frames == 0)
+        return paris_hip_finish(ctx);
+    const uint32_t k_first = dm.row_start[row_first], k_end = dm.row_start[row_first + row_count];
+    if(k_first == k_end) // (a map without a repairable defect in the band)
+        return paris_hip_finish(ctx);
+    char* base = reinterpret_cast<char*>(d_p);
+    // (deferral by reference: a buffer the pending group reads must not be repaired before that group has run)
+    for(uint32_t f = 0; f < n_frames; ++f)
+        if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
+            return rc;
+    const uint32_t* defect = dm.d_plan;
+    const uint32_t* first_source = defect + dm.n;
+    const uint32_t* source = first_source + dm.n + 1u;
+    const float* weight = reinterpret_cast<const float*>(source + dm.m);
+    const uint64_t blocks = (static_cast<uint64_t>(k_end - k_first) + DM_THREADS - 1u) / DM_THREADS;
+    for(uint64_t b0 = 0; b0 < blocks; b0 += DM_MAX_BLOCKS)
+    {
+        const uint32_t gx = static_cast<uint32_t>(std::min<uint64_t>(DM_MAX_BLOCKS, blocks - b0));
+        const uint32_t k0 = k_first + static_cast<uint32_t>(b0 * DM_THREADS);
+        for(uint32_t f0 = 0; f0 < n_frames; f0 += DM_MAX_FRAMES)
+        {
+            const uint32_t gz = std::min(DM_MAX_FRAMES, n_frames - f0);
+            hipLaunchKernelGGL(defect_repair_kernel, dim3(gx, 1u, gz), dim3(DM_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
+                               pitch / sizeof(float), dim_x, defect, first_source, source, weight, k0, k_end);
+            PARIS_HIP_TRY(hipGetLastError());
+        }
+    }
+    // the launch reads up to reach_rows rows beyond the band on either side
+    const uint32_t lo = row_first - std::min(row_first, dm.stats.reach_rows);
+    const uint32_t hi = row_first + row_count + std::min(dim_y - (row_first + row_count), dm.stats.reach_rows);
+    for(uint32_t f = 0; f < n_frames; ++f)
+        if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(lo) * pitch, pitch * (hi - lo)))
+            return rc;
+    return paris_hip_finish(ctx);
+}
+
+void paris_hip_warm_defect_map()
+{
+    hipFuncAttributes a{};
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&defect_repair_kernel));
+}

@@ -105,6 +105,15 @@ extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark,
     if(h_flat == nullptr || dim_x == 0 || dim_y == 0 || !(t_min > 0.f && t_min <= 1.f)) // (NaN fails both, +inf the second)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     const size_t n = static_cast<size_t>(dim_x) * dim_y;
+    // the pixels that are dead whatever a frame holds (flat_field_line_integral's rule on D and F alone), for
+    // paris_hip_flat_field_dead_pixels
+    std::vector<uint8_t> dead(n);
+    for(size_t k = 0; k < n; ++k)
+    {
+        const double dk = h_dark != nullptr ? static_cast<double>(h_dark[k]) : 0.0;
+        const double den = static_cast<double>(h_flat[k]) - dk;
+        dead[k] = (!(den > 0.0) || !std::isfinite(dk) || !std::isfinite(static_cast<double>(h_flat[k]))) ? 1u : 0u;
+    }
     float* d = nullptr;
     hipError_t err = hipMalloc(reinterpret_cast<void**>(&d), 2u * n * sizeof(float));
     if(err == hipErrorOutOfMemory)
@@ -140,6 +149,15 @@ extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark,
     ff.dim_x = dim_x;
     ff.dim_y = dim_y;
     ff.t_min = t_min;
+    ff.dead.swap(dead);
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_flat_field_dead_pixels(paris_hip_ctx* ctx, uint8_t* mask)
+{
+    if(ctx == nullptr || mask == nullptr || ctx->flat_field.d_ref == nullptr)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    std::copy(ctx->flat_field.dead.begin(), ctx->flat_field.dead.end(), mask);
     return PARIS_HIP_SUCCESS;
 }
 

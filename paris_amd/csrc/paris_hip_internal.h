@@ -120,8 +120,22 @@ struct paris_hip_ctx
         float* d_ref = nullptr;
         uint32_t dim_x = 0, dim_y = 0;
         double t_min = 1.0;
+        std::vector<uint8_t> dead; // host: 1 where D or F is not finite or F - D <= 0 (paris_hip_flat_field_dead_pixels)
     } flat_field;
     std::vector<std::pair<float*, hipEvent_t>> flat_field_retired;
+    // Defect map (paris_hip_set_defect_map): the plan of defect_plan.cpp in one device buffer -- defect[n], first_source[n + 1],
+    // source[m], weight[m], 4 bytes each -- read by the repair kernel on the compute stream only, so it is replaced, retired and freed
+    // as the flat-field frames are. A plan without a repairable defect has no buffer (d_plan == nullptr while set).
+    struct defect_map_t
+    {
+        bool set = false;
+        uint32_t* d_plan = nullptr;
+        uint32_t dim_x = 0, dim_y = 0;
+        uint32_t n = 0, m = 0; // repairable defects, sources
+        paris_hip_defect_stats stats{};
+        std::vector<uint32_t> row_start; // host, dim_y + 1: the sorted defect list's range per detector row
+    } defect_map;
+    std::vector<std::pair<uint32_t*, hipEvent_t>> defect_map_retired;
     // K cached by paris_hip_stage_filter (reference: thread_local static in src/filtering.cpp:42)
     float* stage_k = nullptr;
     uint32_t stage_k_size = 0;
@@ -348,7 +362,7 @@ int paris_hip_run_check(paris_hip_ctx* ctx, const std::array<uint32_t, 4>& key, 
                         const void* arg, bool* ok, bool* known);
 int paris_hip_ensure_upload_stream(paris_hip_ctx* ctx); // upload_stream + its event ring
 int paris_hip_ensure_bp_stream(paris_hip_ctx* ctx);     // bp_stream + its events
-// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip / forward_project.hip: one cheap query per
+// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip / forward_project.hip / defect_map.hip: one cheap query per
 // translation unit that makes the
 // runtime load its code object now rather than at the first launch
 void paris_hip_warm_backproject();
@@ -361,6 +375,7 @@ void paris_hip_warm_widen();
 void paris_hip_warm_redundancy_weights(); // short_scan.hip: the Parker and offset-detector kernels
 void paris_hip_warm_flat_field();
 void paris_hip_warm_forward_project();
+void paris_hip_warm_defect_map();
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
 // tail of their float rows (paris_hip_upload_projection_raw)
@@ -372,6 +387,8 @@ int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitc
                                  uint32_t row0);
 // flat_field.hip: the ctx's reference frames go, their memory freed as soon as no queued work can read them (ctx destroy: at once)
 void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying);
+// defect_map.hip: the same for the ctx's defect plan
+void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying);
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events
 int paris_hip_take_event(paris_hip_ctx* ctx, hipEvent_t* out);

@@ -5,7 +5,7 @@
 //                       <n_proj> <in.raw | lcg> <out.raw> [--no-weight] [--no-filter]
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
-//                       [--reproject frames.raw]
+//                       [--reproject frames.raw] [--defects mask.raw]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -16,6 +16,8 @@
 // that paris::weight() applies the offset-detector redundancy weight before the cosine weight.
 // --flat: the frames are intensities; dark.raw and flat.raw hold one n_col x n_row float32 frame each ("none": a zero dark).
 // set_flat_field() before the loops, so that paris::weight() turns each frame into line integrals first.
+// --defects: mask.raw holds n_col x n_row bytes, nonzero = defective pixel. set_defect_map() before the loops, so that paris::weight()
+// repairs each frame's defective pixels after the dark / flat correction and before the weights.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
 // frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
 // host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
@@ -72,7 +74,7 @@ int main(int argc, char** argv)
         bool short_scan = false;
         float scan_start = 0.f, scan_range = 0.f;
         bool offset_detector = false, offset_first = false; // offset_first: --offset-detector came before --short-scan (setter order)
-        std::string dark_path, flat_path, reproject_path;
+        std::string dark_path, flat_path, reproject_path, defects_path;
         float t_min = 1e-5f;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
@@ -106,6 +108,7 @@ int main(int argc, char** argv)
                 a += 3;
             }
             else if(!std::strcmp(argv[a], "--reproject") && a + 1 < argc) reproject_path = argv[++a];
+            else if(!std::strcmp(argv[a], "--defects") && a + 1 < argc) defects_path = argv[++a];
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
                 enable_roi = true;
@@ -161,6 +164,18 @@ int main(int argc, char** argv)
             const auto flat = read_frame(flat_path);
             const auto dark = dark_path == "none" ? std::vector<float>{} : read_frame(dark_path);
             paris::backend::set_flat_field(dark.empty() ? nullptr : dark.data(), flat.data(), det.n_row, det.n_col, t_min);
+        }
+        if(!defects_path.empty())
+        {
+            const auto n = std::size_t{det.n_row} * det.n_col;
+            auto mask = std::vector<std::uint8_t>(n);
+            std::FILE* f = std::fopen(defects_path.c_str(), "rb");
+            const bool ok = f != nullptr && std::fread(mask.data(), 1u, n, f) == n;
+            if(f != nullptr)
+                std::fclose(f);
+            if(!ok)
+                throw paris::stage_construction_error{"cannot read " + defects_path};
+            paris::backend::set_defect_map(mask.data(), det.n_row, det.n_col);
         }
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");

@@ -6,6 +6,7 @@
 //             [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
+//             [--defects mask.raw] [--defects-from-flat]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -79,6 +80,7 @@ int main(int argc, char** argv)
                             "          [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]\n"
                             "          [--slabs n] [--devices n] [--f16] [--window ramp|shepp-logan] [--batch n] [--no-row-band] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]\n"
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
+                            "          [--defects mask.raw] [--defects-from-flat]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -86,7 +88,10 @@ int main(int argc, char** argv)
                             "--offset-detector: the detector is shifted sideways (delta_s) over a full circle (half fan); each projection is\n"
                             "weighted by the offset-detector redundancy weight before the cosine weight.\n"
                             "--flat / --dark: the projections are detector counts; each is corrected with the mean flat (and dark) frame of\n"
-                            "these HIS files to line integrals -ln(max((I - D) / (F - D), t)) on the device, t = --min-transmission (1e-5).\n");
+                            "these HIS files to line integrals -ln(max((I - D) / (F - D), t)) on the device, t = --min-transmission (1e-5).\n"
+                            "--defects: n_col x n_row raw bytes, nonzero = defective pixel; --defects-from-flat: the pixels whose flat is not above\n"
+                            "their dark as well (needs --flat). Each defective pixel is replaced on the device, after the correction and before\n"
+                            "the weights, by the inverse-square-distance weighted mean of the good pixels on the nearest ring that holds one.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -110,6 +115,8 @@ int main(int argc, char** argv)
             else if(k == "--flat") po.flat_path = val();
             else if(k == "--dark") po.dark_path = val();
             else if(k == "--min-transmission") po.t_min = std::stof(val());
+            else if(k == "--defects") po.defects_path = val();
+            else if(k == "--defects-from-flat") po.defects_from_flat = true;
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -141,6 +148,9 @@ int main(int argc, char** argv)
         if(r.flat_frames != 0)
             std::printf("dark / flat correction on: %u flat frame(s), %u dark frame(s)%s, min transmission %g\n", r.flat_frames, r.dark_frames,
                         r.dark_frames == 0 ? " (zero dark)" : "", static_cast<double>(po.t_min));
+        if(r.defect_map)
+            std::printf("defect map on: %llu defective pixel(s), %llu unrepairable (no good pixel within %d)\n",
+                        static_cast<unsigned long long>(r.defects.defects), static_cast<unsigned long long>(r.defects.unrepairable), PARIS_HIP_DEFECT_R_MAX);
         std::printf("volume %u x %u x %u (%d slab%s) -> %s in %.3f s\n", r.roi_geo.dim_x, r.roi_geo.dim_y, r.roi_geo.dim_z, r.info.num,
                     r.info.num == 1 ? "" : "s", r.output_file.c_str(), r.wall_s);
         if(r.devices.size() > 1 && r.shared_source)

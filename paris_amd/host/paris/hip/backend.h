@@ -127,6 +127,7 @@ namespace paris
                 std::map<const paris_hip_ctx*, short_scan_setting> short_scans; // set_short_scan(), per device of this thread
                 std::set<const paris_hip_ctx*> flat_fields; // set_flat_field(), per device of this thread
                 std::set<const paris_hip_ctx*> offset_detectors; // set_offset_detector(), per device of this thread
+                std::set<const paris_hip_ctx*> defect_maps; // set_defect_map(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -276,6 +277,31 @@ namespace paris
             inline auto has_flat_field(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().flat_fields;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the detector of this thread's current device has defective pixels -- mask is n_col
+        // rows of n_row bytes, nonzero = defective. Until clear_defect_map(), paris::weight() replaces each defective pixel by the
+        // inverse-square-distance weighted mean of the good pixels on the nearest ring that holds one (paris_hip_set_defect_map), after
+        // a dark / flat correction and before every weight. The library keeps its own plan of the map.
+        inline auto set_defect_map(const std::uint8_t* mask, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_set_defect_map(current_ctx(), mask, n_row, n_col), "set_defect_map()");
+            detail::state().defect_maps.insert(current_ctx());
+        }
+
+        inline auto clear_defect_map() -> void
+        {
+            detail::runtime_check(paris_hip_clear_defect_map(current_ctx()), "clear_defect_map()");
+            detail::state().defect_maps.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_defect_map(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().defect_maps;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

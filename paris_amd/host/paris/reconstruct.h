@@ -92,6 +92,14 @@ namespace paris
         std::string flat_path, dark_path;
         float t_min = 1e-5f;
         std::shared_ptr<const his::mean> flat, dark; // filled by run(); dark may stay empty (a zero dark)
+        // repair of defective detector pixels (extension): --defects names a file of n_col x n_row raw bytes
+        // (nonzero = defective), read by run() before any device work (detail::load_defects); --defects-from-flat ORs in the pixels
+        // the flat-field setting finds dead (paris_hip_flat_field_dead_pixels; needs --flat). Every device ctx gets the map, and each
+        // frame is repaired after the dark / flat correction and before the weights
+        std::string defects_path;
+        bool defects_from_flat = false;
+        std::shared_ptr<const std::vector<std::uint8_t>> defect_mask; // filled by run() from --defects
+        std::size_t defect_bytes = 0; // filled by run(): what the plan of --defects occupies on a device
     };
 
     // src/task.h:33-57
@@ -207,6 +215,8 @@ namespace paris
         double drain_wait_s = 0; // the device thread waiting for the drain thread (a volume buffer to come free; the end of the run)
         std::uint64_t h2d_bytes = 0; // projection rows uploaded, in their stored pixel type (paris_hip_upload_projection_raw)
         bool two_volumes = false; // a second slab buffer was in use: slab k went to the file while slab k + 1 was reconstructed
+        bool defect_map = false;  // --defects / --defects-from-flat: a defect map was set; its counts:
+        paris_hip_defect_stats defects{};
         std::vector<std::string> skipped;
     };
 
@@ -254,7 +264,8 @@ namespace paris
             const auto half_row = (static_cast<std::size_t>(po.det_geo.n_row) * 2u + 255u) / 256u * 256u;
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references;
+            // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes;
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -569,6 +580,33 @@ namespace paris
                 rt(rc, "set_flat_field()");
             }
         }
+        // --defects / --defects-from-flat: the map of this run, the same for every device
+        bool repair = false;
+        std::uint32_t reach_rows = 0; // how far beyond a band's rows the repair reads
+        if(po.defect_mask || po.defects_from_flat)
+        {
+            const auto n_px = static_cast<std::size_t>(po.det_geo.n_row) * po.det_geo.n_col;
+            auto mask = po.defect_mask ? *po.defect_mask : std::vector<std::uint8_t>(n_px, 0u);
+            int rc = PARIS_HIP_SUCCESS;
+            if(po.defects_from_flat)
+            {
+                auto dead = std::vector<std::uint8_t>(n_px, 0u);
+                rc = paris_hip_flat_field_dead_pixels(ctx, dead.data());
+                for(std::size_t k = 0; k < n_px; ++k)
+                    mask[k] |= dead[k];
+            }
+            if(rc == PARIS_HIP_SUCCESS)
+                rc = paris_hip_set_defect_map(ctx, mask.data(), po.det_geo.n_row, po.det_geo.n_col);
+            if(rc == PARIS_HIP_SUCCESS)
+                rc = paris_hip_defect_map_info(ctx, &rep.defects);
+            if(rc != PARIS_HIP_SUCCESS)
+            {
+                paris_hip_ctx_destroy(ctx);
+                rt(rc, "set_defect_map()");
+            }
+            rep.defect_map = repair = true;
+            reach_rows = rep.defects.reach_rows;
+        }
 
         // Projections travel in groups: a group of `batch` frames is converted, uploaded, weighted and filtered one by one,
         // then backprojected with ONE fused launch (paris_hip_backproject_batch[_f16]: bit-identical to the sequence, the slab
@@ -678,6 +716,15 @@ namespace paris
                     rt(paris_hip_slab_row_band(&t.det_geo, &t.vol_geo, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, t.enable_roi,
                                                &t.roi, &band_first, &band_count), "slab_row_band()");
                 rep.band_rows += band_count;
+                // With a defect map the repair of a band's defects reads good pixels up to reach_rows rows beyond it: those rows are
+                // read, uploaded and corrected as well (clipped to the detector), and nothing else is done to them -- the band itself
+                // is repaired, weighted and filtered. Every slab's volume then equals the whole-detector run's, bit for bit.
+                std::uint32_t up_first = band_first, up_count = band_count;
+                if(repair && band_count != 0)
+                {
+                    up_first = band_first - std::min(band_first, reach_rows);
+                    up_count = std::min(n_col - (band_first + band_count), reach_rows) + band_first + band_count - up_first;
+                }
 
                 t0 = clock::now();
                 // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
@@ -699,6 +746,9 @@ namespace paris
                     if(filled == 0)
                         return;
                     const auto t1 = clock::now();
+                    if(filter_by_group && band_count != 0 && repair) // the repair before every weight, one launch for the group
+                        rt(paris_hip_defect_repair_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
+                           "defect repair");
                     if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
                         rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
                                                                  band_count, &t.det_geo), "offset-detector weight()");
@@ -733,8 +783,8 @@ namespace paris
                 // With --flat the same pass corrects them to line integrals with the reference rows of their absolute detector rows
                 // (paris_hip_upload_projection_raw_corrected): the short-scan weight and the weight + filter see line integrals.
                 const auto next_frame = [&](float* dst) {
-                    return shared ? shared->next_raw(cur, dst, n_row, n_col, band_first, band_count)
-                                  : own->next_raw(dst, n_row, n_col, band_first, band_count); // :100, straight into pinned memory
+                    return shared ? shared->next_raw(cur, dst, n_row, n_col, up_first, up_count)
+                                  : own->next_raw(dst, n_row, n_col, up_first, up_count); // :100, straight into pinned memory
                 };
                 if(po.read_ahead)
                     feed.reset(new frame_feed{ctx, next_frame, h_buf, batch, fence});
@@ -764,19 +814,21 @@ namespace paris
                         throw stage_runtime_error{"projection size does not match the detector geometry"};
                     t0 = clock::now();
                     const auto px = his::pixel_size(p.pixel);
-                    const auto band_off = static_cast<std::size_t>(band_first) * n_row * px; // bytes
-                    auto* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_buf[slot]) + static_cast<std::size_t>(band_first) * d_pitch);
+                    const auto band_off = static_cast<std::size_t>(up_first) * n_row * px; // bytes
+                    auto* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_buf[slot]) + static_cast<std::size_t>(up_first) * d_pitch);
                     if(band_count != 0)
                     {
                         // :101 -- on the upload stream, overlapping the kernels of the previous projections
                         if(po.flat)
                             rt(paris_hip_upload_projection_raw_corrected(ctx, d_buf[slot], d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off,
-                                                                         n_row * px, n_row, n_col, band_first, band_count, p.pixel), "load()");
+                                                                         n_row * px, n_row, n_col, up_first, up_count, p.pixel), "load()");
                         else
                             rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
-                                                               n_row, band_count, p.pixel), "load()");
-                        rep.h2d_bytes += static_cast<std::uint64_t>(band_count) * n_row * px;
+                                                               n_row, up_count, p.pixel), "load()");
+                        rep.h2d_bytes += static_cast<std::uint64_t>(up_count) * n_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                        if(repair && !filter_by_group) // the band's defective pixels, before every weight
+                            rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "defect repair");
                         if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
                             rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
                                                                      &t.det_geo), "offset-detector weight()");
@@ -845,6 +897,8 @@ namespace paris
         std::vector<std::string> skipped;                  // several devices: invalid files skipped by the shared source
         int batch = 0; // frames per fused launch actually used (program_options::batch, halved until the slots fit the devices)
         std::uint32_t flat_frames = 0, dark_frames = 0; // --flat / --dark: frames averaged into the reference frames (0: no correction)
+        bool defect_map = false;                        // --defects / --defects-from-flat: a map was set, with these counts
+        paris_hip_defect_stats defects{};
         double wall_s = 0;
         std::string output_file;
     };
@@ -959,6 +1013,38 @@ namespace paris
         }
     }
 
+    namespace detail
+    {
+        // --defects: n_col x n_row raw bytes, refused here -- before any device work -- when the file cannot be read or has another size;
+        // --defects-from-flat: refused without --flat
+        inline auto load_defects(program_options& po) -> void
+        {
+            if(po.defects_from_flat && po.flat_path.empty())
+                throw stage_construction_error{"--defects-from-flat needs --flat: the dead pixels are those of the flat-field setting"};
+            if(po.defects_path.empty())
+                return;
+            const auto n = static_cast<std::size_t>(po.det_geo.n_row) * po.det_geo.n_col;
+            auto mask = std::make_shared<std::vector<std::uint8_t>>(n + 1u);
+            std::FILE* f = std::fopen(po.defects_path.c_str(), "rb");
+            if(f == nullptr)
+                throw stage_construction_error{"--defects " + po.defects_path + ": cannot open the file"};
+            const auto got = std::fread(mask->data(), 1u, n + 1u, f); // (one byte more than wanted: a longer file is seen as well)
+            std::fclose(f);
+            if(got != n)
+                throw stage_construction_error{"--defects " + po.defects_path + ": the file holds " + (got > n ? "more than " : "") + std::to_string(std::min(got, n))
+                                               + " bytes, the geometry's detector has " + std::to_string(po.det_geo.n_row) + " x "
+                                               + std::to_string(po.det_geo.n_col) + " = " + std::to_string(n) + " pixels"};
+            mask->resize(n);
+            paris_hip_defect_plan* plan = nullptr;
+            auto st = paris_hip_defect_stats{};
+            rt(paris_hip_defect_plan_create(mask->data(), po.det_geo.n_row, po.det_geo.n_col, &plan), "--defects");
+            (void)paris_hip_defect_plan_stats(plan, &st);
+            (void)paris_hip_defect_plan_destroy(plan);
+            po.defect_bytes = static_cast<std::size_t>(st.device_bytes);
+            po.defect_mask = std::move(mask);
+        }
+    }
+
     // src/main.cpp:120-178
     inline auto run(const program_options& requested) -> run_report
     {
@@ -968,6 +1054,7 @@ namespace paris
         detail::load_flat_field(po);
         r.flat_frames = po.flat ? po.flat->n_frames : 0u;
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
+        detail::load_defects(po);
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1058,6 +1145,8 @@ namespace paris
         }
         else
             r.devices.push_back(reconstruct(queue, 0, out, po)); // :169
+        r.defect_map = r.devices.front().defect_map; // (every device sets the same map)
+        r.defects = r.devices.front().defects;
         r.wall_s = detail::since(start);
         return r;
     }

@@ -28,14 +28,19 @@ namespace paris
         return backend::make_volume_device(subvol_geo.dim_x, subvol_geo.dim_y, dim_z);
     }
 
-    // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with an offset detector
-    // (backend::set_offset_detector) or a short scan set (backend::set_short_scan) its redundancy weight, then the cosine weight: the
-    // only correct order (the weights are linear in the line integrals, the correction is not)
+    // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with a defect map
+    // (backend::set_defect_map) the repair of the defective pixels, then with an offset detector (backend::set_offset_detector) or a
+    // short scan set (backend::set_short_scan) its redundancy weight, then the cosine weight: the only correct order (the weights are
+    // linear in the line integrals, the correction is not; the repair averages line integrals, and every weight varies from pixel
+    // to pixel, so a repaired pixel must get its OWN weight afterwards)
     inline auto weight(backend::projection_device_type& p, const detector_geometry& det_geo) -> void
     {
         if(backend::detail::has_flat_field(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_flat_field_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y,
                                                                      0u, p.dim_y), "weight()");
+        if(backend::detail::has_defect_map(backend::current_ctx()))
+            backend::detail::runtime_check(paris_hip_defect_repair_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                        p.dim_y, 0u, p.dim_y), "weight()");
         if(backend::detail::has_offset_detector(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_stage_offset_detector_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                                                   p.dim_y, &det_geo), "weight()");
