@@ -931,19 +931,9 @@ static int defer_backproject(paris_hip_ctx* ctx, const void* d_p, bool f16, size
     {
         if(ctx->defer_ring == nullptr)
         {
-            hipError_t err = hipMalloc(reinterpret_cast<void**>(&ctx->defer_ring), 2u * ctx->defer_pitch * p_dim_y * ctx->defer_depth); // two halves
-            if(err == hipErrorOutOfMemory)
-            {
-                (void)hipGetLastError();
-                if(int rc = paris_hip_drain_device_pool(ctx))
-                    return give_back(rc);
-                err = hipMalloc(reinterpret_cast<void**>(&ctx->defer_ring), 2u * ctx->defer_pitch * p_dim_y * ctx->defer_depth);
-            }
-            if(err != hipSuccess)
-            {
-                ctx->defer_ring = nullptr;
-                return give_back(static_cast<int>(err));
-            }
+            // two halves; (defer_ring is nullptr again after a failure)
+            if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&ctx->defer_ring), 2u * ctx->defer_pitch * p_dim_y * ctx->defer_depth))
+                return give_back(rc);
             ctx->defer_slots = ctx->defer_depth;
         }
         const uint32_t half = ctx->defer_half;

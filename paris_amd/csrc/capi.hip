@@ -711,6 +711,55 @@ int paris_hip_drain_device_pool(paris_hip_ctx* ctx)
     return PARIS_HIP_SUCCESS;
 }
 
+int paris_hip_device_malloc(paris_hip_ctx* ctx, void** out, size_t bytes)
+{
+    *out = nullptr;
+    hipError_t err = hipMalloc(out, bytes);
+    if(err == hipErrorOutOfMemory)
+    {
+        // buffers parked in the pools (other sizes, a finished job's rotation) are memory too
+        (void)hipGetLastError();
+        if(int rc = paris_hip_drain_device_pool(ctx))
+            return rc;
+        err = hipMalloc(out, bytes);
+    }
+    if(err != hipSuccess)
+        *out = nullptr;
+    return static_cast<int>(err);
+}
+
+void paris_hip_retire_device_buffer(paris_hip_ctx* ctx, void* d, bool now)
+{
+    if(d == nullptr)
+        return;
+    hipEvent_t e = nullptr;
+    if(!now && paris_hip_take_event(ctx, &e) == PARIS_HIP_SUCCESS && hipEventRecord(e, ctx->stream) == hipSuccess)
+    {
+        ctx->retired.emplace_back(d, e);
+        return;
+    }
+    paris_hip_give_event(ctx, e);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+}
+
+void paris_hip_sweep_retired(paris_hip_ctx* ctx, bool all)
+{
+    auto& v = ctx->retired;
+    for(size_t k = 0; k < v.size();)
+    {
+        if(all || hipEventQuery(v[k].second) == hipSuccess)
+        {
+            (void)hipFree(v[k].first);
+            paris_hip_give_event(ctx, v[k].second);
+            v[k] = v.back();
+            v.pop_back();
+        }
+        else
+            ++k;
+    }
+}
+
 int paris_hip_release_group_references(paris_hip_ctx* ctx, uint64_t group)
 {
     int rc = PARIS_HIP_SUCCESS;
@@ -763,16 +812,8 @@ extern "C" int paris_hip_malloc_projection(paris_hip_ctx* ctx, uint32_t dim_x, u
         return rc;
     if(p == nullptr)
     {
-        hipError_t err = hipMalloc(&p, bytes);
-        if(err == hipErrorOutOfMemory)
-        {
-            // buffers parked in the pools (other sizes, a finished job's rotation) are memory too
-            (void)hipGetLastError();
-            if(int rc = paris_hip_drain_device_pool(ctx))
-                return rc;
-            err = hipMalloc(&p, bytes);
-        }
-        PARIS_HIP_TRY(err);
+        if(int rc = paris_hip_device_malloc(ctx, &p, bytes))
+            return rc;
     }
     ctx->proj_allocs[p] = paris_hip_ctx::proj_alloc{bytes, false, 0u, 0u};
     *d_ptr = static_cast<float*>(p);
@@ -928,17 +969,8 @@ extern "C" int paris_hip_malloc_volume(paris_hip_ctx* ctx, uint32_t dim_x, uint3
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     const size_t bytes = static_cast<size_t>(dim_x) * dim_y * dim_z * sizeof(float);
     void* p = nullptr;
-    {
-        hipError_t err = hipMalloc(&p, bytes);
-        if(err == hipErrorOutOfMemory) // projection buffers parked in the pool are memory too
-        {
-            (void)hipGetLastError();
-            if(int rc = paris_hip_drain_device_pool(ctx))
-                return rc;
-            err = hipMalloc(&p, bytes);
-        }
-        PARIS_HIP_TRY(err);
-    }
+    if(int rc = paris_hip_device_malloc(ctx, &p, bytes))
+        return rc;
     // make_volume_* zero-fills: src/openmp/memory.cpp:46-47, src/cuda/memory.cpp:55-56
     const hipError_t err = hipMemsetAsync(p, 0, bytes, ctx->stream);
     if(err != hipSuccess)

@@ -9,7 +9,7 @@
 #include <algorithm>
 
 #include "defect_plan.h"
-#include "paris_hip_internal.h"
+#include "frame_pass.h"
 
 namespace
 {
@@ -39,45 +39,13 @@ namespace
         const uint32_t y = q / dim_x, x = q - y * dim_x;
         frame[static_cast<size_t>(y) * pitch_f + x] = acc;
     }
-
-    // frees the retired plans no queued work can read any more (all of them when the ctx goes)
-    void sweep_retired(paris_hip_ctx* ctx, bool all)
-    {
-        auto& v = ctx->defect_map_retired;
-        for(size_t k = 0; k < v.size();)
-        {
-            if(all || hipEventQuery(v[k].second) == hipSuccess)
-            {
-                (void)hipFree(v[k].first);
-                paris_hip_give_event(ctx, v[k].second);
-                v[k] = v.back();
-                v.pop_back();
-            }
-            else
-                ++k;
-        }
-    }
 }
 
 void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying)
 {
-    paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
-    if(dm.d_plan != nullptr)
-    {
-        hipEvent_t e = nullptr;
-        // work already queued on the compute stream may still read the old plan: it goes once that has run
-        if(!destroying && paris_hip_take_event(ctx, &e) == PARIS_HIP_SUCCESS && hipEventRecord(e, ctx->stream) == hipSuccess)
-            ctx->defect_map_retired.emplace_back(dm.d_plan, e);
-        else
-        {
-            if(e != nullptr)
-                paris_hip_give_event(ctx, e);
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipFree(dm.d_plan);
-        }
-    }
-    dm = paris_hip_ctx::defect_map_t{};
-    sweep_retired(ctx, destroying); // (destroy has drained the streams already)
+    paris_hip_retire_device_buffer(ctx, ctx->defect_map.d_plan, destroying);
+    ctx->defect_map = paris_hip_ctx::defect_map_t{};
+    paris_hip_sweep_retired(ctx, destroying);
 }
 
 extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y)
@@ -94,17 +62,7 @@ extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask,
     int rc = PARIS_HIP_SUCCESS;
     if(n != 0)
     {
-        const size_t bytes = static_cast<size_t>(plan->stats.device_bytes);
-        hipError_t err = hipMalloc(reinterpret_cast<void**>(&d), bytes);
-        if(err == hipErrorOutOfMemory)
-        {
-            (void)hipGetLastError();
-            rc = paris_hip_drain_device_pool(ctx);
-            if(rc == PARIS_HIP_SUCCESS)
-                err = hipMalloc(reinterpret_cast<void**>(&d), bytes);
-        }
-        if(rc == PARIS_HIP_SUCCESS)
-            rc = static_cast<int>(err);
+        rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), static_cast<size_t>(plan->stats.device_bytes));
         // The copies run on the ctx's own auxiliary stream and are waited for there: the plan's host arrays go with this call, and
         // the new plan must be in place before any kernel of the compute stream reads it -- without waiting for the work queued
         // there, which may still read the old setting.
@@ -112,7 +70,7 @@ extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask,
             rc = paris_hip_ensure_aux(ctx);
         if(rc == PARIS_HIP_SUCCESS)
         {
-            err = hipMemcpyAsync(d, plan->defect.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
+            hipError_t err = hipMemcpyAsync(d, plan->defect.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
             if(err == hipSuccess)
                 err = hipMemcpyAsync(d + n, plan->first_source.data(), (n + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
             if(err == hipSuccess)
@@ -164,52 +122,39 @@ extern "C" int paris_hip_defect_map_info(paris_hip_ctx* ctx, paris_hip_defect_st
 extern "C" int paris_hip_defect_repair_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
                                             uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count)
 {
-    if(int rc = paris_hip_bind(ctx))
-        return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
-        return rc;
-    const paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
-    if(!dm.set || dim_x != dm.dim_x || dim_y != dm.dim_y)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
-       || row_count > dim_y - row_first)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
-    if(row_count == 0 || n_frames == 0)
-        return paris_hip_finish(ctx);
-    const uint32_t k_first = dm.row_start[row_first], k_end = dm.row_start[row_first + row_count];
-    if(k_first == k_end) // (a map without a repairable defect in the band)
-        return paris_hip_finish(ctx);
-    char* base = reinterpret_cast<char*>(d_p);
-    // (deferral by reference: a buffer the pending group reads must not be repaired before that group has run)
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
-            return rc;
-    const uint32_t* defect = dm.d_plan;
-    const uint32_t* first_source = defect + dm.n;
-    const uint32_t* source = first_source + dm.n + 1u;
-    const float* weight = reinterpret_cast<const float*>(source + dm.m);
-    const uint64_t blocks = (static_cast<uint64_t>(k_end - k_first) + DM_THREADS - 1u) / DM_THREADS;
-    for(uint64_t b0 = 0; b0 < blocks; b0 += DM_MAX_BLOCKS)
-    {
-        const uint32_t gx = static_cast<uint32_t>(std::min<uint64_t>(DM_MAX_BLOCKS, blocks - b0));
-        const uint32_t k0 = k_first + static_cast<uint32_t>(b0 * DM_THREADS);
-        for(uint32_t f0 = 0; f0 < n_frames; f0 += DM_MAX_FRAMES)
+    const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
+    uint32_t k_first = 0, k_end = 0; // the band's defects in the sorted list
+    const auto refuse = [&]() -> int {
+        const paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+        return !dm.set || dim_x != dm.dim_x || dim_y != dm.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
+    };
+    const auto idle = [&] { // (a map without a repairable defect in the band)
+        k_first = ctx->defect_map.row_start[row_first];
+        k_end = ctx->defect_map.row_start[row_first + row_count];
+        return k_first == k_end;
+    };
+    const auto launch = [&] {
+        const paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+        const uint32_t* defect = dm.d_plan;
+        const uint32_t* first_source = defect + dm.n;
+        const uint32_t* source = first_source + dm.n + 1u;
+        const float* weight = reinterpret_cast<const float*>(source + dm.m);
+        const uint64_t blocks = (static_cast<uint64_t>(k_end - k_first) + DM_THREADS - 1u) / DM_THREADS;
+        for(uint64_t b0 = 0; b0 < blocks; b0 += DM_MAX_BLOCKS)
         {
-            const uint32_t gz = std::min(DM_MAX_FRAMES, n_frames - f0);
-            hipLaunchKernelGGL(defect_repair_kernel, dim3(gx, 1u, gz), dim3(DM_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
-                               pitch / sizeof(float), dim_x, defect, first_source, source, weight, k0, k_end);
-            PARIS_HIP_TRY(hipGetLastError());
+            const uint32_t gx = static_cast<uint32_t>(std::min<uint64_t>(DM_MAX_BLOCKS, blocks - b0));
+            const uint32_t k0 = k_first + static_cast<uint32_t>(b0 * DM_THREADS);
+            for(uint32_t f0 = 0; f0 < n_frames; f0 += DM_MAX_FRAMES)
+                hipLaunchKernelGGL(defect_repair_kernel, dim3(gx, 1u, std::min(DM_MAX_FRAMES, n_frames - f0)), dim3(DM_THREADS), 0, ctx->stream,
+                                   band.frame(f0), frame_stride, pitch / sizeof(float), dim_x, defect, first_source, source, weight, k0, k_end);
         }
-    }
-    // the launch reads up to reach_rows rows beyond the band on either side
-    const uint32_t lo = row_first - std::min(row_first, dm.stats.reach_rows);
-    const uint32_t hi = row_first + row_count + std::min(dim_y - (row_first + row_count), dm.stats.reach_rows);
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(lo) * pitch, pitch * (hi - lo)))
-            return rc;
-    return paris_hip_finish(ctx);
+    };
+    const auto touched = [&] { // the launch reads up to reach_rows rows beyond the band on either side
+        const uint32_t reach = ctx->defect_map.stats.reach_rows, end = row_first + row_count;
+        const uint32_t lo = row_first - std::min(row_first, reach);
+        return paris_hip_row_range{lo, end + std::min(dim_y - end, reach) - lo};
+    };
+    return paris_hip_frame_pass(ctx, band, refuse, idle, launch, touched);
 }
 
 void paris_hip_warm_defect_map()

@@ -14,7 +14,7 @@
 #include <cmath>
 
 #include "flat_field.h"
-#include "paris_hip_internal.h"
+#include "frame_pass.h"
 
 namespace
 {
@@ -56,45 +56,13 @@ namespace
             }
         }
     }
-
-    // frees the retired reference buffers no queued work can read any more (all of them when the ctx goes)
-    void sweep_retired(paris_hip_ctx* ctx, bool all)
-    {
-        auto& v = ctx->flat_field_retired;
-        for(size_t k = 0; k < v.size();)
-        {
-            if(all || hipEventQuery(v[k].second) == hipSuccess)
-            {
-                (void)hipFree(v[k].first);
-                paris_hip_give_event(ctx, v[k].second);
-                v[k] = v.back();
-                v.pop_back();
-            }
-            else
-                ++k;
-        }
-    }
 }
 
 void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying)
 {
-    paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-    if(ff.d_ref != nullptr)
-    {
-        hipEvent_t e = nullptr;
-        // work already queued on the compute stream may still read the old frames: they go once it has run
-        if(!destroying && paris_hip_take_event(ctx, &e) == PARIS_HIP_SUCCESS && hipEventRecord(e, ctx->stream) == hipSuccess)
-            ctx->flat_field_retired.emplace_back(ff.d_ref, e);
-        else
-        {
-            if(e != nullptr)
-                paris_hip_give_event(ctx, e);
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipFree(ff.d_ref);
-        }
-    }
-    ff = paris_hip_ctx::flat_field_t{};
-    sweep_retired(ctx, destroying); // (destroy has drained the streams already)
+    paris_hip_retire_device_buffer(ctx, ctx->flat_field.d_ref, destroying);
+    ctx->flat_field = paris_hip_ctx::flat_field_t{};
+    paris_hip_sweep_retired(ctx, destroying);
 }
 
 extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark, const float* h_flat, uint32_t dim_x, uint32_t dim_y,
@@ -115,23 +83,16 @@ extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark,
         dead[k] = (!(den > 0.0) || !std::isfinite(dk) || !std::isfinite(static_cast<double>(h_flat[k]))) ? 1u : 0u;
     }
     float* d = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d), 2u * n * sizeof(float));
-    if(err == hipErrorOutOfMemory)
-    {
-        (void)hipGetLastError();
-        if(int rc = paris_hip_drain_device_pool(ctx))
-            return rc;
-        err = hipMalloc(reinterpret_cast<void**>(&d), 2u * n * sizeof(float));
-    }
-    PARIS_HIP_TRY(err);
+    if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), 2u * n * sizeof(float)))
+        return rc;
     // The copies run on the ctx's own auxiliary stream and are waited for there: the caller's arrays are pageable memory they may
     // reuse at once, and the new frames must be in place before any kernel of the compute stream reads them -- without waiting for
     // the work queued there, which may still read the old setting.
     int rc = paris_hip_ensure_aux(ctx);
     if(rc == PARIS_HIP_SUCCESS)
     {
-        err = h_dark != nullptr ? hipMemcpyAsync(d, h_dark, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream)
-                                : hipMemsetAsync(d, 0, n * sizeof(float), ctx->aux_stream);
+        hipError_t err = h_dark != nullptr ? hipMemcpyAsync(d, h_dark, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream)
+                                           : hipMemsetAsync(d, 0, n * sizeof(float), ctx->aux_stream);
         if(err == hipSuccess)
             err = hipMemcpyAsync(d + n, h_flat, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream);
         if(err == hipSuccess)
@@ -172,46 +133,31 @@ extern "C" int paris_hip_clear_flat_field(paris_hip_ctx* ctx)
 extern "C" int paris_hip_flat_field_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
                                          uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count)
 {
-    if(int rc = paris_hip_bind(ctx))
-        return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
-        return rc;
-    const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-    if(ff.d_ref == nullptr || dim_x != ff.dim_x || dim_y != ff.dim_y)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
-       || row_count > dim_y - row_first)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
-    if(row_count == 0 || n_frames == 0)
-        return paris_hip_finish(ctx);
-    char* base = reinterpret_cast<char*>(d_p);
-    // (deferral by reference: a buffer the pending group reads must not be corrected before that group has run)
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
-            return rc;
-    const bool vec = dim_x % 4u == 0 && pitch % 16u == 0 && reinterpret_cast<uintptr_t>(d_p) % 16u == 0
-                     && (n_frames == 1u || frame_stride % 16u == 0);
-    const uint32_t lanes = vec ? dim_x / 4u : dim_x;
-    const uint32_t gx = (lanes + FF_THREADS - 1u) / FF_THREADS;
-    const uint32_t gz = std::min(n_frames, FF_MAX_FRAMES);
-    const uint32_t slices = (row_count + FF_ROWS_PER_THREAD - 1u) / FF_ROWS_PER_THREAD;
-    const uint32_t gy = std::max(1u, std::min({slices, 65535u, FF_MAX_BLOCKS / std::max(1u, gx * gz)}));
-    const float* dark = ff.d_ref;
-    const float* flat = ff.d_ref + static_cast<size_t>(ff.dim_x) * ff.dim_y;
-    const dim3 grid(gx, gy, gz);
-    if(vec)
-        hipLaunchKernelGGL(flat_field_kernel<true>, grid, dim3(FF_THREADS), 0, ctx->stream, base, frame_stride, n_frames, pitch / sizeof(float),
-                           dim_x, row_first, row_first + row_count, dark, flat, ff.t_min);
-    else
-        hipLaunchKernelGGL(flat_field_kernel<false>, grid, dim3(FF_THREADS), 0, ctx->stream, base, frame_stride, n_frames, pitch / sizeof(float),
-                           dim_x, row_first, row_first + row_count, dark, flat, ff.t_min);
-    PARIS_HIP_TRY(hipGetLastError());
-    for(uint32_t f = 0; f < n_frames; ++f)
-        if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(row_first) * pitch, pitch * row_count))
-            return rc;
-    return paris_hip_finish(ctx);
+    const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
+    const auto refuse = [&]() -> int {
+        const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
+        return ff.d_ref == nullptr || dim_x != ff.dim_x || dim_y != ff.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
+    };
+    const auto launch = [&] {
+        const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
+        const bool vec = dim_x % 4u == 0 && pitch % 16u == 0 && reinterpret_cast<uintptr_t>(d_p) % 16u == 0
+                         && (n_frames == 1u || frame_stride % 16u == 0);
+        const uint32_t lanes = vec ? dim_x / 4u : dim_x;
+        const uint32_t gx = (lanes + FF_THREADS - 1u) / FF_THREADS;
+        const uint32_t gz = std::min(n_frames, FF_MAX_FRAMES);
+        const uint32_t slices = (row_count + FF_ROWS_PER_THREAD - 1u) / FF_ROWS_PER_THREAD;
+        const uint32_t gy = std::max(1u, std::min({slices, 65535u, FF_MAX_BLOCKS / std::max(1u, gx * gz)}));
+        const float* dark = ff.d_ref;
+        const float* flat = ff.d_ref + static_cast<size_t>(ff.dim_x) * ff.dim_y;
+        const dim3 grid(gx, gy, gz);
+        if(vec)
+            hipLaunchKernelGGL(flat_field_kernel<true>, grid, dim3(FF_THREADS), 0, ctx->stream, band.frame(0), frame_stride, n_frames,
+                               pitch / sizeof(float), dim_x, row_first, row_first + row_count, dark, flat, ff.t_min);
+        else
+            hipLaunchKernelGGL(flat_field_kernel<false>, grid, dim3(FF_THREADS), 0, ctx->stream, band.frame(0), frame_stride, n_frames,
+                               pitch / sizeof(float), dim_x, row_first, row_first + row_count, dark, flat, ff.t_min);
+    };
+    return paris_hip_frame_pass(ctx, band, refuse, launch);
 }
 
 void paris_hip_warm_flat_field()

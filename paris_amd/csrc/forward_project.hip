@@ -32,7 +32,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "paris_hip_internal.h"
+#include "frame_pass.h"
 
 namespace
 {
@@ -215,77 +215,70 @@ extern "C" int paris_hip_forward_project(paris_hip_ctx* ctx, const float* d_v, u
         return rc;
     if(int rc = paris_hip_flush_deferred(ctx)) // the call reads a volume: what is deferred into it comes first
         return rc;
-    if(int rc = paris_hip_flush_pending_weight(ctx)) // and writes projection buffers: an earlier weighting nobody filtered
-        return rc;
-    if(det_geo == nullptr || vol_geo == nullptr || d_p == nullptr || (d_v == nullptr && v_dim_z != 0u)
-       || (n_views != 0u && (sin_phi == nullptr || cos_phi == nullptr)))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(p_dim_x != det_geo->n_row || p_dim_y != det_geo->n_col || p_pitch < static_cast<size_t>(p_dim_x) * sizeof(float)
-       || p_pitch % sizeof(float) != 0)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(n_views > 1u && (p_stride_bytes % sizeof(float) != 0 || p_stride_bytes < p_pitch * static_cast<size_t>(p_dim_y)))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
-    if(v_dim_x != vol_geo->dim_x || v_dim_y != vol_geo->dim_y || v_offset > vol_geo->dim_z || v_dim_z > vol_geo->dim_z - v_offset)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(!positive_finite(det_geo->l_px_row) || !positive_finite(det_geo->l_px_col) || !positive_finite(vol_geo->l_vx_x)
-       || !positive_finite(vol_geo->l_vx_y) || !positive_finite(vol_geo->l_vx_z) || !positive_finite(det_geo->d_so)
-       || !std::isfinite(det_geo->d_od) || !std::isfinite(delta_s) || !std::isfinite(delta_t))
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    for(uint32_t f = 0; f < n_views; ++f)
-        if(!std::isfinite(sin_phi[f]) || !std::isfinite(cos_phi[f]))
+    // and writes projection buffers, whole frames: the rest is the frame passes' scaffold
+    const paris_hip_frame_band frames{d_p, p_pitch, p_stride_bytes, n_views, p_dim_x, p_dim_y, 0u, p_dim_y};
+    const auto refuse = [&]() -> int {
+        if(det_geo == nullptr || vol_geo == nullptr || (d_v == nullptr && v_dim_z != 0u)
+           || (n_views != 0u && (sin_phi == nullptr || cos_phi == nullptr)))
             return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    if(n_views == 0u || p_dim_x == 0u || p_dim_y == 0u || (v_dim_z == 0u && accumulate))
-        return paris_hip_finish(ctx);
-
-    char* base = reinterpret_cast<char*>(d_p);
-    for(uint32_t f = 0; f < n_views; ++f)
-        if(int rc = paris_hip_projection_guard(ctx, base + f * p_stride_bytes, p_pitch * p_dim_y, ctx->stream, true))
-            return rc;
-    fp_geometry g{};
-    g.l_px_row = det_geo->l_px_row;
-    g.l_px_col = det_geo->l_px_col;
-    g.t_half = static_cast<double>(p_dim_x) * g.l_px_row / 2.0;
-    g.z_half = static_cast<double>(p_dim_y) * g.l_px_col / 2.0;
-    g.delta_s = delta_s;
-    g.delta_t = delta_t;
-    g.d_so = det_geo->d_so;
-    g.d_sd = std::abs(static_cast<double>(det_geo->d_so)) + std::abs(static_cast<double>(det_geo->d_od));
-    g.l_vx[0] = vol_geo->l_vx_x;
-    g.l_vx[1] = vol_geo->l_vx_y;
-    g.l_vx[2] = vol_geo->l_vx_z;
-    g.dim[0] = vol_geo->dim_x;
-    g.dim[1] = vol_geo->dim_y;
-    g.dim[2] = vol_geo->dim_z;
-    g.z_first = v_offset;
-    g.z_count = v_dim_z;
-    g.n_row = p_dim_x;
-    g.n_col = p_dim_y;
-    for(uint32_t f0 = 0; f0 < n_views; f0 += FP_MAX_VIEWS)
-    {
-        const uint32_t n = std::min(n_views - f0, FP_MAX_VIEWS);
-        view_angles a{};
-        bool wide = true; // every view of the launch close to the y axis
-        for(uint32_t f = 0; f < n; ++f)
+        if(p_dim_x != det_geo->n_row || p_dim_y != det_geo->n_col)
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        if(v_dim_x != vol_geo->dim_x || v_dim_y != vol_geo->dim_y || v_offset > vol_geo->dim_z || v_dim_z > vol_geo->dim_z - v_offset)
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        if(!positive_finite(det_geo->l_px_row) || !positive_finite(det_geo->l_px_col) || !positive_finite(vol_geo->l_vx_x)
+           || !positive_finite(vol_geo->l_vx_y) || !positive_finite(vol_geo->l_vx_z) || !positive_finite(det_geo->d_so)
+           || !std::isfinite(det_geo->d_od) || !std::isfinite(delta_s) || !std::isfinite(delta_t))
+            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        for(uint32_t f = 0; f < n_views; ++f)
+            if(!std::isfinite(sin_phi[f]) || !std::isfinite(cos_phi[f]))
+                return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+        return PARIS_HIP_SUCCESS;
+    };
+    const auto idle = [&] { return v_dim_z == 0u && accumulate != 0; }; // nothing to add
+    const auto launch = [&] {
+        fp_geometry g{};
+        g.l_px_row = det_geo->l_px_row;
+        g.l_px_col = det_geo->l_px_col;
+        g.t_half = static_cast<double>(p_dim_x) * g.l_px_row / 2.0;
+        g.z_half = static_cast<double>(p_dim_y) * g.l_px_col / 2.0;
+        g.delta_s = delta_s;
+        g.delta_t = delta_t;
+        g.d_so = det_geo->d_so;
+        g.d_sd = std::abs(static_cast<double>(det_geo->d_so)) + std::abs(static_cast<double>(det_geo->d_od));
+        g.l_vx[0] = vol_geo->l_vx_x;
+        g.l_vx[1] = vol_geo->l_vx_y;
+        g.l_vx[2] = vol_geo->l_vx_z;
+        g.dim[0] = vol_geo->dim_x;
+        g.dim[1] = vol_geo->dim_y;
+        g.dim[2] = vol_geo->dim_z;
+        g.z_first = v_offset;
+        g.z_count = v_dim_z;
+        g.n_row = p_dim_x;
+        g.n_col = p_dim_y;
+        for(uint32_t f0 = 0; f0 < n_views; f0 += FP_MAX_VIEWS)
         {
-            a.sin_phi[f] = sin_phi[f0 + f];
-            a.cos_phi[f] = cos_phi[f0 + f];
-            wide = wide && std::abs(a.sin_phi[f]) >= FP_WIDE_MIN_SIN;
+            const uint32_t n = std::min(n_views - f0, FP_MAX_VIEWS);
+            view_angles a{};
+            bool wide = true; // every view of the launch close to the y axis
+            for(uint32_t f = 0; f < n; ++f)
+            {
+                a.sin_phi[f] = sin_phi[f0 + f];
+                a.cos_phi[f] = cos_phi[f0 + f];
+                wide = wide && std::abs(a.sin_phi[f]) >= FP_WIDE_MIN_SIN;
+            }
+            const uint32_t bx = wide ? 64u : 16u, by = FP_THREADS / bx;
+            const uint32_t rows_per_launch = 65535u * by; // grid.y
+            for(uint32_t r0 = 0; r0 < p_dim_y; r0 += rows_per_launch)
+            {
+                const uint32_t rows = std::min(p_dim_y - r0, rows_per_launch);
+                const dim3 grid((p_dim_x + bx - 1u) / bx, (rows + by - 1u) / by, n);
+                const auto kernel = wide ? forward_project_kernel<64u, 4u> : forward_project_kernel<16u, 16u>;
+                hipLaunchKernelGGL(kernel, grid, dim3(bx, by), wide ? 0u : lds_pad(), ctx->stream, d_v, frames.frame(f0), p_stride_bytes,
+                                   static_cast<uint32_t>(p_pitch / sizeof(float)), r0, g, a, accumulate);
+            }
         }
-        const uint32_t bx = wide ? 64u : 16u, by = FP_THREADS / bx;
-        const uint32_t rows_per_launch = 65535u * by; // grid.y
-        for(uint32_t r0 = 0; r0 < p_dim_y; r0 += rows_per_launch)
-        {
-            const uint32_t rows = std::min(p_dim_y - r0, rows_per_launch);
-            const dim3 grid((p_dim_x + bx - 1u) / bx, (rows + by - 1u) / by, n);
-            const auto kernel = wide ? forward_project_kernel<64u, 4u> : forward_project_kernel<16u, 16u>;
-            hipLaunchKernelGGL(kernel, grid, dim3(bx, by), wide ? 0u : lds_pad(), ctx->stream, d_v, base + f0 * p_stride_bytes, p_stride_bytes,
-                               static_cast<uint32_t>(p_pitch / sizeof(float)), r0, g, a, accumulate);
-        }
-    }
-    for(uint32_t f = 0; f < n_views; ++f)
-        if(int rc = paris_hip_note_projection_use(ctx, base + f * p_stride_bytes, p_pitch * p_dim_y))
-            return rc;
-    return paris_hip_finish(ctx);
+    };
+    return paris_hip_frame_pass(ctx, frames, refuse, idle, launch, [&] { return frames.rows(); });
 }
 
 extern "C" int paris_hip_stage_forward_project(paris_hip_ctx* ctx, const float* d_v, uint32_t v_dim_x, uint32_t v_dim_y, uint32_t v_dim_z,

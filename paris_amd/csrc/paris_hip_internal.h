@@ -113,8 +113,7 @@ struct paris_hip_ctx
     std::map<const void*, upload_target> upload_targets;
     // Dark / flat correction (paris_hip_set_flat_field): the reference frames on the device, the dark at d_ref, the flat right behind
     // it (each dim_x x dim_y, rows dim_x floats apart). Only kernels on the compute stream read them, so a replaced or cleared
-    // setting's buffer is retired behind an event recorded there and freed once that event has completed: at a later set / clear,
-    // or at destroy.
+    // setting's buffer is retired (`retired` below).
     struct flat_field_t
     {
         float* d_ref = nullptr;
@@ -122,7 +121,6 @@ struct paris_hip_ctx
         double t_min = 1.0;
         std::vector<uint8_t> dead; // host: 1 where D or F is not finite or F - D <= 0 (paris_hip_flat_field_dead_pixels)
     } flat_field;
-    std::vector<std::pair<float*, hipEvent_t>> flat_field_retired;
     // Defect map (paris_hip_set_defect_map): the plan of defect_plan.cpp in one device buffer -- defect[n], first_source[n + 1],
     // source[m], weight[m], 4 bytes each -- read by the repair kernel on the compute stream only, so it is replaced, retired and freed
     // as the flat-field frames are. A plan without a repairable defect has no buffer (d_plan == nullptr while set).
@@ -135,7 +133,9 @@ struct paris_hip_ctx
         paris_hip_defect_stats stats{};
         std::vector<uint32_t> row_start; // host, dim_y + 1: the sorted defect list's range per detector row
     } defect_map;
-    std::vector<std::pair<uint32_t*, hipEvent_t>> defect_map_retired;
+    // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
+    // once that event has completed -- at a later set / clear, or at destroy.
+    std::vector<std::pair<void*, hipEvent_t>> retired;
     // K cached by paris_hip_stage_filter (reference: thread_local static in src/filtering.cpp:42)
     float* stage_k = nullptr;
     uint32_t stage_k_size = 0;
@@ -339,6 +339,16 @@ void paris_hip_forget_upload_target(paris_hip_ctx* ctx, const void* d_p);
 int paris_hip_group_done(paris_hip_ctx* ctx, uint64_t group, bool wait, bool* done);
 // capi.hip: every parked device buffer goes back to the runtime (after the streams have drained): the answer to hipErrorOutOfMemory
 int paris_hip_drain_device_pool(paris_hip_ctx* ctx);
+#pragma GCC visibility push(hidden) // (library-internal: not in the dynamic symbol table)
+// capi.hip: hipMalloc; on hipErrorOutOfMemory the device pool is drained and the allocation tried once more. *out is nullptr on failure.
+int paris_hip_device_malloc(paris_hip_ctx* ctx, void** out, size_t bytes);
+// capi.hip: a ctx-owned device buffer that only kernels of the compute stream read leaves the ctx (nullptr: nothing to do). Work already
+// queued there may still read it, so it is freed by a later sweep, once that work has run; now = true, or no event to be had: the
+// stream is waited for and the buffer freed at once.
+void paris_hip_retire_device_buffer(paris_hip_ctx* ctx, void* d, bool now);
+// capi.hip: frees the retired buffers no queued work can read any more (all = true: every one -- the streams have been drained)
+void paris_hip_sweep_retired(paris_hip_ctx* ctx, bool all);
+#pragma GCC visibility pop
 // capi.hip: the pending group has been launched as `group` (0: dropped) -- buffers freed meanwhile are parked behind it, the others
 // remember it as their last reader
 int paris_hip_release_group_references(paris_hip_ctx* ctx, uint64_t group);
@@ -362,9 +372,7 @@ int paris_hip_run_check(paris_hip_ctx* ctx, const std::array<uint32_t, 4>& key, 
                         const void* arg, bool* ok, bool* known);
 int paris_hip_ensure_upload_stream(paris_hip_ctx* ctx); // upload_stream + its event ring
 int paris_hip_ensure_bp_stream(paris_hip_ctx* ctx);     // bp_stream + its events
-// backproject.hip / filter.hip / filter_fused.hip / weight.hip / validate.hip / widen.hip / short_scan.hip / flat_field.hip / forward_project.hip / defect_map.hip: one cheap query per
-// translation unit that makes the
-// runtime load its code object now rather than at the first launch
+// one cheap query per translation unit with kernels, which makes the runtime load its code object now rather than at the first launch
 void paris_hip_warm_backproject();
 void paris_hip_warm_backproject_fused();
 void paris_hip_warm_filter();

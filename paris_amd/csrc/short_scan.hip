@@ -1,5 +1,5 @@
 // Redundancy weights for gfx950: Parker's for short scans and Wang's for offset detectors. Both multiply each column of a raw
-// frame by twice a weight of that column's ray, before the cosine weighting, and share one launch scaffold (weight_columns).
+// frame by twice a weight of that column's ray, before the cosine weighting, through the frame-pass scaffold (frame_pass.h).
 //
 // Short scans.
 // A short scan covers [start, start + range] in the projection angle phi (the angle the backprojection uses), with
@@ -34,7 +34,7 @@
 // formed per column in double and rounded once, like Parker's.
 #include <cmath>
 
-#include "paris_hip_internal.h"
+#include "frame_pass.h"
 
 namespace
 {
@@ -175,39 +175,22 @@ namespace
         return PARIS_HIP_SUCCESS;
     }
 
-    // The scaffold both redundancy weights share: binds the ctx, runs an earlier weighting nobody filtered, checks the launch
-    // arguments of a column pass over rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes apart, then
-    // refuse() -- the weight's own checks -- and around launch(base, grid) the guards that keep by-reference groups sound
-    // (deferral by reference: a buffer the pending group reads must not be weighted again before that group has run).
-    // launch() enqueues on ctx->stream; grid.z is left for it to set.
+    // What the two redundancy weights add to the frame-pass scaffold (frame_pass.h): the frame's columns are the geometry's, then
+    // refuse() -- the weight's own checks; launch(grid) enqueues on ctx->stream, grid.z is left for it to set.
     template <typename Refuse, typename Launch>
-    int weight_columns(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
-                       uint32_t dim_y, uint32_t row_first, uint32_t row_count, const paris_detector_geometry* det_geo, Refuse refuse,
-                       Launch launch)
+    int weight_columns(paris_hip_ctx* ctx, const paris_hip_frame_band& b, const paris_detector_geometry* det_geo, Refuse refuse, Launch launch)
     {
-        if(int rc = paris_hip_bind(ctx))
-            return rc;
-        if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
-            return rc;
-        if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0 || row_first > dim_y
-           || row_count > dim_y - row_first || det_geo == nullptr || dim_x != det_geo->n_row)
-            return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-        if(n_frames > 1u && (frame_stride % sizeof(float) != 0 || frame_stride < pitch * static_cast<size_t>(dim_y)))
-            return PARIS_HIP_ERROR_INVALID_ARGUMENT; // frames must not overlap
-        if(int rc = refuse())
-            return rc;
-        if(dim_x == 0 || row_count == 0 || n_frames == 0)
-            return paris_hip_finish(ctx);
-        char* base = reinterpret_cast<char*>(d_p);
-        for(uint32_t f = 0; f < n_frames; ++f)
-            if(int rc = paris_hip_projection_guard(ctx, base + f * frame_stride, pitch * dim_y, ctx->stream, true))
-                return rc;
-        const uint32_t slices = (row_count + SS_ROWS_PER_THREAD - 1u) / SS_ROWS_PER_THREAD;
-        launch(base, dim3((dim_x + SS_THREADS - 1u) / SS_THREADS, slices < 65535u ? slices : 65535u, 1u));
-        for(uint32_t f = 0; f < n_frames; ++f)
-            if(int rc = paris_hip_note_projection_use(ctx, base + f * frame_stride + static_cast<size_t>(row_first) * pitch, pitch * row_count))
-                return rc;
-        return paris_hip_finish(ctx);
+        return paris_hip_frame_pass(
+            ctx, b,
+            [&]() -> int {
+                if(det_geo == nullptr || b.dim_x != det_geo->n_row)
+                    return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+                return refuse();
+            },
+            [&] {
+                const uint32_t slices = (b.row_count + SS_ROWS_PER_THREAD - 1u) / SS_ROWS_PER_THREAD;
+                launch(dim3((b.dim_x + SS_THREADS - 1u) / SS_THREADS, slices < 65535u ? slices : 65535u, 1u));
+            });
     }
 }
 
@@ -224,6 +207,7 @@ extern "C" int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, 
                                                 uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
                                                 const paris_detector_geometry* det_geo, const paris_short_scan* scan, const float* phi_deg)
 {
+    const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     double delta = 0.0;
     const auto refuse = [&]() -> int {
         if(n_frames != 0 && phi_deg == nullptr)
@@ -235,7 +219,7 @@ extern "C" int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, 
                 return PARIS_HIP_ERROR_INVALID_ARGUMENT;
         return PARIS_HIP_SUCCESS;
     };
-    const auto launch = [&](char* base, dim3 grid) {
+    const auto launch = [&](dim3 grid) {
         const column_geometry c = columns_of(*det_geo);
         for(uint32_t f0 = 0; f0 < n_frames; f0 += SS_MAX_FRAMES)
         {
@@ -250,12 +234,12 @@ extern "C" int paris_hip_short_scan_weight_rows(paris_hip_ctx* ctx, float* d_p, 
                 a.beta[f] = b * (M_PI / 180.0);
             }
             grid.z = n;
-            hipLaunchKernelGGL(short_scan_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
+            hipLaunchKernelGGL(short_scan_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, band.frame(f0), frame_stride,
                                static_cast<uint32_t>(pitch / sizeof(float)), dim_x, row_first, row_first + row_count, c.t_half, c.l_px_row,
                                c.d_sd, delta, a);
         }
     };
-    return weight_columns(ctx, d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count, det_geo, refuse, launch);
+    return weight_columns(ctx, band, det_geo, refuse, launch);
 }
 
 extern "C" int paris_hip_stage_short_scan_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
@@ -282,20 +266,21 @@ extern "C" int paris_hip_offset_detector_weight_rows(paris_hip_ctx* ctx, float* 
                                                      uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
                                                      const paris_detector_geometry* det_geo)
 {
+    const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     overlap o{};
     const auto refuse = [&]() -> int { return check_offset_detector(det_geo, &o); };
-    const auto launch = [&](char* base, dim3 grid) {
+    const auto launch = [&](dim3 grid) {
         const column_geometry c = columns_of(*det_geo);
         // the weight does not depend on the angle: no per-frame arguments, only the grid-z limit splits a batch
         for(uint32_t f0 = 0; f0 < n_frames; f0 += 65535u)
         {
             grid.z = std::min(n_frames - f0, 65535u);
-            hipLaunchKernelGGL(offset_detector_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, base + f0 * frame_stride, frame_stride,
+            hipLaunchKernelGGL(offset_detector_kernel, grid, dim3(SS_THREADS), 0, ctx->stream, band.frame(f0), frame_stride,
                                static_cast<uint32_t>(pitch / sizeof(float)), dim_x, row_first, row_first + row_count, c.t_half, c.l_px_row,
                                c.d_sd, o.sigma, o.gamma_tau);
         }
     };
-    return weight_columns(ctx, d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count, det_geo, refuse, launch);
+    return weight_columns(ctx, band, det_geo, refuse, launch);
 }
 
 extern "C" int paris_hip_stage_offset_detector_weight(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,

@@ -4,7 +4,7 @@
 // (src/cuda/weighting.cu:35-73) behind paris_hip_weight. The CUDA backend uses rsqrtf; this kernel uses
 // the OpenMP backend's IEEE sqrt + divide so the result is bit-identical to the parity target.
 // HBM-bound: 8 B per pixel (one read, one write).
-#include "paris_hip_internal.h"
+#include "frame_pass.h"
 
 namespace
 {
@@ -64,17 +64,17 @@ extern "C" int paris_hip_weight_rows(paris_hip_ctx* ctx, float* d_p, size_t pitc
                                      uint32_t row_first, uint32_t row_count, float h_min, float v_min, float d_sd,
                                      float l_px_row, float l_px_col)
 {
+    // the frame passes' argument rule and guard (frame_pass.h); the hold-back below is this pass's own
+    const paris_hip_frame_band band{d_p, pitch, 0u, 1u, dim_x, dim_y, row_first, row_count};
     if(int rc = paris_hip_bind(ctx))
         return rc;
     if(int rc = paris_hip_flush_pending_weight(ctx)) // an earlier weighting nobody filtered
         return rc;
-    if(d_p == nullptr || pitch < static_cast<size_t>(dim_x) * sizeof(float) || pitch % sizeof(float) != 0
-       || row_first > dim_y || row_count > dim_y - row_first)
+    if(!paris_hip_frame_band_valid(band))
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     if(dim_x == 0 || row_count == 0)
         return paris_hip_finish(ctx);
-    // (deferral by reference: a buffer the pending group reads must not be weighted again before that group has run)
-    if(int rc = paris_hip_projection_guard(ctx, d_p, pitch * dim_y, ctx->stream, true))
+    if(int rc = paris_hip_frame_band_guard(ctx, band))
         return rc;
     if(ctx->stage_fusion != 0 && !(ctx->flags & PARIS_HIP_CTX_SYNCHRONOUS))
     {
