@@ -564,6 +564,58 @@ int paris_hip_defect_map_info(paris_hip_ctx* ctx, paris_hip_defect_stats* out);
  * when dim_x / dim_y differ from the setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
 int paris_hip_defect_repair_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
                                  uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+
+/* Extension (no reference counterpart): removal of per-frame outlier pixels ("zingers": direct hits in the sensor, one pixel or a
+ * small blob, in one frame only) on the device, after the defect repair and before every weight.
+ * For pixel (x, y) with value p of a dim_x x dim_y frame:
+ *   window  = the nine values at (clamp(x + dx, 0, dim_x - 1), clamp(y + dy, 0, dim_y - 1)), dx, dy in {-1, 0, 1}: edges are
+ *             replicated, so there are always nine, in a 1-pixel-wide frame too; the clamp is to the FRAME, never to the band;
+ *   if any of the nine is not finite, the pixel is kept as it is;
+ *   m       = the 5th smallest of the nine by value (zeros of either sign compare equal; the sign of a zero result is unspecified);
+ *   d = p - m,  lim = threshold_abs + threshold_rel * |m|, each operation rounded once to fp32 (a multiply, then an add);
+ *   flagged = d > lim (polarity +1),  -d > lim (polarity -1),  |d| > lim (polarity 0);  a flagged pixel becomes m.
+ * Every window is read from the frame AS IT WAS BEFORE THE CALL: a replaced neighbour never feeds another pixel's median, and the
+ * result is a pure function of the input frame. The pass is NOT idempotent: a second call sees the first one's medians.
+ * A frame (the rows of one frame one call examines) in which more than max_hits pixels are flagged is left ENTIRELY as it was and
+ * counted as saturated: it means the threshold is wrong, not that the frame holds that many zingers. max_hits == 0 stands for the
+ * default max(1024, dim_x * dim_y / 256), capped at dim_x * dim_y. The count is per call and band: a frame that saturates as a
+ * whole may be filtered when it is processed band by band, so banded and whole-frame results agree only while neither saturates. */
+typedef struct paris_hip_zinger_filter {
+    float threshold_abs;   /* >= 0, frame units */
+    float threshold_rel;   /* >= 0, times |median| */
+    int polarity;          /* +1 bright (p above its surroundings), -1 dark (below), 0 both */
+    uint32_t max_hits;     /* most pixels replaced per frame; 0 = default */
+} paris_hip_zinger_filter;
+/* what paris_hip_zinger_stats reports (a struct cannot share the function's name in C) */
+typedef struct paris_hip_zinger_counts {
+    uint64_t frames;           /* frames examined (per call: each frame of a non-empty band) */
+    uint64_t replaced;         /* pixels replaced */
+    uint64_t saturated_frames; /* frames left as they were because more than max_hits pixels were flagged */
+} paris_hip_zinger_counts;
+/* one launch serves at most this many frames; calls with more loop */
+#define PARIS_HIP_ZINGER_FRAMES_MAX 64
+/* Host only, no ctx and no device: checks a setting for a detector, resolves the default max_hits (max_hits may be NULL) and reports
+ * what the setting occupies on the device while set (device_bytes may be NULL): three 64-bit accumulators and, per frame of one
+ * launch, a hit counter and max_hits (index, value) pairs. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a zero dimension, a
+ * threshold that is negative or not finite, both thresholds zero, a polarity outside {-1, 0, 1} or max_hits > dim_x * dim_y;
+ * PARIS_HIP_ERROR_UNSUPPORTED when dim_x * dim_y does not fit 32 bits. */
+int paris_hip_zinger_filter_check(const paris_hip_zinger_filter* setting, uint32_t dim_x, uint32_t dim_y, uint32_t* max_hits,
+                                  size_t* device_bytes);
+/* paris_hip_set_zinger_filter runs the check and allocates the scratch in memory the ctx owns, replacing an earlier setting (and
+ * its counts); the old scratch is freed once the work queued before the call no longer uses it. The scratch counts towards
+ * paris_hip_projection_reserve_bytes while set; paris_hip_ctx_destroy frees it. Without a setting nothing else changes. */
+int paris_hip_set_zinger_filter(paris_hip_ctx* ctx, const paris_hip_zinger_filter* setting, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_zinger_filter(paris_hip_ctx* ctx);
+/* In place on float frames: the pixels whose row lies in [row_first, row_first + row_count) of n_frames frames frame_stride bytes
+ * apart, d_p the first frame's row 0, are examined and possibly replaced. Their windows reach one row OUTSIDE the band on either
+ * side (clipped to the frame): the caller guarantees that those rows of every frame hold valid pixels. Call it on line integrals,
+ * after the defect repair and before the redundancy and cosine weights. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when
+ * dim_x / dim_y differ from the setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_zinger_filter_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* The counts since the setting was made or last reset: runs what is pending, waits for the ctx stream and reads them; reset != 0
+ * zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
+int paris_hip_zinger_stats(paris_hip_ctx* ctx, paris_hip_zinger_counts* out, int reset);
 /* paris::backproject (src/backprojection.cpp:37-69): p_idx / p_phi are projection::idx / projection::phi */
 int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_pitch, uint32_t p_dim_x,
                                 uint32_t p_dim_y, uint32_t p_idx, float p_phi, float* d_v, uint32_t v_dim_x,

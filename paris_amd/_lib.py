@@ -64,6 +64,19 @@ class DefectStats(C.Structure):
                 ("reach_rows", C.c_uint32), ("reach_cols", C.c_uint32), ("device_bytes", C.c_uint64)]
 
 
+class ZingerFilter(C.Structure):
+    """paris_hip_zinger_filter: the parameters of the zinger rule (extension)"""
+    _fields_ = [("threshold_abs", C.c_float), ("threshold_rel", C.c_float), ("polarity", C.c_int), ("max_hits", C.c_uint32)]
+
+
+class ZingerCounts(C.Structure):
+    """paris_hip_zinger_counts: what paris_hip_zinger_stats reports (extension)"""
+    _fields_ = [("frames", C.c_uint64), ("replaced", C.c_uint64), ("saturated_frames", C.c_uint64)]
+
+
+ZINGER_FRAMES_MAX = 64  # PARIS_HIP_ZINGER_FRAMES_MAX
+
+
 class SubvolumeInfo(C.Structure):
     """paris::subvolume_info (src/subvolume_information.h:30-34)"""
     _fields_ = [("geo", SubvolumeGeometry), ("num", C.c_int)]
@@ -107,6 +120,11 @@ SIGNATURES = {
     "paris_hip_clear_defect_map": (C.c_int, [_vp]),
     "paris_hip_defect_map_info": (C.c_int, [_vp, _P(DefectStats)]),
     "paris_hip_defect_repair_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_zinger_filter_check": (C.c_int, [_P(ZingerFilter), _u32, _u32, _P(_u32), _P(_sz)]),
+    "paris_hip_set_zinger_filter": (C.c_int, [_vp, _P(ZingerFilter), _u32, _u32]),
+    "paris_hip_clear_zinger_filter": (C.c_int, [_vp]),
+    "paris_hip_zinger_filter_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_zinger_stats": (C.c_int, [_vp, _P(ZingerCounts), C.c_int]),
     "paris_hip_memcpy_projection_d2h": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_memcpy_volume_h2d": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "paris_hip_memcpy_volume_d2h": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),

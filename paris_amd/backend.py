@@ -13,12 +13,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan, SubvolumeGeometry, SubvolumeInfo,
-                   VolumeGeometry, check)
+                   VolumeGeometry, ZingerCounts, ZingerFilter, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
-           "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan"]
+           "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
+           "ZingerFilter", "zinger_filter_check"]
 
 
 class Projection:
@@ -109,6 +110,24 @@ def defect_plan(mask):
     finally:
         L.paris_hip_defect_plan_destroy(plan)
     return DefectPlan(st, defect, first, source, weight)
+
+
+_POLARITIES = {"bright": 1, "dark": -1, "both": 0}
+
+
+def _zinger_setting(threshold_abs, threshold_rel, polarity, max_hits):
+    return ZingerFilter(threshold_abs, threshold_rel, _POLARITIES.get(polarity, polarity), max_hits)
+
+
+def zinger_filter_check(threshold_abs, threshold_rel, polarity, max_hits, dim_x, dim_y):
+    """Host only, no device (paris_hip_zinger_filter_check): checks a zinger-filter setting for a dim_x x dim_y detector -- polarity
+    +1 / "bright", -1 / "dark" or 0 / "both"; max_hits 0 = default -- and returns (max_hits resolved, device_bytes). Raises
+    ParisHipError for a setting the library refuses."""
+    L = _lib.load()
+    hits, nbytes = C.c_uint32(0), C.c_size_t(0)
+    zf = _zinger_setting(threshold_abs, threshold_rel, polarity, max_hits)
+    check(L.paris_hip_zinger_filter_check(C.byref(zf), dim_x, dim_y, C.byref(hits), C.byref(nbytes)), "paris_hip_zinger_filter_check")
+    return hits.value, nbytes.value
 
 
 class Backend:
@@ -368,6 +387,37 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_defect_repair_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_defect_repair_rows")
+
+    # ---- zinger filter ----------------------------------------------------------
+    zinger_filter_check = staticmethod(zinger_filter_check)
+
+    def set_zinger_filter(self, threshold_abs, threshold_rel, polarity, dim_x, dim_y, max_hits=0):
+        """paris_hip_set_zinger_filter for a dim_x x dim_y detector: zinger_filter_rows() then replaces every pixel that differs from
+        the median m of its 3 x 3 window (edges replicated) by more than threshold_abs + threshold_rel * |m| -- above it (polarity +1 /
+        "bright"), below it (-1 / "dark") or either (0 / "both") -- with m, unless more than max_hits (0 = default) pixels of the
+        frame are flagged. Replaces an earlier setting and its counts safely: work already queued keeps the old one."""
+        zf = _zinger_setting(threshold_abs, threshold_rel, polarity, max_hits)
+        check(self._L.paris_hip_set_zinger_filter(self._ctx, C.byref(zf), dim_x, dim_y), "paris_hip_set_zinger_filter")
+
+    def clear_zinger_filter(self):
+        """paris_hip_clear_zinger_filter: no zinger filter from here on"""
+        check(self._L.paris_hip_clear_zinger_filter(self._ctx), "paris_hip_clear_zinger_filter")
+
+    def zinger_filter_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """The rule of set_zinger_filter() in place on float frames (paris_hip_zinger_filter_rows): the pixels in rows [row_first,
+        row_first + row_count) of n_frames frames frame_stride bytes apart starting at p. Windows reach one row outside the band:
+        those rows must hold valid pixels. Every window is read from the frame as it was before the call; not idempotent. Call it
+        after the defect repair, before every weight."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_zinger_filter_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_zinger_filter_rows")
+
+    def zinger_stats(self, reset=False):
+        """The ZingerCounts since set_zinger_filter() or the last reset (paris_hip_zinger_stats): frames, replaced, saturated_frames.
+        Waits for the ctx stream."""
+        st = ZingerCounts()
+        check(self._L.paris_hip_zinger_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_zinger_stats")
+        return st
 
     def copy_d2h(self, d, h):
         if isinstance(d, Projection):

@@ -1016,6 +1016,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += 2u * sizeof(float) * static_cast<size_t>(ctx->flat_field.dim_x) * ctx->flat_field.dim_y;
     if(ctx->defect_map.set) // the plan of paris_hip_set_defect_map
         total += static_cast<size_t>(ctx->defect_map.stats.device_bytes);
+    if(ctx->zinger.set) // the scratch of paris_hip_set_zinger_filter
+        total += ctx->zinger.device_bytes;
     *bytes = total;
     return PARIS_HIP_SUCCESS;
 }

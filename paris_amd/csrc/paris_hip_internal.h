@@ -133,6 +133,18 @@ struct paris_hip_ctx
         paris_hip_defect_stats stats{};
         std::vector<uint32_t> row_start; // host, dim_y + 1: the sorted defect list's range per detector row
     } defect_map;
+    // Zinger filter (paris_hip_set_zinger_filter): the rule with max_hits resolved, and one device buffer -- three 64-bit accumulators
+    // (padded to 32 bytes), `frames` x max_hits (index, value) pairs, `frames` hit counters -- read and written by the kernels of
+    // zinger.hip on the compute stream only, so it is replaced, retired and freed as the defect plan is.
+    struct zinger_t
+    {
+        bool set = false;
+        paris_hip_zinger_filter rule{};
+        uint32_t dim_x = 0, dim_y = 0;
+        uint32_t frames = 0; // frames one launch serves
+        size_t device_bytes = 0;
+        char* d_scratch = nullptr;
+    } zinger;
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
     std::vector<std::pair<void*, hipEvent_t>> retired;
@@ -384,6 +396,9 @@ void paris_hip_warm_redundancy_weights(); // short_scan.hip: the Parker and offs
 void paris_hip_warm_flat_field();
 void paris_hip_warm_forward_project();
 void paris_hip_warm_defect_map();
+#pragma GCC visibility push(hidden)
+void paris_hip_warm_zinger();
+#pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
 // tail of their float rows (paris_hip_upload_projection_raw)
@@ -397,6 +412,10 @@ int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitc
 void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying);
 // defect_map.hip: the same for the ctx's defect plan
 void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying);
+#pragma GCC visibility push(hidden)
+// zinger.hip: the same for the zinger filter's scratch
+void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying);
+#pragma GCC visibility pop
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events
 int paris_hip_take_event(paris_hip_ctx* ctx, hipEvent_t* out);

@@ -5,7 +5,7 @@
 //                       <n_proj> <in.raw | lcg> <out.raw> [--no-weight] [--no-filter]
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
-//                       [--reproject frames.raw] [--defects mask.raw]
+//                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -18,6 +18,8 @@
 // set_flat_field() before the loops, so that paris::weight() turns each frame into line integrals first.
 // --defects: mask.raw holds n_col x n_row bytes, nonzero = defective pixel. set_defect_map() before the loops, so that paris::weight()
 // repairs each frame's defective pixels after the dark / flat correction and before the weights.
+// --zingers: threshold_abs, threshold_rel and the polarity (1 bright, -1 dark, 0 both) of the zinger rule. set_zinger_filter() before the
+// loops, so that paris::weight() removes each frame's outlier pixels after the repair and before the weights.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
 // frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
 // host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
@@ -76,6 +78,9 @@ int main(int argc, char** argv)
         bool offset_detector = false, offset_first = false; // offset_first: --offset-detector came before --short-scan (setter order)
         std::string dark_path, flat_path, reproject_path, defects_path;
         float t_min = 1e-5f;
+        bool zingers = false;
+        float zinger_abs = 0.f, zinger_rel = 0.f;
+        int zinger_polarity = 1;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
         auto vol_geo = paris::calculate_volume_geometry(det);
@@ -109,6 +114,14 @@ int main(int argc, char** argv)
             }
             else if(!std::strcmp(argv[a], "--reproject") && a + 1 < argc) reproject_path = argv[++a];
             else if(!std::strcmp(argv[a], "--defects") && a + 1 < argc) defects_path = argv[++a];
+            else if(!std::strcmp(argv[a], "--zingers") && a + 3 < argc)
+            {
+                zingers = true;
+                zinger_abs = std::strtof(argv[a + 1], nullptr);
+                zinger_rel = std::strtof(argv[a + 2], nullptr);
+                zinger_polarity = std::atoi(argv[a + 3]);
+                a += 3;
+            }
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
                 enable_roi = true;
@@ -177,6 +190,8 @@ int main(int argc, char** argv)
                 throw paris::stage_construction_error{"cannot read " + defects_path};
             paris::backend::set_defect_map(mask.data(), det.n_row, det.n_col);
         }
+        if(zingers)
+            paris::backend::set_zinger_filter(zinger_abs, zinger_rel, zinger_polarity, det.n_row, det.n_col);
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 

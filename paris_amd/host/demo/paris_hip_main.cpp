@@ -6,7 +6,7 @@
 //             [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
-//             [--defects mask.raw] [--defects-from-flat]
+//             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -80,7 +80,7 @@ int main(int argc, char** argv)
                             "          [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]\n"
                             "          [--slabs n] [--devices n] [--f16] [--window ramp|shepp-logan] [--batch n] [--no-row-band] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]\n"
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
-                            "          [--defects mask.raw] [--defects-from-flat]\n"
+                            "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -91,7 +91,10 @@ int main(int argc, char** argv)
                             "these HIS files to line integrals -ln(max((I - D) / (F - D), t)) on the device, t = --min-transmission (1e-5).\n"
                             "--defects: n_col x n_row raw bytes, nonzero = defective pixel; --defects-from-flat: the pixels whose flat is not above\n"
                             "their dark as well (needs --flat). Each defective pixel is replaced on the device, after the correction and before\n"
-                            "the weights, by the inverse-square-distance weighted mean of the good pixels on the nearest ring that holds one.\n");
+                            "the weights, by the inverse-square-distance weighted mean of the good pixels on the nearest ring that holds one.\n"
+                            "--zingers: every pixel that differs from the median m of its 3 x 3 window by more than ABS + REL * |m| is replaced by\n"
+                            "m on the device, after the repair and before the weights -- pixels above m (bright: the default), below it (dark: the\n"
+                            "default with --flat) or both; a frame with more flagged pixels than 1/256 of the detector (1024 at least) is left as it is.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -117,6 +120,8 @@ int main(int argc, char** argv)
             else if(k == "--min-transmission") po.t_min = std::stof(val());
             else if(k == "--defects") po.defects_path = val();
             else if(k == "--defects-from-flat") po.defects_from_flat = true;
+            else if(k == "--zingers") paris::detail::parse_zingers(val(), po);
+            else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -151,6 +156,10 @@ int main(int argc, char** argv)
         if(r.defect_map)
             std::printf("defect map on: %llu defective pixel(s), %llu unrepairable (no good pixel within %d)\n",
                         static_cast<unsigned long long>(r.defects.defects), static_cast<unsigned long long>(r.defects.unrepairable), PARIS_HIP_DEFECT_R_MAX);
+        if(r.zinger_filter)
+            std::printf("zinger filter on: %llu frame band(s) examined, %llu pixel(s) replaced, %llu saturated (left as they were)\n",
+                        static_cast<unsigned long long>(r.zingers.frames), static_cast<unsigned long long>(r.zingers.replaced),
+                        static_cast<unsigned long long>(r.zingers.saturated_frames));
         std::printf("volume %u x %u x %u (%d slab%s) -> %s in %.3f s\n", r.roi_geo.dim_x, r.roi_geo.dim_y, r.roi_geo.dim_z, r.info.num,
                     r.info.num == 1 ? "" : "s", r.output_file.c_str(), r.wall_s);
         if(r.devices.size() > 1 && r.shared_source)

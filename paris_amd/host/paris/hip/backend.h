@@ -128,6 +128,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> flat_fields; // set_flat_field(), per device of this thread
                 std::set<const paris_hip_ctx*> offset_detectors; // set_offset_detector(), per device of this thread
                 std::set<const paris_hip_ctx*> defect_maps; // set_defect_map(), per device of this thread
+                std::set<const paris_hip_ctx*> zinger_filters; // set_zinger_filter(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -302,6 +303,34 @@ namespace paris
             inline auto has_defect_map(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().defect_maps;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the frames of this thread's current device (n_row x n_col pixels) hold zingers --
+        // direct hits in the sensor, in one frame only. Until clear_zinger_filter(), paris::weight() replaces every pixel that differs
+        // from the median m of its 3 x 3 window by more than threshold_abs + threshold_rel * |m| -- above it (polarity +1), below it
+        // (-1) or either (0) -- with m, unless more than max_hits (0 = default) pixels of the frame are flagged
+        // (paris_hip_set_zinger_filter), after the defect repair and before every weight.
+        inline auto set_zinger_filter(float threshold_abs, float threshold_rel, int polarity, std::uint32_t n_row, std::uint32_t n_col,
+                                      std::uint32_t max_hits = 0u) -> void
+        {
+            const auto setting = paris_hip_zinger_filter{threshold_abs, threshold_rel, polarity, max_hits};
+            detail::runtime_check(paris_hip_set_zinger_filter(current_ctx(), &setting, n_row, n_col), "set_zinger_filter()");
+            detail::state().zinger_filters.insert(current_ctx());
+        }
+
+        inline auto clear_zinger_filter() -> void
+        {
+            detail::runtime_check(paris_hip_clear_zinger_filter(current_ctx()), "clear_zinger_filter()");
+            detail::state().zinger_filters.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_zinger_filter(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().zinger_filters;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

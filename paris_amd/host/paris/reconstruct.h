@@ -100,6 +100,14 @@ namespace paris
         bool defects_from_flat = false;
         std::shared_ptr<const std::vector<std::uint8_t>> defect_mask; // filled by run() from --defects
         std::size_t defect_bytes = 0; // filled by run(): what the plan of --defects occupies on a device
+        // removal of per-frame outlier pixels (extension): --zingers ABS[:REL] and --zinger-polarity
+        // bright|dark|both (default: dark with --flat, where a hit's high count is a deep negative line integral, else bright), checked
+        // by run() before any device work (detail::check_zingers). Every device ctx gets the setting, and each frame is filtered after
+        // the defect repair and before the weights
+        bool zingers = false;
+        float zinger_abs = 0.f, zinger_rel = 0.f;
+        int zinger_polarity = 2;      // +1 bright, -1 dark, 0 both; 2: the default, resolved by run()
+        std::size_t zinger_bytes = 0; // filled by run(): what the setting occupies on a device
     };
 
     // src/task.h:33-57
@@ -217,6 +225,8 @@ namespace paris
         bool two_volumes = false; // a second slab buffer was in use: slab k went to the file while slab k + 1 was reconstructed
         bool defect_map = false;  // --defects / --defects-from-flat: a defect map was set; its counts:
         paris_hip_defect_stats defects{};
+        bool zinger_filter = false; // --zingers: a zinger filter was set; its counts over this device's tasks:
+        paris_hip_zinger_counts zingers{};
         std::vector<std::string> skipped;
     };
 
@@ -265,7 +275,7 @@ namespace paris
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
             // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes;
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes;
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -607,6 +617,19 @@ namespace paris
             rep.defect_map = repair = true;
             reach_rows = rep.defects.reach_rows;
         }
+        // --zingers: the rule of this run, the same for every device
+        if(po.zingers)
+        {
+            const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
+            const int rc = paris_hip_set_zinger_filter(ctx, &setting, po.det_geo.n_row, po.det_geo.n_col);
+            if(rc != PARIS_HIP_SUCCESS)
+            {
+                paris_hip_ctx_destroy(ctx);
+                rt(rc, "set_zinger_filter()");
+            }
+            rep.zinger_filter = true;
+        }
+        const std::uint32_t zinger_rows = po.zingers ? 1u : 0u; // how far beyond a band's rows the zinger filter reads
 
         // Projections travel in groups: a group of `batch` frames is converted, uploaded, weighted and filtered one by one,
         // then backprojected with ONE fused launch (paris_hip_backproject_batch[_f16]: bit-identical to the sequence, the slab
@@ -719,11 +742,20 @@ namespace paris
                 // With a defect map the repair of a band's defects reads good pixels up to reach_rows rows beyond it: those rows are
                 // read, uploaded and corrected as well (clipped to the detector), and nothing else is done to them -- the band itself
                 // is repaired, weighted and filtered. Every slab's volume then equals the whole-detector run's, bit for bit.
-                std::uint32_t up_first = band_first, up_count = band_count;
-                if(repair && band_count != 0)
+                // With --zingers the windows of the band's pixels reach one row beyond it: the rows read, uploaded and corrected are the
+                // band widened by 1 -- by reach_rows + 1 with a defect map, whose repair then covers the band widened by 1, so that a
+                // window on the band's edge sees the repaired pixels the whole-detector run sees -- and the zinger filter covers the band
+                // itself. The extra rows are never weighted or filtered. (Saturation is counted per band, against a max_hits made for
+                // the whole detector: the slabs' volumes equal the whole-detector run's only while no frame saturates in either.)
+                const auto widened = [&](std::uint32_t by, std::uint32_t& first, std::uint32_t& count) {
+                    first = band_first - std::min(band_first, by);
+                    count = std::min(n_col - (band_first + band_count), by) + band_first + band_count - first;
+                };
+                std::uint32_t up_first = band_first, up_count = band_count, fix_first = band_first, fix_count = band_count;
+                if(band_count != 0)
                 {
-                    up_first = band_first - std::min(band_first, reach_rows);
-                    up_count = std::min(n_col - (band_first + band_count), reach_rows) + band_first + band_count - up_first;
+                    widened((repair ? reach_rows : 0u) + zinger_rows, up_first, up_count);
+                    widened(zinger_rows, fix_first, fix_count);
                 }
 
                 t0 = clock::now();
@@ -747,8 +779,11 @@ namespace paris
                         return;
                     const auto t1 = clock::now();
                     if(filter_by_group && band_count != 0 && repair) // the repair before every weight, one launch for the group
-                        rt(paris_hip_defect_repair_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
+                        rt(paris_hip_defect_repair_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count),
                            "defect repair");
+                    if(filter_by_group && band_count != 0 && po.zingers) // then the zinger filter, one call for the group
+                        rt(paris_hip_zinger_filter_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
+                           "zinger filter");
                     if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
                         rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
                                                                  band_count, &t.det_geo), "offset-detector weight()");
@@ -828,7 +863,9 @@ namespace paris
                         rep.h2d_bytes += static_cast<std::uint64_t>(up_count) * n_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
                         if(repair && !filter_by_group) // the band's defective pixels, before every weight
-                            rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "defect repair");
+                            rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, fix_first, fix_count), "defect repair");
+                        if(po.zingers && !filter_by_group) // then the band's outlier pixels
+                            rt(paris_hip_zinger_filter_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "zinger filter");
                         if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
                             rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
                                                                      &t.det_geo), "offset-detector weight()");
@@ -874,6 +911,8 @@ namespace paris
             const auto t_end = clock::now();
             drain->finish();
             rep.drain_wait_s += since(t_end);
+            if(po.zingers)
+                rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
             rep.drain_s = drain->drain_seconds();
             rep.save_s = drain->save_seconds();
         }
@@ -899,6 +938,8 @@ namespace paris
         std::uint32_t flat_frames = 0, dark_frames = 0; // --flat / --dark: frames averaged into the reference frames (0: no correction)
         bool defect_map = false;                        // --defects / --defects-from-flat: a map was set, with these counts
         paris_hip_defect_stats defects{};
+        bool zinger_filter = false;                     // --zingers: the filter was on; its counts over all devices and slabs (a
+        paris_hip_zinger_counts zingers{};              // frame counts once per slab: each slab filters its own row band)
         double wall_s = 0;
         std::string output_file;
     };
@@ -1045,6 +1086,61 @@ namespace paris
         }
     }
 
+    namespace detail
+    {
+        // --zingers / --zinger-polarity: the default polarity is resolved and the setting checked here, before any device work
+        inline auto check_zingers(program_options& po) -> void
+        {
+            if(!po.zingers)
+            {
+                if(po.zinger_polarity != 2)
+                    throw stage_construction_error{"--zinger-polarity needs --zingers"};
+                return;
+            }
+            if(po.zinger_polarity == 2)
+                po.zinger_polarity = po.flat_path.empty() ? 1 : -1;
+            const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
+            const int rc = paris_hip_zinger_filter_check(&setting, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.zinger_bytes);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--zingers: the detector has more than 2^32 - 1 pixels"};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--zingers ABS[:REL]: the thresholds must be finite, not negative and not both zero (got "
+                                               + std::to_string(po.zinger_abs) + ":" + std::to_string(po.zinger_rel) + ")"};
+        }
+
+        // --zingers ABS[:REL] as typed; refuses anything that is not one or two numbers
+        inline auto parse_zingers(const std::string& v, program_options& po) -> void
+        {
+            const auto number = [&v](const std::string& t) -> float {
+                std::size_t used = 0;
+                float x = 0.f;
+                try
+                {
+                    x = std::stof(t, &used);
+                }
+                catch(const std::exception&)
+                {
+                    used = 0;
+                }
+                if(t.empty() || used != t.size())
+                    throw stage_construction_error{"--zingers ABS[:REL]: cannot read '" + v + "'"};
+                return x;
+            };
+            const auto colon = v.find(':');
+            po.zinger_abs = number(v.substr(0, colon));
+            po.zinger_rel = colon == std::string::npos ? 0.f : number(v.substr(colon + 1u));
+            po.zingers = true;
+        }
+
+        inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
+        {
+            if(v == "bright") po.zinger_polarity = 1;
+            else if(v == "dark") po.zinger_polarity = -1;
+            else if(v == "both") po.zinger_polarity = 0;
+            else throw stage_construction_error{"--zinger-polarity bright|dark|both: unknown polarity " + v};
+        }
+    }
+
     // src/main.cpp:120-178
     inline auto run(const program_options& requested) -> run_report
     {
@@ -1055,6 +1151,7 @@ namespace paris
         r.flat_frames = po.flat ? po.flat->n_frames : 0u;
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         detail::load_defects(po);
+        detail::check_zingers(po);
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1147,6 +1244,13 @@ namespace paris
             r.devices.push_back(reconstruct(queue, 0, out, po)); // :169
         r.defect_map = r.devices.front().defect_map; // (every device sets the same map)
         r.defects = r.devices.front().defects;
+        for(const auto& d : r.devices)
+        {
+            r.zinger_filter = r.zinger_filter || d.zinger_filter;
+            r.zingers.frames += d.zingers.frames;
+            r.zingers.replaced += d.zingers.replaced;
+            r.zingers.saturated_frames += d.zingers.saturated_frames;
+        }
         r.wall_s = detail::since(start);
         return r;
     }
