@@ -616,6 +616,52 @@ int paris_hip_zinger_filter_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, s
 /* The counts since the setting was made or last reset: runs what is pending, waits for the ctx stream and reads them; reset != 0
  * zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
 int paris_hip_zinger_stats(paris_hip_ctx* ctx, paris_hip_zinger_counts* out, int reset);
+/* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
+ * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
+ * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter
+ * acts as if each row q (n = dim_x pixels, as the transform sees it) continued to the left as a * t(k) and to the right as b * t(k),
+ * k = 1 .. W pixels beyond the edge. No extended signal is built: the filter is linear, so the filtered extended row, restricted to
+ * the detector, is the zero-padded result plus a rank-2 update,
+ *   out[s] = F(q)[s] + a * c[s] + b * c[n - 1 - s],
+ * with ONE vector c per (n, tau, W), computed on the host. It has no circular wrap, whatever the taper length.
+ *   setting  edge_pixels m in {1, 2, 4, 8}, taper_pixels W in [1, 16384];
+ *   kernel   g[d] = -1 / (2 pi^2 d^2 tau) for odd d >= 1, 0 for even d >= 2 (g[0] is not used): the spatial kernel of the
+ *            reference's ramp (make_filter_real, src/openmp/filtering.cpp:52-73) times tau;
+ *   taper    t(k) = cos^2(pi k / (2 (W + 1))), k = 1 .. W;
+ *   response c[s] = sum_{k = 1 .. W} t(k) * g[s + k], s = 0 .. n - 1, summed in double in ascending k and rounded once to fp32;
+ *            it depends on n, tau and W only. c <= 0 everywhere. g vanishes at even distances, so c is two interleaved
+ *            sequences, even s and odd s: each increases towards 0, but c is not monotone from one s to the next, and with
+ *            W = 1 every odd c[s] is exactly 0;
+ *   means    a = ((q[0] + q[1]) + ...) * (1 / m) over the first m pixels, b the same over the last m pixels in ascending index: a
+ *            sequential fp32 sum followed by an exact scaling. q is the row as the transform sees it: after the cosine weight when
+ *            the weight rides in the load, the stored pixels otherwise. dim_x < m is PARIS_HIP_ERROR_INVALID_ARGUMENT;
+ *   store    with y the value the plain filter stores (v * (1 / filter_size)), the stored pixel is
+ *            fmaf(b, c[n - 1 - s], fmaf(a, c[s], y)); the half-precision output is that fp32 value rounded to nearest even.
+ * Rows whose a and b are both 0 are therefore bit-identical to the plain filter's -- an untruncated scan with m = 1 is unchanged.
+ * c is always the plain ramp's response, also for a Shepp-Logan K. That is a limit, not an equivalence: the window changes the
+ * kernel's nearest taps most, so the windowed response differs from c by 0.19 of max|c| at s = 0, 0.08 and 0.03 at s = 1 and 2, and
+ * by less than 0.003 from s = 8 (n = 2048, W = 512) -- with a Shepp-Logan K the outermost 2 to 3 pixels of a
+ * truncated row carry that error. tau is the one the K was made with: with a setting in force a filter call with a K this ctx did not make is PARIS_HIP_ERROR_UNSUPPORTED.
+ * Known limit: a low-frequency offset remains inside the field of view, and longer tapers are not better. */
+typedef struct paris_hip_row_extension {
+    uint32_t edge_pixels;  /* m: pixels averaged at either end of a row: 1, 2, 4 or 8 */
+    uint32_t taper_pixels; /* W: length of the cos^2 taper beyond either end, 1 .. 16384 */
+} paris_hip_row_extension;
+/* Host only, no ctx. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, m outside {1, 2, 4, 8}, W outside [1, 16384], dim_x == 0 or
+ * dim_x < m. */
+int paris_hip_row_extension_check(const paris_hip_row_extension* setting, uint32_t dim_x);
+/* Host only: c[0 .. dim_x) as stated above -- the single implementation of c; the device copies are made from it.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, for a tau that is not finite or <= 0, or a NULL c. */
+int paris_hip_row_extension_response(const paris_hip_row_extension* setting, uint32_t dim_x, float tau, float* c);
+/* Both first run whatever is held back or pending -- a held-back weighting or filter, the pending backprojection group -- so no row
+ * queued before the call sees the change. From then on every filter path honours the setting: paris_hip_apply_filter (with a
+ * held-back weighting fused into its load or not, the radix-16 and the radix-2 kernel), paris_hip_weight_filter_rows / _batch, the
+ * paris_hip_stage_* forms, the half-precision output and filter deferral. The device copies of c are made on first use and cached
+ * per (dim_x, tau, W); they count towards paris_hip_projection_reserve_bytes while set, are freed once the work queued before a
+ * set / clear no longer reads them, and by paris_hip_ctx_destroy. Without a setting nothing changes.
+ * paris_hip_set_row_extension: PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL ctx or a setting the check refuses for dim_x = 8. */
+int paris_hip_set_row_extension(paris_hip_ctx* ctx, const paris_hip_row_extension* setting);
+int paris_hip_clear_row_extension(paris_hip_ctx* ctx);
 /* paris::backproject (src/backprojection.cpp:37-69): p_idx / p_phi are projection::idx / projection::phi */
 int paris_hip_stage_backproject(paris_hip_ctx* ctx, const float* d_p, size_t p_pitch, uint32_t p_dim_x,
                                 uint32_t p_dim_y, uint32_t p_idx, float p_phi, float* d_v, uint32_t v_dim_x,

@@ -77,6 +77,11 @@ class ZingerCounts(C.Structure):
 ZINGER_FRAMES_MAX = 64  # PARIS_HIP_ZINGER_FRAMES_MAX
 
 
+class RowExtension(C.Structure):
+    """paris_hip_row_extension: the row extension for truncated projections (extension)"""
+    _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
+
+
 class SubvolumeInfo(C.Structure):
     """paris::subvolume_info (src/subvolume_information.h:30-34)"""
     _fields_ = [("geo", SubvolumeGeometry), ("num", C.c_int)]
@@ -125,6 +130,10 @@ SIGNATURES = {
     "paris_hip_clear_zinger_filter": (C.c_int, [_vp]),
     "paris_hip_zinger_filter_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_zinger_stats": (C.c_int, [_vp, _P(ZingerCounts), C.c_int]),
+    "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
+    "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
+    "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),
+    "paris_hip_clear_row_extension": (C.c_int, [_vp]),
     "paris_hip_memcpy_projection_d2h": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _u32, _u32]),
     "paris_hip_memcpy_volume_h2d": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "paris_hip_memcpy_volume_d2h": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _u32]),

@@ -12,14 +12,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, ShortScan, SubvolumeGeometry, SubvolumeInfo,
-                   VolumeGeometry, ZingerCounts, ZingerFilter, check)
+from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RowExtension, ShortScan, SubvolumeGeometry,
+                   SubvolumeInfo, VolumeGeometry, ZingerCounts, ZingerFilter, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
            "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
-           "ZingerFilter", "zinger_filter_check"]
+           "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response"]
 
 
 class Projection:
@@ -128,6 +128,23 @@ def zinger_filter_check(threshold_abs, threshold_rel, polarity, max_hits, dim_x,
     zf = _zinger_setting(threshold_abs, threshold_rel, polarity, max_hits)
     check(L.paris_hip_zinger_filter_check(C.byref(zf), dim_x, dim_y, C.byref(hits), C.byref(nbytes)), "paris_hip_zinger_filter_check")
     return hits.value, nbytes.value
+
+
+def row_extension_check(edge_pixels, taper_pixels, dim_x):
+    """Host only, no device (paris_hip_row_extension_check): raises ParisHipError unless edge_pixels is 1, 2, 4 or 8, taper_pixels lies
+    in [1, 16384] and rows of dim_x pixels hold at least edge_pixels."""
+    re = RowExtension(edge_pixels, taper_pixels)
+    check(_lib.load().paris_hip_row_extension_check(C.byref(re), dim_x), "paris_hip_row_extension_check")
+
+
+def row_extension_response(edge_pixels, taper_pixels, dim_x, tau):
+    """Host only, no device (paris_hip_row_extension_response): the ramp's response c[dim_x] (float32) to the cos^2 taper of
+    taper_pixels pixels beyond a row's edge, for the pixel pitch tau -- what the filter adds at its store, times the edge means
+    (DESIGN.md section 4.11)."""
+    re = RowExtension(edge_pixels, taper_pixels)
+    c = np.empty(max(int(dim_x), 0), np.float32)
+    check(_lib.load().paris_hip_row_extension_response(C.byref(re), dim_x, tau, c.ctypes.data), "paris_hip_row_extension_response")
+    return c
 
 
 class Backend:
@@ -411,6 +428,21 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_zinger_filter_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_zinger_filter_rows")
+
+    # ---- row extension -----------------------------------------------------------
+    row_extension_check = staticmethod(row_extension_check)
+    row_extension_response = staticmethod(row_extension_response)
+
+    def set_row_extension(self, edge_pixels, taper_pixels):
+        """paris_hip_set_row_extension: from here on every row filter acts as if each row continued beyond either edge as the mean of
+        its edge_pixels (1, 2, 4 or 8) outermost pixels times a cos^2 taper of taper_pixels pixels -- for laterally truncated
+        projections. Runs what is held back or pending first."""
+        re = RowExtension(edge_pixels, taper_pixels)
+        check(self._L.paris_hip_set_row_extension(self._ctx, C.byref(re)), "paris_hip_set_row_extension")
+
+    def clear_row_extension(self):
+        """paris_hip_clear_row_extension: zero padding from here on"""
+        check(self._L.paris_hip_clear_row_extension(self._ctx), "paris_hip_clear_row_extension")
 
     def zinger_stats(self, reset=False):
         """The ZingerCounts since set_zinger_filter() or the last reset (paris_hip_zinger_stats): frames, replaced, saturated_frames.

@@ -1018,6 +1018,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += static_cast<size_t>(ctx->defect_map.stats.device_bytes);
     if(ctx->zinger.set) // the scratch of paris_hip_set_zinger_filter
         total += ctx->zinger.device_bytes;
+    if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached
+        total += ctx->row_extension.device_bytes;
     *bytes = total;
     return PARIS_HIP_SUCCESS;
 }

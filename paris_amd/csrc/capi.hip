@@ -352,6 +352,9 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
         ctx->defer_count = 0;
     }
     if(ctx->bp_stream != nullptr)
+        (void)hipStreamSynchronize(ctx->bp_stream);
+    paris_hip_row_extension_release(ctx, true); // (after the deferred group above: its filter launch reads the responses)
+    if(ctx->bp_stream != nullptr)
     {
         (void)hipStreamSynchronize(ctx->bp_stream); // fused launches the caller never joined (it never looked at the volume again)
         if(ctx->bp_ring_ready != nullptr)

@@ -18,6 +18,7 @@
 #include "paris_hip_internal.h"
 
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace
@@ -126,11 +127,13 @@ namespace
         }
     }
 
-    // src/openmp/filtering.cpp:167-219 for rows 2*blockIdx.x and 2*blockIdx.x + 1
-    __global__ void apply_filter_kernel(float* __restrict__ p, uint32_t pitch_f, uint32_t dim_x, uint32_t dim_y,
-                                        const float* __restrict__ k, const float2* __restrict__ tw, uint32_t log2n)
+    // src/openmp/filtering.cpp:167-219 for rows 2*blockIdx.x and 2*blockIdx.x + 1. EXTEND: the row extension's update at the store
+    // (include/paris_hip.h), c the response of dim_x floats, m the number of edge pixels averaged.
+    template <bool EXTEND>
+    __device__ __forceinline__ void apply_filter_rows(float2* fx, float* __restrict__ p, uint32_t pitch_f, uint32_t dim_x, uint32_t dim_y,
+                                                      const float* __restrict__ k, const float2* __restrict__ tw, uint32_t log2n,
+                                                      const float* __restrict__ c, uint32_t m)
     {
-        extern __shared__ __attribute__((aligned(16))) float2 fx[];
         const uint32_t n = 1u << log2n;
         const uint32_t tid = threadIdx.x;
         const uint32_t nthreads = blockDim.x;
@@ -154,6 +157,24 @@ namespace
         }
         __syncthreads();
 
+        float2 mean_l = make_float2(0.f, 0.f), mean_r = make_float2(0.f, 0.f);
+        if constexpr(EXTEND)
+        {
+            // every thread sums the edge pixels itself, in ascending index (the same LDS words for all: broadcast reads), before the
+            // transform overwrites them
+            float2 l = fx[0], r = fx[dim_x - m];
+            for(uint32_t e = 1; e < m; ++e)
+            {
+                const float2 le = fx[e], re = fx[dim_x - m + e];
+                l = make_float2(l.x + le.x, l.y + le.y);
+                r = make_float2(r.x + re.x, r.y + re.y);
+            }
+            const float inv_m = 1.f / static_cast<float>(m); // m is a power of two: an exact scaling
+            mean_l = make_float2(l.x * inv_m, l.y * inv_m);
+            mean_r = make_float2(r.x * inv_m, r.y * inv_m);
+            __syncthreads();
+        }
+
         fft_dif(fx, tw, log2n, tid, nthreads); // forward :208
 
         // do_filtering :92-105 -- K is real and even: K[n - f] = K[f]
@@ -175,10 +196,32 @@ namespace
         for(uint32_t s = tid; s < dim_x; s += nthreads)
         {
             const float2 v = fx[s];
-            pa[s] = v.x / n_f;
+            float ya = v.x / n_f, yb = v.y / n_f;
+            if constexpr(EXTEND)
+            {
+                const float cl = c[s], ch = c[dim_x - 1u - s];
+                ya = __builtin_fmaf(mean_r.x, ch, __builtin_fmaf(mean_l.x, cl, ya));
+                yb = __builtin_fmaf(mean_r.y, ch, __builtin_fmaf(mean_l.y, cl, yb));
+            }
+            pa[s] = ya;
             if(has_b)
-                pb[s] = v.y / n_f;
+                pb[s] = yb;
         }
+    }
+
+    __global__ void apply_filter_kernel(float* __restrict__ p, uint32_t pitch_f, uint32_t dim_x, uint32_t dim_y,
+                                        const float* __restrict__ k, const float2* __restrict__ tw, uint32_t log2n)
+    {
+        extern __shared__ __attribute__((aligned(16))) float2 fx[];
+        apply_filter_rows<false>(fx, p, pitch_f, dim_x, dim_y, k, tw, log2n, nullptr, 0u);
+    }
+
+    __global__ void apply_filter_extend_kernel(float* __restrict__ p, uint32_t pitch_f, uint32_t dim_x, uint32_t dim_y,
+                                               const float* __restrict__ k, const float2* __restrict__ tw, uint32_t log2n,
+                                               const float* __restrict__ c, uint32_t m)
+    {
+        extern __shared__ __attribute__((aligned(16))) float2 fx[];
+        apply_filter_rows<true>(fx, p, pitch_f, dim_x, dim_y, k, tw, log2n, c, m);
     }
 
     // ------------------------------------------------------------------------------------------------------------
@@ -224,6 +267,8 @@ namespace
             PARIS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(apply_filter_kernel),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, MAX_N * sizeof(float2)));
             PARIS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(make_filter_kernel),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, MAX_N * sizeof(float2)));
+            PARIS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(apply_filter_extend_kernel),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, MAX_N * sizeof(float2)));
             ctx->filter_lds_attr_set = true;
         }
@@ -286,6 +331,7 @@ extern "C" int paris_hip_make_filter_windowed(paris_hip_ctx* ctx, uint32_t size,
                        plan->d_twiddle, ilog2(size), tau, window);
     paris_hip_filter_info info;
     info.size = size;
+    info.tau = tau;
     if(size >= 1024u) // the fused kernel reads K in the order its middle pass holds the frequencies
         if(int rc = paris_hip_fused_filter_permute_k(ctx, k, size, &info.d_kp))
         {
@@ -309,6 +355,113 @@ static const paris_hip_filter_info* fused_filter_of(paris_hip_ctx* ctx, const fl
     return &it->second;
 }
 
+// ---- row extension (include/paris_hip.h) ----------------------------------------------------------------
+void paris_hip_row_extension_release(paris_hip_ctx* ctx, bool destroying)
+{
+    for(auto& kv : ctx->row_extension.cache)
+        paris_hip_retire_device_buffer(ctx, kv.second, destroying);
+    ctx->row_extension = paris_hip_ctx::row_extension_t{};
+    paris_hip_sweep_retired(ctx, destroying);
+}
+
+static int row_extension_device(paris_hip_ctx* ctx, float tau, uint32_t dim_x, const float** d_c, uint32_t* m)
+{
+    auto& re = ctx->row_extension;
+    if(dim_x < re.rule.edge_pixels)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    uint32_t tau_bits = 0;
+    std::memcpy(&tau_bits, &tau, sizeof tau_bits);
+    const std::array<uint32_t, 3> key{dim_x, tau_bits, re.rule.taper_pixels};
+    auto it = re.cache.find(key);
+    if(it == re.cache.end())
+    {
+        std::vector<float> c(dim_x);
+        if(int rc = paris_hip_row_extension_response(&re.rule, dim_x, tau, c.data()))
+            return rc;
+        float* d = nullptr;
+        const size_t bytes = static_cast<size_t>(dim_x) * sizeof(float);
+        if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), bytes))
+            return rc;
+        // copied on the ctx's auxiliary stream and waited for there (as the defect plan is): in place before the launch that follows
+        // reads it, without waiting for the work queued on the compute stream
+        int rc = paris_hip_ensure_aux(ctx);
+        if(rc == PARIS_HIP_SUCCESS)
+        {
+            const hipError_t err = hipMemcpyAsync(d, c.data(), bytes, hipMemcpyHostToDevice, ctx->aux_stream);
+            const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
+            rc = static_cast<int>(err != hipSuccess ? err : waited);
+        }
+        if(rc != PARIS_HIP_SUCCESS)
+        {
+            (void)hipFree(d);
+            return rc;
+        }
+        it = re.cache.emplace(key, d).first;
+        re.device_bytes += bytes;
+    }
+    *d_c = it->second;
+    *m = re.rule.edge_pixels;
+    return PARIS_HIP_SUCCESS;
+}
+
+int paris_hip_row_extension_for_k(paris_hip_ctx* ctx, const float* d_k, uint32_t dim_x, const float** d_c, uint32_t* m)
+{
+    *d_c = nullptr;
+    *m = 0u;
+    if(!ctx->row_extension.set)
+        return PARIS_HIP_SUCCESS;
+    auto it = ctx->filters.find(d_k);
+    if(it == ctx->filters.end()) // a K this ctx did not make: its tau is unknown
+        return PARIS_HIP_ERROR_UNSUPPORTED;
+    return row_extension_device(ctx, it->second.tau, dim_x, d_c, m);
+}
+
+int paris_hip_row_extension_for(paris_hip_ctx* ctx, const float* d_kp, uint32_t dim_x, const float** d_c, uint32_t* m)
+{
+    *d_c = nullptr;
+    *m = 0u;
+    if(!ctx->row_extension.set)
+        return PARIS_HIP_SUCCESS;
+    for(const auto& kv : ctx->filters) // (a handful per ctx)
+        if(kv.second.d_kp == d_kp)
+            return row_extension_device(ctx, kv.second.tau, dim_x, d_c, m);
+    return PARIS_HIP_ERROR_UNSUPPORTED;
+}
+
+extern "C" int paris_hip_set_row_extension(paris_hip_ctx* ctx, const paris_hip_row_extension* setting)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_row_extension_check(setting, 8u))
+        return rc;
+    if(int rc = paris_hip_flush_deferred(ctx)) // (runs a held-back weighting / filter as well): no queued row sees the change
+        return rc;
+    paris_hip_row_extension_release(ctx, false);
+    ctx->row_extension.set = true;
+    ctx->row_extension.rule = *setting;
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_clear_row_extension(paris_hip_ctx* ctx)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_flush_deferred(ctx))
+        return rc;
+    paris_hip_row_extension_release(ctx, false);
+    return PARIS_HIP_SUCCESS;
+}
+
+// with a setting in force: rows narrower than edge_pixels, or a K whose tau is unknown, are refused before anything is held back
+static int row_extension_refuses(paris_hip_ctx* ctx, const float* d_k, uint32_t dim_x)
+{
+    if(!ctx->row_extension.set || dim_x == 0u)
+        return PARIS_HIP_SUCCESS;
+    if(dim_x < ctx->row_extension.rule.edge_pixels)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    return ctx->filters.find(d_k) == ctx->filters.end() ? PARIS_HIP_ERROR_UNSUPPORTED : PARIS_HIP_SUCCESS;
+}
+
 extern "C" int paris_hip_apply_filter(paris_hip_ctx* ctx, float* d_p, size_t pitch, uint32_t dim_x, uint32_t dim_y,
                                       const float* d_k, uint32_t filter_size, uint32_t n_col)
 {
@@ -319,6 +472,11 @@ extern "C" int paris_hip_apply_filter(paris_hip_ctx* ctx, float* d_p, size_t pit
     {
         (void)paris_hip_flush_pending_weight(ctx);
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    }
+    if(int rc = row_extension_refuses(ctx, d_k, dim_y != 0 ? dim_x : 0u))
+    {
+        (void)paris_hip_flush_pending_weight(ctx);
+        return rc;
     }
     if(dim_x == 0 || dim_y == 0)
     {
@@ -379,7 +537,7 @@ extern "C" int paris_hip_apply_filter(paris_hip_ctx* ctx, float* d_p, size_t pit
     if(int rc = paris_hip_flush_pending_weight(ctx))
         return rc;
 #ifdef PARIS_HIP_EXPERIMENTS
-    if(ctx->filter_variant != 1 && log2n >= 10u)
+    if(ctx->filter_variant != 1 && log2n >= 10u && !ctx->row_extension.set) // (the row extension lives in the radix-2 kernel here)
     {
         int rc = PARIS_HIP_SUCCESS;
         switch(log2n)
@@ -397,8 +555,16 @@ extern "C" int paris_hip_apply_filter(paris_hip_ctx* ctx, float* d_p, size_t pit
         return paris_hip_finish(ctx);
     }
 #endif // (product build: a K this ctx did not make, or a length below 1024, runs the radix-2 kernel)
-    hipLaunchKernelGGL(apply_filter_kernel, dim3((dim_y + 1u) / 2u), dim3(threads_for(filter_size)),
-                       filter_size * sizeof(float2), ctx->stream, d_p, pitch_f, dim_x, dim_y, d_k, plan->d_twiddle, log2n);
+    const float* ext_c = nullptr;
+    uint32_t ext_m = 0u;
+    if(int rc = paris_hip_row_extension_for_k(ctx, d_k, dim_x, &ext_c, &ext_m)) // (nullptr without a setting)
+        return rc;
+    if(ext_c != nullptr)
+        hipLaunchKernelGGL(apply_filter_extend_kernel, dim3((dim_y + 1u) / 2u), dim3(threads_for(filter_size)),
+                           filter_size * sizeof(float2), ctx->stream, d_p, pitch_f, dim_x, dim_y, d_k, plan->d_twiddle, log2n, ext_c, ext_m);
+    else
+        hipLaunchKernelGGL(apply_filter_kernel, dim3((dim_y + 1u) / 2u), dim3(threads_for(filter_size)),
+                           filter_size * sizeof(float2), ctx->stream, d_p, pitch_f, dim_x, dim_y, d_k, plan->d_twiddle, log2n);
     if(int rc = paris_hip_note_projection_use(ctx, d_p, pitch * dim_y))
         return rc;
     return paris_hip_finish(ctx);
@@ -425,6 +591,8 @@ extern "C" int paris_hip_weight_filter_rows(paris_hip_ctx* ctx, float* d_p, size
     const paris_hip_filter_info* info = fused_filter_of(ctx, d_k, filter_size);
     if(info == nullptr)
         return PARIS_HIP_ERROR_UNSUPPORTED;
+    if(int rc = row_extension_refuses(ctx, d_k, dim_x))
+        return rc;
     paris_hip_fft_plan* plan = nullptr;
     if(int rc = paris_hip_get_plan(ctx, filter_size, &plan))
         return rc;
@@ -474,6 +642,8 @@ extern "C" int paris_hip_weight_filter_batch(paris_hip_ctx* ctx, float* d_p, siz
     const paris_hip_filter_info* info = fused_filter_of(ctx, d_k, filter_size);
     if(info == nullptr)
         return PARIS_HIP_ERROR_UNSUPPORTED;
+    if(int rc = row_extension_refuses(ctx, d_k, dim_x))
+        return rc;
     paris_hip_fft_plan* plan = nullptr;
     if(int rc = paris_hip_get_plan(ctx, filter_size, &plan))
         return rc;

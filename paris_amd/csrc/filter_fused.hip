@@ -211,11 +211,21 @@ namespace
         // first band row of each frame (n_tab != 0: at most FRAME_TAB_MAX frames per launch, fp32 in place)
         uint32_t n_tab;
         float* frame_tab[FRAME_TAB_MAX];
+        // EXTEND (row extension): the ramp's response c[dim_x] to the taper and the number of edge pixels averaged
+        const float* ext_c;
+        uint32_t ext_m;
     };
 
+    // EXTEND: LDS behind the block-256 twiddles -- the weighted edge pixels of the two rows (left at [0, 8), right at [8, 16)), then
+    // their means (left at 16, right at 17); .x is row a's, .y row b's
+    constexpr uint32_t EXT_LEFT = 0u, EXT_RIGHT = 8u, EXT_MEAN = 16u, EXT_SLOTS = 20u;
+
     // HALF: dim_x <= N/2 (always true for the reference's filter length 2 * 2^ceil(log2 n_row)); WEIGHT: apply the cosine
-    // weight in the load; F16OUT: store halves into half_out instead of fp32 in place
-    template <int LOG2N, bool HALF, bool WEIGHT, bool F16OUT>
+    // weight in the load; F16OUT: store halves into half_out instead of fp32 in place; EXTEND: the row extension's rank-2 update
+    // out[s] = fmaf(b, c[dim_x - 1 - s], fmaf(a, c[s], y)) at the store, a / b the means of the row's first / last ext_m pixels as
+    // the transform sees them (include/paris_hip.h). The threads that own those pixels in the first pass leave them in LDS, thread 0
+    // sums them in index order between the first two barriers, and every thread reads the four means after the last one.
+    template <int LOG2N, bool HALF, bool WEIGHT, bool F16OUT, bool EXTEND>
     __global__ void __launch_bounds__((1 << LOG2N) / 16, 4) filter_rows_kernel(const FusedFilterArgs a) // 4 waves per SIMD: at most 128 VGPRs
     {
         constexpr uint32_t N = 1u << LOG2N;
@@ -229,6 +239,7 @@ namespace
         // LDS behind the data: read at LDS latency inside the passes instead of L2 latency
         float2* ltab = fx + (N + N / 16u);
         constexpr uint32_t LTAB = 15u * 16u;
+        float2* edge = ltab + LTAB; // EXTEND only (EXT_SLOTS values)
 
         const uint32_t tid = threadIdx.x;
         const uint32_t row_a = 2u * blockIdx.x;
@@ -306,6 +317,13 @@ namespace
                     const bool inside = idx < a.dim_x;
                     x = inside ? x : 0.f;
                     y = (inside && has_b) ? y : 0.f;
+                    if constexpr(EXTEND)
+                    {
+                        if(idx < a.ext_m)
+                            edge[EXT_LEFT + idx] = make_float2(x, y);
+                        if(inside && idx + a.ext_m >= a.dim_x)
+                            edge[EXT_RIGHT + (idx + a.ext_m - a.dim_x)] = make_float2(x, y);
+                    }
                 }
                 v[j] = make_float2(x, y);
             }
@@ -338,6 +356,21 @@ namespace
         return;
 #endif
         __syncthreads();
+        if constexpr(EXTEND)
+            if(tid == 0u)
+            {
+                // sequential fp32 sums in ascending index, then the exact scaling by 1 / m (m is a power of two)
+                float2 l = edge[EXT_LEFT], r = edge[EXT_RIGHT];
+                for(uint32_t k = 1; k < a.ext_m; ++k)
+                {
+                    const float2 lk = edge[EXT_LEFT + k], rk = edge[EXT_RIGHT + k];
+                    l = make_float2(l.x + lk.x, l.y + lk.y);
+                    r = make_float2(r.x + rk.x, r.y + rk.y);
+                }
+                const float inv_m = 1.f / static_cast<float>(a.ext_m);
+                edge[EXT_MEAN] = make_float2(l.x * inv_m, l.y * inv_m);      // read after the barrier that precedes the last pass
+                edge[EXT_MEAN + 1u] = make_float2(r.x * inv_m, r.y * inv_m);
+            }
 
         // ---- forward middle passes: radix 16 on blocks of B = 16^(NPASS - pass)
 #pragma unroll
@@ -420,8 +453,28 @@ namespace
 #pragma unroll
         for(uint32_t q = 1; q < EF; ++q)
             tw_last[q - 1u] = a.tab_first[(q - 1u) * NO + tid];
+        // EXTEND: so are the first group's responses c[s] and c[dim_x - 1 - s] (a pixel beyond the row reads column 0 and is discarded)
+        constexpr uint32_t JL = HALF ? (EF / 2u > 0u ? EF / 2u : 1u) : EF;
+        float c_lo[EXTEND ? JL : 1u], c_hi[EXTEND ? JL : 1u];
+        if constexpr(EXTEND)
+        {
+#pragma unroll
+            for(uint32_t j = 0; j < JL; ++j)
+            {
+                const uint32_t idx = tid + j * NO;
+                const uint32_t at = idx < a.dim_x ? idx : 0u;
+                c_lo[j] = a.ext_c[at];
+                c_hi[j] = a.ext_c[a.dim_x - 1u - at];
+            }
+        }
         if(NPASS >= 3)
             __syncthreads();
+        float2 mean_l = make_float2(0.f, 0.f), mean_r = make_float2(0.f, 0.f);
+        if constexpr(EXTEND)
+        {
+            mean_l = edge[EXT_MEAN];
+            mean_r = edge[EXT_MEAN + 1u];
+        }
 
         // ---- inverse last pass: radix EF, shrink (:107-118) + normalize (:120-131; N is a power of two: exact) + store
         constexpr float inv_n = 1.f / static_cast<float>(N);
@@ -448,23 +501,35 @@ namespace
                 const uint32_t idx = o + j * NO;
                 if(idx < a.dim_x)
                 {
+                    if constexpr(EXTEND)
+                    {
+                        const float cl = g == 0u ? c_lo[j < JL ? j : 0u] : a.ext_c[idx];
+                        const float ch = g == 0u ? c_hi[j < JL ? j : 0u] : a.ext_c[a.dim_x - 1u - idx];
+                        v[j].x = __builtin_fmaf(mean_r.x, ch, __builtin_fmaf(mean_l.x, cl, v[j].x * inv_n));
+                        v[j].y = __builtin_fmaf(mean_r.y, ch, __builtin_fmaf(mean_l.y, cl, v[j].y * inv_n));
+                        // the half output is THIS fp32 value rounded to nearest even: left to itself the compiler folds the conversion
+                        // into the multiply-add (v_fma_mixlo_f16), which rounds the exact sum once, straight to half
+                        if(F16OUT)
+                            asm("" : "+v"(v[j].x), "+v"(v[j].y));
+                    }
+                    constexpr float scale = EXTEND ? 1.f : inv_n; // (EXTEND: scaled above; x * 1 is x)
                     if(F16OUT)
                     {
-                        half_frame[static_cast<size_t>(row_a) * a.half_pitch + idx] = static_cast<_Float16>(v[j].x * inv_n);
+                        half_frame[static_cast<size_t>(row_a) * a.half_pitch + idx] = static_cast<_Float16>(v[j].x * scale);
                         if(has_b)
-                            half_frame[static_cast<size_t>(row_b) * a.half_pitch + idx] = static_cast<_Float16>(v[j].y * inv_n);
+                            half_frame[static_cast<size_t>(row_b) * a.half_pitch + idx] = static_cast<_Float16>(v[j].y * scale);
                     }
                     else
                     {
 #ifdef PARIS_FILTER_TIMING_NO_MEMORY
                         if(v[j].x == 123456.789f) // never: keeps the arithmetic alive without the stores
 #endif
-                        pa[idx] = v[j].x * inv_n;
+                        pa[idx] = v[j].x * scale;
                         if(has_b)
 #ifdef PARIS_FILTER_TIMING_NO_MEMORY
                             if(v[j].y == 123456.789f)
 #endif
-                            pb[idx] = v[j].y * inv_n;
+                            pb[idx] = v[j].y * scale;
                     }
                 }
             }
@@ -502,17 +567,25 @@ namespace
         kp[p] = k[f <= n / 2u ? f : n - f]; // K is real and even
     }
 
+    template <int LOG2N, bool HALF, bool WEIGHT, bool F16OUT, bool EXTEND>
+    int launch_kernel(paris_hip_ctx* ctx, const FusedFilterArgs& a, uint32_t n_frames)
+    {
+        constexpr uint32_t N = 1u << LOG2N;
+        // data + the block-256 twiddles (+ the row extension's edge pixels and means)
+        constexpr uint32_t lds_bytes = (N + N / 16u + 15u * 16u + (EXTEND ? EXT_SLOTS : 0u)) * sizeof(float2);
+        if(lds_bytes > 64u * 1024u)
+            PARIS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(filter_rows_kernel<LOG2N, HALF, WEIGHT, F16OUT, EXTEND>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        hipLaunchKernelGGL((filter_rows_kernel<LOG2N, HALF, WEIGHT, F16OUT, EXTEND>), dim3((a.n_rows + 1u) / 2u, n_frames), dim3(N / 16u),
+                           lds_bytes, ctx->stream, a);
+        return PARIS_HIP_SUCCESS;
+    }
+
     template <int LOG2N, bool HALF, bool WEIGHT, bool F16OUT>
     int launch(paris_hip_ctx* ctx, const FusedFilterArgs& a, uint32_t n_frames)
     {
-        constexpr uint32_t N = 1u << LOG2N;
-        constexpr uint32_t lds_bytes = (N + N / 16u + 15u * 16u) * sizeof(float2); // data + the block-256 twiddles
-        if(lds_bytes > 64u * 1024u)
-            PARIS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(filter_rows_kernel<LOG2N, HALF, WEIGHT, F16OUT>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL((filter_rows_kernel<LOG2N, HALF, WEIGHT, F16OUT>), dim3((a.n_rows + 1u) / 2u, n_frames), dim3(N / 16u), lds_bytes,
-                           ctx->stream, a);
-        return PARIS_HIP_SUCCESS;
+        return a.ext_c != nullptr ? launch_kernel<LOG2N, HALF, WEIGHT, F16OUT, true>(ctx, a, n_frames)
+                                  : launch_kernel<LOG2N, HALF, WEIGHT, F16OUT, false>(ctx, a, n_frames);
     }
 
     template <int LOG2N>
@@ -648,6 +721,8 @@ int paris_hip_fused_filter_launch(paris_hip_ctx* ctx, float* d_rows, uint32_t pi
         a.tab_mid[k] = plan->d_tab_mid[k];
     a.half_out = reinterpret_cast<_Float16*>(d_half);
     a.half_pitch = half_pitch;
+    if(int rc = paris_hip_row_extension_for(ctx, d_kp, dim_x, &a.ext_c, &a.ext_m)) // (nullptr without a setting)
+        return rc;
     const bool half_ok = dim_x <= filter_size / 2u;
     const bool f16out = d_half != nullptr;
     switch(ilog2(filter_size))

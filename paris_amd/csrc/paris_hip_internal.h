@@ -37,6 +37,7 @@ struct paris_hip_filter_info
 {
     uint32_t size = 0;
     float* d_kp = nullptr;
+    float tau = 0.f; // the pixel pitch K was made for (the row extension's response needs it)
 };
 
 struct paris_hip_ctx
@@ -145,6 +146,16 @@ struct paris_hip_ctx
         size_t device_bytes = 0;
         char* d_scratch = nullptr;
     } zinger;
+    // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
+    // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
+    // retired and freed as the defect plan is.
+    struct row_extension_t
+    {
+        bool set = false;
+        paris_hip_row_extension rule{};
+        std::map<std::array<uint32_t, 3>, float*> cache;
+        size_t device_bytes = 0;
+    } row_extension;
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
     std::vector<std::pair<void*, hipEvent_t>> retired;
@@ -413,6 +424,13 @@ void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying);
 // defect_map.hip: the same for the ctx's defect plan
 void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility push(hidden)
+// filter.hip: the same for the row extension's cached responses
+void paris_hip_row_extension_release(paris_hip_ctx* ctx, bool destroying);
+// filter.hip: what a filter launch of rows of dim_x pixels with the K whose permuted copy is d_kp (d_k: the K itself) adds at its
+// store: *d_c = nullptr without a setting, else the device copy of c (made and cached on first use) and *m = edge_pixels.
+// PARIS_HIP_ERROR_INVALID_ARGUMENT for dim_x < m, PARIS_HIP_ERROR_UNSUPPORTED for a K this ctx did not make.
+int paris_hip_row_extension_for(paris_hip_ctx* ctx, const float* d_kp, uint32_t dim_x, const float** d_c, uint32_t* m);
+int paris_hip_row_extension_for_k(paris_hip_ctx* ctx, const float* d_k, uint32_t dim_x, const float** d_c, uint32_t* m);
 // zinger.hip: the same for the zinger filter's scratch
 void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop

@@ -308,6 +308,45 @@ extern "C" int paris_hip_slab_row_band(const paris_detector_geometry* det_geo, c
     return PARIS_HIP_SUCCESS;
 }
 
+// Row extension (include/paris_hip.h): the check and the one implementation of the response c.
+extern "C" int paris_hip_row_extension_check(const paris_hip_row_extension* setting, uint32_t dim_x)
+{
+    if(setting == nullptr || dim_x == 0u)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    const uint32_t m = setting->edge_pixels, w = setting->taper_pixels;
+    if((m != 1u && m != 2u && m != 4u && m != 8u) || w < 1u || w > 16384u || dim_x < m)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_row_extension_response(const paris_hip_row_extension* setting, uint32_t dim_x, float tau, float* c)
+{
+    if(int rc = paris_hip_row_extension_check(setting, dim_x))
+        return rc;
+    if(c == nullptr || !std::isfinite(tau) || !(tau > 0.f))
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    const uint32_t w = setting->taper_pixels;
+    std::vector<double> t(w + 1u);
+    for(uint32_t k = 1; k <= w; ++k)
+    {
+        const double cs = std::cos(M_PI * static_cast<double>(k) / (2.0 * (static_cast<double>(w) + 1.0)));
+        t[k] = cs * cs;
+    }
+    const double scale = 2.0 * M_PI * M_PI, tau_d = static_cast<double>(tau);
+    for(uint32_t s = 0; s < dim_x; ++s)
+    {
+        double sum = 0.0;
+        for(uint32_t k = 1; k <= w; ++k) // ascending k; g vanishes at even distances
+        {
+            const double d = static_cast<double>(s) + static_cast<double>(k);
+            if(((s + k) & 1u) != 0u)
+                sum += t[k] * (-1.0 / (scale * d * d * tau_d));
+        }
+        c[s] = static_cast<float>(sum);
+    }
+    return PARIS_HIP_SUCCESS;
+}
+
 extern "C" int paris_hip_set_filter_window(paris_hip_ctx* ctx, int window)
 {
     if(ctx == nullptr || (window != PARIS_HIP_WINDOW_RAMP && window != PARIS_HIP_WINDOW_SHEPP_LOGAN))

@@ -6,6 +6,7 @@
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
+//                       [--extend-rows W M]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -20,6 +21,8 @@
 // repairs each frame's defective pixels after the dark / flat correction and before the weights.
 // --zingers: threshold_abs, threshold_rel and the polarity (1 bright, -1 dark, 0 both) of the zinger rule. set_zinger_filter() before the
 // loops, so that paris::weight() removes each frame's outlier pixels after the repair and before the weights.
+// --extend-rows: the taper length W and the number of edge pixels M of the row extension for truncated projections.
+// set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
 // frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
 // host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
@@ -81,6 +84,8 @@ int main(int argc, char** argv)
         bool zingers = false;
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 1;
+        bool extend_rows = false;
+        std::uint32_t extend_taper = 0, extend_edge = 0;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
         auto vol_geo = paris::calculate_volume_geometry(det);
@@ -121,6 +126,13 @@ int main(int argc, char** argv)
                 zinger_rel = std::strtof(argv[a + 2], nullptr);
                 zinger_polarity = std::atoi(argv[a + 3]);
                 a += 3;
+            }
+            else if(!std::strcmp(argv[a], "--extend-rows") && a + 2 < argc)
+            {
+                extend_rows = true;
+                extend_taper = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
+                extend_edge = static_cast<std::uint32_t>(std::strtoul(argv[a + 2], nullptr, 10));
+                a += 2;
             }
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
@@ -192,6 +204,8 @@ int main(int argc, char** argv)
         }
         if(zingers)
             paris::backend::set_zinger_filter(zinger_abs, zinger_rel, zinger_polarity, det.n_row, det.n_col);
+        if(extend_rows)
+            paris::backend::set_row_extension(extend_edge, extend_taper);
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 

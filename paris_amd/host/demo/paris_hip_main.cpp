@@ -81,6 +81,7 @@ int main(int argc, char** argv)
                             "          [--slabs n] [--devices n] [--f16] [--window ramp|shepp-logan] [--batch n] [--no-row-band] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]\n"
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
+                            "          [--extend-rows W[:M]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -94,7 +95,10 @@ int main(int argc, char** argv)
                             "the weights, by the inverse-square-distance weighted mean of the good pixels on the nearest ring that holds one.\n"
                             "--zingers: every pixel that differs from the median m of its 3 x 3 window by more than ABS + REL * |m| is replaced by\n"
                             "m on the device, after the repair and before the weights -- pixels above m (bright: the default), below it (dark: the\n"
-                            "default with --flat) or both; a frame with more flagged pixels than 1/256 of the detector (1024 at least) is left as it is.\n");
+                            "default with --flat) or both; a frame with more flagged pixels than 1/256 of the detector (1024 at least) is left as it is.\n"
+                            "--extend-rows: the object is wider than the detector (truncated rows). The row filter acts as if every row went on\n"
+                            "beyond either edge as the mean of its M outermost pixels (1, 2, 4 or 8; default 4) times a cos^2 taper of W pixels\n"
+                            "(1 .. 16384; 16 is a good start, longer is not better) instead of dropping to 0.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -122,6 +126,7 @@ int main(int argc, char** argv)
             else if(k == "--defects-from-flat") po.defects_from_flat = true;
             else if(k == "--zingers") paris::detail::parse_zingers(val(), po);
             else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
+            else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -156,6 +161,8 @@ int main(int argc, char** argv)
         if(r.defect_map)
             std::printf("defect map on: %llu defective pixel(s), %llu unrepairable (no good pixel within %d)\n",
                         static_cast<unsigned long long>(r.defects.defects), static_cast<unsigned long long>(r.defects.unrepairable), PARIS_HIP_DEFECT_R_MAX);
+        if(r.row_extension)
+            std::printf("row extension on: cos^2 taper of %u pixel(s), mean of %u edge pixel(s)\n", po.extend_taper, po.extend_edge);
         if(r.zinger_filter)
             std::printf("zinger filter on: %llu frame band(s) examined, %llu pixel(s) replaced, %llu saturated (left as they were)\n",
                         static_cast<unsigned long long>(r.zingers.frames), static_cast<unsigned long long>(r.zingers.replaced),

@@ -326,6 +326,21 @@ namespace paris
             detail::state().zinger_filters.erase(current_ctx());
         }
 
+        // Extension (no reference counterpart): the projections of this thread's current device are laterally truncated -- the object
+        // is wider than the detector. Until clear_row_extension(), paris::filter() acts as if every row continued beyond either edge
+        // as the mean of its edge_pixels (1, 2, 4 or 8) outermost weighted pixels times a cos^2 taper of taper_pixels pixels, instead
+        // of dropping to 0 (paris_hip_set_row_extension). Runs what is held back or pending first.
+        inline auto set_row_extension(std::uint32_t edge_pixels, std::uint32_t taper_pixels) -> void
+        {
+            const auto setting = paris_hip_row_extension{edge_pixels, taper_pixels};
+            detail::runtime_check(paris_hip_set_row_extension(current_ctx(), &setting), "set_row_extension()");
+        }
+
+        inline auto clear_row_extension() -> void
+        {
+            detail::runtime_check(paris_hip_clear_row_extension(current_ctx()), "clear_row_extension()");
+        }
+
         namespace detail
         {
             inline auto has_zinger_filter(const paris_hip_ctx* ctx) -> bool

@@ -108,6 +108,12 @@ namespace paris
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 2;      // +1 bright, -1 dark, 0 both; 2: the default, resolved by run()
         std::size_t zinger_bytes = 0; // filled by run(): what the setting occupies on a device
+        // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
+        // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
+        // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
+        bool extend_rows = false;
+        std::uint32_t extend_taper = 0, extend_edge = 4;
+        std::size_t extend_bytes = 0; // filled by run(): the response vector a device keeps while set
     };
 
     // src/task.h:33-57
@@ -227,6 +233,7 @@ namespace paris
         paris_hip_defect_stats defects{};
         bool zinger_filter = false; // --zingers: a zinger filter was set; its counts over this device's tasks:
         paris_hip_zinger_counts zingers{};
+        bool row_extension = false; // --extend-rows: the setting was made on this device's ctx
         std::vector<std::string> skipped;
     };
 
@@ -275,7 +282,7 @@ namespace paris
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
             // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes;
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes;
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -629,6 +636,18 @@ namespace paris
             }
             rep.zinger_filter = true;
         }
+        // --extend-rows: the same setting on every device
+        if(po.extend_rows)
+        {
+            const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
+            const int rc = paris_hip_set_row_extension(ctx, &setting);
+            if(rc != PARIS_HIP_SUCCESS)
+            {
+                paris_hip_ctx_destroy(ctx);
+                rt(rc, "set_row_extension()");
+            }
+            rep.row_extension = true;
+        }
         const std::uint32_t zinger_rows = po.zingers ? 1u : 0u; // how far beyond a band's rows the zinger filter reads
 
         // Projections travel in groups: a group of `batch` frames is converted, uploaded, weighted and filtered one by one,
@@ -940,6 +959,7 @@ namespace paris
         paris_hip_defect_stats defects{};
         bool zinger_filter = false;                     // --zingers: the filter was on; its counts over all devices and slabs (a
         paris_hip_zinger_counts zingers{};              // frame counts once per slab: each slab filters its own row band)
+        bool row_extension = false;                     // --extend-rows: every device filtered with the setting
         double wall_s = 0;
         std::string output_file;
     };
@@ -1132,6 +1152,32 @@ namespace paris
             po.zingers = true;
         }
 
+        // --extend-rows W[:M] as typed; refuses anything that is not one or two unsigned integers
+        inline auto parse_extend_rows(const std::string& v, program_options& po) -> void
+        {
+            const auto number = [&v](const std::string& t) -> std::uint32_t {
+                if(t.empty() || t.size() > 9u || t.find_first_not_of("0123456789") != std::string::npos)
+                    throw stage_construction_error{"--extend-rows W[:M]: cannot read '" + v + "'"};
+                return static_cast<std::uint32_t>(std::stoul(t));
+            };
+            const auto colon = v.find(':');
+            po.extend_taper = number(v.substr(0, colon));
+            po.extend_edge = colon == std::string::npos ? 4u : number(v.substr(colon + 1u));
+            po.extend_rows = true;
+        }
+
+        // --extend-rows: the setting is checked for this detector here, before any device work
+        inline auto check_extend_rows(program_options& po) -> void
+        {
+            if(!po.extend_rows)
+                return;
+            const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
+            if(paris_hip_row_extension_check(&setting, po.det_geo.n_row) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--extend-rows W[:M]: W must lie in 1 .. 16384 and M must be 1, 2, 4 or 8 and at most n_row (got "
+                                               + std::to_string(po.extend_taper) + ":" + std::to_string(po.extend_edge) + ")"};
+            po.extend_bytes = std::size_t{po.det_geo.n_row} * sizeof(float);
+        }
+
         inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
         {
             if(v == "bright") po.zinger_polarity = 1;
@@ -1152,6 +1198,7 @@ namespace paris
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         detail::load_defects(po);
         detail::check_zingers(po);
+        detail::check_extend_rows(po);
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1246,6 +1293,7 @@ namespace paris
         r.defects = r.devices.front().defects;
         for(const auto& d : r.devices)
         {
+            r.row_extension = r.row_extension || d.row_extension;
             r.zinger_filter = r.zinger_filter || d.zinger_filter;
             r.zingers.frames += d.zingers.frames;
             r.zingers.replaced += d.zingers.replaced;
