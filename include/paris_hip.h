@@ -616,6 +616,91 @@ int paris_hip_zinger_filter_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, s
 /* The counts since the setting was made or last reset: runs what is pending, waits for the ctx stream and reads them; reset != 0
  * zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
 int paris_hip_zinger_stats(paris_hip_ctx* ctx, paris_hip_zinger_counts* out, int reset);
+/* Extension (no reference counterpart): removal of ring artefacts -- stationary detector offsets, a small constant error a working
+ * pixel carries in every frame, which FDK turns into a ring around the rotation axis. The mean of every
+ * pixel over the scan is compared with a running median of that mean along the detector row; clear outliers are subtracted from
+ * every frame.
+ * Setting paris_hip_ring_filter { uint32_t half_width; float floor_abs; float limit_abs; }.
+ *   half_width h is in [1, 32].
+ *   floor_abs is >= 0 and finite.
+ *   limit_abs is finite. It is either 0, which means no upper limit, or > floor_abs.
+ * Profile. For pixel (x, y), S[y][x] is the sum, in DOUBLE, of the fp32 pixel values of every frame added. The order is the one in
+ * which they were added: call order, and frame 0 .. n - 1 within a call.
+ *   N[y] is the number of frames added for row y. Bands may differ, so the host keeps the count per row.
+ *   Every pixel has one owner thread per launch, and there are no atomics. The sum is therefore reproducible and equals numpy's
+ *   sequential float64 sum bit for bit.
+ * Mean. mean[y][x] = (float)(S[y][x] / (double)N[y]), rounded once. Rows with N[y] == 0 have no mean and get c = 0.
+ * Correction.
+ *   window is the 2h + 1 values mean[y][clamp(x + d, 0, dim_x - 1)], d = -h .. h. Edges are replicated.
+ *   If any value of the window is not finite, c = +0.
+ *   med is the (h + 1)-th smallest value by value.
+ *   c = mean - med in fp32.
+ *   c is kept iff floor_abs <= |c| and (limit_abs == 0 or |c| <= limit_abs). Otherwise c = +0.
+ *   A kept c that is -0 counts as 0.
+ * Apply. p <- p - c[y][x], one fp32 subtraction. Pixels with c == 0 are NOT WRITTEN: their bits stay, NaN payloads included.
+ * Further properties of the rule:
+ *   It runs on line integrals, after the zinger filter and before the redundancy and cosine weights.
+ *   The correction of a row depends on that row only, so a row band needs no extra rows.
+ *   The rule for c reads one frame once per scan. It has ONE implementation, on the host (paris_hip_ring_correction_from_mean), as
+ *   the defect plan and the row-extension response have.
+ *   The device does the two passes that touch every frame. */
+typedef struct paris_hip_ring_filter {
+    uint32_t half_width; /* h: the running median spans 2h + 1 pixels of a row, 1 .. 32 */
+    float floor_abs;     /* dead band: smaller |c| are not corrected; >= 0, frame units */
+    float limit_abs;     /* larger |c| are not corrected; 0 = no limit, else > floor_abs */
+} paris_hip_ring_filter;
+typedef struct paris_hip_ring_stats {
+    uint64_t corrected;   /* pixels with c != 0 */
+    uint64_t below_floor; /* pixels whose |c| was below floor_abs */
+    uint64_t above_limit; /* pixels whose |c| was above limit_abs */
+    uint64_t not_finite;  /* pixels whose window held a value that is not finite */
+    float max_abs;        /* the largest kept |c| (0 when none) */
+    uint32_t frames_min;  /* the smallest and the largest N[y] over the rows; both 0 when the counts were not given */
+    uint32_t frames_max;
+} paris_hip_ring_stats;
+/* one accumulate launch serves at most this many frames; calls with more loop */
+#define PARIS_HIP_RING_FRAMES_MAX 64
+/* Host only, no ctx and no device: checks a setting for a detector and reports what an open profile (8 bytes per pixel) and a
+ * correction frame (4 bytes per pixel) occupy on the device; either pointer may be NULL. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL
+ * setting, a zero dimension, or a setting the rule excludes; PARIS_HIP_ERROR_UNSUPPORTED when dim_x * dim_y does not fit 32 bits. */
+int paris_hip_ring_filter_check(const paris_hip_ring_filter* setting, uint32_t dim_x, uint32_t dim_y, size_t* profile_bytes,
+                                size_t* correction_bytes);
+/* Host only: the rule above from the mean frame (dim_y rows of dim_x floats) to c (the same shape) -- the single implementation
+ * of c. count_per_row is N[y], dim_y entries; NULL stands for "every row present" (frames_min and frames_max are then 0). out may be
+ * NULL. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL mean or c. */
+int paris_hip_ring_correction_from_mean(const paris_hip_ring_filter* setting, const float* mean, const uint32_t* count_per_row,
+                                        uint32_t dim_x, uint32_t dim_y, float* c, paris_hip_ring_stats* out);
+/* The profile: paris_hip_ring_profile_begin opens one for dim_x x dim_y frames -- zeroed double sums in memory the ctx owns, which
+ * count towards paris_hip_projection_reserve_bytes while open and are freed by finish, discard or paris_hip_ctx_destroy. begin on an
+ * open profile replaces it; work queued before keeps the old one. PARIS_HIP_ERROR_INVALID_ARGUMENT for a zero dimension,
+ * PARIS_HIP_ERROR_UNSUPPORTED when dim_x * dim_y does not fit 32 bits.
+ * paris_hip_ring_profile_add_rows adds rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes apart, d_p the
+ * first frame's row 0, to the sums, and n_frames to N[y] of those rows; the frames are only read. A held-back weighting runs first,
+ * and a frame of the pending by-reference group has that group launched first. PARIS_HIP_ERROR_INVALID_ARGUMENT without an open
+ * profile, when dim_x / dim_y differ from the profile's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse.
+ * paris_hip_ring_profile_finish runs what is pending, waits for the ctx stream, copies the sums down, forms the means and calls
+ * paris_hip_ring_correction_from_mean with the counts; h_c and h_mean (may be NULL) receive dim_y rows of dim_x floats, rows without
+ * a frame a mean of 0. The profile is then closed and its memory freed. A profile with no frame at all gives c = 0 everywhere and
+ * frames_max = 0. PARIS_HIP_ERROR_INVALID_ARGUMENT without an open profile, for a NULL h_c, or as the check; the profile stays open.
+ * paris_hip_ring_profile_discard closes an open profile (no error without one). */
+int paris_hip_ring_profile_begin(paris_hip_ctx* ctx, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_ring_profile_add_rows(paris_hip_ctx* ctx, const float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                    uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+int paris_hip_ring_profile_finish(paris_hip_ctx* ctx, const paris_hip_ring_filter* setting, float* h_c, float* h_mean,
+                                  paris_hip_ring_stats* out);
+int paris_hip_ring_profile_discard(paris_hip_ctx* ctx);
+/* paris_hip_set_ring_correction copies the dim_x x dim_y correction frame c (rows dim_x floats apart) into memory the ctx owns,
+ * replacing an earlier one; the old frame is freed once the work queued before the call no longer reads it. The frame counts towards
+ * paris_hip_projection_reserve_bytes while set; paris_hip_ctx_destroy frees it. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL h_c, a
+ * zero dimension or a value that is not finite. Without a setting nothing else changes. */
+int paris_hip_set_ring_correction(paris_hip_ctx* ctx, const float* h_c, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_ring_correction(paris_hip_ctx* ctx);
+/* In place on float frames: every pixel with c != 0 in rows [row_first, row_first + row_count) of n_frames frames frame_stride
+ * bytes apart, d_p the first frame's row 0, becomes p - c. A correction frame that is zero everywhere makes the call idle: nothing
+ * is launched, no pending group either. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when dim_x / dim_y differ from the
+ * setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                uint32_t dim_y, uint32_t row_first, uint32_t row_count);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

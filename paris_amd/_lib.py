@@ -77,6 +77,20 @@ class ZingerCounts(C.Structure):
 ZINGER_FRAMES_MAX = 64  # PARIS_HIP_ZINGER_FRAMES_MAX
 
 
+class RingFilter(C.Structure):
+    """paris_hip_ring_filter: the parameters of the ring rule (extension)"""
+    _fields_ = [("half_width", C.c_uint32), ("floor_abs", C.c_float), ("limit_abs", C.c_float)]
+
+
+class RingStats(C.Structure):
+    """paris_hip_ring_stats: what the ring rule did to a mean frame (extension)"""
+    _fields_ = [("corrected", C.c_uint64), ("below_floor", C.c_uint64), ("above_limit", C.c_uint64), ("not_finite", C.c_uint64),
+                ("max_abs", C.c_float), ("frames_min", C.c_uint32), ("frames_max", C.c_uint32)]
+
+
+RING_FRAMES_MAX = 64  # PARIS_HIP_RING_FRAMES_MAX
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -130,6 +144,15 @@ SIGNATURES = {
     "paris_hip_clear_zinger_filter": (C.c_int, [_vp]),
     "paris_hip_zinger_filter_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_zinger_stats": (C.c_int, [_vp, _P(ZingerCounts), C.c_int]),
+    "paris_hip_ring_filter_check": (C.c_int, [_P(RingFilter), _u32, _u32, _P(_sz), _P(_sz)]),
+    "paris_hip_ring_correction_from_mean": (C.c_int, [_P(RingFilter), _vp, _vp, _u32, _u32, _vp, _P(RingStats)]),
+    "paris_hip_ring_profile_begin": (C.c_int, [_vp, _u32, _u32]),
+    "paris_hip_ring_profile_add_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_ring_profile_finish": (C.c_int, [_vp, _P(RingFilter), _vp, _vp, _P(RingStats)]),
+    "paris_hip_ring_profile_discard": (C.c_int, [_vp]),
+    "paris_hip_set_ring_correction": (C.c_int, [_vp, _vp, _u32, _u32]),
+    "paris_hip_clear_ring_correction": (C.c_int, [_vp]),
+    "paris_hip_ring_correct_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

@@ -12,14 +12,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RowExtension, ShortScan, SubvolumeGeometry,
-                   SubvolumeInfo, VolumeGeometry, ZingerCounts, ZingerFilter, check)
+from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+                   SubvolumeGeometry, SubvolumeInfo, VolumeGeometry, ZingerCounts, ZingerFilter, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
            "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
-           "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response"]
+           "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
+           "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean"]
 
 
 class Projection:
@@ -128,6 +129,36 @@ def zinger_filter_check(threshold_abs, threshold_rel, polarity, max_hits, dim_x,
     zf = _zinger_setting(threshold_abs, threshold_rel, polarity, max_hits)
     check(L.paris_hip_zinger_filter_check(C.byref(zf), dim_x, dim_y, C.byref(hits), C.byref(nbytes)), "paris_hip_zinger_filter_check")
     return hits.value, nbytes.value
+
+
+def ring_filter_check(half_width, floor_abs, limit_abs, dim_x, dim_y):
+    """Host only, no device (paris_hip_ring_filter_check): checks a ring-filter setting for a dim_x x dim_y detector -- half_width in
+    [1, 32], floor_abs >= 0, limit_abs 0 (none) or above floor_abs -- and returns (profile_bytes, correction_bytes). Raises
+    ParisHipError for a setting the library refuses."""
+    rf = RingFilter(half_width, floor_abs, limit_abs)
+    profile, correction = C.c_size_t(0), C.c_size_t(0)
+    check(_lib.load().paris_hip_ring_filter_check(C.byref(rf), dim_x, dim_y, C.byref(profile), C.byref(correction)),
+          "paris_hip_ring_filter_check")
+    return profile.value, correction.value
+
+
+def ring_correction_from_mean(half_width, floor_abs, limit_abs, mean, count_per_row=None):
+    """Host only, no device (paris_hip_ring_correction_from_mean): the ring rule from a scan's mean frame, a 2-D array of the
+    detector's size (n_col, n_row) taken as float32, to (c, RingStats) -- c the stationary offset to subtract from every frame, 0
+    where the rule keeps none. count_per_row: how many frames each row's mean holds (rows with 0 get
+    c = 0); None = every row present."""
+    m = np.ascontiguousarray(mean, np.float32)
+    if m.ndim != 2:
+        raise ValueError("ring_correction_from_mean: the mean must be a 2-D array (n_col, n_row)")
+    counts = None if count_per_row is None else np.ascontiguousarray(count_per_row, np.uint32)
+    if counts is not None and counts.shape != (m.shape[0],):
+        raise ValueError("ring_correction_from_mean: count_per_row must hold one count per detector row")
+    rf = RingFilter(half_width, floor_abs, limit_abs)
+    c, st = np.empty(m.shape, np.float32), RingStats()
+    check(_lib.load().paris_hip_ring_correction_from_mean(C.byref(rf), m.ctypes.data, None if counts is None else counts.ctypes.data,
+                                                          m.shape[1], m.shape[0], c.ctypes.data, C.byref(st)),
+          "paris_hip_ring_correction_from_mean")
+    return c, st
 
 
 def row_extension_check(edge_pixels, taper_pixels, dim_x):
@@ -428,6 +459,64 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_zinger_filter_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_zinger_filter_rows")
+
+    # ---- ring filter ------------------------------------------------------------
+    ring_filter_check = staticmethod(ring_filter_check)
+    ring_correction_from_mean = staticmethod(ring_correction_from_mean)
+
+    def ring_profile_begin(self, dim_x, dim_y):
+        """paris_hip_ring_profile_begin: opens the scan's profile for a dim_x x dim_y detector -- zeroed double sums on the device.
+        Replaces an open one safely: work already queued keeps the old sums."""
+        check(self._L.paris_hip_ring_profile_begin(self._ctx, dim_x, dim_y), "paris_hip_ring_profile_begin")
+        self._ring_shape = (dim_y, dim_x)
+
+    def ring_profile_add_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """Adds rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes apart starting at p to the open
+        profile, frame after frame (paris_hip_ring_profile_add_rows). The frames are only read. Call it on line integrals, after the
+        zinger filter and before every weight."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_ring_profile_add_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_ring_profile_add_rows")
+
+    def ring_profile_finish(self, half_width, floor_abs=0.0, limit_abs=0.0):
+        """paris_hip_ring_profile_finish: waits for the ctx stream, forms every pixel's mean over the frames added and applies the
+        ring rule to it. Returns (c, mean, RingStats), float32 arrays (n_col, n_row); the profile is closed. Hand c to
+        set_ring_correction()."""
+        shape = getattr(self, "_ring_shape", None)
+        if shape is None:
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_ring_profile_finish")
+        rf = RingFilter(half_width, floor_abs, limit_abs)
+        c, mean, st = np.empty(shape, np.float32), np.empty(shape, np.float32), RingStats()
+        check(self._L.paris_hip_ring_profile_finish(self._ctx, C.byref(rf), c.ctypes.data, mean.ctypes.data, C.byref(st)),
+              "paris_hip_ring_profile_finish")
+        self._ring_shape = None
+        return c, mean, st
+
+    def ring_profile_discard(self):
+        """paris_hip_ring_profile_discard: closes an open profile without a result"""
+        check(self._L.paris_hip_ring_profile_discard(self._ctx), "paris_hip_ring_profile_discard")
+        self._ring_shape = None
+
+    def set_ring_correction(self, c):
+        """paris_hip_set_ring_correction: c is a 2-D array of the detector's size (n_col, n_row), taken as float32, every value
+        finite; ring_correct_rows() then subtracts it from frames. Replaces an earlier one safely: work already queued keeps the
+        old frame."""
+        a = np.ascontiguousarray(c, np.float32)
+        if a.ndim != 2:
+            raise ValueError("set_ring_correction: c must be a 2-D array (n_col, n_row)")
+        check(self._L.paris_hip_set_ring_correction(self._ctx, a.ctypes.data, a.shape[1], a.shape[0]), "paris_hip_set_ring_correction")
+
+    def clear_ring_correction(self):
+        """paris_hip_clear_ring_correction: no ring correction from here on"""
+        check(self._L.paris_hip_clear_ring_correction(self._ctx), "paris_hip_clear_ring_correction")
+
+    def ring_correct_rows(self, p, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """p <- p - c in place on float frames (paris_hip_ring_correct_rows): the pixels with c != 0 in rows [row_first, row_first +
+        row_count) of n_frames frames frame_stride bytes apart starting at p; every other pixel keeps its bits. Call it after the
+        zinger filter, before every weight."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_ring_correct_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_ring_correct_rows")
 
     # ---- row extension (DESIGN.md section 4.11) -----------------------------------------------------------
     row_extension_check = staticmethod(row_extension_check)

@@ -1018,6 +1018,10 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += static_cast<size_t>(ctx->defect_map.stats.device_bytes);
     if(ctx->zinger.set) // the scratch of paris_hip_set_zinger_filter
         total += ctx->zinger.device_bytes;
+    if(ctx->ring.d_sum != nullptr) // the open profile of paris_hip_ring_profile_begin
+        total += sizeof(double) * static_cast<size_t>(ctx->ring.sum_dim_x) * ctx->ring.sum_dim_y;
+    if(ctx->ring.set) // the correction frame of paris_hip_set_ring_correction
+        total += sizeof(float) * static_cast<size_t>(ctx->ring.dim_x) * ctx->ring.dim_y;
     if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached
         total += ctx->row_extension.device_bytes;
     *bytes = total;

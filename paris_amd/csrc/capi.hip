@@ -111,6 +111,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_forward_project();
             paris_hip_warm_defect_map();
             paris_hip_warm_zinger();
+            paris_hip_warm_ring();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -324,6 +325,8 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     paris_hip_flat_field_release(ctx, true); // (nothing reads the reference frames but the compute stream, drained above)
     paris_hip_defect_map_release(ctx, true);
     paris_hip_zinger_release(ctx, true);
+    paris_hip_ring_profile_release(ctx, true);
+    paris_hip_ring_correction_release(ctx, true);
     if(ctx->defer_count != 0)
     {
         // Projections still deferred belong to key_v. Every library entry point that reads or frees a volume has flushed them

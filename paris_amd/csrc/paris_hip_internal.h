@@ -146,6 +146,20 @@ struct paris_hip_ctx
         size_t device_bytes = 0;
         char* d_scratch = nullptr;
     } zinger;
+    // Ring filter. The open profile (paris_hip_ring_profile_begin): the double sums on the device, rows
+    // sum_dim_x doubles apart, and on the host how many frames each row has received. The correction frame
+    // (paris_hip_set_ring_correction): rows dim_x floats apart; `zero`: it holds no pixel to correct, paris_hip_ring_correct_rows is
+    // idle. Both are touched by the kernels of ring.hip on the compute stream only (the sums by the copy of finish as well, on the same
+    // stream), so they are replaced, retired and freed as the defect plan is.
+    struct ring_t
+    {
+        double* d_sum = nullptr;
+        uint32_t sum_dim_x = 0, sum_dim_y = 0;
+        std::vector<uint32_t> count;
+        bool set = false, zero = false;
+        float* d_c = nullptr;
+        uint32_t dim_x = 0, dim_y = 0;
+    } ring;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -409,6 +423,7 @@ void paris_hip_warm_forward_project();
 void paris_hip_warm_defect_map();
 #pragma GCC visibility push(hidden)
 void paris_hip_warm_zinger();
+void paris_hip_warm_ring();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -433,6 +448,9 @@ int paris_hip_row_extension_for(paris_hip_ctx* ctx, const float* d_kp, uint32_t 
 int paris_hip_row_extension_for_k(paris_hip_ctx* ctx, const float* d_k, uint32_t dim_x, const float** d_c, uint32_t* m);
 // zinger.hip: the same for the zinger filter's scratch
 void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying);
+// ring.hip: the same for the ring filter's open profile and for its correction frame
+void paris_hip_ring_profile_release(paris_hip_ctx* ctx, bool destroying);
+void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events

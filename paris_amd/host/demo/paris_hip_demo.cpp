@@ -6,6 +6,7 @@
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
+//                       [--rings half_width floor limit]
 //                       [--extend-rows W M]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
@@ -21,6 +22,8 @@
 // repairs each frame's defective pixels after the dark / flat correction and before the weights.
 // --zingers: threshold_abs, threshold_rel and the polarity (1 bright, -1 dark, 0 both) of the zinger rule. set_zinger_filter() before the
 // loops, so that paris::weight() removes each frame's outlier pixels after the repair and before the weights.
+// --rings: half_width, floor_abs and limit_abs of the ring rule. A pre-pass before the loops sums every frame (ring_profile_add()) and
+// set_ring_correction() gets the rule's correction frame, so that paris::weight() subtracts it after the zinger filter.
 // --extend-rows: the taper length W and the number of edge pixels M of the row extension for truncated projections.
 // set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
@@ -84,6 +87,9 @@ int main(int argc, char** argv)
         bool zingers = false;
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 1;
+        bool rings = false;
+        std::uint32_t ring_half_width = 0;
+        float ring_floor = 0.f, ring_limit = 0.f;
         bool extend_rows = false;
         std::uint32_t extend_taper = 0, extend_edge = 0;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
@@ -125,6 +131,14 @@ int main(int argc, char** argv)
                 zinger_abs = std::strtof(argv[a + 1], nullptr);
                 zinger_rel = std::strtof(argv[a + 2], nullptr);
                 zinger_polarity = std::atoi(argv[a + 3]);
+                a += 3;
+            }
+            else if(!std::strcmp(argv[a], "--rings") && a + 3 < argc)
+            {
+                rings = true;
+                ring_half_width = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
+                ring_floor = std::strtof(argv[a + 2], nullptr);
+                ring_limit = std::strtof(argv[a + 3], nullptr);
                 a += 3;
             }
             else if(!std::strcmp(argv[a], "--extend-rows") && a + 2 < argc)
@@ -228,6 +242,22 @@ int main(int argc, char** argv)
             if(f == nullptr || std::fread(frames.data(), sizeof(float), frames.size(), f) != frames.size())
                 throw paris::stage_runtime_error{"cannot read " + in_path};
             std::fclose(f);
+        }
+
+        if(rings) // the pre-pass: every frame through correction, repair and zinger filter into the profile, then the correction frame
+        {
+            paris::backend::ring_profile_begin(det.n_row, det.n_col);
+            for(std::uint32_t i = 0; i < n_proj; ++i)
+            {
+                auto p = paris::backend::make_projection_host(det.n_row, det.n_col);
+                std::memcpy(p.buf.get(), frames.data() + frame * (i % n_held), frame * sizeof(float));
+                p.idx = i;
+                auto d_p = paris::load(p);
+                paris::ring_profile_add(d_p);
+            }
+            auto c = std::vector<float>(frame);
+            paris::backend::ring_profile_finish(ring_half_width, ring_floor, ring_limit, c.data());
+            paris::backend::set_ring_correction(c.data(), det.n_row, det.n_col);
         }
 
         std::FILE* out = write_out ? std::fopen(out_path.c_str(), "wb") : nullptr;

@@ -6,7 +6,7 @@
 //             [--roi --roi-x1 a --roi-x2 b --roi-y1 c --roi-y2 d --roi-z1 e --roi-z2 f]
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
-//             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]
+//             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -81,6 +81,7 @@ int main(int argc, char** argv)
                             "          [--slabs n] [--devices n] [--f16] [--window ramp|shepp-logan] [--batch n] [--no-row-band] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]\n"
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
+                            "          [--rings H[:FLOOR[:LIMIT]]]\n"
                             "          [--extend-rows W[:M]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
@@ -96,6 +97,10 @@ int main(int argc, char** argv)
                             "--zingers: every pixel that differs from the median m of its 3 x 3 window by more than ABS + REL * |m| is replaced by\n"
                             "m on the device, after the repair and before the weights -- pixels above m (bright: the default), below it (dark: the\n"
                             "default with --flat) or both; a frame with more flagged pixels than 1/256 of the detector (1024 at least) is left as it is.\n"
+                            "--rings: stationary detector offsets, which reconstruct to rings. The scan is read once before the reconstruction;\n"
+                            "every pixel's mean over the views is compared with the running median of 2 H + 1 pixels (H in 1 .. 32) along its\n"
+                            "detector row, and a difference c with FLOOR <= |c| (and |c| <= LIMIT unless LIMIT is 0; both default to 0) is\n"
+                            "subtracted from every frame on the device, after the zinger filter and before the weights.\n"
                             "--extend-rows: the object is wider than the detector (truncated rows). The row filter acts as if every row went on\n"
                             "beyond either edge as the mean of its M outermost pixels (1, 2, 4 or 8; default 4) times a cos^2 taper of W pixels\n"
                             "(1 .. 16384; 16 is a good start, longer is not better) instead of dropping to 0.\n");
@@ -127,6 +132,7 @@ int main(int argc, char** argv)
             else if(k == "--zingers") paris::detail::parse_zingers(val(), po);
             else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
             else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
+            else if(k == "--rings") paris::detail::parse_rings(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -167,6 +173,11 @@ int main(int argc, char** argv)
             std::printf("zinger filter on: %llu frame band(s) examined, %llu pixel(s) replaced, %llu saturated (left as they were)\n",
                         static_cast<unsigned long long>(r.zingers.frames), static_cast<unsigned long long>(r.zingers.replaced),
                         static_cast<unsigned long long>(r.zingers.saturated_frames));
+        if(r.ring_filter)
+            std::printf("ring filter on: %u frame(s) in the pre-pass (%.3f s), %llu pixel(s) corrected, %llu below the floor, %llu above the limit, "
+                        "%llu not finite, largest |c| %.6g\n", r.ring_frames, r.ring_prepass_s, static_cast<unsigned long long>(r.rings.corrected),
+                        static_cast<unsigned long long>(r.rings.below_floor), static_cast<unsigned long long>(r.rings.above_limit),
+                        static_cast<unsigned long long>(r.rings.not_finite), static_cast<double>(r.rings.max_abs));
         std::printf("volume %u x %u x %u (%d slab%s) -> %s in %.3f s\n", r.roi_geo.dim_x, r.roi_geo.dim_y, r.roi_geo.dim_z, r.info.num,
                     r.info.num == 1 ? "" : "s", r.output_file.c_str(), r.wall_s);
         if(r.devices.size() > 1 && r.shared_source)

@@ -129,6 +129,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> offset_detectors; // set_offset_detector(), per device of this thread
                 std::set<const paris_hip_ctx*> defect_maps; // set_defect_map(), per device of this thread
                 std::set<const paris_hip_ctx*> zinger_filters; // set_zinger_filter(), per device of this thread
+                std::set<const paris_hip_ctx*> ring_corrections; // set_ring_correction(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -346,6 +347,50 @@ namespace paris
             inline auto has_zinger_filter(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().zinger_filters;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the pixels of this thread's current device's detector carry stationary offsets, which
+        // reconstruct to rings. A pre-pass over the scan sums the frames -- ring_profile_begin(), then
+        // ring_profile_add() on every frame as paris::weight() would see it after the zinger filter, then ring_profile_finish(), which
+        // returns the correction frame c (n_row x n_col floats, rows n_row apart) of the rule in include/paris_hip.h. Until
+        // clear_ring_correction(), paris::weight() subtracts the c given to set_ring_correction() from every frame, after the zinger
+        // filter and before every weight (paris_hip_ring_correct_rows). The library keeps its own copy of c.
+        inline auto ring_profile_begin(std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_ring_profile_begin(current_ctx(), n_row, n_col), "ring_profile_begin()");
+        }
+
+        inline auto ring_profile_add(const float* d_p, std::size_t pitch, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_ring_profile_add_rows(current_ctx(), d_p, pitch, 0u, 1u, n_row, n_col, 0u, n_col), "ring_profile_add()");
+        }
+
+        inline auto ring_profile_finish(std::uint32_t half_width, float floor_abs, float limit_abs, float* c, paris_hip_ring_stats* stats = nullptr)
+            -> void
+        {
+            const auto setting = paris_hip_ring_filter{half_width, floor_abs, limit_abs};
+            detail::runtime_check(paris_hip_ring_profile_finish(current_ctx(), &setting, c, nullptr, stats), "ring_profile_finish()");
+        }
+
+        inline auto set_ring_correction(const float* c, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_set_ring_correction(current_ctx(), c, n_row, n_col), "set_ring_correction()");
+            detail::state().ring_corrections.insert(current_ctx());
+        }
+
+        inline auto clear_ring_correction() -> void
+        {
+            detail::runtime_check(paris_hip_clear_ring_correction(current_ctx()), "clear_ring_correction()");
+            detail::state().ring_corrections.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_ring_correction(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().ring_corrections;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

@@ -108,6 +108,15 @@ namespace paris
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 2;      // +1 bright, -1 dark, 0 both; 2: the default, resolved by run()
         std::size_t zinger_bytes = 0; // filled by run(): what the setting occupies on a device
+        // removal of ring artefacts (extension): --rings H[:FLOOR[:LIMIT]], checked by run() before any device
+        // work (detail::check_rings). run() then reads the scan once on the first device (detail::ring_prepass): every frame goes
+        // through the chain the reconstruction uses -- correction, repair, zinger filter -- into the profile, and the rule's correction
+        // frame is kept here. Every device ctx gets it, and each frame is corrected after the zinger filter and before the weights
+        bool rings = false;
+        std::uint32_t ring_half_width = 0;
+        float ring_floor = 0.f, ring_limit = 0.f;
+        std::size_t ring_bytes = 0;                             // filled by run(): what the correction frame occupies on a device
+        std::shared_ptr<const std::vector<float>> ring_c;       // filled by run(): the correction frame
         // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
         // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
         // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
@@ -263,6 +272,40 @@ namespace paris
         using clock = std::chrono::steady_clock;
         inline double since(clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); }
 
+        // the settings of the frame chain in front of the weights, the same for every device ctx of a run: --flat / --dark, --defects /
+        // --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
+        inline void set_frame_chain(paris_hip_ctx* ctx, const program_options& po, device_report& rep)
+        {
+            if(po.flat)
+                rt(paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row, po.det_geo.n_col,
+                                            po.t_min), "set_flat_field()");
+            if(po.defect_mask || po.defects_from_flat)
+            {
+                const auto n_px = static_cast<std::size_t>(po.det_geo.n_row) * po.det_geo.n_col;
+                auto mask = po.defect_mask ? *po.defect_mask : std::vector<std::uint8_t>(n_px, 0u);
+                int rc = PARIS_HIP_SUCCESS;
+                if(po.defects_from_flat)
+                {
+                    auto dead = std::vector<std::uint8_t>(n_px, 0u);
+                    rc = paris_hip_flat_field_dead_pixels(ctx, dead.data());
+                    for(std::size_t k = 0; k < n_px; ++k)
+                        mask[k] |= dead[k];
+                }
+                if(rc == PARIS_HIP_SUCCESS)
+                    rc = paris_hip_set_defect_map(ctx, mask.data(), po.det_geo.n_row, po.det_geo.n_col);
+                if(rc == PARIS_HIP_SUCCESS)
+                    rc = paris_hip_defect_map_info(ctx, &rep.defects);
+                rt(rc, "set_defect_map()");
+                rep.defect_map = true;
+            }
+            if(po.zingers)
+            {
+                const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
+                rt(paris_hip_set_zinger_filter(ctx, &setting, po.det_geo.n_row, po.det_geo.n_col), "set_zinger_filter()");
+                rep.zinger_filter = true;
+            }
+        }
+
         // frames per group and groups, as reconstruct() lays its slots out
         inline auto slot_shape(const program_options& po) -> std::pair<std::uint32_t, std::uint32_t>
         {
@@ -282,7 +325,7 @@ namespace paris
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
             // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes;
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes;
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -587,54 +630,20 @@ namespace paris
         const auto t_setup = clock::now();
         paris_hip_ctx* ctx = nullptr;
         rt(paris_hip_ctx_create(device, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()"); // :87
-        if(po.flat)
-        {
-            const int rc = paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row,
-                                                    po.det_geo.n_col, po.t_min);
-            if(rc != PARIS_HIP_SUCCESS)
-            {
-                paris_hip_ctx_destroy(ctx);
-                rt(rc, "set_flat_field()");
-            }
-        }
-        // --defects / --defects-from-flat: the map of this run, the same for every device
         bool repair = false;
         std::uint32_t reach_rows = 0; // how far beyond a band's rows the repair reads
-        if(po.defect_mask || po.defects_from_flat)
+        try
         {
-            const auto n_px = static_cast<std::size_t>(po.det_geo.n_row) * po.det_geo.n_col;
-            auto mask = po.defect_mask ? *po.defect_mask : std::vector<std::uint8_t>(n_px, 0u);
-            int rc = PARIS_HIP_SUCCESS;
-            if(po.defects_from_flat)
-            {
-                auto dead = std::vector<std::uint8_t>(n_px, 0u);
-                rc = paris_hip_flat_field_dead_pixels(ctx, dead.data());
-                for(std::size_t k = 0; k < n_px; ++k)
-                    mask[k] |= dead[k];
-            }
-            if(rc == PARIS_HIP_SUCCESS)
-                rc = paris_hip_set_defect_map(ctx, mask.data(), po.det_geo.n_row, po.det_geo.n_col);
-            if(rc == PARIS_HIP_SUCCESS)
-                rc = paris_hip_defect_map_info(ctx, &rep.defects);
-            if(rc != PARIS_HIP_SUCCESS)
-            {
-                paris_hip_ctx_destroy(ctx);
-                rt(rc, "set_defect_map()");
-            }
-            rep.defect_map = repair = true;
+            set_frame_chain(ctx, po, rep);
+            repair = rep.defect_map;
             reach_rows = rep.defects.reach_rows;
+            if(po.ring_c) // --rings: the correction frame of run()'s pre-pass, the same for every device
+                rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
         }
-        // --zingers: the rule of this run, the same for every device
-        if(po.zingers)
+        catch(...)
         {
-            const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
-            const int rc = paris_hip_set_zinger_filter(ctx, &setting, po.det_geo.n_row, po.det_geo.n_col);
-            if(rc != PARIS_HIP_SUCCESS)
-            {
-                paris_hip_ctx_destroy(ctx);
-                rt(rc, "set_zinger_filter()");
-            }
-            rep.zinger_filter = true;
+            paris_hip_ctx_destroy(ctx);
+            throw;
         }
         // --extend-rows: the same setting on every device
         if(po.extend_rows)
@@ -803,6 +812,9 @@ namespace paris
                     if(filter_by_group && band_count != 0 && po.zingers) // then the zinger filter, one call for the group
                         rt(paris_hip_zinger_filter_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
                            "zinger filter");
+                    if(filter_by_group && band_count != 0 && po.ring_c) // then the detector's stationary offsets, on the band itself
+                        rt(paris_hip_ring_correct_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
+                           "ring correction");
                     if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
                         rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
                                                                  band_count, &t.det_geo), "offset-detector weight()");
@@ -885,6 +897,8 @@ namespace paris
                             rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, fix_first, fix_count), "defect repair");
                         if(po.zingers && !filter_by_group) // then the band's outlier pixels
                             rt(paris_hip_zinger_filter_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "zinger filter");
+                        if(po.ring_c && !filter_by_group) // then the detector's stationary offsets
+                            rt(paris_hip_ring_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "ring correction");
                         if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
                             rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
                                                                      &t.det_geo), "offset-detector weight()");
@@ -960,6 +974,10 @@ namespace paris
         bool zinger_filter = false;                     // --zingers: the filter was on; its counts over all devices and slabs (a
         paris_hip_zinger_counts zingers{};              // frame counts once per slab: each slab filters its own row band)
         bool row_extension = false;                     // --extend-rows: every device filtered with the setting
+        bool ring_filter = false;                       // --rings: the pre-pass ran; what the rule did to the scan's mean frame, and
+        paris_hip_ring_stats rings{};                   // how long the pre-pass took (reading the scan included)
+        std::uint32_t ring_frames = 0;
+        double ring_prepass_s = 0;
         double wall_s = 0;
         std::string output_file;
     };
@@ -1178,6 +1196,134 @@ namespace paris
             po.extend_bytes = std::size_t{po.det_geo.n_row} * sizeof(float);
         }
 
+        // --rings H[:FLOOR[:LIMIT]] as typed; refuses anything that is not an unsigned integer and up to two numbers
+        inline auto parse_rings(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: cannot read '" + v + "'"}; };
+            const auto number = [&bad](const std::string& t) -> float {
+                std::size_t used = 0;
+                float x = 0.f;
+                try
+                {
+                    x = std::stof(t, &used);
+                }
+                catch(const std::exception&)
+                {
+                    used = 0;
+                }
+                if(t.empty() || used != t.size())
+                    throw bad();
+                return x;
+            };
+            const auto first = v.find(':');
+            const auto second = first == std::string::npos ? first : v.find(':', first + 1u);
+            const auto h = v.substr(0, first);
+            if(h.empty() || h.size() > 9u || h.find_first_not_of("0123456789") != std::string::npos
+               || (second != std::string::npos && v.find(':', second + 1u) != std::string::npos))
+                throw bad();
+            po.ring_half_width = static_cast<std::uint32_t>(std::stoul(h));
+            po.ring_floor = first == std::string::npos ? 0.f : number(v.substr(first + 1u, second == std::string::npos ? second : second - first - 1u));
+            po.ring_limit = second == std::string::npos ? 0.f : number(v.substr(second + 1u));
+            po.rings = true;
+        }
+
+        // --rings: the setting is checked for this detector here, before any device work
+        inline auto check_rings(program_options& po) -> void
+        {
+            if(!po.rings)
+                return;
+            const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
+            const int rc = paris_hip_ring_filter_check(&setting, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.ring_bytes);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--rings: the detector has more than 2^32 - 1 pixels"};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: H must lie in 1 .. 32, FLOOR must be finite and not negative, LIMIT 0 (none) or "
+                                               "finite and above FLOOR (got " + std::to_string(po.ring_half_width) + ":" + std::to_string(po.ring_floor)
+                                               + ":" + std::to_string(po.ring_limit) + ")"};
+        }
+
+        // --rings: the pre-pass. Every projection the run uses is read once as a whole frame on the first device and goes through the
+        // chain the reconstruction uses -- the raw upload (corrected with --flat), the defect repair, the zinger filter -- into the ring
+        // profile, a group of po.batch frames per call as the main loop groups them. Then the rule makes the correction frame, which
+        // is kept in po. Everything allocated here is freed before it returns: run() plans the slabs afterwards.
+        inline auto ring_prepass(program_options& po, run_report& r) -> void
+        {
+            const auto t_start = clock::now();
+            const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+            const std::uint32_t batch = slot_shape(po).first;
+            if(static_cast<std::uint64_t>(n_col) * batch > 0xffffffffull)
+                throw stage_construction_error{"too many projection slots for this detector"};
+            paris_hip_ctx* ctx = nullptr;
+            rt(paris_hip_ctx_create(0, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
+            auto h_buf = std::vector<float*>(batch, nullptr);
+            float* d_all = nullptr;
+            const auto cleanup = [&] {
+                for(auto h : h_buf)
+                    paris_hip_free_host(ctx, h);
+                paris_hip_free(ctx, d_all);
+                paris_hip_ctx_destroy(ctx);
+            };
+            try
+            {
+                auto rep = device_report{};
+                set_frame_chain(ctx, po, rep);
+                std::size_t d_pitch = 0;
+                rt(paris_hip_malloc_projection(ctx, n_row, n_col * batch, &d_all, &d_pitch), "make_projection_device()");
+                const auto d_stride = d_pitch * n_col;
+                for(auto& h : h_buf)
+                {
+                    void* p = nullptr;
+                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(n_row) * n_col * sizeof(float), &p), "make_projection_host()");
+                    h = static_cast<float*>(p);
+                }
+                rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
+                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
+                for(bool more = true; more;)
+                {
+                    std::uint32_t filled = 0;
+                    for(; filled < batch; ++filled)
+                    {
+                        const auto p = source.next_raw(h_buf[filled], n_row, n_col, 0u, n_col);
+                        if(!p.valid())
+                        {
+                            more = false;
+                            break;
+                        }
+                        if(p.dim_x != n_row || p.dim_y != n_col)
+                            throw stage_runtime_error{"projection size does not match the detector geometry"};
+                        auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * filled);
+                        const auto px = his::pixel_size(p.pixel);
+                        if(po.flat)
+                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[filled], n_row * px, n_row, n_col, 0u, n_col, p.pixel),
+                               "load()");
+                        else
+                            rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[filled], n_row * px, n_row, n_col, p.pixel), "load()");
+                    }
+                    if(filled == 0)
+                        break;
+                    if(rep.defect_map)
+                        rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "defect repair");
+                    if(po.zingers)
+                        rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "zinger filter");
+                    rt(paris_hip_ring_profile_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
+                    rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
+                    r.ring_frames += filled;
+                }
+                auto c = std::make_shared<std::vector<float>>(static_cast<std::size_t>(n_row) * n_col);
+                const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
+                rt(paris_hip_ring_profile_finish(ctx, &setting, c->data(), nullptr, &r.rings), "ring_profile_finish()");
+                po.ring_c = std::move(c);
+                r.ring_filter = true;
+            }
+            catch(...)
+            {
+                cleanup();
+                throw;
+            }
+            cleanup();
+            r.ring_prepass_s = since(t_start);
+        }
+
         inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
         {
             if(v == "bright") po.zinger_polarity = 1;
@@ -1199,6 +1345,7 @@ namespace paris
         detail::load_defects(po);
         detail::check_zingers(po);
         detail::check_extend_rows(po);
+        detail::check_rings(po);
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1216,6 +1363,8 @@ namespace paris
             n_dev = po.devices;
         po = detail::fit_batch(po, n_dev);
         r.batch = po.batch;
+        if(po.rings) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
+            detail::ring_prepass(po, r);
 
         if(po.slabs > 0) // fixed split (src/cuda/subvolume_information.cpp:112-116 with a given count)
         {

@@ -28,24 +28,46 @@ namespace paris
         return backend::make_volume_device(subvol_geo.dim_x, subvol_geo.dim_y, dim_z);
     }
 
+    namespace detail
+    {
+        // the part of the chain that makes the line integrals the ring profile sums: correction, repair, zinger filter
+        inline auto line_integrals(backend::projection_device_type& p, const char* what) -> void
+        {
+            if(backend::detail::has_flat_field(backend::current_ctx()))
+                backend::detail::runtime_check(paris_hip_flat_field_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y,
+                                                                         0u, p.dim_y), what);
+            if(backend::detail::has_defect_map(backend::current_ctx()))
+                backend::detail::runtime_check(paris_hip_defect_repair_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                            p.dim_y, 0u, p.dim_y), what);
+            if(backend::detail::has_zinger_filter(backend::current_ctx()))
+                backend::detail::runtime_check(paris_hip_zinger_filter_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                            p.dim_y, 0u, p.dim_y), what);
+        }
+    }
+
+    // the ring filter's pre-pass over one loaded frame, between backend::ring_profile_begin() and backend::ring_profile_finish(): the
+    // frame goes through the chain paris::weight() runs in front of the ring correction and is added to the profile. It is not
+    // weighted: reconstruct from a fresh load.
+    inline auto ring_profile_add(backend::projection_device_type& p) -> void
+    {
+        detail::line_integrals(p, "ring_profile_add()");
+        backend::ring_profile_add(p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y);
+    }
+
     // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with a defect map
     // (backend::set_defect_map) the repair of the defective pixels, then with a zinger filter (backend::set_zinger_filter) the removal
-    // of the frame's outlier pixels, then with an offset detector (backend::set_offset_detector) or a short scan set
-    // (backend::set_short_scan) its redundancy weight, then the cosine weight: the only correct order (the weights are linear in the
+    // of the frame's outlier pixels, then with a ring correction (backend::set_ring_correction) the subtraction of the detector's
+    // stationary offsets (additive in line integrals, so before every weight), then with an offset detector
+    // (backend::set_offset_detector) or a short scan set (backend::set_short_scan) its redundancy weight, then the cosine weight: the only correct order (the weights are linear in the
     // line integrals, the correction is not; the repair averages line integrals, and every weight varies from pixel to pixel, so a
     // repaired pixel must get its OWN weight afterwards; a dead pixel the correction left at 0 must be repaired before the zinger
     // filter sees it, or it would be patched as a dark outlier by the wrong rule; and a median of weighted pixels is no weighted median)
     inline auto weight(backend::projection_device_type& p, const detector_geometry& det_geo) -> void
     {
-        if(backend::detail::has_flat_field(backend::current_ctx()))
-            backend::detail::runtime_check(paris_hip_flat_field_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y,
-                                                                     0u, p.dim_y), "weight()");
-        if(backend::detail::has_defect_map(backend::current_ctx()))
-            backend::detail::runtime_check(paris_hip_defect_repair_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
-                                                                        p.dim_y, 0u, p.dim_y), "weight()");
-        if(backend::detail::has_zinger_filter(backend::current_ctx()))
-            backend::detail::runtime_check(paris_hip_zinger_filter_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
-                                                                        p.dim_y, 0u, p.dim_y), "weight()");
+        detail::line_integrals(p, "weight()");
+        if(backend::detail::has_ring_correction(backend::current_ctx()))
+            backend::detail::runtime_check(paris_hip_ring_correct_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                       p.dim_y, 0u, p.dim_y), "weight()");
         if(backend::detail::has_offset_detector(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_stage_offset_detector_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                                                   p.dim_y, &det_geo), "weight()");
