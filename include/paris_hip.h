@@ -794,6 +794,95 @@ int paris_hip_stage_forward_project(paris_hip_ctx* ctx, const float* d_v, uint32
                                     float* d_p, size_t p_pitch, uint32_t p_dim_x, uint32_t p_dim_y, uint32_t p_idx, float p_phi,
                                     int enable_angles, int accumulate);
 
+/* ---- volume export (extension, no reference counterpart): 8- or 16-bit voxels over a grey window ---------
+ * A finished volume leaves the device as unsigned integers quantised over a chosen window [lo, hi], 1 or 2 bytes per voxel instead
+ * of 4, and the statistics a window is chosen from -- extremes and a histogram -- are taken on the device.
+ * Setting paris_hip_volume_window { float lo; float hi; int voxel_type; }.
+ *   voxel_type is PARIS_HIP_VOXEL_U8 with L = 255, or PARIS_HIP_VOXEL_U16 with L = 65535.
+ * Quantise.
+ *   scale = (float)(L / ((double)hi - (double)lo)), rounded once.
+ *   Per voxel v, in fp32, each operation rounded once and no contraction: x = (v - lo) * scale.
+ *   q = 0 when v is NaN or x <= 0.
+ *   q = L when x >= L.
+ *   Otherwise q = rint(x): to nearest, ties to even.
+ *   So +inf gives L, -inf gives 0, and +0 and -0 behave alike. u16 is stored as the machine stores it, little-endian.
+ * Counts are 64-bit and accumulated per ctx until reset.
+ *   voxels is the number of voxels examined.
+ *   below is the number of finite voxels with v < lo, above the number of finite voxels with v > hi.
+ *   not_finite counts NaN, +inf and -inf.
+ * Check (paris_hip_volume_window_check) refuses a NULL setting, an unknown type, a lo or hi that is not finite, hi <= lo,
+ *   (double)hi - lo < 2^-100, and a scale that is not finite.
+ * Stats look at finite voxels only.
+ *   min and max are the extremes of the finite voxels; without one, min = +inf and max = -inf. The sign of a zero extreme is
+ *   unspecified.
+ *   not_finite counts the others.
+ *   Optionally a linear histogram of n_bins counters, 1 <= n_bins <= PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, over [h_lo, h_hi], which
+ *   the check's rules apply to with n_bins in the place of L:
+ *     bscale = (float)(n_bins / ((double)h_hi - h_lo)).
+ *     A finite v with h_lo <= v <= h_hi goes to bin min(n_bins - 1, (uint32_t)((v - h_lo) * bscale)): fp32 operations, and the
+ *     conversion truncates (a product beyond every bin, +inf included, lands in the last bin).
+ *     Finite voxels outside the range count as below or above.
+ *   All counters are integers, so no result depends on the order of the device's atomics.
+ * Window from a histogram (paris_hip_volume_window_from_histogram), on the host, the single implementation. It needs
+ *   0 <= p_lo < p_hi <= 100. Everything is computed in double and rounded once.
+ *   T is the sum of the bins, width = ((double)h_hi - h_lo) / n_bins, C(b) the inclusive cumulative count.
+ *   b_lo is the smallest b with C(b) > T * p_lo / 100, and w_lo = (float)(h_lo + b_lo * width).
+ *   b_hi is the smallest b with C(b) >= T * p_hi / 100, and w_hi = (float)(h_lo + (b_hi + 1) * width).
+ *   (Where rounding leaves no such b, it is the last bin.) T == 0 is PARIS_HIP_ERROR_INVALID_ARGUMENT. */
+#define PARIS_HIP_VOXEL_U8 1
+#define PARIS_HIP_VOXEL_U16 2
+#define PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX 4096
+typedef struct paris_hip_volume_window {
+    float lo;       /* the voxel value stored as 0 */
+    float hi;       /* the voxel value stored as L; > lo */
+    int voxel_type; /* PARIS_HIP_VOXEL_U8 or PARIS_HIP_VOXEL_U16 */
+} paris_hip_volume_window;
+/* what paris_hip_volume_quantize_counts reports */
+typedef struct paris_hip_volume_counts {
+    uint64_t voxels;     /* voxels examined */
+    uint64_t below;      /* finite voxels below lo (stored as 0) */
+    uint64_t above;      /* finite voxels above hi (stored as L) */
+    uint64_t not_finite; /* NaN and +-inf */
+} paris_hip_volume_counts;
+/* what paris_hip_volume_stats reports */
+typedef struct paris_hip_volume_statistics {
+    float min;           /* of the finite voxels; +inf without one */
+    float max;           /* of the finite voxels; -inf without one */
+    uint64_t below;      /* finite voxels below h_lo (0 without a histogram) */
+    uint64_t above;      /* finite voxels above h_hi (0 without a histogram) */
+    uint64_t not_finite; /* NaN and +-inf */
+    uint64_t voxels;     /* voxels examined */
+} paris_hip_volume_statistics;
+/* Host only, no ctx and no device. */
+int paris_hip_volume_window_check(const paris_hip_volume_window* setting);
+/* Host only: hist is n_bins counters over [h_lo, h_hi], p_lo and p_hi are percentiles. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL
+ * pointer, n_bins == 0, a range the check refuses, percentiles outside 0 <= p_lo < p_hi <= 100, or an empty histogram. The window
+ * it returns still has to pass paris_hip_volume_window_check: both ends may round to one float. */
+int paris_hip_volume_window_from_histogram(const uint64_t* hist, uint32_t n_bins, float h_lo, float h_hi, double p_lo, double p_hi,
+                                           float* w_lo, float* w_hi);
+/* Quantises the n_voxels floats at d_v into d_q (n_voxels bytes, or 2 n_voxels), device to device, on the ctx stream, and adds to
+ * the ctx's counts. What is deferred runs first. [d_q, d_q + bytes) is treated as paris_hip_volume_mark_dirty treats it: the
+ * destination may be memory of paris_hip_malloc_volume, and it now holds arbitrary bits. Aligned or not: 16-byte vectors are used
+ * where source and destination reach a 16-byte boundary at the same voxel, single voxels otherwise.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for null pointers, a setting the check refuses, a d_v that is not 4-byte aligned, a u16 d_q that
+ * is not 2-byte aligned, or a destination range that overlaps the source range. n_voxels == 0 does nothing. */
+int paris_hip_volume_quantize(paris_hip_ctx* ctx, const float* d_v, uint64_t n_voxels, const paris_hip_volume_window* setting, void* d_q);
+/* The same into a scratch the ctx owns, followed by an asynchronous copy of the bytes to h_q (pinned memory, to overlap anything)
+ * on the ctx stream: the host reads h_q after paris_hip_ctx_synchronize or a fence. The scratch grows on demand and is reused --
+ * stream order makes one enough; it counts towards paris_hip_projection_reserve_bytes while it exists and paris_hip_ctx_destroy
+ * frees it. */
+int paris_hip_volume_quantize_d2h(paris_hip_ctx* ctx, const float* d_v, uint64_t n_voxels, const paris_hip_volume_window* setting,
+                                  void* h_q);
+/* The counts of the ctx's quantise calls since it was created or last reset: runs what is pending, waits for the ctx stream and
+ * reads them; reset != 0 zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL out. */
+int paris_hip_volume_quantize_counts(paris_hip_ctx* ctx, paris_hip_volume_counts* out, int reset);
+/* Synchronous: runs what is deferred, examines the n_voxels floats at d_v (4-byte aligned) on the device and returns the results
+ * to the host. n_bins == 0: no histogram, h_lo / h_hi are ignored, hist may be NULL. Otherwise hist receives n_bins counters.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL d_v or out, n_bins beyond the maximum, a NULL hist or a refused range with
+ * n_bins != 0. n_voxels == 0 gives the empty result. */
+int paris_hip_volume_stats(paris_hip_ctx* ctx, const float* d_v, uint64_t n_voxels, float h_lo, float h_hi, uint32_t n_bins,
+                           uint64_t* hist, paris_hip_volume_statistics* out);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 const char* paris_hip_strerror(int status);
 /* library version "major.minor.patch" */

@@ -96,6 +96,28 @@ class RowExtension(C.Structure):
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
 
 
+# voxel types of paris_hip_volume_quantize
+VOXEL_U8 = 1
+VOXEL_U16 = 2
+VOLUME_HISTOGRAM_BINS_MAX = 4096  # PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX
+
+
+class VolumeWindow(C.Structure):
+    """paris_hip_volume_window: the grey window and integer type a volume is quantised to (extension)"""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("voxel_type", C.c_int)]
+
+
+class VolumeCounts(C.Structure):
+    """paris_hip_volume_counts: what paris_hip_volume_quantize_counts reports (extension)"""
+    _fields_ = [("voxels", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64), ("not_finite", C.c_uint64)]
+
+
+class VolumeStatistics(C.Structure):
+    """paris_hip_volume_statistics: what paris_hip_volume_stats reports (extension)"""
+    _fields_ = [("min", C.c_float), ("max", C.c_float), ("below", C.c_uint64), ("above", C.c_uint64), ("not_finite", C.c_uint64),
+                ("voxels", C.c_uint64)]
+
+
 class SubvolumeInfo(C.Structure):
     """paris::subvolume_info (src/subvolume_information.h:30-34)"""
     _fields_ = [("geo", SubvolumeGeometry), ("num", C.c_int)]
@@ -232,6 +254,12 @@ SIGNATURES = {
                                             _u32, _u32, _u32, _P(_f), _P(_f), _f, _f, C.c_int]),
     "paris_hip_stage_forward_project": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _P(DetectorGeometry), _P(VolumeGeometry), _vp, _sz,
                                                   _u32, _u32, _u32, _f, C.c_int, C.c_int]),
+    "paris_hip_volume_window_check": (C.c_int, [_P(VolumeWindow)]),
+    "paris_hip_volume_window_from_histogram": (C.c_int, [_vp, _u32, _f, _f, C.c_double, C.c_double, _P(_f), _P(_f)]),
+    "paris_hip_volume_quantize": (C.c_int, [_vp, _vp, C.c_uint64, _P(VolumeWindow), _vp]),
+    "paris_hip_volume_quantize_d2h": (C.c_int, [_vp, _vp, C.c_uint64, _P(VolumeWindow), _vp]),
+    "paris_hip_volume_quantize_counts": (C.c_int, [_vp, _P(VolumeCounts), C.c_int]),
+    "paris_hip_volume_stats": (C.c_int, [_vp, _vp, C.c_uint64, _f, _f, _u32, _vp, _P(VolumeStatistics)]),
     "paris_hip_strerror": (C.c_char_p, [C.c_int]),
     "paris_hip_version": (C.c_char_p, []),
     "paris_hip_last_backproject_ms": (C.c_int, [_vp, _P(_f)]),

@@ -13,14 +13,16 @@ import numpy as np
 
 from . import _lib
 from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
-                   SubvolumeGeometry, SubvolumeInfo, VolumeGeometry, ZingerCounts, ZingerFilter, check)
+                   SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
+                   ZingerFilter, check)
 
 __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfInterest", "SubvolumeInfo",
            "ParisHipError", "ShortScan", "Projection", "Volume", "FilterBuffer", "Backend", "get_devices", "set_device",
            "calculate_volume_geometry", "apply_roi", "filter_size", "load", "make_volume", "weight", "filter",
            "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
            "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
-           "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean"]
+           "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean", "VolumeWindow", "VolumeCounts",
+           "VolumeStatistics", "volume_window_check", "volume_window_from_histogram"]
 
 
 class Projection:
@@ -178,6 +180,37 @@ def row_extension_response(edge_pixels, taper_pixels, dim_x, tau):
     return c
 
 
+_VOXEL_TYPES = {np.dtype(np.uint8): _lib.VOXEL_U8, np.dtype(np.uint16): _lib.VOXEL_U16}
+
+
+def _volume_window(lo, hi, dtype):
+    """the setting for a numpy integer type; an unknown one gets the voxel type 0, which the library refuses"""
+    try:
+        voxel_type = _VOXEL_TYPES.get(np.dtype(dtype), 0)
+    except TypeError:
+        voxel_type = 0
+    return VolumeWindow(lo, hi, voxel_type)
+
+
+def volume_window_check(lo, hi, dtype):
+    """Host only, no device (paris_hip_volume_window_check): raises ParisHipError unless dtype is uint8 or uint16, lo and hi are
+    finite, hi > lo and the window is neither too narrow nor too wide for the rule's scale."""
+    w = _volume_window(lo, hi, dtype)
+    check(_lib.load().paris_hip_volume_window_check(C.byref(w)), "paris_hip_volume_window_check")
+
+
+def volume_window_from_histogram(hist, h_lo, h_hi, p_lo=0.1, p_hi=99.9):
+    """Host only, no device (paris_hip_volume_window_from_histogram): the window (w_lo, w_hi) between the percentiles p_lo and p_hi
+    of a linear histogram over [h_lo, h_hi], as two Python floats that are exact float32 values."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    if h.ndim != 1:
+        raise ValueError("volume_window_from_histogram: the histogram must be a 1-D array")
+    w_lo, w_hi = C.c_float(0), C.c_float(0)
+    check(_lib.load().paris_hip_volume_window_from_histogram(h.ctypes.data if h.size else None, h.size, h_lo, h_hi, p_lo, p_hi,
+                                                             C.byref(w_lo), C.byref(w_hi)), "paris_hip_volume_window_from_histogram")
+    return w_lo.value, w_hi.value
+
+
 class Backend:
     """One device + stream: the state the reference keeps in thread_local statics after set_device
     (src/main.cpp:87). synchronous=True reproduces the reference's blocking calls. stream: None = a private stream of
@@ -314,6 +347,48 @@ class Backend:
         check(self._L.paris_hip_volume_scan_clean(self._ctx, v.ptr, 4 * v.dim_x * v.dim_y * v.dim_z, C.byref(n)),
               "paris_hip_volume_scan_clean")
         return int(n.value)
+
+    # ---- volume export ----------------------------------------------------------
+    volume_window_check = staticmethod(volume_window_check)
+    volume_window_from_histogram = staticmethod(volume_window_from_histogram)
+
+    def volume_stats(self, v, lo=None, hi=None, n_bins=0):
+        """paris_hip_volume_stats of a device volume: (VolumeStatistics, hist). The statistics hold min and max of the finite voxels
+        (+inf / -inf without one), not_finite and voxels; with n_bins > 0 hist is the linear histogram of n_bins uint64 counters over
+        [lo, hi], and below / above count the finite voxels outside it; with n_bins == 0 hist is None. Runs what is deferred first
+        and waits for the result."""
+        st = VolumeStatistics()
+        hist = np.zeros(n_bins, np.uint64) if n_bins else None
+        if n_bins and (lo is None or hi is None):
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_volume_stats")
+        check(self._L.paris_hip_volume_stats(self._ctx, v.ptr, v.dim_x * v.dim_y * v.dim_z, lo if n_bins else 0.0, hi if n_bins else 0.0,
+                                             n_bins, hist.ctypes.data if n_bins else None, C.byref(st)), "paris_hip_volume_stats")
+        return st, hist
+
+    def quantize_volume(self, v, lo, hi, dtype, out=None):
+        """The device volume v as unsigned integers over the window [lo, hi] (dtype numpy uint8 or uint16): q = rint((v - lo) * scale)
+        clamped to [0, L], NaN as 0. Without `out` the voxels come back as a numpy array of the volume's shape
+        (paris_hip_volume_quantize_d2h, then a wait). With `out` -- a device address, or an object with .ptr -- they are written
+        there, device to device (paris_hip_volume_quantize; no wait), and out is returned. Runs what is deferred first and adds to
+        volume_quantize_counts()."""
+        w = _volume_window(lo, hi, dtype)
+        n = v.dim_x * v.dim_y * v.dim_z
+        if out is not None:
+            check(self._L.paris_hip_volume_quantize(self._ctx, v.ptr, n, C.byref(w), out.ptr if hasattr(out, "ptr") else out),
+                  "paris_hip_volume_quantize")
+            return out
+        check(self._L.paris_hip_volume_window_check(C.byref(w)), "paris_hip_volume_window_check")
+        q = np.empty((v.dim_z, v.dim_y, v.dim_x), np.dtype(dtype))
+        check(self._L.paris_hip_volume_quantize_d2h(self._ctx, v.ptr, n, C.byref(w), q.ctypes.data), "paris_hip_volume_quantize_d2h")
+        self.synchronize()
+        return q
+
+    def volume_quantize_counts(self, reset=False):
+        """The VolumeCounts of this backend's quantize_volume() calls since it was made or last reset
+        (paris_hip_volume_quantize_counts): voxels, below, above, not_finite. Waits for the ctx stream."""
+        st = VolumeCounts()
+        check(self._L.paris_hip_volume_quantize_counts(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_volume_quantize_counts")
+        return st
 
     def memset_volume(self, v):
         check(self._L.paris_hip_memset_volume(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z), "paris_hip_memset_volume")

@@ -1024,6 +1024,9 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += sizeof(float) * static_cast<size_t>(ctx->ring.dim_x) * ctx->ring.dim_y;
     if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached
         total += ctx->row_extension.device_bytes;
+    if(ctx->volume_window.d_acc != nullptr) // the volume export's counters
+        total += PARIS_HIP_VOLUME_WINDOW_ACC_BYTES;
+    total += ctx->volume_window.stage_bytes; // the staging buffer of paris_hip_volume_quantize_d2h
     *bytes = total;
     return PARIS_HIP_SUCCESS;
 }

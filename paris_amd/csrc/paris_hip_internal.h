@@ -40,6 +40,9 @@ struct paris_hip_filter_info
     float tau = 0.f; // the pixel pitch K was made for (the row extension's response needs it)
 };
 
+// what paris_hip_ctx::volume_window_t::d_acc occupies: 32 bytes of quantise counters, 32 bytes of stats results, the 64-bit bins
+constexpr size_t PARIS_HIP_VOLUME_WINDOW_ACC_BYTES = 64u + 8u * PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX;
+
 struct paris_hip_ctx
 {
     int device = 0;
@@ -170,6 +173,18 @@ struct paris_hip_ctx
         std::map<std::array<uint32_t, 3>, float*> cache;
         size_t device_bytes = 0;
     } row_extension;
+    // Volume export (volume_window.hip), both made on first use. d_acc: the three 64-bit counters of the
+    // quantise calls (padded to 32 bytes), then the stats kernel's results -- two 32-bit extremes, three 64-bit counters (32 bytes) --
+    // and its PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX 64-bit bins. d_stage: where paris_hip_volume_quantize_d2h quantises to before its
+    // copy to the host; grows on demand, the outgrown one is retired. Touched on the compute stream only. `voxels` is kept here: it
+    // is the sum of the calls' n_voxels.
+    struct volume_window_t
+    {
+        char* d_acc = nullptr;
+        char* d_stage = nullptr;
+        size_t stage_bytes = 0;
+        uint64_t voxels = 0;
+    } volume_window;
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
     std::vector<std::pair<void*, hipEvent_t>> retired;
@@ -424,6 +439,7 @@ void paris_hip_warm_defect_map();
 #pragma GCC visibility push(hidden)
 void paris_hip_warm_zinger();
 void paris_hip_warm_ring();
+void paris_hip_warm_volume_window();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -451,6 +467,8 @@ void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying);
 // ring.hip: the same for the ring filter's open profile and for its correction frame
 void paris_hip_ring_profile_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying);
+// volume_window.hip: the same for the volume export's counters and its staging buffer
+void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events

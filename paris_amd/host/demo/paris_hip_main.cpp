@@ -7,6 +7,7 @@
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
 //             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
+//             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -82,7 +83,7 @@ int main(int argc, char** argv)
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
                             "          [--rings H[:FLOOR[:LIMIT]]]\n"
-                            "          [--extend-rows W[:M]]\n"
+                            "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -103,7 +104,11 @@ int main(int argc, char** argv)
                             "subtracted from every frame on the device, after the zinger filter and before the weights.\n"
                             "--extend-rows: the object is wider than the detector (truncated rows). The row filter acts as if every row went on\n"
                             "beyond either edge as the mean of its M outermost pixels (1, 2, 4 or 8; default 4) times a cos^2 taper of W pixels\n"
-                            "(1 .. 16384; 16 is a good start, longer is not better) instead of dropping to 0.\n");
+                            "(1 .. 16384; 16 is a good start, longer is not better) instead of dropping to 0.\n"
+                            "--voxel-type / --voxel-range: the voxels are written as 8- or 16-bit integers over the grey window [LO, HI], quantised\n"
+                            "on the device, into <output>/<name>.raw with the MetaImage header <name>.mhd beside it, instead of the float DDBVF.\n"
+                            "auto: the window between the percentiles P_LO and P_HI (0.1 and 99.9) of the finished volume's 4096-bin histogram;\n"
+                            "needs --slabs 1 on one device.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -133,6 +138,8 @@ int main(int argc, char** argv)
             else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
             else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
             else if(k == "--rings") paris::detail::parse_rings(val(), po);
+            else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
+            else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -178,6 +185,11 @@ int main(int argc, char** argv)
                         "%llu not finite, largest |c| %.6g\n", r.ring_frames, r.ring_prepass_s, static_cast<unsigned long long>(r.rings.corrected),
                         static_cast<unsigned long long>(r.rings.below_floor), static_cast<unsigned long long>(r.rings.above_limit),
                         static_cast<unsigned long long>(r.rings.not_finite), static_cast<double>(r.rings.max_abs));
+        if(r.voxel_type != 0)
+            std::printf("%llu voxel(s) written as %s over [%.9g, %.9g]: %llu below, %llu above, %llu not finite\n",
+                        static_cast<unsigned long long>(r.voxels.voxels), r.voxel_type == PARIS_HIP_VOXEL_U8 ? "u8" : "u16", static_cast<double>(r.voxel_lo),
+                        static_cast<double>(r.voxel_hi), static_cast<unsigned long long>(r.voxels.below), static_cast<unsigned long long>(r.voxels.above),
+                        static_cast<unsigned long long>(r.voxels.not_finite));
         std::printf("volume %u x %u x %u (%d slab%s) -> %s in %.3f s\n", r.roi_geo.dim_x, r.roi_geo.dim_y, r.roi_geo.dim_z, r.info.num,
                     r.info.num == 1 ? "" : "s", r.output_file.c_str(), r.wall_s);
         if(r.devices.size() > 1 && r.shared_source)

@@ -56,6 +56,28 @@ namespace paris
             return h;
         }
 
+        // `left` bytes at file position `at`, with positioned writes on the descriptor (no shared stream position); `what` names the caller
+        inline void write_at(int fd, const void* data, std::uint64_t left, std::uint64_t at, const char* what)
+        {
+            const auto* bytes = static_cast<const char*>(data);
+            while(left != 0)
+            {
+                const auto chunk = left < (std::uint64_t{1} << 30) ? static_cast<std::size_t>(left) : (std::size_t{1} << 30);
+                const auto done = ::pwrite(fd, bytes, chunk, static_cast<off_t>(at));
+                if(done < 0)
+                {
+                    if(errno == EINTR)
+                        continue;
+                    throw std::system_error{errno, std::generic_category(), what};
+                }
+                if(done == 0) // no progress and no error (a full device can do this): never spin on it
+                    throw std::runtime_error{std::string{what} + ": pwrite made no progress"};
+                bytes += done;
+                at += static_cast<std::uint64_t>(done);
+                left -= static_cast<std::uint64_t>(done);
+            }
+        }
+
         // src/ddbvf.cpp:125-153: writes a slab of dim_z_slab slices starting at global slice `first`
         inline void write(handle_type& h, const float* voxels, std::uint32_t dim_x, std::uint32_t dim_y,
                           std::uint32_t dim_z_slab, std::uint32_t first)
@@ -72,26 +94,7 @@ namespace paris
             const auto pos = static_cast<std::uint64_t>(first_pos) + slice * first;
             // positioned writes on the descriptor: no shared stream position, so slabs of different device threads can be
             // written concurrently (the reference's fseek + fwrite needs the mutex of src/sink.cpp:79-80)
-            const int fd = fileno(h->file);
-            const auto* bytes = reinterpret_cast<const char*>(voxels);
-            auto left = static_cast<std::uint64_t>(dim_x) * dim_y * dim_z_slab * sizeof(float);
-            auto at = pos;
-            while(left != 0)
-            {
-                const auto chunk = left < (std::uint64_t{1} << 30) ? static_cast<std::size_t>(left) : (std::size_t{1} << 30);
-                const auto done = ::pwrite(fd, bytes, chunk, static_cast<off_t>(at));
-                if(done < 0)
-                {
-                    if(errno == EINTR)
-                        continue;
-                    throw std::system_error{errno, std::generic_category(), "ddbvf::write()"};
-                }
-                if(done == 0) // no progress and no error (a full device can do this): never spin on it
-                    throw std::runtime_error{"ddbvf::write(): pwrite made no progress"};
-                bytes += done;
-                at += static_cast<std::uint64_t>(done);
-                left -= static_cast<std::uint64_t>(done);
-            }
+            write_at(fileno(h->file), voxels, static_cast<std::uint64_t>(dim_x) * dim_y * dim_z_slab * sizeof(float), pos, "ddbvf::write()");
         }
     }
 }

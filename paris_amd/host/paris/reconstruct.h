@@ -49,6 +49,16 @@ namespace paris
                       && his::pixel_f32 == PARIS_HIP_PIXEL_F32,
                   "his::pixel_type names the pixel types of paris_hip_upload_projection_raw");
 
+    // --voxel-type / --voxel-range as given (program_options, below); what a drain thread needs to know about the output
+    struct voxel_output
+    {
+        int type = 0;             // 0: float voxels into the DDBVF; PARIS_HIP_VOXEL_U8 / _U16
+        bool range_given = false; // --voxel-range was given
+        bool automatic = false;   // ... as auto
+        float lo = 0.f, hi = 0.f;
+        double p_lo = 0.1, p_hi = 99.9;
+    };
+
     // src/program_options.h:34-50 (the parts the hot path needs)
     struct program_options
     {
@@ -123,6 +133,12 @@ namespace paris
         bool extend_rows = false;
         std::uint32_t extend_taper = 0, extend_edge = 4;
         std::size_t extend_bytes = 0; // filled by run(): the response vector a device keeps while set
+        // voxels written as 8- or 16-bit integers over a grey window (extension): --voxel-type u8|u16 with
+        // --voxel-range LO:HI or auto[:P_LO:P_HI], checked by run() before any device work (detail::check_voxels). The drain threads
+        // then quantise each chunk on the device and copy 1 or 2 bytes per voxel down; the file is <name>.raw with <name>.mhd beside
+        // it. auto: the window between two percentiles of the finished volume's histogram -- one slab on one device only.
+        // Without --voxel-type (0) the float DDBVF is written as ever.
+        voxel_output voxels;
     };
 
     // src/task.h:33-57
@@ -243,6 +259,7 @@ namespace paris
         bool zinger_filter = false; // --zingers: a zinger filter was set; its counts over this device's tasks:
         paris_hip_zinger_counts zingers{};
         bool row_extension = false; // --extend-rows: the setting was made on this device's ctx
+        paris_hip_volume_counts voxels{}; // --voxel-type: the counts of this device's drain ctx
         std::vector<std::string> skipped;
     };
 
@@ -315,7 +332,8 @@ namespace paris
         }
 
         // device memory reconstruct() keeps per device beside the slab: every slot's fp32 frame (rows padded to 256 B), its
-        // half copy with --f16, and two drain chunks' worth of slack for the runtime's own staging
+        // half copy with --f16, and two drain chunks' worth of slack for the runtime's own staging; with --voxel-type the drain ctx's
+        // scratch, one more chunk (a chunk is a whole slice at least: for slices beyond the chunk size the slack covers it), and its counters
         inline auto driver_bytes(const program_options& po) -> std::size_t
         {
             const auto shape = slot_shape(po);
@@ -325,7 +343,8 @@ namespace paris
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
             // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes;
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes
+                   + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -352,6 +371,9 @@ namespace paris
         // (D2H of chunk k + 1 on the drain ctx's stream overlaps the file write of chunk k) and writes them at the slab's slice
         // offset. The device thread meanwhile reconstructs its next slab in another volume buffer; it only waits when it wants a
         // buffer back (wait) or is done (finish). An error in here is rethrown in the device thread by the next wait / finish.
+        // With --voxel-type each chunk is quantised on the device into a scratch of the drain ctx and 1 or 2 bytes per voxel come down
+        // (paris_hip_volume_quantize_d2h in the place of the copy); chunks stay whole slices, the two pinned buffers stay. With
+        // --voxel-range auto the thread first takes the slab's extremes and histogram on the device and chooses the window.
         class volume_drain
         {
         public:
@@ -363,7 +385,8 @@ namespace paris
                 int buffer = 0;                                            // which of the device thread's volume buffers d_v is
             };
 
-            volume_drain(int device, sink& out, std::size_t chunk_bytes) : device_{device}, out_(out), chunk_bytes_{chunk_bytes}
+            volume_drain(int device, sink& out, std::size_t chunk_bytes, const voxel_output& voxels)
+            : device_{device}, out_(out), chunk_bytes_{chunk_bytes}, voxels_(voxels)
             {
                 thread_ = std::thread{[this] { work(); }};
             }
@@ -406,14 +429,17 @@ namespace paris
             }
             auto drain_seconds() -> double { std::lock_guard<std::mutex> lock{m_}; return drain_s_; }
             auto save_seconds() -> double { std::lock_guard<std::mutex> lock{m_}; return save_s_; }
+            auto voxel_counts() -> paris_hip_volume_counts { std::lock_guard<std::mutex> lock{m_}; return counts_; }
 
         private:
             void work()
             {
                 paris_hip_ctx* ctx = nullptr;
-                float* h_stage[2] = {nullptr, nullptr};
+                char* h_stage[2] = {nullptr, nullptr};
                 paris_hip_fence* stage_fence[2] = {nullptr, nullptr};
-                std::size_t stage_floats = 0;
+                std::size_t stage_voxels = 0;
+                const std::size_t voxel_bytes = voxels_.type == 0 ? sizeof(float) : (voxels_.type == PARIS_HIP_VOXEL_U8 ? 1u : 2u);
+                auto window = paris_hip_volume_window{voxels_.lo, voxels_.hi, voxels_.type};
                 try
                 {
                     rt(paris_hip_ctx_create(device_, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
@@ -435,28 +461,48 @@ namespace paris
                         // src/sink.cpp:76); pinning gigabytes costs more than the reconstruction of a small data set
                         const auto slice_floats = static_cast<std::size_t>(j.dim_x) * j.dim_y;
                         const auto voxels = slice_floats * j.dim_z;
-                        const auto want_floats = std::max(slice_floats, std::min(voxels, chunk_bytes_ / sizeof(float)) / slice_floats * slice_floats);
-                        if(want_floats > stage_floats)
+                        if(voxels_.automatic) // the window from the finished volume: extremes, then 4096 bins over them, then the percentiles
+                        {
+                            auto st = paris_hip_volume_statistics{};
+                            rt(paris_hip_volume_stats(ctx, j.d_v, voxels, 0.f, 0.f, 0u, nullptr, &st), "volume stats");
+                            if(!(st.min < st.max))
+                                throw stage_runtime_error{"--voxel-range auto: the volume holds fewer than two different finite values"};
+                            auto hist = std::vector<std::uint64_t>(PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, 0u);
+                            rt(paris_hip_volume_stats(ctx, j.d_v, voxels, st.min, st.max, PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, hist.data(), &st),
+                               "volume histogram");
+                            rt(paris_hip_volume_window_from_histogram(hist.data(), PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, st.min, st.max, voxels_.p_lo,
+                                                                      voxels_.p_hi, &window.lo, &window.hi), "window from histogram");
+                            if(paris_hip_volume_window_check(&window) != PARIS_HIP_SUCCESS)
+                                throw stage_runtime_error{"--voxel-range auto: the percentiles leave no window (" + std::to_string(window.lo) + " .. "
+                                                          + std::to_string(window.hi) + ")"};
+                            out_.set_window(window.lo, window.hi); // writes the .mhd
+                        }
+                        const auto want_voxels = std::max(slice_floats, std::min(voxels, chunk_bytes_ / voxel_bytes) / slice_floats * slice_floats);
+                        if(want_voxels > stage_voxels)
                         {
                             for(int s = 0; s < 2; ++s)
                             {
                                 rt(paris_hip_free_host(ctx, h_stage[s]), "free");
                                 h_stage[s] = nullptr;
                                 void* p = nullptr;
-                                rt(paris_hip_malloc_host(ctx, want_floats * sizeof(float), &p), "make_volume_host()");
-                                h_stage[s] = static_cast<float*>(p);
+                                rt(paris_hip_malloc_host(ctx, want_voxels * voxel_bytes, &p), "make_volume_host()");
+                                h_stage[s] = static_cast<char*>(p);
                                 if(stage_fence[s] == nullptr)
                                     rt(paris_hip_fence_create(ctx, &stage_fence[s]), "fence");
                             }
-                            stage_floats = want_floats;
+                            stage_voxels = want_voxels;
                         }
-                        const auto chunk_z = static_cast<std::uint32_t>(stage_floats / slice_floats);
+                        const auto chunk_z = static_cast<std::uint32_t>(stage_voxels / slice_floats);
                         const auto n_chunks = (j.dim_z + chunk_z - 1u) / chunk_z;
                         const auto copy_down = [&](std::uint32_t c) {
                             const auto z0 = c * chunk_z;
                             const auto nz = std::min(chunk_z, j.dim_z - z0);
-                            rt(paris_hip_memcpy_volume_d2h(ctx, h_stage[c % 2u], j.d_v + static_cast<std::size_t>(z0) * slice_floats, j.dim_x, j.dim_y, nz),
-                               "copy_d2h()");
+                            const float* d_chunk = j.d_v + static_cast<std::size_t>(z0) * slice_floats;
+                            if(voxels_.type == 0)
+                                rt(paris_hip_memcpy_volume_d2h(ctx, reinterpret_cast<float*>(h_stage[c % 2u]), d_chunk, j.dim_x, j.dim_y, nz), "copy_d2h()");
+                            else
+                                rt(paris_hip_volume_quantize_d2h(ctx, d_chunk, static_cast<std::uint64_t>(slice_floats) * nz, &window, h_stage[c % 2u]),
+                                   "quantize_d2h()");
                             rt(paris_hip_fence_record(ctx, stage_fence[c % 2u]), "fence record");
                         };
                         copy_down(0);
@@ -470,11 +516,21 @@ namespace paris
                             drain_s += since(t0);
                             t0 = clock::now();
                             const auto z0 = c * chunk_z;
-                            out_.save(h_stage[c % 2u], j.dim_x, j.dim_y, std::min(chunk_z, j.dim_z - z0), j.first + z0); // :107
+                            if(voxels_.type == 0)
+                                out_.save(reinterpret_cast<const float*>(h_stage[c % 2u]), j.dim_x, j.dim_y, std::min(chunk_z, j.dim_z - z0), j.first + z0); // :107
+                            else
+                                out_.save_quantised(h_stage[c % 2u], j.dim_x, j.dim_y, std::min(chunk_z, j.dim_z - z0), j.first + z0);
                             save_s += since(t0);
                         }
+                        auto counts = paris_hip_volume_counts{};
+                        if(voxels_.type != 0) // (every copy of the slab has been waited for: this reads, and zeroes, at once)
+                            rt(paris_hip_volume_quantize_counts(ctx, &counts, 1), "quantize counts");
                         {
                             std::lock_guard<std::mutex> lock{m_};
+                            counts_.voxels += counts.voxels;
+                            counts_.below += counts.below;
+                            counts_.above += counts.above;
+                            counts_.not_finite += counts.not_finite;
                             --busy_[j.buffer & 1];
                             drain_s_ += drain_s;
                             save_s_ += save_s;
@@ -500,6 +556,8 @@ namespace paris
             int device_;
             sink& out_;
             std::size_t chunk_bytes_;
+            voxel_output voxels_;
+            paris_hip_volume_counts counts_{};
             std::mutex m_;
             std::condition_variable cv_;
             std::deque<job> jobs_;
@@ -726,7 +784,7 @@ namespace paris
 
             for(auto& f : slab_done)
                 rt(paris_hip_fence_create(ctx, &f), "fence");
-            drain.reset(new volume_drain{device, out, po.drain_chunk_bytes});
+            drain.reset(new volume_drain{device, out, po.drain_chunk_bytes, po.voxels});
             rep.setup_s = since(t_setup);
             task t{};
             bool two = false, decided = false;
@@ -948,6 +1006,7 @@ namespace paris
                 rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
             rep.drain_s = drain->drain_seconds();
             rep.save_s = drain->save_seconds();
+            rep.voxels = drain->voxel_counts();
         }
         catch(...)
         {
@@ -978,6 +1037,9 @@ namespace paris
         paris_hip_ring_stats rings{};                   // how long the pre-pass took (reading the scan included)
         std::uint32_t ring_frames = 0;
         double ring_prepass_s = 0;
+        int voxel_type = 0;                             // --voxel-type: the voxels were quantised over [voxel_lo, voxel_hi] (with
+        float voxel_lo = 0.f, voxel_hi = 0.f;           // --voxel-range auto: the window chosen); the counts of every drain ctx, added
+        paris_hip_volume_counts voxels{};
         double wall_s = 0;
         std::string output_file;
     };
@@ -1144,6 +1206,84 @@ namespace paris
             if(rc != PARIS_HIP_SUCCESS)
                 throw stage_construction_error{"--zingers ABS[:REL]: the thresholds must be finite, not negative and not both zero (got "
                                                + std::to_string(po.zinger_abs) + ":" + std::to_string(po.zinger_rel) + ")"};
+        }
+
+        // --voxel-type u8|u16 as typed
+        inline auto parse_voxel_type(const std::string& v, program_options& po) -> void
+        {
+            if(v == "u8") po.voxels.type = PARIS_HIP_VOXEL_U8;
+            else if(v == "u16") po.voxels.type = PARIS_HIP_VOXEL_U16;
+            else throw stage_construction_error{"--voxel-type u8|u16: unknown type " + v};
+        }
+
+        // --voxel-range LO:HI or auto[:P_LO:P_HI] as typed; refuses anything else
+        inline auto parse_voxel_range(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&]() -> stage_construction_error {
+                return stage_construction_error{"--voxel-range LO:HI | auto[:P_LO:P_HI]: cannot read '" + v + "'"};
+            };
+            auto parts = std::vector<std::string>{};
+            for(std::size_t at = 0;;)
+            {
+                const auto colon = v.find(':', at);
+                parts.push_back(v.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
+                if(colon == std::string::npos)
+                    break;
+                at = colon + 1u;
+            }
+            const auto number = [&](const std::string& t) -> double {
+                if(t.empty())
+                    throw bad();
+                char* end = nullptr;
+                const double x = std::strtod(t.c_str(), &end);
+                if(end == t.c_str() || *end != '\0')
+                    throw bad();
+                return x;
+            };
+            if(parts.front() == "auto")
+            {
+                if(parts.size() != 1u && parts.size() != 3u)
+                    throw bad();
+                po.voxels.automatic = true;
+                if(parts.size() == 3u)
+                {
+                    po.voxels.p_lo = number(parts[1]);
+                    po.voxels.p_hi = number(parts[2]);
+                }
+            }
+            else
+            {
+                if(parts.size() != 2u)
+                    throw bad();
+                po.voxels.automatic = false;
+                po.voxels.lo = static_cast<float>(number(parts[0]));
+                po.voxels.hi = static_cast<float>(number(parts[1]));
+            }
+            po.voxels.range_given = true;
+        }
+
+        // --voxel-type / --voxel-range: both or neither, a window the library accepts, and auto only where one drain thread sees the
+        // whole volume -- here, before any device work and before the output directory is made
+        inline auto check_voxels(const program_options& po) -> void
+        {
+            if(po.voxels.type == 0 && !po.voxels.range_given)
+                return;
+            if(po.voxels.type == 0)
+                throw stage_construction_error{"--voxel-range needs --voxel-type u8|u16"};
+            if(!po.voxels.range_given)
+                throw stage_construction_error{"--voxel-type needs --voxel-range LO:HI | auto[:P_LO:P_HI]"};
+            if(po.voxels.automatic)
+            {
+                if(!(po.voxels.p_lo >= 0.0) || !(po.voxels.p_lo < po.voxels.p_hi) || !(po.voxels.p_hi <= 100.0))
+                    throw stage_construction_error{"--voxel-range auto:P_LO:P_HI: the percentiles must satisfy 0 <= P_LO < P_HI <= 100"};
+                if(po.slabs != 1)
+                    throw stage_construction_error{"--voxel-range auto needs the whole volume in one slab on one device: give --slabs 1 (and --devices 1)"};
+                return;
+            }
+            const auto window = paris_hip_volume_window{po.voxels.lo, po.voxels.hi, po.voxels.type};
+            if(paris_hip_volume_window_check(&window) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--voxel-range LO:HI: LO and HI must be finite, with HI > LO by at least 2^-100 (got " + std::to_string(po.voxels.lo)
+                                               + ":" + std::to_string(po.voxels.hi) + ")"};
         }
 
         // --zingers ABS[:REL] as typed; refuses anything that is not one or two numbers
@@ -1346,6 +1486,7 @@ namespace paris
         detail::check_zingers(po);
         detail::check_extend_rows(po);
         detail::check_rings(po);
+        detail::check_voxels(po);
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1361,6 +1502,9 @@ namespace paris
             throw stage_construction_error{"no HIP device"};
         if(po.devices > 0 && po.devices < n_dev)
             n_dev = po.devices;
+        if(po.voxels.automatic && n_dev != 1)
+            throw stage_construction_error{"--voxel-range auto needs the whole volume in one slab on one device: give --devices 1 (" + std::to_string(n_dev)
+                                           + " devices would be used)"};
         po = detail::fit_batch(po, n_dev);
         r.batch = po.batch;
         if(po.rings) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
@@ -1392,8 +1536,10 @@ namespace paris
         }
 
         task_queue queue{make_tasks(po, r.vol_geo, r.info)}; // :140-141
-        sink out{po.output_path, po.prefix, r.roi_geo};           // :154
+        sink out{po.output_path, po.prefix, r.roi_geo, po.voxels.type == 0 ? 0u : (po.voxels.type == PARIS_HIP_VOXEL_U8 ? 1u : 2u)}; // :154
         r.output_file = out.file_path();
+        if(po.voxels.type != 0 && !po.voxels.automatic)
+            out.set_window(po.voxels.lo, po.voxels.hi); // (with auto the drain thread does, once it has chosen the window)
 
         if(n_dev > 1) // :157-167
         {
@@ -1447,7 +1593,14 @@ namespace paris
             r.zingers.frames += d.zingers.frames;
             r.zingers.replaced += d.zingers.replaced;
             r.zingers.saturated_frames += d.zingers.saturated_frames;
+            r.voxels.voxels += d.voxels.voxels;
+            r.voxels.below += d.voxels.below;
+            r.voxels.above += d.voxels.above;
+            r.voxels.not_finite += d.voxels.not_finite;
         }
+        r.voxel_type = po.voxels.type;
+        if(po.voxels.type != 0)
+            out.window(r.voxel_lo, r.voxel_hi);
         r.wall_s = detail::since(start);
         return r;
     }
