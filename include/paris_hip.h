@@ -701,6 +701,65 @@ int paris_hip_clear_ring_correction(paris_hip_ctx* ctx);
  * setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
 int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* Extension (no reference counterpart): detector binning on the device, between paris_hip_upload_projection_raw and
+ * paris_hip_flat_field_rows, where the pixels are detector counts as fp32. One definition; the device
+ * (paris_hip_bin_frames) and the host (paris_hip_bin_frame_host) both implement it.
+ * Setting paris_hip_binning { uint32_t bin_x, bin_y; }. Each factor is 1, 2, 4 or 8, chosen independently.
+ *   A dim_x x dim_y source frame gives a binned frame of out_x = dim_x / bin_x by out_y = dim_y / bin_y pixels (integer division).
+ *   The trailing r_x = dim_x - out_x bin_x columns and r_y = dim_y - out_y bin_y rows are dropped.
+ *   out_x == 0 or out_y == 0 is PARIS_HIP_ERROR_INVALID_ARGUMENT.
+ * Mask (optional): dim_y rows of dim_x bytes at SOURCE size, in the defect map's format: nonzero = bad. Without one every pixel is good.
+ * Binned pixel (X, Y).
+ *   Its source pixels are (x, y), x in [X bin_x, (X + 1) bin_x), y in [Y bin_y, (Y + 1) bin_y), visited row-major: y outer, x inner.
+ *   acc = +0, n = 0. For each GOOD source pixel p in that order: acc = acc + p, one fp32 addition, no contraction; n += 1.
+ *   out = acc / (float)n, one IEEE fp32 division, when n >= 1; out = +0 when n == 0.
+ *   Pixels that are not finite get no special treatment and propagate (the flat-field rule turns them into dead pixels).
+ * What follows from it:
+ *   u8 and u16 counts widened to fp32 sum exactly in any order (64 * 65535 < 2^24); for u32 and f32 frames the order above is the
+ *   definition.
+ *   The binned mask (paris_hip_bin_mask) has byte (X, Y) = 1 iff n == 0 -- a bin with one good pixel is good. It is what
+ *   paris_hip_set_defect_map takes at binned size.
+ *   Dark and flat frames are binned by the same rule with the same mask, on the host; the correction then runs unchanged on the
+ *   binned frame against the binned references.
+ * Binned geometry (paris_hip_binned_geometry), each field computed in double and rounded once to fp32:
+ *   n_row' = out_x, n_col' = out_y, l_px_row' = bin_x l_px_row, l_px_col' = bin_y l_px_col,
+ *   delta_s' = (delta_s + r_x / 2) / bin_x, delta_t' = (delta_t + r_y / 2) / bin_y; d_so, d_od and delta_phi are unchanged.
+ *   In the backprojector's coordinates, t = (i + 1/2) l - n l / 2 - delta_s l and the same form for rows, the centre of a binned
+ *   pixel is then the mean of its source pixels' centres: the dropped remainder does not shift the rotation axis. */
+typedef struct paris_hip_binning {
+    uint32_t bin_x; /* source columns per binned pixel: 1, 2, 4 or 8 */
+    uint32_t bin_y; /* source rows per binned pixel: 1, 2, 4 or 8 */
+} paris_hip_binning;
+/* Host only, no ctx and no device: checks a setting for a dim_x x dim_y detector and returns the binned size (either pointer may be
+ * NULL). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a factor outside {1, 2, 4, 8}, or a binned size of 0. */
+int paris_hip_binning_check(const paris_hip_binning* setting, uint32_t dim_x, uint32_t dim_y, uint32_t* out_x, uint32_t* out_y);
+/* Host only: the geometry rule above for det_geo's n_row x n_col detector. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL
+ * geometry. out_geo may be det_geo. */
+int paris_hip_binned_geometry(const paris_hip_binning* setting, const paris_detector_geometry* det_geo, paris_detector_geometry* out_geo);
+/* Host only: the pixel rule on a dense frame -- src dim_y rows of dim_x floats, dst out_y rows of out_x floats, mask as above or
+ * NULL. For the references. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL src or dst. */
+int paris_hip_bin_frame_host(const paris_hip_binning* setting, const uint8_t* mask, const float* src, uint32_t dim_x, uint32_t dim_y,
+                             float* dst);
+/* Host only: the binned mask, out_y rows of out_x bytes of 0 / 1. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL pointer. */
+int paris_hip_bin_mask(const paris_hip_binning* setting, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y, uint8_t* out_mask);
+/* paris_hip_set_binning runs the check and stores the setting for dim_x x dim_y source frames; the mask (may be NULL) is copied into
+ * memory the ctx owns, replacing an earlier setting; the old mask is freed once the work queued before the call no longer reads it.
+ * The mask counts towards paris_hip_projection_reserve_bytes while set; paris_hip_ctx_destroy frees it. Without a setting nothing
+ * else changes. */
+int paris_hip_set_binning(paris_hip_ctx* ctx, const paris_hip_binning* setting, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_binning(paris_hip_ctx* ctx);
+/* Writes BINNED rows [row_first, row_first + row_count) of n_frames binned frames (out_x x out_y, rows dst_pitch bytes apart, frames
+ * dst_frame_stride bytes apart, d_dst the first frame's row 0) from source rows [bin_y row_first, bin_y (row_first + row_count)) of
+ * n_frames source frames (dim_x x dim_y, src_pitch, src_frame_stride, d_src the first frame's row 0). The source is only read; bytes
+ * of a destination row past 4 out_x are not written. 16-byte vectors are used where both bases, both pitches and (n_frames > 1)
+ * both strides are multiples of 16, single pixels otherwise. A held-back weighting runs first; a source or destination frame of the
+ * pending by-reference group has that group launched first, and both are noted as used, so a later upload into either waits.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when dim_x / dim_y differ from the setting's, for a band outside out_y, for a
+ * pitch or stride paris_hip_flat_field_rows would refuse (the source's for dim_x x dim_y, the destination's for out_x x out_y), or
+ * when the source and destination ranges overlap. */
+int paris_hip_bin_frames(paris_hip_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
+                         size_t dst_frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y, uint32_t row_first,
+                         uint32_t row_count);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

@@ -91,6 +91,11 @@ class RingStats(C.Structure):
 RING_FRAMES_MAX = 64  # PARIS_HIP_RING_FRAMES_MAX
 
 
+class Binning(C.Structure):
+    """paris_hip_binning: detector binning factors, each 1, 2, 4 or 8 (extension)"""
+    _fields_ = [("bin_x", C.c_uint32), ("bin_y", C.c_uint32)]
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -175,6 +180,13 @@ SIGNATURES = {
     "paris_hip_set_ring_correction": (C.c_int, [_vp, _vp, _u32, _u32]),
     "paris_hip_clear_ring_correction": (C.c_int, [_vp]),
     "paris_hip_ring_correct_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_binning_check": (C.c_int, [_P(Binning), _u32, _u32, _P(_u32), _P(_u32)]),
+    "paris_hip_binned_geometry": (C.c_int, [_P(Binning), _P(DetectorGeometry), _P(DetectorGeometry)]),
+    "paris_hip_bin_frame_host": (C.c_int, [_P(Binning), _vp, _vp, _u32, _u32, _vp]),
+    "paris_hip_bin_mask": (C.c_int, [_P(Binning), _vp, _u32, _u32, _vp]),
+    "paris_hip_set_binning": (C.c_int, [_vp, _P(Binning), _vp, _u32, _u32]),
+    "paris_hip_clear_binning": (C.c_int, [_vp]),
+    "paris_hip_bin_frames": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -22,7 +22,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
            "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
            "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean", "VolumeWindow", "VolumeCounts",
-           "VolumeStatistics", "volume_window_check", "volume_window_from_histogram"]
+           "VolumeStatistics", "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
+           "binned_geometry", "bin_frame_host", "bin_mask"]
 
 
 class Projection:
@@ -161,6 +162,50 @@ def ring_correction_from_mean(half_width, floor_abs, limit_abs, mean, count_per_
                                                           m.shape[1], m.shape[0], c.ctypes.data, C.byref(st)),
           "paris_hip_ring_correction_from_mean")
     return c, st
+
+
+def binning_check(bin_x, bin_y, dim_x, dim_y):
+    """Host only, no device (paris_hip_binning_check): checks detector binning by bin_x x bin_y, each 1, 2, 4 or 8, for a dim_x x dim_y
+    detector and returns the binned size (out_x, out_y). Raises ParisHipError for a setting the library refuses."""
+    bn = Binning(bin_x, bin_y)
+    ox, oy = C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().paris_hip_binning_check(C.byref(bn), dim_x, dim_y, C.byref(ox), C.byref(oy)), "paris_hip_binning_check")
+    return ox.value, oy.value
+
+
+def binned_geometry(bin_x, bin_y, det_geo):
+    """Host only, no device (paris_hip_binned_geometry): the DetectorGeometry of det_geo's detector binned by bin_x x bin_y -- the
+    pixel pitches scaled, the offsets chosen so that the dropped remainder does not shift the rotation axis."""
+    bn, out = Binning(bin_x, bin_y), DetectorGeometry()
+    check(_lib.load().paris_hip_binned_geometry(C.byref(bn), C.byref(det_geo), C.byref(out)), "paris_hip_binned_geometry")
+    return out
+
+
+def bin_frame_host(bin_x, bin_y, frame, mask=None):
+    """Host only, no device (paris_hip_bin_frame_host): the binning rule on a 2-D array of the detector's size (n_col, n_row), taken as
+    float32 -- every binned pixel the mean of its good source pixels, summed row-major in fp32, +0 without one. mask: the same
+    shape, nonzero = bad; None = every pixel good. For dark and flat frames."""
+    a = np.ascontiguousarray(frame, np.float32)
+    if a.ndim != 2:
+        raise ValueError("bin_frame_host: the frame must be a 2-D array (n_col, n_row)")
+    m = None if mask is None else _mask_bytes(mask, "bin_frame_host")
+    if m is not None and m.shape != a.shape:
+        raise ValueError("bin_frame_host: frame and mask differ in shape")
+    ox, oy = binning_check(bin_x, bin_y, a.shape[1], a.shape[0])
+    bn, out = Binning(bin_x, bin_y), np.empty((oy, ox), np.float32)
+    check(_lib.load().paris_hip_bin_frame_host(C.byref(bn), None if m is None else m.ctypes.data, a.ctypes.data, a.shape[1], a.shape[0],
+                                               out.ctypes.data), "paris_hip_bin_frame_host")
+    return out
+
+
+def bin_mask(bin_x, bin_y, mask):
+    """Host only, no device (paris_hip_bin_mask): the binned mask, uint8 0 / 1 -- 1 where no source pixel of the bin is good. Hand it
+    to set_defect_map() at binned size."""
+    m = _mask_bytes(mask, "bin_mask")
+    ox, oy = binning_check(bin_x, bin_y, m.shape[1], m.shape[0])
+    bn, out = Binning(bin_x, bin_y), np.empty((oy, ox), np.uint8)
+    check(_lib.load().paris_hip_bin_mask(C.byref(bn), m.ctypes.data, m.shape[1], m.shape[0], out.ctypes.data), "paris_hip_bin_mask")
+    return out
 
 
 def row_extension_check(edge_pixels, taper_pixels, dim_x):
@@ -592,6 +637,37 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_ring_correct_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_ring_correct_rows")
+
+    # ---- detector binning --------------------------------------------------------
+    binning_check = staticmethod(binning_check)
+    binned_geometry = staticmethod(binned_geometry)
+    bin_frame_host = staticmethod(bin_frame_host)
+    bin_mask = staticmethod(bin_mask)
+
+    def set_binning(self, bin_x, bin_y, dim_x, dim_y, mask=None):
+        """paris_hip_set_binning for dim_x x dim_y source frames: bin_frames() then makes every binned pixel the mean of the good ones
+        among its bin_x x bin_y source pixels. mask: a 2-D array of the source detector's size (n_col, n_row), nonzero = bad; None =
+        every pixel good. Replaces an earlier setting safely: work already queued keeps the old mask. Returns (out_x, out_y)."""
+        m = None if mask is None else _mask_bytes(mask, "set_binning")
+        if m is not None and m.shape != (dim_y, dim_x):
+            raise ValueError("set_binning: the mask must have the source detector's size (n_col, n_row)")
+        bn = Binning(bin_x, bin_y)
+        check(self._L.paris_hip_set_binning(self._ctx, C.byref(bn), None if m is None else m.ctypes.data, dim_x, dim_y),
+              "paris_hip_set_binning")
+        return binning_check(bin_x, bin_y, dim_x, dim_y)
+
+    def clear_binning(self):
+        """paris_hip_clear_binning: no binning setting from here on"""
+        check(self._L.paris_hip_clear_binning(self._ctx), "paris_hip_clear_binning")
+
+    def bin_frames(self, src, dst, row_first=0, row_count=None, src_frame_stride=0, dst_frame_stride=0, n_frames=1):
+        """The rule of set_binning() from float source frames into binned frames (paris_hip_bin_frames): binned rows [row_first,
+        row_first + row_count) of n_frames frames dst_frame_stride bytes apart starting at dst, from source rows [bin_y * row_first,
+        bin_y * (row_first + row_count)) of the frames src_frame_stride bytes apart starting at src. The source is only read. Call it
+        on detector counts, after upload_raw() and before flat_field_rows()."""
+        count = dst.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_bin_frames(self._ctx, src.ptr, src.pitch, src_frame_stride, dst.ptr, dst.pitch, dst_frame_stride, n_frames,
+                                           src.dim_x, src.dim_y, row_first, count), "paris_hip_bin_frames")
 
     # ---- row extension (DESIGN.md section 4.11) -----------------------------------------------------------
     row_extension_check = staticmethod(row_extension_check)

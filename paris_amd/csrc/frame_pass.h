@@ -1,5 +1,6 @@
 // The one launch scaffold of the passes that rewrite projection frames in place on the compute stream (DESIGN.md section 1,
-// "Ordering"): the redundancy weights, the flat-field rows pass, the defect repair and the forward projector. Inline host code.
+// "Ordering"): the redundancy weights, the flat-field rows pass, the defect repair and the forward projector -- and, in its two-band
+// form, of the binning pass, which reads one set of frames and writes another. Inline host code.
 #ifndef PARIS_HIP_FRAME_PASS_H_
 #define PARIS_HIP_FRAME_PASS_H_
 
@@ -83,6 +84,45 @@ template <typename Refuse, typename Launch>
 inline int paris_hip_frame_pass(paris_hip_ctx* ctx, const paris_hip_frame_band& b, Refuse refuse, Launch launch)
 {
     return paris_hip_frame_pass(ctx, b, refuse, [] { return false; }, launch, [&b] { return b.rows(); });
+}
+
+// the bytes from row 0 of the first frame to the end of the last frame's last row (band_valid has passed)
+inline size_t paris_hip_frame_band_extent(const paris_hip_frame_band& b)
+{
+    if(b.n_frames == 0u || b.dim_y == 0u)
+        return 0u;
+    return (b.n_frames - 1u) * b.frame_stride + (b.dim_y - 1u) * b.pitch + static_cast<size_t>(b.dim_x) * sizeof(float);
+}
+
+// A pass that reads the band `src` of one set of frames and writes the band `dst` of another (the two may differ in size): the same
+// order of steps, both bands checked, both sets of frames guarded and noted as used. Ranges that overlap are refused.
+template <typename Refuse, typename Launch>
+inline int paris_hip_frame_pass(paris_hip_ctx* ctx, const paris_hip_frame_band& src, const paris_hip_frame_band& dst, Refuse refuse, Launch launch)
+{
+    if(int rc = paris_hip_bind(ctx))
+        return rc;
+    if(int rc = paris_hip_flush_pending_weight(ctx))
+        return rc;
+    if(!paris_hip_frame_band_valid(src) || !paris_hip_frame_band_valid(dst) || src.n_frames != dst.n_frames)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(int rc = refuse())
+        return rc;
+    const char* s = reinterpret_cast<const char*>(src.d_p);
+    const char* d = reinterpret_cast<const char*>(dst.d_p);
+    if(s < d + paris_hip_frame_band_extent(dst) && d < s + paris_hip_frame_band_extent(src))
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    if(dst.dim_x == 0 || dst.row_count == 0 || dst.n_frames == 0)
+        return paris_hip_finish(ctx);
+    if(int rc = paris_hip_frame_band_guard(ctx, src))
+        return rc;
+    if(int rc = paris_hip_frame_band_guard(ctx, dst))
+        return rc;
+    launch();
+    for(const paris_hip_frame_band* b : {&src, &dst})
+        for(uint32_t f = 0; f < b->n_frames; ++f)
+            if(int rc = paris_hip_note_projection_use(ctx, b->frame(f) + static_cast<size_t>(b->row_first) * b->pitch, b->pitch * b->row_count))
+                return rc;
+    return paris_hip_finish(ctx);
 }
 
 #pragma GCC visibility pop

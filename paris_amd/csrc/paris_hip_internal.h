@@ -163,6 +163,16 @@ struct paris_hip_ctx
         float* d_c = nullptr;
         uint32_t dim_x = 0, dim_y = 0;
     } ring;
+    // Detector binning (paris_hip_set_binning): the setting for one source detector, the binned size, and the
+    // device copy of the optional source-size mask (nullptr: every pixel good) -- read by the kernels of bin_frames.hip on the compute
+    // stream only, so it is replaced, retired and freed as the defect plan is.
+    struct binning_t
+    {
+        bool set = false;
+        paris_hip_binning rule{};
+        uint8_t* d_mask = nullptr;
+        uint32_t dim_x = 0, dim_y = 0, out_x = 0, out_y = 0;
+    } binning;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -440,6 +450,7 @@ void paris_hip_warm_defect_map();
 void paris_hip_warm_zinger();
 void paris_hip_warm_ring();
 void paris_hip_warm_volume_window();
+void paris_hip_warm_binning();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -469,6 +480,8 @@ void paris_hip_ring_profile_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying);
 // volume_window.hip: the same for the volume export's counters and its staging buffer
 void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying);
+// bin_frames.hip: the same for the binning's mask
+void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events

@@ -7,7 +7,7 @@
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
 //                       [--rings half_width floor limit]
-//                       [--extend-rows W M]
+//                       [--extend-rows W M] [--bin BX BY mask.raw|none]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -26,6 +26,10 @@
 // set_ring_correction() gets the rule's correction frame, so that paris::weight() subtracts it after the zinger filter.
 // --extend-rows: the taper length W and the number of edge pixels M of the row extension for truncated projections.
 // set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
+// --bin: the geometry on the command line is the SOURCE detector's and in.raw holds frames of that size; each loaded frame is binned
+// into a buffer of the binned detector (set_binning() before the loops, bin_frame() after paris::load()) and everything downstream runs
+// with binned_geometry(). mask.raw: n_col x n_row bytes at source size, nonzero = left out of its bin. --flat, --defects and the other
+// settings take frames of the BINNED size. Refused together with --rings and --reproject.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
 // frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
 // host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
@@ -92,6 +96,9 @@ int main(int argc, char** argv)
         float ring_floor = 0.f, ring_limit = 0.f;
         bool extend_rows = false;
         std::uint32_t extend_taper = 0, extend_edge = 0;
+        std::uint32_t bin_x = 1, bin_y = 1;
+        std::string bin_mask_path;
+        bool vol_given = false;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
         auto vol_geo = paris::calculate_volume_geometry(det);
@@ -148,6 +155,13 @@ int main(int argc, char** argv)
                 extend_edge = static_cast<std::uint32_t>(std::strtoul(argv[a + 2], nullptr, 10));
                 a += 2;
             }
+            else if(!std::strcmp(argv[a], "--bin") && a + 3 < argc)
+            {
+                bin_x = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
+                bin_y = static_cast<std::uint32_t>(std::strtoul(argv[a + 2], nullptr, 10));
+                bin_mask_path = argv[a + 3];
+                a += 3;
+            }
             else if(!std::strcmp(argv[a], "--roi") && a + 6 < argc)
             {
                 enable_roi = true;
@@ -160,6 +174,7 @@ int main(int argc, char** argv)
             {
                 vol_geo.dim_x = std::atoi(argv[a + 1]); vol_geo.dim_y = std::atoi(argv[a + 2]); vol_geo.dim_z = std::atoi(argv[a + 3]);
                 vol_geo.l_vx_x = vol_geo.l_vx_y = vol_geo.l_vx_z = std::strtof(argv[a + 4], nullptr);
+                vol_given = true;
                 a += 4;
             }
             else
@@ -172,6 +187,19 @@ int main(int argc, char** argv)
         {
             std::fprintf(stderr, "--reproject cannot be combined with --roi: the forward projector has no ROI form\n");
             return 2;
+        }
+        const bool binning = !bin_mask_path.empty();
+        if(binning && (rings || !reproject_path.empty()))
+        {
+            std::fprintf(stderr, "--bin cannot be combined with --rings or --reproject\n");
+            return 2;
+        }
+        const auto src_det = det; // the detector the frames of in.raw come from
+        if(binning)
+        {
+            det = paris::backend::binned_geometry(bin_x, bin_y, src_det);
+            if(!vol_given)
+                vol_geo = paris::calculate_volume_geometry(det);
         }
         auto roi_geo = vol_geo;
         if(enable_roi)
@@ -216,6 +244,22 @@ int main(int argc, char** argv)
                 throw paris::stage_construction_error{"cannot read " + defects_path};
             paris::backend::set_defect_map(mask.data(), det.n_row, det.n_col);
         }
+        if(binning)
+        {
+            const auto n = std::size_t{src_det.n_row} * src_det.n_col;
+            auto mask = std::vector<std::uint8_t>{};
+            if(bin_mask_path != "none")
+            {
+                mask.resize(n);
+                std::FILE* f = std::fopen(bin_mask_path.c_str(), "rb");
+                const bool ok = f != nullptr && std::fread(mask.data(), 1u, n, f) == n;
+                if(f != nullptr)
+                    std::fclose(f);
+                if(!ok)
+                    throw paris::stage_construction_error{"cannot read " + bin_mask_path};
+            }
+            paris::backend::set_binning(bin_x, bin_y, mask.empty() ? nullptr : mask.data(), src_det.n_row, src_det.n_col);
+        }
         if(zingers)
             paris::backend::set_zinger_filter(zinger_abs, zinger_rel, zinger_polarity, det.n_row, det.n_col);
         if(extend_rows)
@@ -230,7 +274,7 @@ int main(int argc, char** argv)
                     roi_geo.dim_z % static_cast<std::uint32_t>(info.num)};
 
         // all frames in host memory (the reference re-reads them per task: src/main.cpp:93)
-        const auto frame = std::size_t{det.n_row} * det.n_col;
+        const auto frame = std::size_t{src_det.n_row} * src_det.n_col;
         const auto n_held = (in_path == "lcg" && cycle != 0 && cycle < n_proj) ? cycle : n_proj;
         auto frames = std::vector<float>(frame * n_held);
         if(in_path == "lcg")
@@ -280,12 +324,21 @@ int main(int argc, char** argv)
             {
                 // every call of one iteration of src/main.cpp:98-105 between two clock reads (~20 ns each)
                 const auto c0 = clock::now();
-                auto p = paris::backend::make_projection_host(det.n_row, det.n_col);
+                auto p = paris::backend::make_projection_host(src_det.n_row, src_det.n_col);
                 const auto c1 = clock::now();
                 std::memcpy(p.buf.get(), frames.data() + frame * (i % n_held), frame * sizeof(float));
                 const auto c2 = clock::now();
                 p.idx = i;
                 auto d_p = paris::load(p);
+                if(binning) // the loaded source frame into a buffer of the binned detector, which takes its place
+                {
+                    auto d_b = paris::backend::make_projection_device(det.n_row, det.n_col);
+                    d_b.idx = d_p.idx;
+                    d_b.phi = d_p.phi;
+                    d_b.meta = d_p.meta;
+                    paris::backend::bin_frame(d_p.buf.get(), d_p.buf.pitch(), d_b.buf.get(), d_b.buf.pitch(), src_det.n_row, src_det.n_col, det.n_col);
+                    d_p = std::move(d_b);
+                }
                 const auto c3 = clock::now();
                 if(do_weight) paris::weight(d_p, det);
                 const auto c4 = clock::now();

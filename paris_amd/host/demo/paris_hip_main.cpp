@@ -7,7 +7,7 @@
 //             [--slabs n] [--devices n] [--f16] [--no-row-band] [--batch n] [--drain-chunk-kib n] [--share-frames 0|1] [--one-volume] [--pipeline-slabs n] [--no-read-ahead]
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
 //             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
-//             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]]
+//             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -83,7 +83,7 @@ int main(int argc, char** argv)
                             "          [--drain-chunk-kib n] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]\n"
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
                             "          [--rings H[:FLOOR[:LIMIT]]]\n"
-                            "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]]\n"
+                            "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -108,7 +108,11 @@ int main(int argc, char** argv)
                             "--voxel-type / --voxel-range: the voxels are written as 8- or 16-bit integers over the grey window [LO, HI], quantised\n"
                             "on the device, into <output>/<name>.raw with the MetaImage header <name>.mhd beside it, instead of the float DDBVF.\n"
                             "auto: the window between the percentiles P_LO and P_HI (0.1 and 99.9) of the finished volume's 4096-bin histogram;\n"
-                            "needs --slabs 1 on one device.\n");
+                            "needs --slabs 1 on one device.\n"
+                            "--bin: the detector is read as bins of BX x BY pixels (each 1, 2, 4 or 8; BY defaults to BX): every frame is uploaded as\n"
+                            "stored and binned on the device before the correction, each binned pixel the mean of its pixels that --defects (and\n"
+                            "--defects-from-flat) do not mark; the dark, the flat and the defect map are binned alike, and the geometry -- and with\n"
+                            "it the volume -- is the binned detector's.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -138,6 +142,7 @@ int main(int argc, char** argv)
             else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
             else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
             else if(k == "--rings") paris::detail::parse_rings(val(), po);
+            else if(k == "--bin") paris::detail::parse_bin(val(), po);
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -161,13 +166,20 @@ int main(int argc, char** argv)
         po.det_geo = parse_geometry(geometry);
         if(po.input_path.empty() || po.output_path.empty()) // src/program_options.cpp:117-122: both or neither
         {
-            const auto v = paris::calculate_volume_geometry(po.det_geo);
+            const auto setting = paris_hip_binning{po.bin_x, po.bin_y};
+            auto geo = po.det_geo;
+            if(paris_hip_binned_geometry(&setting, &po.det_geo, &geo) != PARIS_HIP_SUCCESS)
+                throw paris::stage_construction_error{"--bin: the detector does not hold one bin"};
+            const auto v = paris::calculate_volume_geometry(geo);
             std::printf("Volume dimensions [vx]: %u x %u x %u, voxel size %.6g mm (no --input/--output: nothing to do)\n", v.dim_x, v.dim_y,
                         v.dim_z, v.l_vx_x);
             return 0;
         }
         po.enable_io = true;
         const auto r = paris::run(po);
+        if(r.binning)
+            std::printf("binning on: %u x %u bins, detector %u x %u -> %u x %u, %llu binned pixel(s) without a good source pixel marked defective\n",
+                        r.bin_x, r.bin_y, r.src_row, r.src_col, r.binned_row, r.binned_col, static_cast<unsigned long long>(r.binned_defective));
         if(r.flat_frames != 0)
             std::printf("dark / flat correction on: %u flat frame(s), %u dark frame(s)%s, min transmission %g\n", r.flat_frames, r.dark_frames,
                         r.dark_frames == 0 ? " (zero dark)" : "", static_cast<double>(po.t_min));

@@ -395,6 +395,39 @@ namespace paris
             }
         }
 
+        // Extension (no reference counterpart): detector binning. The frames of this thread's current device
+        // arrive as n_row x n_col detector counts and are to be reconstructed as bin_x x bin_y bins (each 1, 2, 4 or 8): until
+        // clear_binning(), bin_frame() makes every binned pixel the mean of the good ones among its source pixels, between the raw
+        // upload and the dark / flat correction. mask: n_col rows of n_row bytes, nonzero = bad, or nullptr; the library keeps its own
+        // copy. The geometry, the references and the defect map of everything downstream are the binned ones (binned_geometry(),
+        // paris_hip_bin_frame_host, paris_hip_bin_mask).
+        inline auto set_binning(std::uint32_t bin_x, std::uint32_t bin_y, const std::uint8_t* mask, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            const auto setting = paris_hip_binning{bin_x, bin_y};
+            detail::runtime_check(paris_hip_set_binning(current_ctx(), &setting, mask, n_row, n_col), "set_binning()");
+        }
+
+        inline auto clear_binning() -> void
+        {
+            detail::runtime_check(paris_hip_clear_binning(current_ctx()), "clear_binning()");
+        }
+
+        inline auto binned_geometry(std::uint32_t bin_x, std::uint32_t bin_y, const detector_geometry& det_geo) -> detector_geometry
+        {
+            const auto setting = paris_hip_binning{bin_x, bin_y};
+            auto out = detector_geometry{};
+            detail::construction_check(paris_hip_binned_geometry(&setting, &det_geo, &out), "binned_geometry()");
+            return out;
+        }
+
+        // one whole n_row x n_col source frame at d_src into the binned frame at d_dst, all its binned_n_col rows
+        inline auto bin_frame(const float* d_src, std::size_t src_pitch, float* d_dst, std::size_t dst_pitch, std::uint32_t n_row, std::uint32_t n_col,
+                              std::uint32_t binned_n_col) -> void
+        {
+            detail::runtime_check(paris_hip_bin_frames(current_ctx(), d_src, src_pitch, 0u, d_dst, dst_pitch, 0u, 1u, n_row, n_col, 0u, binned_n_col),
+                                  "bin_frame()");
+        }
+
         // ---- buffers ------------------------------------------------------------------------------------------
         struct device_free { void operator()(float* p) const noexcept { paris_hip_free(current_ctx(), p); } };
         struct host_free { void operator()(float* p) const noexcept { paris_hip_free_host(current_ctx(), p); } };

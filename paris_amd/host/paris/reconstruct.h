@@ -127,6 +127,14 @@ namespace paris
         float ring_floor = 0.f, ring_limit = 0.f;
         std::size_t ring_bytes = 0;                             // filled by run(): what the correction frame occupies on a device
         std::shared_ptr<const std::vector<float>> ring_c;       // filled by run(): the correction frame
+        // detector binning (extension): --bin BX[:BY], each 1, 2, 4 or 8; 1 x 1 is no binning. run() checks the
+        // setting before any device work and replaces det_geo by the binned geometry (detail::apply_binning), so that everything
+        // derived from it follows; the dark and flat means and the defect mask are binned on the host, the frames on the device, each
+        // between its raw upload into a full-width slot and the correction
+        std::uint32_t bin_x = 1, bin_y = 1;
+        std::uint32_t src_row = 0, src_col = 0;                         // filled by run() with binning: the source detector (0: no binning)
+        std::shared_ptr<const std::vector<std::uint8_t>> bin_mask;      // filled by run(): the bad source pixels left out of their bins (may be empty)
+        bool binning() const { return src_row != 0; }
         // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
         // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
         // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
@@ -289,10 +297,15 @@ namespace paris
         using clock = std::chrono::steady_clock;
         inline double since(clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); }
 
-        // the settings of the frame chain in front of the weights, the same for every device ctx of a run: --flat / --dark, --defects /
-        // --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
+        // the settings of the frame chain in front of the weights, the same for every device ctx of a run: --bin, --flat / --dark,
+        // --defects / --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
         inline void set_frame_chain(paris_hip_ctx* ctx, const program_options& po, device_report& rep)
         {
+            if(po.binning()) // --bin: the source detector's setting; everything below is at binned size
+            {
+                const auto setting = paris_hip_binning{po.bin_x, po.bin_y};
+                rt(paris_hip_set_binning(ctx, &setting, po.bin_mask ? po.bin_mask->data() : nullptr, po.src_row, po.src_col), "set_binning()");
+            }
             if(po.flat)
                 rt(paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row, po.det_geo.n_col,
                                             po.t_min), "set_flat_field()");
@@ -343,8 +356,11 @@ namespace paris
             // with --flat, the ctx's dark and flat frames (paris_hip_set_flat_field)
             const auto references = po.flat_path.empty() ? 0u : 2u * sizeof(float) * po.det_geo.n_row * static_cast<std::size_t>(po.det_geo.n_col);
             // (with --defects, the plan of the file's map; the few pixels --defects-from-flat may add are not known before a ctx exists)
+            // with --bin, every slot's full-width source frame as well, and the source-size mask
+            const auto src_row = (static_cast<std::size_t>(po.src_row) * sizeof(float) + 255u) / 256u * 256u;
+            const auto binning = po.binning() ? slots * po.src_col * src_row + (po.bin_mask ? po.bin_mask->size() : 0u) : 0u;
             return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes
-                   + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
+                   + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
         // Large detectors: halve the frames per group until the driver's buffers take at most a quarter of the smallest
@@ -725,9 +741,16 @@ namespace paris
         rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
         const int slots = static_cast<int>(batch * groups);
         const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
-        const auto frame_bytes = static_cast<std::size_t>(n_row) * n_col * sizeof(float);
+        // --bin: frames are read and uploaded at the source detector's size into full-width slots of their own and binned from there
+        // into the slots everything downstream works on; without it the two sizes are one and there are no full-width slots
+        const bool binning = po.binning();
+        const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
+        const auto frame_bytes = static_cast<std::size_t>(sn_row) * sn_col * sizeof(float);
         auto h_buf = std::vector<float*>(slots, nullptr);
         auto d_buf = std::vector<float*>(slots, nullptr);
+        auto d_src = std::vector<float*>(slots, nullptr);
+        float* d_src_all = nullptr; // --bin: the full-width frames of all slots, one under the other like d_all
+        std::size_t s_pitch = 0;
         auto fence = std::vector<paris_hip_fence*>(groups, nullptr);
         float* d_all = nullptr; // the device frames of all slots, one under the other: slot s starts at row s * n_col
         std::size_t d_pitch = 0, h16_pitch = 0, h16_stride = 0;
@@ -746,6 +769,7 @@ namespace paris
             for(int s = 0; s < slots; ++s)
                 paris_hip_free_host(ctx, h_buf[s]);
             paris_hip_free(ctx, d_all);
+            paris_hip_free(ctx, d_src_all);
             paris_hip_free(ctx, d_half);
             for(int s = 0; s < 2; ++s)
             {
@@ -760,12 +784,20 @@ namespace paris
                 throw stage_construction_error{"too many projection slots for this detector"};
             rt(paris_hip_malloc_projection(ctx, n_row, n_col * static_cast<std::uint32_t>(slots), &d_all, &d_pitch), "make_projection_device()");
             const auto d_stride = d_pitch * n_col; // bytes from one slot's frame to the next
+            if(binning)
+            {
+                if(static_cast<std::uint64_t>(sn_col) * static_cast<std::uint64_t>(slots) > 0xffffffffull)
+                    throw stage_construction_error{"too many projection slots for this detector"};
+                rt(paris_hip_malloc_projection(ctx, sn_row, sn_col * static_cast<std::uint32_t>(slots), &d_src_all, &s_pitch), "make_projection_device()");
+            }
             for(int s = 0; s < slots; ++s)
             {
                 void* p = nullptr;
                 rt(paris_hip_malloc_host(ctx, frame_bytes, &p), "make_projection_host()");
                 h_buf[s] = static_cast<float*>(p);
                 d_buf[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * static_cast<std::size_t>(s));
+                if(binning)
+                    d_src[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * static_cast<std::size_t>(s));
             }
             for(auto& f : fence)
                 rt(paris_hip_fence_create(ctx, &f), "fence");
@@ -843,6 +875,8 @@ namespace paris
                     widened((repair ? reach_rows : 0u) + zinger_rows, up_first, up_count);
                     widened(zinger_rows, fix_first, fix_count);
                 }
+                // --bin: the source rows the uploaded band is binned from (the band itself without it)
+                const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
 
                 t0 = clock::now();
                 // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
@@ -907,8 +941,8 @@ namespace paris
                 // With --flat the same pass corrects them to line integrals with the reference rows of their absolute detector rows
                 // (paris_hip_upload_projection_raw_corrected): the short-scan weight and the weight + filter see line integrals.
                 const auto next_frame = [&](float* dst) {
-                    return shared ? shared->next_raw(cur, dst, n_row, n_col, up_first, up_count)
-                                  : own->next_raw(dst, n_row, n_col, up_first, up_count); // :100, straight into pinned memory
+                    return shared ? shared->next_raw(cur, dst, sn_row, sn_col, src_first, src_count)
+                                  : own->next_raw(dst, sn_row, sn_col, src_first, src_count); // :100, straight into pinned memory
                 };
                 if(po.read_ahead)
                     feed.reset(new frame_feed{ctx, next_frame, h_buf, batch, fence});
@@ -934,22 +968,33 @@ namespace paris
                     }
                     if(!p.valid())
                         break;
-                    if(p.dim_x != n_row || p.dim_y != n_col)
+                    if(p.dim_x != sn_row || p.dim_y != sn_col)
                         throw stage_runtime_error{"projection size does not match the detector geometry"};
                     t0 = clock::now();
                     const auto px = his::pixel_size(p.pixel);
-                    const auto band_off = static_cast<std::size_t>(up_first) * n_row * px; // bytes
+                    const auto band_off = static_cast<std::size_t>(src_first) * sn_row * px; // bytes
                     auto* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_buf[slot]) + static_cast<std::size_t>(up_first) * d_pitch);
                     if(band_count != 0)
                     {
                         // :101 -- on the upload stream, overlapping the kernels of the previous projections
-                        if(po.flat)
+                        if(binning)
+                        {
+                            // the source rows as stored into the slot's full-width frame, binned from there into the slot's binned
+                            // frame, which is then corrected in place: the same bits as the corrected upload of a binned frame
+                            auto* d_src_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src[slot]) + static_cast<std::size_t>(src_first) * s_pitch);
+                            rt(paris_hip_upload_projection_raw(ctx, d_src_band, s_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, sn_row * px,
+                                                               sn_row, src_count, p.pixel), "load()");
+                            rt(paris_hip_bin_frames(ctx, d_src[slot], s_pitch, 0u, d_buf[slot], d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
+                            if(po.flat)
+                                rt(paris_hip_flat_field_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
+                        }
+                        else if(po.flat)
                             rt(paris_hip_upload_projection_raw_corrected(ctx, d_buf[slot], d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off,
                                                                          n_row * px, n_row, n_col, up_first, up_count, p.pixel), "load()");
                         else
                             rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
                                                                n_row, up_count, p.pixel), "load()");
-                        rep.h2d_bytes += static_cast<std::uint64_t>(up_count) * n_row * px;
+                        rep.h2d_bytes += static_cast<std::uint64_t>(src_count) * sn_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
                         if(repair && !filter_by_group) // the band's defective pixels, before every weight
                             rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, fix_first, fix_count), "defect repair");
@@ -1037,6 +1082,10 @@ namespace paris
         paris_hip_ring_stats rings{};                   // how long the pre-pass took (reading the scan included)
         std::uint32_t ring_frames = 0;
         double ring_prepass_s = 0;
+        bool binning = false;                           // --bin: the factors, the source and the binned detector, and how many binned
+        std::uint32_t bin_x = 1, bin_y = 1;             // pixels have no good source pixel (they join the defect map)
+        std::uint32_t src_row = 0, src_col = 0, binned_row = 0, binned_col = 0;
+        std::uint64_t binned_defective = 0;
         int voxel_type = 0;                             // --voxel-type: the voxels were quantised over [voxel_lo, voxel_hi] (with
         float voxel_lo = 0.f, voxel_hi = 0.f;           // --voxel-range auto: the window chosen); the counts of every drain ctx, added
         paris_hip_volume_counts voxels{};
@@ -1188,6 +1237,87 @@ namespace paris
 
     namespace detail
     {
+        // --bin BX[:BY] as typed; BY defaults to BX
+        inline auto parse_bin(const std::string& v, program_options& po) -> void
+        {
+            const auto factor = [&v](const std::string& t) -> std::uint32_t {
+                if(t != "1" && t != "2" && t != "4" && t != "8")
+                    throw stage_construction_error{"--bin BX[:BY]: each factor is 1, 2, 4 or 8 (got '" + v + "')"};
+                return static_cast<std::uint32_t>(t[0] - '0');
+            };
+            const auto colon = v.find(':');
+            po.bin_x = factor(v.substr(0, colon));
+            po.bin_y = colon == std::string::npos ? po.bin_x : factor(v.substr(colon + 1u));
+        }
+
+        // --bin: checked here, before any device work; 1 x 1 changes nothing. Otherwise the dark and flat means and the defect mask are
+        // binned on the host by the rule the device applies to the frames (paris_hip_bin_frame_host, paris_hip_bin_mask), the dead
+        // pixels of the SOURCE references (--defects-from-flat: paris_hip_set_flat_field's rule on D and F) join the source mask first,
+        // so that they are left out of their bins, and po.det_geo becomes the binned geometry. --defects-from-flat stays on: a binned
+        // reference pixel that is dead all the same joins the binned map on each ctx, as without --bin.
+        inline auto apply_binning(program_options& po, run_report& r) -> void
+        {
+            if(po.bin_x == 1u && po.bin_y == 1u)
+                return;
+            const auto setting = paris_hip_binning{po.bin_x, po.bin_y};
+            const auto s_row = po.det_geo.n_row, s_col = po.det_geo.n_col;
+            std::uint32_t b_row = 0, b_col = 0;
+            if(paris_hip_binning_check(&setting, s_row, s_col, &b_row, &b_col) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--bin " + std::to_string(po.bin_x) + ":" + std::to_string(po.bin_y) + ": each factor is 1, 2, 4 or 8 and the "
+                                               + std::to_string(s_row) + " x " + std::to_string(s_col) + " detector must hold at least one bin"};
+            const auto n_src = static_cast<std::size_t>(s_row) * s_col, n_bin = static_cast<std::size_t>(b_row) * b_col;
+            auto mask = std::shared_ptr<std::vector<std::uint8_t>>{};
+            if(po.defect_mask || po.defects_from_flat)
+                mask = po.defect_mask ? std::make_shared<std::vector<std::uint8_t>>(*po.defect_mask) : std::make_shared<std::vector<std::uint8_t>>(n_src, 0u);
+            if(po.defects_from_flat)
+                for(std::size_t k = 0; k < n_src; ++k)
+                {
+                    const double dk = po.dark ? static_cast<double>(po.dark->pixels[k]) : 0.0, fl = static_cast<double>(po.flat->pixels[k]);
+                    if(!(fl - dk > 0.0) || !std::isfinite(dk) || !std::isfinite(fl))
+                        (*mask)[k] = 1u;
+                }
+            const auto binned = [&](const std::shared_ptr<const his::mean>& m) -> std::shared_ptr<const his::mean> {
+                auto out = std::make_shared<his::mean>();
+                out->dim_x = b_row;
+                out->dim_y = b_col;
+                out->n_frames = m->n_frames;
+                out->pixels.resize(n_bin);
+                rt(paris_hip_bin_frame_host(&setting, mask ? mask->data() : nullptr, m->pixels.data(), s_row, s_col, out->pixels.data()), "--bin");
+                return out;
+            };
+            if(po.flat)
+                po.flat = binned(po.flat);
+            if(po.dark)
+                po.dark = binned(po.dark);
+            if(mask)
+            {
+                auto small = std::make_shared<std::vector<std::uint8_t>>(n_bin);
+                rt(paris_hip_bin_mask(&setting, mask->data(), s_row, s_col, small->data()), "--bin");
+                for(const auto b : *small)
+                    r.binned_defective += b;
+                paris_hip_defect_plan* plan = nullptr;
+                auto st = paris_hip_defect_stats{};
+                rt(paris_hip_defect_plan_create(small->data(), b_row, b_col, &plan), "--bin");
+                (void)paris_hip_defect_plan_stats(plan, &st);
+                (void)paris_hip_defect_plan_destroy(plan);
+                po.defect_bytes = static_cast<std::size_t>(st.device_bytes);
+                po.defect_mask = std::move(small);
+                po.bin_mask = std::move(mask);
+            }
+            auto geo = po.det_geo;
+            rt(paris_hip_binned_geometry(&setting, &po.det_geo, &geo), "--bin");
+            po.det_geo = geo;
+            po.src_row = s_row;
+            po.src_col = s_col;
+            r.binning = true;
+            r.bin_x = po.bin_x;
+            r.bin_y = po.bin_y;
+            r.src_row = s_row;
+            r.src_col = s_col;
+            r.binned_row = b_row;
+            r.binned_col = b_col;
+        }
+
         // --zingers / --zinger-polarity: the default polarity is resolved and the setting checked here, before any device work
         inline auto check_zingers(program_options& po) -> void
         {
@@ -1397,10 +1527,15 @@ namespace paris
             rt(paris_hip_ctx_create(0, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
             auto h_buf = std::vector<float*>(batch, nullptr);
             float* d_all = nullptr;
+            // --bin: the profile is taken on binned frames; the source frames go through full-width slots as in reconstruct()
+            const bool binning = po.binning();
+            const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
+            float* d_src_all = nullptr;
             const auto cleanup = [&] {
                 for(auto h : h_buf)
                     paris_hip_free_host(ctx, h);
                 paris_hip_free(ctx, d_all);
+                paris_hip_free(ctx, d_src_all);
                 paris_hip_ctx_destroy(ctx);
             };
             try
@@ -1410,10 +1545,17 @@ namespace paris
                 std::size_t d_pitch = 0;
                 rt(paris_hip_malloc_projection(ctx, n_row, n_col * batch, &d_all, &d_pitch), "make_projection_device()");
                 const auto d_stride = d_pitch * n_col;
+                std::size_t s_pitch = 0;
+                if(binning)
+                {
+                    if(static_cast<std::uint64_t>(sn_col) * batch > 0xffffffffull)
+                        throw stage_construction_error{"too many projection slots for this detector"};
+                    rt(paris_hip_malloc_projection(ctx, sn_row, sn_col * batch, &d_src_all, &s_pitch), "make_projection_device()");
+                }
                 for(auto& h : h_buf)
                 {
                     void* p = nullptr;
-                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(n_row) * n_col * sizeof(float), &p), "make_projection_host()");
+                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(sn_row) * sn_col * sizeof(float), &p), "make_projection_host()");
                     h = static_cast<float*>(p);
                 }
                 rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
@@ -1423,17 +1565,25 @@ namespace paris
                     std::uint32_t filled = 0;
                     for(; filled < batch; ++filled)
                     {
-                        const auto p = source.next_raw(h_buf[filled], n_row, n_col, 0u, n_col);
+                        const auto p = source.next_raw(h_buf[filled], sn_row, sn_col, 0u, sn_col);
                         if(!p.valid())
                         {
                             more = false;
                             break;
                         }
-                        if(p.dim_x != n_row || p.dim_y != n_col)
+                        if(p.dim_x != sn_row || p.dim_y != sn_col)
                             throw stage_runtime_error{"projection size does not match the detector geometry"};
                         auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * filled);
                         const auto px = his::pixel_size(p.pixel);
-                        if(po.flat)
+                        if(binning)
+                        {
+                            auto* d_full = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * filled);
+                            rt(paris_hip_upload_projection_raw(ctx, d_full, s_pitch, h_buf[filled], sn_row * px, sn_row, sn_col, p.pixel), "load()");
+                            rt(paris_hip_bin_frames(ctx, d_full, s_pitch, 0u, d_frame, d_pitch, 0u, 1u, sn_row, sn_col, 0u, n_col), "bin()");
+                            if(po.flat)
+                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, 0u, n_col), "flat field");
+                        }
+                        else if(po.flat)
                             rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[filled], n_row * px, n_row, n_col, 0u, n_col, p.pixel),
                                "load()");
                         else
@@ -1483,6 +1633,7 @@ namespace paris
         r.flat_frames = po.flat ? po.flat->n_frames : 0u;
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         detail::load_defects(po);
+        detail::apply_binning(po, r); // from here on po.det_geo is the binned detector
         detail::check_zingers(po);
         detail::check_extend_rows(po);
         detail::check_rings(po);
@@ -1567,7 +1718,8 @@ namespace paris
             else
                 r.rows_per_pass = static_cast<double>(first_pass);
             r.shared_source = po.share_frames < 0 ? r.rows_per_pass > 2.0 : po.share_frames != 0;
-            frame_pool pool{n_dev, po.det_geo.n_row, po.det_geo.n_col}; // every HIS frame is read once per pass, not once per device
+            // every HIS frame is read once per pass, not once per device (with --bin: at the source detector's size)
+            frame_pool pool{n_dev, po.binning() ? po.src_row : po.det_geo.n_row, po.binning() ? po.src_col : po.det_geo.n_col};
             auto* shared = r.shared_source ? &pool : nullptr;
             auto futures = std::vector<std::future<device_report>>{};
             for(int d = 0; d < n_dev; ++d)
