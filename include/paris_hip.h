@@ -701,6 +701,109 @@ int paris_hip_clear_ring_correction(paris_hip_ctx* ctx);
  * setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
 int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* Extension (no reference counterpart): finding the rotation axis, delta_s, from the scan itself by the fan-beam consistency of
+ * the mid-plane. With the ray the backprojector and paris_hip_forward_project define -- source
+ * (-d_so cos phi, -d_so sin phi), direction (d_sd cos phi - t sin phi, d_sd sin phi + t cos phi) -- the ray at view angle phi and
+ * fan angle gamma = atan(t / d_sd) is the same line as the ray at phi + 180 deg + 2 gamma and fan angle -gamma. With
+ * t_i = ((i + 1/2) - n / 2 - c) l the conjugate of column i lies at column (n - 1 - i) + 2 c. The cost of a candidate c is the mean
+ * squared difference between every mid-plane sample and its conjugate, interpolated linearly in column and in view; it has its
+ * minimum at the true c.
+ * Setting paris_hip_axis_search { float lo; float step; uint32_t count; uint32_t rows; uint32_t min_columns; }.
+ *   Candidates are c_k = (float)((double)lo + k (double)step), k = 0 .. count - 1, in detector pixels: values of delta_s.
+ *   1 <= count <= 1024; lo is finite; step > 0 and finite.
+ *   rows R is in [1, 64] and R <= n_col.
+ *   min_columns = 0 stands for max(8, n_row / 16).
+ * Scan. N frames, N >= 4, frame f taken at f 360 / N degrees: a full, equidistant circle. The pixels are line integrals, as the ring
+ *   profile sees them: after the zinger filter, before the ring correction and every weight. n = n_row.
+ *   The geometry needs l_px_row > 0, d_sd = |d_so| + |d_od| > 0 and delta_t, all finite.
+ * Band. j_c = n_col / 2 + delta_t - 1/2; row_first = floor(j_c - (R - 1) / 2 + 1/2), in double, clamped to [0, n_col - R].
+ * Sinogram. S[f][i] is the fp32 sum of rows row_first .. row_first + R - 1 of frame f at column i: acc = +0; acc = acc + p in ascending
+ *   row order, each addition rounded once, no contraction.
+ * Plan (host only, the single implementation: paris_hip_axis_search_plan). For candidate c and column i, everything in double and
+ *   rounded once:
+ *   ip = (n - 1 - i) + 2 c; i0 = floor(ip); wi = (float)(ip - i0). The column is valid iff 0 <= i0 and i0 + 1 <= n - 1.
+ *   gamma = atan((((i + 1/2) - n / 2 - c) l_px_row) / d_sd).
+ *   kk = N / 2 + (gamma N) / pi; k0 = floor(kk) reduced into [0, N); wf = (float)(kk - floor(kk)).
+ *   One 16-byte entry per (c, i): { int32 i0 (-1 = invalid); uint32 k0; float wi; float wf }; an invalid entry is { -1, 0, 0, 0 }.
+ * Pair (device). For a valid column, with fa = (f + k0) mod N and fb = (fa + 1) mod N, all in fp32, each operation rounded once, no
+ *   contraction:
+ *   a = S[fa][i0] + wi (S[fa][i0 + 1] - S[fa][i0]); b is the same on fb.
+ *   m = a + wf (b - a); d = S[f][i] - m. A pair whose d is not finite is skipped and counted.
+ * Cost. J[k] = sum of (double)d (double)d over all f and valid i, divided by the integer number of pairs summed. The sum is
+ *   accumulated in double. There are no floating-point atomics: every partial sum has one owner and the partial sums are combined in
+ *   a fixed order, so two runs give the same bits. A candidate with fewer than min_columns valid columns, or with no pair summed, is
+ *   unscored: J = +inf.
+ * Estimate (host only, the single implementation: paris_hip_axis_estimate_from_costs). A candidate is scored iff its J is finite.
+ *   m = the index of the smallest J among the scored; ties go to the lowest index.
+ *   The parabola applies if m - 1 and m + 1 exist and are scored, and q = J[m-1] - 2 J[m] + J[m+1] > 0. Then
+ *   off = (1/2) (J[m-1] - J[m+1]) / q, clamped to [-1/2, 1/2], and delta_s = (float)(c_m + off step), in double.
+ *   Otherwise delta_s = c_m and at_edge = 1.
+ *   The median reported is the lower one: the ((s - 1) / 2 + 1)-th smallest of the s scored J.
+ * Limits: the mid-plane only -- the cone angle across the R rows is ignored; a full equidistant circle; detector tilt and in-plane
+ * rotation are not estimated. */
+typedef struct paris_hip_axis_search {
+    float lo;             /* the first candidate [px] */
+    float step;           /* the distance between candidates [px], > 0 */
+    uint32_t count;       /* candidates, 1 .. 1024 */
+    uint32_t rows;        /* R: detector rows summed into the mid-plane line, 1 .. 64 */
+    uint32_t min_columns; /* a candidate with fewer valid columns is unscored; 0 = max(8, n_row / 16) */
+} paris_hip_axis_search;
+typedef struct paris_hip_axis_entry {
+    int32_t i0;  /* the conjugate's left column; -1: the column has no conjugate on the detector */
+    uint32_t k0; /* the conjugate's first view is (f + k0) mod N */
+    float wi;    /* the weight of column i0 + 1 */
+    float wf;    /* the weight of view (f + k0 + 1) mod N */
+} paris_hip_axis_entry;
+typedef struct paris_hip_axis_result {
+    float delta_s;      /* the estimate [px] */
+    uint32_t best;      /* m: the index of the smallest scored J */
+    double cost_min;    /* J[m] */
+    double cost_median; /* the lower median of the scored J */
+    uint32_t scored;    /* candidates with a finite J */
+    uint32_t columns;   /* the valid columns of candidate m (0 when the columns were not given) */
+    uint64_t skipped;   /* pairs whose difference was not finite, over all candidates (paris_hip_axis_search_finish only) */
+    uint32_t at_edge;   /* 1: no parabola -- the minimum is at an end, beside an unscored candidate, or not convex */
+    uint32_t row_first; /* the band's first row (paris_hip_axis_search_finish only) */
+} paris_hip_axis_result;
+/* one collect launch serves at most this many frames; calls with more loop */
+#define PARIS_HIP_AXIS_FRAMES_MAX 64
+/* Host only, no ctx and no device: checks a setting for a detector and a scan of n_frames frames, and reports the band's first row
+ * and what an open search occupies on the device (sinogram, plan, partial sums); either pointer may be NULL.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting or geometry or for what the rule above excludes; PARIS_HIP_ERROR_UNSUPPORTED when
+ * n_row count or n_frames n_row does not fit 32 bits, or n_row does not fit 31. */
+int paris_hip_axis_search_check(const paris_hip_axis_search* setting, const paris_detector_geometry* det_geo, uint32_t n_frames,
+                                uint32_t* row_first, size_t* device_bytes);
+/* Host only: the n_row plan entries of candidate k -- the single implementation of the plan. PARIS_HIP_ERROR_INVALID_ARGUMENT as the
+ * check, for k >= count or a NULL entries. */
+int paris_hip_axis_search_plan(const paris_hip_axis_search* setting, const paris_detector_geometry* det_geo, uint32_t n_frames, uint32_t k,
+                               paris_hip_axis_entry* entries);
+/* Host only: the estimate from the `count` costs -- the single implementation. columns (count entries, may be NULL) only supplies
+ * result->columns; skipped and row_first are set to 0. Only lo, step and count of the setting are read.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, cost or result, a count outside 1 .. 1024, a lo or step the rule excludes, or
+ * when no candidate is scored (the result then has scored = 0). */
+int paris_hip_axis_estimate_from_costs(const paris_hip_axis_search* setting, const double* cost, const uint32_t* columns,
+                                       paris_hip_axis_result* result);
+/* The search: paris_hip_axis_search_begin runs the check, makes the plan of every candidate on the host and copies it into memory the
+ * ctx owns, beside the n_frames x n_row sinogram and the partial sums. That memory counts towards
+ * paris_hip_projection_reserve_bytes while the search is open and is freed by finish, discard or paris_hip_ctx_destroy. begin on an
+ * open search replaces it; work queued before keeps the old one.
+ * paris_hip_axis_search_add_rows sums the band of n_frames frames frame_stride bytes apart, d_p the first frame's row 0, into the
+ * sinogram rows frame_first .. frame_first + n_frames - 1; the frames are only read. 16-byte loads are used where the base, the pitch,
+ * the stride (n_frames > 1) and dim_x are multiples of 16 bytes, single pixels otherwise. The host counts each sinogram row: a row
+ * added twice, or one beyond n_frames, is PARIS_HIP_ERROR_INVALID_ARGUMENT and adds nothing. A held-back weighting runs first, and a
+ * frame of the pending by-reference group has that group launched first. PARIS_HIP_ERROR_INVALID_ARGUMENT also without an open
+ * search, when dim_x / dim_y differ from n_row / n_col, or for a pitch or stride paris_hip_flat_field_rows would refuse.
+ * paris_hip_axis_search_finish refuses while a sinogram row is missing (PARIS_HIP_ERROR_INVALID_ARGUMENT; the search stays open, as
+ * for a NULL cost or result). Otherwise it scores every candidate on the device, waits for the ctx stream, fills cost[count] and
+ * columns[count] (may be NULL; the valid columns per candidate), runs the estimate and closes the search, whatever the estimate
+ * answers. h_sinogram (may be NULL) receives n_frames rows of n_row floats.
+ * paris_hip_axis_search_discard closes an open search (no error without one). */
+int paris_hip_axis_search_begin(paris_hip_ctx* ctx, const paris_hip_axis_search* setting, const paris_detector_geometry* det_geo,
+                                uint32_t n_frames);
+int paris_hip_axis_search_add_rows(paris_hip_ctx* ctx, const float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames,
+                                   uint32_t dim_x, uint32_t dim_y, uint32_t frame_first);
+int paris_hip_axis_search_finish(paris_hip_ctx* ctx, double* cost, uint32_t* columns, paris_hip_axis_result* result, float* h_sinogram);
+int paris_hip_axis_search_discard(paris_hip_ctx* ctx);
 /* Extension (no reference counterpart): detector binning on the device, between paris_hip_upload_projection_raw and
  * paris_hip_flat_field_rows, where the pixels are detector counts as fp32. One definition; the device
  * (paris_hip_bin_frames) and the host (paris_hip_bin_frame_host) both implement it.

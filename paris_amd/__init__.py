@@ -5,4 +5,4 @@ voxel-driven cone-beam backprojection as hand-written HIP kernels behind a C ABI
 """
 from . import backend  # noqa: F401
 
-__version__ = "0.1.0"
+__version__ = "0.2.0"

@@ -96,6 +96,26 @@ class Binning(C.Structure):
     _fields_ = [("bin_x", C.c_uint32), ("bin_y", C.c_uint32)]
 
 
+class AxisSearch(C.Structure):
+    """paris_hip_axis_search: the candidates and the band of the axis search (extension)"""
+    _fields_ = [("lo", C.c_float), ("step", C.c_float), ("count", C.c_uint32), ("rows", C.c_uint32), ("min_columns", C.c_uint32)]
+
+
+class AxisEntry(C.Structure):
+    """paris_hip_axis_entry: where one column's conjugate lies for one candidate (extension)"""
+    _fields_ = [("i0", C.c_int32), ("k0", C.c_uint32), ("wi", C.c_float), ("wf", C.c_float)]
+
+
+class AxisResult(C.Structure):
+    """paris_hip_axis_result: the estimate of the axis search (extension)"""
+    _fields_ = [("delta_s", C.c_float), ("best", C.c_uint32), ("cost_min", C.c_double), ("cost_median", C.c_double),
+                ("scored", C.c_uint32), ("columns", C.c_uint32), ("skipped", C.c_uint64), ("at_edge", C.c_uint32),
+                ("row_first", C.c_uint32)]
+
+
+AXIS_FRAMES_MAX = 64  # PARIS_HIP_AXIS_FRAMES_MAX
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -180,6 +200,13 @@ SIGNATURES = {
     "paris_hip_set_ring_correction": (C.c_int, [_vp, _vp, _u32, _u32]),
     "paris_hip_clear_ring_correction": (C.c_int, [_vp]),
     "paris_hip_ring_correct_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_axis_search_check": (C.c_int, [_P(AxisSearch), _P(DetectorGeometry), _u32, _P(_u32), _P(_sz)]),
+    "paris_hip_axis_search_plan": (C.c_int, [_P(AxisSearch), _P(DetectorGeometry), _u32, _u32, _vp]),
+    "paris_hip_axis_estimate_from_costs": (C.c_int, [_P(AxisSearch), _vp, _vp, _P(AxisResult)]),
+    "paris_hip_axis_search_begin": (C.c_int, [_vp, _P(AxisSearch), _P(DetectorGeometry), _u32]),
+    "paris_hip_axis_search_add_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32]),
+    "paris_hip_axis_search_finish": (C.c_int, [_vp, _vp, _vp, _P(AxisResult), _vp]),
+    "paris_hip_axis_search_discard": (C.c_int, [_vp]),
     "paris_hip_binning_check": (C.c_int, [_P(Binning), _u32, _u32, _P(_u32), _P(_u32)]),
     "paris_hip_binned_geometry": (C.c_int, [_P(Binning), _P(DetectorGeometry), _P(DetectorGeometry)]),
     "paris_hip_bin_frame_host": (C.c_int, [_P(Binning), _vp, _vp, _u32, _u32, _vp]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -162,6 +162,44 @@ def ring_correction_from_mean(half_width, floor_abs, limit_abs, mean, count_per_
                                                           m.shape[1], m.shape[0], c.ctypes.data, C.byref(st)),
           "paris_hip_ring_correction_from_mean")
     return c, st
+
+
+def _axis_setting(lo, step, count, rows=2, min_columns=0):
+    return AxisSearch(lo, step, count, rows, min_columns)
+
+
+def axis_search_check(lo, step, count, det_geo, n_frames, rows=2, min_columns=0):
+    """Host only, no device (paris_hip_axis_search_check): checks an axis search -- `count` candidates lo, lo + step, ... for delta_s in
+    detector pixels, `rows` detector rows summed into the mid-plane line -- for det_geo's detector and a full circle of n_frames
+    frames, and returns (row_first, device_bytes). Raises ParisHipError for what the library refuses."""
+    s, first, nbytes = _axis_setting(lo, step, count, rows, min_columns), C.c_uint32(0), C.c_size_t(0)
+    check(_lib.load().paris_hip_axis_search_check(C.byref(s), C.byref(det_geo), n_frames, C.byref(first), C.byref(nbytes)),
+          "paris_hip_axis_search_check")
+    return first.value, nbytes.value
+
+
+def axis_search_plan(lo, step, count, det_geo, n_frames, k, rows=2, min_columns=0):
+    """Host only, no device (paris_hip_axis_search_plan): candidate k's plan as a structured array of n_row entries with the fields
+    i0 (-1: no conjugate on the detector), k0, wi and wf."""
+    s = _axis_setting(lo, step, count, rows, min_columns)
+    entries = np.empty(det_geo.n_row, np.dtype([("i0", np.int32), ("k0", np.uint32), ("wi", np.float32), ("wf", np.float32)]))
+    check(_lib.load().paris_hip_axis_search_plan(C.byref(s), C.byref(det_geo), n_frames, k, entries.ctypes.data), "paris_hip_axis_search_plan")
+    return entries
+
+
+def axis_estimate_from_costs(lo, step, cost, columns=None):
+    """Host only, no device (paris_hip_axis_estimate_from_costs): the estimate from one cost per candidate lo, lo + step, ... --
+    +inf marks an unscored candidate. Returns the AxisResult: delta_s, best, cost_min, cost_median, scored, columns, at_edge."""
+    j = np.ascontiguousarray(cost, np.float64)
+    if j.ndim != 1:
+        raise ValueError("axis_estimate_from_costs: one cost per candidate")
+    cols = None if columns is None else np.ascontiguousarray(columns, np.uint32)
+    if cols is not None and cols.shape != j.shape:
+        raise ValueError("axis_estimate_from_costs: one column count per candidate")
+    s, out = _axis_setting(lo, step, j.size), AxisResult()
+    check(_lib.load().paris_hip_axis_estimate_from_costs(C.byref(s), j.ctypes.data, None if cols is None else cols.ctypes.data, C.byref(out)),
+          "paris_hip_axis_estimate_from_costs")
+    return out
 
 
 def binning_check(bin_x, bin_y, dim_x, dim_y):
@@ -637,6 +675,47 @@ class Backend:
         count = p.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_ring_correct_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
               "paris_hip_ring_correct_rows")
+
+    # ---- axis search --------------------------------------------------------------
+    axis_search_check = staticmethod(axis_search_check)
+    axis_search_plan = staticmethod(axis_search_plan)
+    axis_estimate_from_costs = staticmethod(axis_estimate_from_costs)
+
+    def axis_search_begin(self, lo, step, count, det_geo, n_frames, rows=2, min_columns=0):
+        """paris_hip_axis_search_begin: opens the search for delta_s among `count` candidates lo, lo + step, ... [px] on a full circle
+        of n_frames frames of det_geo's detector -- the plan and an n_frames x n_row sinogram on the device. Replaces an open one
+        safely: work already queued keeps the old one."""
+        s = _axis_setting(lo, step, count, rows, min_columns)
+        check(self._L.paris_hip_axis_search_begin(self._ctx, C.byref(s), C.byref(det_geo), n_frames), "paris_hip_axis_search_begin")
+        self._axis_shape = (count, n_frames, det_geo.n_row)
+
+    def axis_search_add(self, p, frame_first, frame_stride=0, n_frames=1):
+        """Sums the mid-plane band of n_frames frames frame_stride bytes apart starting at p into the sinogram rows frame_first ...
+        (paris_hip_axis_search_add_rows). The frames are only read; every frame of the circle is added exactly once, in any order.
+        Call it on line integrals, after the zinger filter and before every weight."""
+        check(self._L.paris_hip_axis_search_add_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, frame_first),
+              "paris_hip_axis_search_add_rows")
+
+    def axis_search_finish(self, sinogram=False):
+        """paris_hip_axis_search_finish: scores every candidate on the device, waits for the ctx stream and runs the estimate. Returns
+        (AxisResult, cost, columns) -- float64 costs (+inf: unscored) and the valid columns per candidate -- and the float32 sinogram
+        (n_frames, n_row) as a fourth value when asked for. The search is closed, unless a frame is still missing."""
+        shape = getattr(self, "_axis_shape", None)
+        if shape is None:
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_axis_search_finish")
+        cost, columns, out = np.empty(shape[0], np.float64), np.empty(shape[0], np.uint32), AxisResult()
+        s = np.empty(shape[1:], np.float32) if sinogram else None
+        out.scored = 0xFFFFFFFF          # a finish refused before scoring writes no result and leaves the search open
+        rc = self._L.paris_hip_axis_search_finish(self._ctx, cost.ctypes.data, columns.ctypes.data, C.byref(out), None if s is None else s.ctypes.data)
+        if rc == _lib.SUCCESS or out.scored == 0:
+            self._axis_shape = None      # scored -- also when no candidate had a cost -- and closed
+        check(rc, "paris_hip_axis_search_finish")
+        return (out, cost, columns, s) if sinogram else (out, cost, columns)
+
+    def axis_search_discard(self):
+        """paris_hip_axis_search_discard: closes an open search without a result"""
+        check(self._L.paris_hip_axis_search_discard(self._ctx), "paris_hip_axis_search_discard")
+        self._axis_shape = None
 
     # ---- detector binning (DESIGN.md section 4.14) --------------------------------------------------------
     binning_check = staticmethod(binning_check)

@@ -1022,6 +1022,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += sizeof(double) * static_cast<size_t>(ctx->ring.sum_dim_x) * ctx->ring.sum_dim_y;
     if(ctx->ring.set) // the correction frame of paris_hip_set_ring_correction
         total += sizeof(float) * static_cast<size_t>(ctx->ring.dim_x) * ctx->ring.dim_y;
+    if(ctx->axis.d_mem != nullptr) // the sinogram, plan and partial sums of paris_hip_axis_search_begin
+        total += ctx->axis.device_bytes;
     if(ctx->binning.d_mask != nullptr) // the mask of paris_hip_set_binning
         total += static_cast<size_t>(ctx->binning.dim_x) * ctx->binning.dim_y;
     if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached

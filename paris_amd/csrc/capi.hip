@@ -114,6 +114,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_ring();
             paris_hip_warm_volume_window();
             paris_hip_warm_binning();
+            paris_hip_warm_axis_search();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -331,6 +332,7 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     paris_hip_ring_correction_release(ctx, true);
     paris_hip_volume_window_release(ctx, true);
     paris_hip_binning_release(ctx, true);
+    paris_hip_axis_search_release(ctx, true);
     if(ctx->defer_count != 0)
     {
         // Projections still deferred belong to key_v. Every library entry point that reads or frees a volume has flushed them
@@ -1502,5 +1504,5 @@ extern "C" const char* paris_hip_strerror(int status)
 
 extern "C" const char* paris_hip_version(void)
 {
-    return "0.1.0";
+    return "0.2.0";
 }

@@ -163,6 +163,20 @@ struct paris_hip_ctx
         float* d_c = nullptr;
         uint32_t dim_x = 0, dim_y = 0;
     } ring;
+    // Axis search (paris_hip_axis_search_begin): ONE device allocation that holds, in this order, the
+    // sinogram (n_frames rows of n floats), the plan (count rows of n 16-byte entries), the score kernel's partial sums and the
+    // per-candidate totals (paris_hip_axis_layout). On the host: which sinogram rows have been added and every candidate's valid
+    // columns. Touched by the kernels of axis_search.hip and the copies of finish on the compute stream only (the plan's upload
+    // runs on the auxiliary stream and is waited for in begin), so it is replaced, retired and freed as the ring profile is.
+    struct axis_t
+    {
+        char* d_mem = nullptr;
+        size_t device_bytes = 0;
+        paris_hip_axis_search setting{};
+        uint32_t n = 0, n_col = 0, n_frames = 0, row_first = 0, missing = 0;
+        std::vector<uint8_t> seen;
+        std::vector<uint32_t> columns;
+    } axis;
     // Detector binning (paris_hip_set_binning): the setting for one source detector, the binned size, and the
     // device copy of the optional source-size mask (nullptr: every pixel good) -- read by the kernels of bin_frames.hip on the compute
     // stream only, so it is replaced, retired and freed as the defect plan is.
@@ -451,6 +465,7 @@ void paris_hip_warm_zinger();
 void paris_hip_warm_ring();
 void paris_hip_warm_volume_window();
 void paris_hip_warm_binning();
+void paris_hip_warm_axis_search();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -482,7 +497,31 @@ void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying);
 // bin_frames.hip: the same for the binning's mask
 void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
+// axis_search.hip: the same for an open axis search
+void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop
+
+// Where the pieces of an open axis search lie in its one allocation (axis_search.hip), each 256-byte aligned; axis_rule.cpp reports
+// the total. The score kernel's grid: a workgroup takes one candidate, PARIS_HIP_AXIS_TILE_COLUMNS columns (one per lane) and
+// PARIS_HIP_AXIS_TILE_VIEWS consecutive views, and leaves one 16-byte partial sum.
+constexpr uint32_t PARIS_HIP_AXIS_TILE_COLUMNS = 256u, PARIS_HIP_AXIS_TILE_VIEWS = 32u;
+struct paris_hip_axis_layout
+{
+    uint32_t col_tiles, view_tiles;
+    size_t plan, partial, total_of, bytes; // byte offsets of the plan, the partial sums and the totals; the whole size
+};
+inline paris_hip_axis_layout paris_hip_axis_layout_of(uint32_t n, uint32_t n_frames, uint32_t count)
+{
+    const auto up = [](size_t v) { return (v + 255u) & ~static_cast<size_t>(255u); };
+    paris_hip_axis_layout l{};
+    l.col_tiles = (n + PARIS_HIP_AXIS_TILE_COLUMNS - 1u) / PARIS_HIP_AXIS_TILE_COLUMNS;
+    l.view_tiles = (n_frames + PARIS_HIP_AXIS_TILE_VIEWS - 1u) / PARIS_HIP_AXIS_TILE_VIEWS;
+    l.plan = up(static_cast<size_t>(n_frames) * n * sizeof(float));
+    l.partial = l.plan + up(static_cast<size_t>(count) * n * sizeof(paris_hip_axis_entry));
+    l.total_of = l.partial + up(static_cast<size_t>(count) * l.col_tiles * l.view_tiles * 16u);
+    l.bytes = l.total_of + up(static_cast<size_t>(count) * 24u);
+    return l;
+}
 
 // capi.hip: timing-disabled events, recycled through ctx->spare_events
 int paris_hip_take_event(paris_hip_ctx* ctx, hipEvent_t* out);

@@ -6,7 +6,7 @@
 //                       [--slabs N] [--roi x1 x2 y1 y2 z1 z2] [--vol dx dy dz l_vx] [--cycle K] [--no-out] [--order N] [--json]
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
-//                       [--rings half_width floor limit]
+//                       [--rings half_width floor limit] [--find-axis lo step count rows]
 //                       [--extend-rows W M] [--bin BX BY mask.raw|none]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
@@ -24,6 +24,9 @@
 // loops, so that paris::weight() removes each frame's outlier pixels after the repair and before the weights.
 // --rings: half_width, floor_abs and limit_abs of the ring rule. A pre-pass before the loops sums every frame (ring_profile_add()) and
 // set_ring_correction() gets the rule's correction frame, so that paris::weight() subtracts it after the zinger filter.
+// --find-axis: the first candidate, the step, the number of candidates [pixels of delta_s] and the rows of the axis search. The same
+// pre-pass hands every frame to axis_search_add() as well (the frames are a full circle at equal steps); the estimate is printed as
+// "axis: delta_s = ..." and replaces the geometry's delta_s in the loops. The volume grid stays the one of the geometry given.
 // --extend-rows: the taper length W and the number of edge pixels M of the row extension for truncated projections.
 // set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
 // --bin: the geometry on the command line is the SOURCE detector's and in.raw holds frames of that size; each loaded frame is binned
@@ -94,6 +97,8 @@ int main(int argc, char** argv)
         bool rings = false;
         std::uint32_t ring_half_width = 0;
         float ring_floor = 0.f, ring_limit = 0.f;
+        bool find_axis = false;
+        auto axis = paris_hip_axis_search{};
         bool extend_rows = false;
         std::uint32_t extend_taper = 0, extend_edge = 0;
         std::uint32_t bin_x = 1, bin_y = 1;
@@ -148,6 +153,15 @@ int main(int argc, char** argv)
                 ring_limit = std::strtof(argv[a + 3], nullptr);
                 a += 3;
             }
+            else if(!std::strcmp(argv[a], "--find-axis") && a + 4 < argc)
+            {
+                find_axis = true;
+                axis.lo = std::strtof(argv[a + 1], nullptr);
+                axis.step = std::strtof(argv[a + 2], nullptr);
+                axis.count = static_cast<std::uint32_t>(std::strtoul(argv[a + 3], nullptr, 10));
+                axis.rows = static_cast<std::uint32_t>(std::strtoul(argv[a + 4], nullptr, 10));
+                a += 4;
+            }
             else if(!std::strcmp(argv[a], "--extend-rows") && a + 2 < argc)
             {
                 extend_rows = true;
@@ -189,9 +203,9 @@ int main(int argc, char** argv)
             return 2;
         }
         const bool binning = !bin_mask_path.empty();
-        if(binning && (rings || !reproject_path.empty()))
+        if(binning && (rings || find_axis || !reproject_path.empty()))
         {
-            std::fprintf(stderr, "--bin cannot be combined with --rings or --reproject\n");
+            std::fprintf(stderr, "--bin cannot be combined with --rings, --find-axis or --reproject\n");
             return 2;
         }
         const auto src_det = det; // the detector the frames of in.raw come from
@@ -288,20 +302,39 @@ int main(int argc, char** argv)
             std::fclose(f);
         }
 
-        if(rings) // the pre-pass: every frame through correction, repair and zinger filter into the profile, then the correction frame
+        if(rings || find_axis) // the pre-pass: every frame through correction, repair and zinger filter into the profile and the search
         {
-            paris::backend::ring_profile_begin(det.n_row, det.n_col);
+            if(rings)
+                paris::backend::ring_profile_begin(det.n_row, det.n_col);
+            if(find_axis)
+                paris::backend::axis_search_begin(axis, det, n_proj);
             for(std::uint32_t i = 0; i < n_proj; ++i)
             {
                 auto p = paris::backend::make_projection_host(det.n_row, det.n_col);
                 std::memcpy(p.buf.get(), frames.data() + frame * (i % n_held), frame * sizeof(float));
                 p.idx = i;
                 auto d_p = paris::load(p);
-                paris::ring_profile_add(d_p);
+                if(rings)
+                    paris::ring_profile_add(d_p);
+                if(find_axis && rings) // the chain has run
+                    paris::backend::axis_search_add(d_p.buf.get(), d_p.buf.pitch(), d_p.dim_x, d_p.dim_y, i);
+                else if(find_axis)
+                    paris::axis_search_add(d_p, i);
             }
-            auto c = std::vector<float>(frame);
-            paris::backend::ring_profile_finish(ring_half_width, ring_floor, ring_limit, c.data());
-            paris::backend::set_ring_correction(c.data(), det.n_row, det.n_col);
+            if(rings)
+            {
+                auto c = std::vector<float>(frame);
+                paris::backend::ring_profile_finish(ring_half_width, ring_floor, ring_limit, c.data());
+                paris::backend::set_ring_correction(c.data(), det.n_row, det.n_col);
+            }
+            if(find_axis)
+            {
+                auto cost = std::vector<double>(axis.count);
+                const auto found = paris::backend::axis_search_finish(cost.data());
+                std::printf("axis: delta_s = %.9g (candidate %u of %u, J_min / J_median %.3g, at_edge %u)\n", static_cast<double>(found.delta_s), found.best,
+                            axis.count, found.cost_median > 0.0 ? found.cost_min / found.cost_median : 0.0, found.at_edge);
+                det.delta_s = found.delta_s;
+            }
         }
 
         std::FILE* out = write_out ? std::fopen(out_path.c_str(), "wb") : nullptr;

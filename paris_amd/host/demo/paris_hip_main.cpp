@@ -8,6 +8,7 @@
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
 //             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
 //             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]
+//             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -84,6 +85,7 @@ int main(int argc, char** argv)
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
                             "          [--rings H[:FLOOR[:LIMIT]]]\n"
                             "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]\n"
+                            "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -112,7 +114,14 @@ int main(int argc, char** argv)
                             "--bin: the detector is read as bins of BX x BY pixels (each 1, 2, 4 or 8; BY defaults to BX): every frame is uploaded as\n"
                             "stored and binned on the device before the correction, each binned pixel the mean of its pixels that --defects (and\n"
                             "--defects-from-flat) do not mark; the dark, the flat and the defect map are binned alike, and the geometry -- and with\n"
-                            "it the volume -- is the binned detector's.\n");
+                            "it the volume -- is the binned detector's.\n"
+                            "--find-axis: delta_s, the horizontal offset of the rotation axis, is found from the scan itself and replaces the\n"
+                            "geometry file's. The projections must form a full circle at equal steps (no --short-scan, no --angles). The scan is\n"
+                            "read once before the reconstruction (together with --rings when both are given; alone, only the rows it needs): the\n"
+                            "R rows (--axis-rows, 1 .. 64, default 2) about the mid-plane are summed into a sinogram, and each candidate LO,\n"
+                            "LO + STEP .. HI [pixels; binned pixels with --bin; STEP defaults to 0.25, at most 1024 candidates] is scored on the\n"
+                            "device by the mean squared difference between every sample and its conjugate ray half a turn away. The estimate is\n"
+                            "the minimum of a parabola through the best candidate and its neighbours. --axis-only prints it and stops.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -143,6 +152,9 @@ int main(int argc, char** argv)
             else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
             else if(k == "--rings") paris::detail::parse_rings(val(), po);
             else if(k == "--bin") paris::detail::parse_bin(val(), po);
+            else if(k == "--find-axis") paris::detail::parse_find_axis(val(), po);
+            else if(k == "--axis-rows") paris::detail::parse_axis_rows(val(), po);
+            else if(k == "--axis-only") po.axis_only = true;
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -197,6 +209,19 @@ int main(int argc, char** argv)
                         "%llu not finite, largest |c| %.6g\n", r.ring_frames, r.ring_prepass_s, static_cast<unsigned long long>(r.rings.corrected),
                         static_cast<unsigned long long>(r.rings.below_floor), static_cast<unsigned long long>(r.rings.above_limit),
                         static_cast<unsigned long long>(r.rings.not_finite), static_cast<double>(r.rings.max_abs));
+        if(r.axis_search)
+        {
+            std::printf("axis search on: delta_s = %.4f px (the geometry file gave %.4f), candidate %u of %u at step %g, J_min / J_median = %.3g, "
+                        "%u candidate(s) scored, %llu pair(s) skipped, %u frame(s) of %u row(s) from row %u in the pre-pass (%.3f s)\n",
+                        static_cast<double>(r.axis.delta_s), static_cast<double>(r.axis_given), r.axis.best, r.axis_count, static_cast<double>(po.axis_step),
+                        r.axis.cost_median > 0.0 ? r.axis.cost_min / r.axis.cost_median : 0.0, r.axis.scored,
+                        static_cast<unsigned long long>(r.axis.skipped), r.axis_frames, po.axis_rows, r.axis.row_first, r.axis_prepass_s);
+            if(r.axis.at_edge != 0u)
+                std::printf("warning: the axis search's minimum has no scored neighbour on both sides or is not convex: delta_s is the best candidate itself; "
+                            "widen the range of --find-axis\n");
+            if(po.axis_only)
+                return 0;
+        }
         if(r.voxel_type != 0)
             std::printf("%llu voxel(s) written as %s over [%.9g, %.9g]: %llu below, %llu above, %llu not finite\n",
                         static_cast<unsigned long long>(r.voxels.voxels), r.voxel_type == PARIS_HIP_VOXEL_U8 ? "u8" : "u16", static_cast<double>(r.voxel_lo),

@@ -374,6 +374,28 @@ namespace paris
             detail::runtime_check(paris_hip_ring_profile_finish(current_ctx(), &setting, c, nullptr, stats), "ring_profile_finish()");
         }
 
+        // Extension (no reference counterpart): the rotation axis, delta_s, found from the scan itself. A
+        // pre-pass over a full, equidistant circle of n_frames frames -- axis_search_begin(), then axis_search_add() on every frame
+        // as paris::weight() would see it after the zinger filter, each exactly once, then axis_search_finish(), which returns the
+        // estimate of the rule in include/paris_hip.h. cost and columns (may be NULL) receive one value per candidate.
+        inline auto axis_search_begin(const paris_hip_axis_search& setting, const detector_geometry& det_geo, std::uint32_t n_frames) -> void
+        {
+            detail::runtime_check(paris_hip_axis_search_begin(current_ctx(), &setting, detail::as_c<paris_detector_geometry>(det_geo), n_frames),
+                                  "axis_search_begin()");
+        }
+
+        inline auto axis_search_add(const float* d_p, std::size_t pitch, std::uint32_t n_row, std::uint32_t n_col, std::uint32_t frame) -> void
+        {
+            detail::runtime_check(paris_hip_axis_search_add_rows(current_ctx(), d_p, pitch, 0u, 1u, n_row, n_col, frame), "axis_search_add()");
+        }
+
+        inline auto axis_search_finish(double* cost, std::uint32_t* columns = nullptr) -> paris_hip_axis_result
+        {
+            auto result = paris_hip_axis_result{};
+            detail::runtime_check(paris_hip_axis_search_finish(current_ctx(), cost, columns, &result, nullptr), "axis_search_finish()");
+            return result;
+        }
+
         inline auto set_ring_correction(const float* c, std::uint32_t n_row, std::uint32_t n_col) -> void
         {
             detail::runtime_check(paris_hip_set_ring_correction(current_ctx(), c, n_row, n_col), "set_ring_correction()");

@@ -127,6 +127,15 @@ namespace paris
         float ring_floor = 0.f, ring_limit = 0.f;
         std::size_t ring_bytes = 0;                             // filled by run(): what the correction frame occupies on a device
         std::shared_ptr<const std::vector<float>> ring_c;       // filled by run(): the correction frame
+        // the rotation axis from the scan itself (extension): --find-axis LO:HI[:STEP] [--axis-rows R]
+        // [--axis-only], checked by run() before any device work (detail::check_axis). run() then reads the scan once on the first
+        // device (detail::prepass, the ring filter's pre-pass: with --rings each group of frames feeds both), scores the candidates
+        // and replaces det_geo.delta_s by the estimate before anything is derived from it
+        bool find_axis = false, axis_only = false;
+        float axis_lo = 0.f, axis_hi = 0.f, axis_step = 0.25f;
+        std::uint32_t axis_rows = 2;
+        bool axis_rows_given = false;
+        std::uint32_t axis_count = 0, axis_frames = 0;          // filled by run(): the candidates, and the frames of the circle
         // detector binning (extension): --bin BX[:BY], each 1, 2, 4 or 8; 1 x 1 is no binning. run() checks the
         // setting before any device work and replaces det_geo by the binned geometry (detail::apply_binning), so that everything
         // derived from it follows; the dark and flat means and the defect mask are binned on the host, the frames on the device, each
@@ -1082,6 +1091,11 @@ namespace paris
         paris_hip_ring_stats rings{};                   // how long the pre-pass took (reading the scan included)
         std::uint32_t ring_frames = 0;
         double ring_prepass_s = 0;
+        bool axis_search = false;                       // --find-axis: the search ran over axis_frames frames and axis_count
+        paris_hip_axis_result axis{};                   // candidates; the delta_s of the geometry file it replaced, and how long the
+        std::uint32_t axis_frames = 0, axis_count = 0;  // pre-pass took (reading the scan included; with --rings the same pre-pass)
+        float axis_given = 0.f;
+        double axis_prepass_s = 0;
         bool binning = false;                           // --bin: the factors, the source and the binned detector, and how many binned
         std::uint32_t bin_x = 1, bin_y = 1;             // pixels have no good source pixel (they join the defect map)
         std::uint32_t src_row = 0, src_col = 0, binned_row = 0, binned_col = 0;
@@ -1512,14 +1526,18 @@ namespace paris
                                                + ":" + std::to_string(po.ring_limit) + ")"};
         }
 
-        // --rings: the pre-pass. Every projection the run uses is read once as a whole frame on the first device and goes through the
+        // --rings and --find-axis: the pre-pass. Every projection the run uses is read once on the first device and goes through the
         // chain the reconstruction uses -- the raw upload (corrected with --flat), the defect repair, the zinger filter -- into the ring
-        // profile, a group of po.batch frames per call as the main loop groups them. Then the rule makes the correction frame, which
-        // is kept in po. Everything allocated here is freed before it returns: run() plans the slabs afterwards.
-        inline auto ring_prepass(program_options& po, run_report& r) -> void
+        // profile (rings), into the axis search's sinogram (axis), or into both: a group of po.batch frames per call as the main loop
+        // groups them. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by the reach
+        // of the repair and of the zinger filter as a slab's band is in reconstruct(). Then the ring rule makes the correction frame,
+        // which is kept in po, and the search gives its estimate, which is kept in r. Everything allocated here is freed before it
+        // returns: run() plans the slabs afterwards.
+        inline auto prepass(program_options& po, run_report& r, bool rings, bool axis) -> void
         {
             const auto t_start = clock::now();
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+            const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
             const std::uint32_t batch = slot_shape(po).first;
             if(static_cast<std::uint64_t>(n_col) * batch > 0xffffffffull)
                 throw stage_construction_error{"too many projection slots for this detector"};
@@ -1558,14 +1576,34 @@ namespace paris
                     rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(sn_row) * sn_col * sizeof(float), &p), "make_projection_host()");
                     h = static_cast<float*>(p);
                 }
-                rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
+                // the rows of every frame that are read, uploaded and corrected (up), repaired (fix) and filtered and consumed (band)
+                std::uint32_t band_first = 0, band_count = n_col;
+                if(axis && !rings)
+                {
+                    rt(paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, &band_first, nullptr), "axis_search_check()");
+                    band_count = po.axis_rows;
+                }
+                const auto widened = [&](std::uint32_t by, std::uint32_t& first, std::uint32_t& count) {
+                    first = band_first - std::min(band_first, by);
+                    count = std::min(n_col - (band_first + band_count), by) + band_first + band_count - first;
+                };
+                const std::uint32_t zinger_rows = po.zingers ? 1u : 0u;
+                std::uint32_t up_first = 0, up_count = 0, fix_first = 0, fix_count = 0;
+                widened((rep.defect_map ? rep.defects.reach_rows : 0u) + zinger_rows, up_first, up_count);
+                widened(zinger_rows, fix_first, fix_count);
+                const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
+                if(rings)
+                    rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
+                if(axis)
+                    rt(paris_hip_axis_search_begin(ctx, &search, &po.det_geo, po.axis_frames), "axis_search_begin()");
+                std::uint32_t frames = 0;
                 auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
                 for(bool more = true; more;)
                 {
                     std::uint32_t filled = 0;
                     for(; filled < batch; ++filled)
                     {
-                        const auto p = source.next_raw(h_buf[filled], sn_row, sn_col, 0u, sn_col);
+                        const auto p = source.next_raw(h_buf[filled], sn_row, sn_col, src_first, src_count);
                         if(!p.valid())
                         {
                             more = false;
@@ -1575,35 +1613,60 @@ namespace paris
                             throw stage_runtime_error{"projection size does not match the detector geometry"};
                         auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * filled);
                         const auto px = his::pixel_size(p.pixel);
+                        const auto* h_band = reinterpret_cast<const char*>(h_buf[filled]) + static_cast<std::size_t>(src_first) * sn_row * px;
                         if(binning)
                         {
                             auto* d_full = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * filled);
-                            rt(paris_hip_upload_projection_raw(ctx, d_full, s_pitch, h_buf[filled], sn_row * px, sn_row, sn_col, p.pixel), "load()");
-                            rt(paris_hip_bin_frames(ctx, d_full, s_pitch, 0u, d_frame, d_pitch, 0u, 1u, sn_row, sn_col, 0u, n_col), "bin()");
+                            auto* d_full_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_full) + static_cast<std::size_t>(src_first) * s_pitch);
+                            rt(paris_hip_upload_projection_raw(ctx, d_full_band, s_pitch, h_band, sn_row * px, sn_row, src_count, p.pixel), "load()");
+                            rt(paris_hip_bin_frames(ctx, d_full, s_pitch, 0u, d_frame, d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
                             if(po.flat)
-                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, 0u, n_col), "flat field");
+                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
                         }
                         else if(po.flat)
-                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[filled], n_row * px, n_row, n_col, 0u, n_col, p.pixel),
+                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_band, n_row * px, n_row, n_col, up_first, up_count, p.pixel),
                                "load()");
                         else
-                            rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[filled], n_row * px, n_row, n_col, p.pixel), "load()");
+                            rt(paris_hip_upload_projection_raw(ctx, reinterpret_cast<float*>(reinterpret_cast<char*>(d_frame) + static_cast<std::size_t>(up_first) * d_pitch),
+                                                               d_pitch, h_band, n_row * px, n_row, up_count, p.pixel), "load()");
                     }
                     if(filled == 0)
                         break;
+                    if(axis && filled > po.axis_frames - frames)
+                        throw stage_runtime_error{"--find-axis: the input holds more frames than were counted"};
                     if(rep.defect_map)
-                        rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "defect repair");
+                        rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count), "defect repair");
                     if(po.zingers)
-                        rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "zinger filter");
-                    rt(paris_hip_ring_profile_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
+                        rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, band_first, band_count), "zinger filter");
+                    if(rings)
+                        rt(paris_hip_ring_profile_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
+                    if(axis)
+                        rt(paris_hip_axis_search_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, frames), "axis_search_add_rows()");
                     rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
-                    r.ring_frames += filled;
+                    frames += filled;
                 }
-                auto c = std::make_shared<std::vector<float>>(static_cast<std::size_t>(n_row) * n_col);
-                const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
-                rt(paris_hip_ring_profile_finish(ctx, &setting, c->data(), nullptr, &r.rings), "ring_profile_finish()");
-                po.ring_c = std::move(c);
-                r.ring_filter = true;
+                if(rings)
+                {
+                    auto c = std::make_shared<std::vector<float>>(static_cast<std::size_t>(n_row) * n_col);
+                    const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
+                    rt(paris_hip_ring_profile_finish(ctx, &setting, c->data(), nullptr, &r.rings), "ring_profile_finish()");
+                    po.ring_c = std::move(c);
+                    r.ring_filter = true;
+                    r.ring_frames = frames;
+                }
+                if(axis)
+                {
+                    if(frames != po.axis_frames)
+                        throw stage_runtime_error{"--find-axis: the input holds fewer frames than were counted"};
+                    auto cost = std::vector<double>(po.axis_count);
+                    const int rc = paris_hip_axis_search_finish(ctx, cost.data(), nullptr, &r.axis, nullptr);
+                    if(rc == PARIS_HIP_ERROR_INVALID_ARGUMENT && r.axis.scored == 0u)
+                        throw stage_runtime_error{"--find-axis: no candidate has enough detector columns with a conjugate on the detector"};
+                    rt(rc, "axis_search_finish()");
+                    r.axis_search = true;
+                    r.axis_frames = frames;
+                    r.axis_count = po.axis_count;
+                }
             }
             catch(...)
             {
@@ -1611,7 +1674,84 @@ namespace paris
                 throw;
             }
             cleanup();
-            r.ring_prepass_s = since(t_start);
+            if(rings)
+                r.ring_prepass_s = since(t_start);
+            if(axis)
+                r.axis_prepass_s = since(t_start);
+        }
+
+        // --find-axis LO:HI[:STEP] as typed; refuses anything but two or three numbers
+        inline auto parse_find_axis(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--find-axis LO:HI[:STEP]: cannot read '" + v + "'"}; };
+            const auto number = [&bad](const std::string& t) -> float {
+                if(t.empty())
+                    throw bad();
+                char* end = nullptr;
+                const float f = std::strtof(t.c_str(), &end);
+                if(end == nullptr || *end != '\0')
+                    throw bad();
+                return f;
+            };
+            const auto first = v.find(':');
+            if(first == std::string::npos)
+                throw bad();
+            const auto second = v.find(':', first + 1u);
+            if(second != std::string::npos && v.find(':', second + 1u) != std::string::npos)
+                throw bad();
+            po.axis_lo = number(v.substr(0, first));
+            po.axis_hi = number(v.substr(first + 1u, second == std::string::npos ? second : second - first - 1u));
+            po.axis_step = second == std::string::npos ? 0.25f : number(v.substr(second + 1u));
+            po.find_axis = true;
+        }
+
+        inline auto parse_axis_rows(const std::string& v, program_options& po) -> void
+        {
+            if(v.empty() || v.size() > 9u || v.find_first_not_of("0123456789") != std::string::npos)
+                throw stage_construction_error{"--axis-rows R: cannot read '" + v + "'"};
+            po.axis_rows = static_cast<std::uint32_t>(std::stoul(v));
+            po.axis_rows_given = true;
+        }
+
+        // --find-axis: the candidates, the scan and the setting are checked for this detector here, before any device work. The
+        // search needs a full, equidistant circle: it is refused with --short-scan, with an angle file, and for frames (after the
+        // quality stride) whose count times their angle step differs from 360 degrees by more than half a step
+        inline auto check_axis(program_options& po) -> void
+        {
+            if(!po.find_axis)
+            {
+                if(po.axis_only || po.axis_rows_given)
+                    throw stage_construction_error{"--axis-rows and --axis-only need --find-axis"};
+                return;
+            }
+            if(po.short_scan)
+                throw stage_construction_error{"--find-axis needs a full circle: it cannot be combined with --short-scan"};
+            if(po.enable_angles)
+                throw stage_construction_error{"--find-axis needs equidistant projections: it cannot be combined with an angle file (--angles)"};
+            const double span = static_cast<double>(po.axis_hi) - static_cast<double>(po.axis_lo);
+            if(!std::isfinite(po.axis_lo) || !std::isfinite(po.axis_hi) || !std::isfinite(po.axis_step) || !(po.axis_step > 0.f) || !(span >= 0.0)
+               || span / static_cast<double>(po.axis_step) > 1023.0)
+                throw stage_construction_error{"--find-axis LO:HI[:STEP]: LO <= HI and STEP > 0, all finite, and at most 1024 candidates (got "
+                                               + std::to_string(po.axis_lo) + ":" + std::to_string(po.axis_hi) + ":" + std::to_string(po.axis_step) + ")"};
+            po.axis_count = static_cast<std::uint32_t>(std::floor(span / static_cast<double>(po.axis_step) + 0.5)) + 1u;
+            const auto a = frame_angles(po.input_path, false, po.angle_path, po.quality, po.det_geo.delta_phi);
+            const double step = a.size() >= 2u ? static_cast<double>(a[1]) - static_cast<double>(a[0]) : 0.0;
+            if(a.size() < 4u || !(step > 0.0) || std::abs(static_cast<double>(a.size()) * step - 360.0) > 0.5 * step)
+            {
+                char msg[256];
+                std::snprintf(msg, sizeof msg, "--find-axis needs a full circle of at least 4 projections at a positive angle step: %zu projection(s) "
+                              "%.6g degrees apart cover %.6g degrees", a.size(), step, static_cast<double>(a.size()) * step);
+                throw stage_construction_error{msg};
+            }
+            po.axis_frames = static_cast<std::uint32_t>(a.size());
+            const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
+            const int rc = paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, nullptr, nullptr);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--find-axis: the candidates times the detector's columns, or the sinogram, exceed 2^32 - 1 entries"};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--find-axis / --axis-rows: R must lie in 1 .. 64 and within the detector's " + std::to_string(po.det_geo.n_col)
+                                               + " rows, and the geometry needs a positive pixel size and source distance (got R = "
+                                               + std::to_string(po.axis_rows) + ")"};
         }
 
         inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
@@ -1638,6 +1778,26 @@ namespace paris
         detail::check_extend_rows(po);
         detail::check_rings(po);
         detail::check_voxels(po);
+        detail::check_axis(po);
+        if(po.find_axis)
+        {
+            // before anything is derived from delta_s: the offset-detector check, the short-scan check and the volume geometry below
+            // are those of the found axis. The pre-pass sizes its groups as the run will (the slot frames do not depend on delta_s).
+            int n_pre = 0;
+            detail::rt(paris_hip_device_count(&n_pre), "get_devices()");
+            if(n_pre == 0)
+                throw stage_construction_error{"no HIP device"};
+            auto pre = detail::fit_batch(po, po.devices > 0 && po.devices < n_pre ? po.devices : n_pre);
+            detail::prepass(pre, r, po.rings, true);
+            po.ring_c = pre.ring_c;
+            r.axis_given = po.det_geo.delta_s;
+            po.det_geo.delta_s = r.axis.delta_s;
+            if(po.axis_only)
+            {
+                r.wall_s = detail::since(start);
+                return r;
+            }
+        }
         if(po.offset_detector)
             detail::check_offset_detector(po);
         if(po.short_scan)
@@ -1658,8 +1818,8 @@ namespace paris
                                            + " devices would be used)"};
         po = detail::fit_batch(po, n_dev);
         r.batch = po.batch;
-        if(po.rings) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
-            detail::ring_prepass(po, r);
+        if(po.rings && !po.find_axis) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
+            detail::prepass(po, r, true, false);
 
         if(po.slabs > 0) // fixed split (src/cuda/subvolume_information.cpp:112-116 with a given count)
         {

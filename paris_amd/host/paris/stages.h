@@ -54,6 +54,15 @@ namespace paris
         backend::ring_profile_add(p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y);
     }
 
+    // the axis search's pre-pass over one loaded frame, between backend::axis_search_begin() and backend::axis_search_finish(): the
+    // frame goes through the same chain and its mid-plane band becomes row `frame` of the sinogram. A frame that also feeds the ring
+    // profile goes through ring_profile_add() first and then straight to backend::axis_search_add(): the chain runs once.
+    inline auto axis_search_add(backend::projection_device_type& p, std::uint32_t frame) -> void
+    {
+        detail::line_integrals(p, "axis_search_add()");
+        backend::axis_search_add(p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y, frame);
+    }
+
     // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with a defect map
     // (backend::set_defect_map) the repair of the defective pixels, then with a zinger filter (backend::set_zinger_filter) the removal
     // of the frame's outlier pixels, then with a ring correction (backend::set_ring_correction) the subtraction of the detector's
