@@ -863,6 +863,83 @@ int paris_hip_clear_binning(paris_hip_ctx* ctx);
 int paris_hip_bin_frames(paris_hip_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
                          size_t dst_frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y, uint32_t row_first,
                          uint32_t row_count);
+/* Extension (no reference counterpart): normalisation of every frame to an air region -- the flat is taken once, but the source's
+ * output drifts from frame to frame; a frame taken at (1 + e) of the flat's flux comes out of the dark / flat correction as
+ * p - ln(1 + e), a constant over the frame, which FDK turns into shading and streaks. A rectangle of the
+ * detector that sees only air in every view measures that constant: its mean line integral is subtracted from the whole frame.
+ * One definition; the device (paris_hip_air_normalize_rows, paris_hip_air_measure) and the host (paris_hip_air_value_host) both
+ * implement it and give the same bits.
+ * Setting paris_hip_air_region { uint32_t x0, y0, width, height; uint32_t min_pixels; float limit_abs; }.
+ *   The rectangle is columns [x0, x0 + width) and rows [y0, y0 + height) of the dim_x x dim_y frame as the reconstruction sees it
+ *   (the binned frame with binning). width, height >= 1, the rectangle lies inside the frame, width * height <= 2^20.
+ *   min_pixels = 0 stands for (width * height + 1) / 2; otherwise 1 <= min_pixels <= width * height.
+ *   limit_abs is finite and >= 0; 0 means no limit.
+ * Mask (optional, given with the setting): dim_y rows of dim_x bytes in the defect map's format, nonzero = bad. Only the rectangle's
+ *   bytes are kept.
+ * A pixel of the rectangle COUNTS iff its mask byte is 0 and its value is finite.
+ * Value of frame f, with 256 partial sums:
+ *   for l in 0 .. 255, c = l mod 64, r = l div 64: acc_l = +0.0 in DOUBLE, n_l = 0;
+ *   for y = y0 + r, y0 + r + 4, ... ascending, and within a row x = x0 + c, x0 + c + 64, ... ascending: if the pixel counts,
+ *   acc_l += (double)p and n_l += 1;
+ *   S = ((acc_0 + acc_1) + acc_2) + ..., ascending l, in double; n = sum of the n_l.
+ *   n < min_pixels: a_f = +0, the frame is counted as too_few.
+ *   Otherwise a_f = (float)(S / (double)n), rounded once.
+ *   limit_abs != 0 and |a_f| > limit_abs: a_f = +0, the frame is counted as above_limit -- the object has entered the rectangle,
+ *   which is a wrong setting, not drift.
+ * Apply. Every pixel of rows [row_first, row_first + row_count) of frame f becomes p - a_f, one fp32 subtraction. A frame whose a_f
+ *   is zero of either sign is NOT WRITTEN at all: its bits stay, NaN payloads included.
+ * Order. The pass runs on line integrals, directly after the dark / flat correction and before the defect repair, the zinger filter,
+ *   the ring profile and correction, the axis search and every weight. It reads the rectangle's rows of each frame and writes the
+ *   band's rows: the caller guarantees that the rectangle's rows hold corrected pixels. The value is read before anything is written,
+ *   also when the rectangle lies inside the band. The pass is not idempotent in bits: a second call finds a value near 0.
+ * Limits: one rectangle; a mean, so a zinger inside the rectangle shifts a_f by its value / n; no smoothing of a_f over the scan. */
+typedef struct paris_hip_air_region {
+    uint32_t x0, y0;        /* the rectangle's first column and row */
+    uint32_t width, height; /* >= 1 each, width * height <= 2^20 */
+    uint32_t min_pixels;    /* a frame with fewer counting pixels is not normalised; 0 = (width * height + 1) / 2 */
+    float limit_abs;        /* a frame whose |a_f| is larger is not normalised; 0 = no limit */
+} paris_hip_air_region;
+/* what paris_hip_air_stats reports */
+typedef struct paris_hip_air_counts {
+    uint64_t frames;      /* frames the normalise calls measured (per call: each frame of a non-empty band) */
+    uint64_t normalised;  /* of those, frames whose a_f was kept (it may still be zero) */
+    uint64_t too_few;     /* frames with fewer than min_pixels counting pixels */
+    uint64_t above_limit; /* frames whose |a_f| exceeded limit_abs */
+    float min_a, max_a;   /* the smallest and the largest a_f over the normalised frames; +inf / -inf without one */
+} paris_hip_air_counts;
+/* one launch pair serves at most this many frames; calls with more loop */
+#define PARIS_HIP_AIR_FRAMES_MAX 64
+/* Host only, no ctx and no device: checks a setting for a dim_x x dim_y frame, resolves the default min_pixels (may be NULL) and
+ * reports what the setting occupies on the device while set (may be NULL): the rectangle's mask bytes, the values and counts of one
+ * launch and the counters. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a zero dimension or anything the rule excludes. */
+int paris_hip_air_region_check(const paris_hip_air_region* setting, uint32_t dim_x, uint32_t dim_y, uint32_t* min_pixels,
+                               size_t* device_bytes);
+/* Host only: the rule on a dense frame (dim_y rows of dim_x floats; mask as above or NULL) -- the second implementation of the one
+ * definition. *a is the value after the too_few / above_limit rule, *n the count (either may be NULL).
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL frame. */
+int paris_hip_air_value_host(const paris_hip_air_region* setting, const uint8_t* mask, const float* frame, uint32_t dim_x, uint32_t dim_y,
+                             float* a, uint32_t* n);
+/* paris_hip_set_air_region runs the check and keeps the setting for dim_x x dim_y frames; the rectangle's mask bytes (zeros for a
+ * NULL mask), the per-launch values and the counters live in memory the ctx owns, replacing an earlier setting (and its counts); the
+ * old memory is freed once the work queued before the call no longer uses it. It counts towards paris_hip_projection_reserve_bytes
+ * while set; paris_hip_ctx_destroy frees it. Without a setting nothing else changes. */
+int paris_hip_set_air_region(paris_hip_ctx* ctx, const paris_hip_air_region* setting, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_air_region(paris_hip_ctx* ctx);
+/* In place on float frames, asynchronous: per launch pair of up to PARIS_HIP_AIR_FRAMES_MAX frames, a_f of every frame is measured
+ * from the rectangle, then rows [row_first, row_first + row_count) of every frame with a_f != 0 become p - a_f (n_frames frames
+ * frame_stride bytes apart, d_p the first frame's row 0). A band of zero rows does nothing. 16-byte vectors are used for the
+ * subtraction where the base, the pitch, the stride (n_frames > 1) and dim_x allow, single pixels otherwise. The rectangle's rows
+ * are noted as used beside the band's, so a later upload into either waits. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when
+ * dim_x / dim_y differ from the setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_air_normalize_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* Synchronous: the same reduction, nothing written to the frames and nothing added to the counters; h_a and h_n (either may be NULL)
+ * receive n_frames values (after the too_few / above_limit rule) and counts. Refusals as paris_hip_air_normalize_rows. */
+int paris_hip_air_measure(paris_hip_ctx* ctx, const float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                          uint32_t dim_y, float* h_a, uint32_t* h_n);
+/* The counts of the normalise calls since the setting was made or last reset: runs what is pending, waits for the ctx stream and
+ * reads them; reset != 0 zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
+int paris_hip_air_stats(paris_hip_ctx* ctx, paris_hip_air_counts* out, int reset);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

@@ -116,6 +116,21 @@ class AxisResult(C.Structure):
 AXIS_FRAMES_MAX = 64  # PARIS_HIP_AXIS_FRAMES_MAX
 
 
+class AirRegion(C.Structure):
+    """paris_hip_air_region: the rectangle of the detector that sees only air, and when a frame is not normalised (extension)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("min_pixels", C.c_uint32),
+                ("limit_abs", C.c_float)]
+
+
+class AirCounts(C.Structure):
+    """paris_hip_air_counts: what paris_hip_air_stats reports (extension)"""
+    _fields_ = [("frames", C.c_uint64), ("normalised", C.c_uint64), ("too_few", C.c_uint64), ("above_limit", C.c_uint64),
+                ("min_a", C.c_float), ("max_a", C.c_float)]
+
+
+AIR_FRAMES_MAX = 64  # PARIS_HIP_AIR_FRAMES_MAX
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -214,6 +229,13 @@ SIGNATURES = {
     "paris_hip_set_binning": (C.c_int, [_vp, _P(Binning), _vp, _u32, _u32]),
     "paris_hip_clear_binning": (C.c_int, [_vp]),
     "paris_hip_bin_frames": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_air_region_check": (C.c_int, [_P(AirRegion), _u32, _u32, _P(_u32), _P(_sz)]),
+    "paris_hip_air_value_host": (C.c_int, [_P(AirRegion), _vp, _vp, _u32, _u32, _P(_f), _P(_u32)]),
+    "paris_hip_set_air_region": (C.c_int, [_vp, _P(AirRegion), _vp, _u32, _u32]),
+    "paris_hip_clear_air_region": (C.c_int, [_vp]),
+    "paris_hip_air_normalize_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_air_measure": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _vp, _vp]),
+    "paris_hip_air_stats": (C.c_int, [_vp, _P(AirCounts), C.c_int]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -23,7 +23,7 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
            "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean", "VolumeWindow", "VolumeCounts",
            "VolumeStatistics", "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
-           "binned_geometry", "bin_frame_host", "bin_mask"]
+           "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host"]
 
 
 class Projection:
@@ -244,6 +244,35 @@ def bin_mask(bin_x, bin_y, mask):
     bn, out = Binning(bin_x, bin_y), np.empty((oy, ox), np.uint8)
     check(_lib.load().paris_hip_bin_mask(C.byref(bn), m.ctypes.data, m.shape[1], m.shape[0], out.ctypes.data), "paris_hip_bin_mask")
     return out
+
+
+def _air_setting(x0, y0, width, height, min_pixels=0, limit_abs=0.0):
+    return AirRegion(x0, y0, width, height, min_pixels, limit_abs)
+
+
+def air_region_check(x0, y0, width, height, dim_x, dim_y, min_pixels=0, limit_abs=0.0):
+    """Host only, no device (paris_hip_air_region_check): checks an air region -- columns [x0, x0 + width), rows [y0, y0 + height) of a
+    dim_x x dim_y frame, at most 2^20 pixels; min_pixels 0 = half of them, rounded up; limit_abs 0 = no limit -- and returns
+    (min_pixels resolved, device_bytes). Raises ParisHipError for a setting the library refuses."""
+    ar, least, nbytes = _air_setting(x0, y0, width, height, min_pixels, limit_abs), C.c_uint32(0), C.c_size_t(0)
+    check(_lib.load().paris_hip_air_region_check(C.byref(ar), dim_x, dim_y, C.byref(least), C.byref(nbytes)), "paris_hip_air_region_check")
+    return least.value, nbytes.value
+
+
+def air_value_host(x0, y0, width, height, frame, mask=None, min_pixels=0, limit_abs=0.0):
+    """Host only, no device (paris_hip_air_value_host): the air rule on a 2-D array of the detector's size (n_col, n_row), taken as
+    float32 -- the mean of the rectangle's counting pixels (mask byte 0, value finite), summed in double through 256 partial sums in
+    the order DESIGN.md section 4.16 fixes, +0 with fewer than min_pixels of them or beyond limit_abs. Returns (a as np.float32, n)."""
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.ndim != 2:
+        raise ValueError("air_value_host: the frame must be a 2-D array (n_col, n_row)")
+    m = None if mask is None else _mask_bytes(mask, "air_value_host")
+    if m is not None and m.shape != f.shape:
+        raise ValueError("air_value_host: frame and mask differ in shape")
+    ar, a, n = _air_setting(x0, y0, width, height, min_pixels, limit_abs), C.c_float(0.0), C.c_uint32(0)
+    check(_lib.load().paris_hip_air_value_host(C.byref(ar), None if m is None else m.ctypes.data, f.ctypes.data, f.shape[1], f.shape[0],
+                                               C.byref(a), C.byref(n)), "paris_hip_air_value_host")
+    return np.float32(a.value), n.value
 
 
 def row_extension_check(edge_pixels, taper_pixels, dim_x):
@@ -747,6 +776,51 @@ class Backend:
         count = dst.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_bin_frames(self._ctx, src.ptr, src.pitch, src_frame_stride, dst.ptr, dst.pitch, dst_frame_stride, n_frames,
                                            src.dim_x, src.dim_y, row_first, count), "paris_hip_bin_frames")
+
+    # ---- air region --------------------------------------------------------------
+    air_region_check = staticmethod(air_region_check)
+    air_value_host = staticmethod(air_value_host)
+
+    def set_air_region(self, x0, y0, width, height, dim_x, dim_y, min_pixels=0, limit_abs=0.0, mask=None):
+        """paris_hip_set_air_region for dim_x x dim_y frames: air_normalize() then subtracts from every frame the mean line integral
+        of the rectangle columns [x0, x0 + width), rows [y0, y0 + height) -- the frame's flux drift against the flat. mask: a 2-D
+        array of the detector's size (n_col, n_row), nonzero = bad; None = every pixel good. Replaces an earlier setting and its
+        counts safely: work already queued keeps the old one."""
+        m = None if mask is None else _mask_bytes(mask, "set_air_region")
+        if m is not None and m.shape != (dim_y, dim_x):
+            raise ValueError("set_air_region: the mask must have the detector's size (n_col, n_row)")
+        ar = _air_setting(x0, y0, width, height, min_pixels, limit_abs)
+        check(self._L.paris_hip_set_air_region(self._ctx, C.byref(ar), None if m is None else m.ctypes.data, dim_x, dim_y),
+              "paris_hip_set_air_region")
+
+    def clear_air_region(self):
+        """paris_hip_clear_air_region: no air region from here on"""
+        check(self._L.paris_hip_clear_air_region(self._ctx), "paris_hip_clear_air_region")
+
+    def air_normalize(self, p, frame_stride=0, n_frames=1, rows=None):
+        """The rule of set_air_region() in place on float frames (paris_hip_air_normalize_rows): every frame's value a_f is measured
+        from the rectangle, then rows (first, count) -- None: every row -- of the n_frames frames frame_stride bytes apart starting at
+        p become p - a_f; a frame whose a_f is zero keeps its bits. The rectangle's rows must hold corrected pixels. Call it on line
+        integrals, directly after the dark / flat correction and before the defect repair."""
+        first, count = (0, p.dim_y) if rows is None else rows
+        check(self._L.paris_hip_air_normalize_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, first, count),
+              "paris_hip_air_normalize_rows")
+
+    def air_measure(self, p, frame_stride=0, n_frames=1):
+        """paris_hip_air_measure: the values air_normalize() would subtract, and the counting pixels, of n_frames frames frame_stride
+        bytes apart starting at p -- (float32[n_frames], uint32[n_frames]). Nothing is written to the frames or added to the
+        counts. Waits for the ctx stream."""
+        a, n = np.empty(n_frames, np.float32), np.empty(n_frames, np.uint32)
+        check(self._L.paris_hip_air_measure(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, a.ctypes.data, n.ctypes.data),
+              "paris_hip_air_measure")
+        return a, n
+
+    def air_stats(self, reset=False):
+        """The AirCounts of the air_normalize() calls since set_air_region() or the last reset (paris_hip_air_stats): frames,
+        normalised, too_few, above_limit, min_a, max_a. Waits for the ctx stream."""
+        st = AirCounts()
+        check(self._L.paris_hip_air_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_air_stats")
+        return st
 
     # ---- row extension (DESIGN.md section 4.11) -----------------------------------------------------------
     row_extension_check = staticmethod(row_extension_check)

@@ -187,6 +187,18 @@ struct paris_hip_ctx
         uint8_t* d_mask = nullptr;
         uint32_t dim_x = 0, dim_y = 0, out_x = 0, out_y = 0;
     } binning;
+    // Air region (paris_hip_set_air_region): the rule with min_pixels resolved, and one device buffer laid
+    // out by paris_hip_air_layout_of -- the counters, the values and counts of one launch, the rectangle's mask bytes -- read and
+    // written by the kernels of air_region.hip (and the copies of measure and stats) on the compute stream only, so it is replaced,
+    // retired and freed as the zinger filter's scratch is.
+    struct air_t
+    {
+        bool set = false;
+        paris_hip_air_region rule{};
+        uint32_t dim_x = 0, dim_y = 0;
+        size_t device_bytes = 0;
+        char* d_mem = nullptr;
+    } air;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -466,6 +478,7 @@ void paris_hip_warm_ring();
 void paris_hip_warm_volume_window();
 void paris_hip_warm_binning();
 void paris_hip_warm_axis_search();
+void paris_hip_warm_air_region();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -499,7 +512,26 @@ void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
 // axis_search.hip: the same for an open axis search
 void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying);
+// air_region.hip: the same for the air region's memory
+void paris_hip_air_region_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility pop
+
+// Where the pieces of an air region's one allocation lie (air_region.hip); air_rule.cpp reports the total. The counters: four 64-bit
+// counts (frames, normalised, too_few, above_limit), then the smallest and the largest value as ordered 32-bit keys, padded to 64 bytes.
+constexpr size_t PARIS_HIP_AIR_COUNTER_BYTES = 64u;
+struct paris_hip_air_layout
+{
+    size_t value, count, mask, bytes; // byte offsets of the launch's values, its counts and the mask; the whole size
+};
+inline paris_hip_air_layout paris_hip_air_layout_of(uint32_t width, uint32_t height)
+{
+    paris_hip_air_layout l{};
+    l.value = PARIS_HIP_AIR_COUNTER_BYTES;
+    l.count = l.value + PARIS_HIP_AIR_FRAMES_MAX * sizeof(float);
+    l.mask = l.count + PARIS_HIP_AIR_FRAMES_MAX * sizeof(uint32_t);
+    l.bytes = l.mask + ((static_cast<size_t>(width) * height + 15u) & ~static_cast<size_t>(15u));
+    return l;
+}
 
 // Where the pieces of an open axis search lie in its one allocation (axis_search.hip), each 256-byte aligned; axis_rule.cpp reports
 // the total. The score kernel's grid: a workgroup takes one candidate, PARIS_HIP_AXIS_TILE_COLUMNS columns (one per lane) and

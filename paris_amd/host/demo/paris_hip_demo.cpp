@@ -7,7 +7,7 @@
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
 //                       [--rings half_width floor limit] [--find-axis lo step count rows]
-//                       [--extend-rows W M] [--bin BX BY mask.raw|none]
+//                       [--extend-rows W M] [--bin BX BY mask.raw|none] [--air-region x0 y0 width height limit]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -20,6 +20,9 @@
 // set_flat_field() before the loops, so that paris::weight() turns each frame into line integrals first.
 // --defects: mask.raw holds n_col x n_row bytes, nonzero = defective pixel. set_defect_map() before the loops, so that paris::weight()
 // repairs each frame's defective pixels after the dark / flat correction and before the weights.
+// --air-region: the rectangle of the (binned) frame that sees only air, and limit_abs (0: none). set_air_region() before the loops, with the
+// mask of --defects if there is one, so that paris::weight() subtracts each frame's own flux drift after the dark / flat correction and
+// before the repair; the counts of air_stats() are printed as "air: ..." after the loops.
 // --zingers: threshold_abs, threshold_rel and the polarity (1 bright, -1 dark, 0 both) of the zinger rule. set_zinger_filter() before the
 // loops, so that paris::weight() removes each frame's outlier pixels after the repair and before the weights.
 // --rings: half_width, floor_abs and limit_abs of the ring rule. A pre-pass before the loops sums every frame (ring_profile_add()) and
@@ -94,6 +97,9 @@ int main(int argc, char** argv)
         bool zingers = false;
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 1;
+        bool air = false;
+        std::uint32_t air_rect[4] = {0, 0, 0, 0};
+        float air_limit = 0.f;
         bool rings = false;
         std::uint32_t ring_half_width = 0;
         float ring_floor = 0.f, ring_limit = 0.f;
@@ -144,6 +150,14 @@ int main(int argc, char** argv)
                 zinger_rel = std::strtof(argv[a + 2], nullptr);
                 zinger_polarity = std::atoi(argv[a + 3]);
                 a += 3;
+            }
+            else if(!std::strcmp(argv[a], "--air-region") && a + 5 < argc)
+            {
+                air = true;
+                for(int k = 0; k < 4; ++k)
+                    air_rect[k] = static_cast<std::uint32_t>(std::strtoul(argv[a + 1 + k], nullptr, 10));
+                air_limit = std::strtof(argv[a + 5], nullptr);
+                a += 5;
             }
             else if(!std::strcmp(argv[a], "--rings") && a + 3 < argc)
             {
@@ -246,10 +260,12 @@ int main(int argc, char** argv)
             const auto dark = dark_path == "none" ? std::vector<float>{} : read_frame(dark_path);
             paris::backend::set_flat_field(dark.empty() ? nullptr : dark.data(), flat.data(), det.n_row, det.n_col, t_min);
         }
+        auto defect_mask = std::vector<std::uint8_t>{}; // --defects: the air region leaves its pixels out as well
         if(!defects_path.empty())
         {
             const auto n = std::size_t{det.n_row} * det.n_col;
-            auto mask = std::vector<std::uint8_t>(n);
+            auto& mask = defect_mask;
+            mask.resize(n);
             std::FILE* f = std::fopen(defects_path.c_str(), "rb");
             const bool ok = f != nullptr && std::fread(mask.data(), 1u, n, f) == n;
             if(f != nullptr)
@@ -258,6 +274,9 @@ int main(int argc, char** argv)
                 throw paris::stage_construction_error{"cannot read " + defects_path};
             paris::backend::set_defect_map(mask.data(), det.n_row, det.n_col);
         }
+        if(air)
+            paris::backend::set_air_region(air_rect[0], air_rect[1], air_rect[2], air_rect[3], det.n_row, det.n_col, 0u, air_limit,
+                                           defect_mask.empty() ? nullptr : defect_mask.data());
         if(binning)
         {
             const auto n = std::size_t{src_det.n_row} * src_det.n_col;
@@ -428,6 +447,13 @@ int main(int argc, char** argv)
             if(f == nullptr || std::fwrite(reprojected.data(), sizeof(float), reprojected.size(), f) != reprojected.size())
                 throw paris::stage_runtime_error{"cannot write " + reproject_path};
             std::fclose(f);
+        }
+        if(air)
+        {
+            const auto c = paris::backend::air_stats();
+            std::printf("air: %llu frames, %llu normalised, %llu too few, %llu above the limit, values %.9g .. %.9g\n",
+                        static_cast<unsigned long long>(c.frames), static_cast<unsigned long long>(c.normalised), static_cast<unsigned long long>(c.too_few),
+                        static_cast<unsigned long long>(c.above_limit), static_cast<double>(c.min_a), static_cast<double>(c.max_a));
         }
         std::printf("ok %u %u %u\n", roi_geo.dim_x, roi_geo.dim_y, roi_geo.dim_z);
         std::printf("projection loops %.3f s: %.1f GVoxel-updates/s through paris::load / weight / filter / backproject (deferral depth %d, %s)\n", loop_s,

@@ -8,7 +8,7 @@
 //             [--window ramp|shepp-logan] [--short-scan] [--offset-detector] [--flat file.his [--dark file.his] [--min-transmission t]]
 //             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
 //             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]
-//             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]]
+//             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -85,7 +85,7 @@ int main(int argc, char** argv)
                             "          [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]]\n"
                             "          [--rings H[:FLOOR[:LIMIT]]]\n"
                             "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]\n"
-                            "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]]\n"
+                            "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -121,7 +121,13 @@ int main(int argc, char** argv)
                             "R rows (--axis-rows, 1 .. 64, default 2) about the mid-plane are summed into a sinogram, and each candidate LO,\n"
                             "LO + STEP .. HI [pixels; binned pixels with --bin; STEP defaults to 0.25, at most 1024 candidates] is scored on the\n"
                             "device by the mean squared difference between every sample and its conjugate ray half a turn away. The estimate is\n"
-                            "the minimum of a parabola through the best candidate and its neighbours. --axis-only prints it and stops.\n");
+                            "the minimum of a parabola through the best candidate and its neighbours. --axis-only prints it and stops.\n"
+                            "--air-region: the source's output drifts from frame to frame while the flat was taken once. Columns X0 .. X0 + W - 1,\n"
+                            "rows Y0 .. Y0 + H - 1 of the frame [binned pixels with --bin; at most 2^20 pixels] see only air in every view: the\n"
+                            "mean line integral of the rectangle's pixels (those --defects marks and values that are not finite left out) is\n"
+                            "subtracted from the whole frame on the device, directly after the correction and before the repair. A frame with\n"
+                            "fewer than half the rectangle's pixels left, or whose mean exceeds LIMIT in size (0, the default: no limit), stays\n"
+                            "as it is and is counted.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -155,6 +161,7 @@ int main(int argc, char** argv)
             else if(k == "--find-axis") paris::detail::parse_find_axis(val(), po);
             else if(k == "--axis-rows") paris::detail::parse_axis_rows(val(), po);
             else if(k == "--axis-only") po.axis_only = true;
+            else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -198,6 +205,23 @@ int main(int argc, char** argv)
         if(r.defect_map)
             std::printf("defect map on: %llu defective pixel(s), %llu unrepairable (no good pixel within %d)\n",
                         static_cast<unsigned long long>(r.defects.defects), static_cast<unsigned long long>(r.defects.unrepairable), PARIS_HIP_DEFECT_R_MAX);
+        const auto air_line = [&](const char* where, const paris_hip_air_counts& c) {
+            std::printf("air region %s: columns %u .. %u, rows %u .. %u of the %u x %u frame, %llu frame band(s) measured, %llu normalised, "
+                        "%llu with too few pixels, %llu above the limit", where, po.air_region.x0, po.air_region.x0 + po.air_region.width - 1u,
+                        po.air_region.y0, po.air_region.y0 + po.air_region.height - 1u, r.air_row, r.air_col,
+                        static_cast<unsigned long long>(c.frames), static_cast<unsigned long long>(c.normalised),
+                        static_cast<unsigned long long>(c.too_few), static_cast<unsigned long long>(c.above_limit));
+            if(c.normalised != 0u)
+                std::printf(", values %.6g .. %.6g", static_cast<double>(c.min_a), static_cast<double>(c.max_a));
+            std::printf("\n");
+            if(c.normalised != c.frames)
+                std::printf("warning: %llu frame band(s) were not normalised %s: the air region holds too few good pixels, or the object reaches into it\n",
+                            static_cast<unsigned long long>(c.frames - c.normalised), where);
+        };
+        if(po.air && (r.ring_filter || r.axis_search))
+            air_line("in the pre-pass", r.air_prepass);
+        if(r.air_region)
+            air_line("on", r.air);
         if(r.row_extension)
             std::printf("row extension on: cos^2 taper of %u pixel(s), mean of %u edge pixel(s)\n", po.extend_taper, po.extend_edge);
         if(r.zinger_filter)

@@ -130,6 +130,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> defect_maps; // set_defect_map(), per device of this thread
                 std::set<const paris_hip_ctx*> zinger_filters; // set_zinger_filter(), per device of this thread
                 std::set<const paris_hip_ctx*> ring_corrections; // set_ring_correction(), per device of this thread
+                std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -279,6 +280,45 @@ namespace paris
             inline auto has_flat_field(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().flat_fields;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the source's output drifts from frame to frame while the flat was taken once, and
+        // the rectangle columns [x0, x0 + width), rows [y0, y0 + height) of this thread's current device's frames (n_row x n_col
+        // pixels) sees only air in every view. Until clear_air_region(), paris::weight() subtracts from every
+        // frame the mean line integral of the rectangle's counting pixels -- mask byte 0 (mask: n_col rows of n_row bytes, nonzero =
+        // bad, or nullptr) and a finite value -- directly after the dark / flat correction and before the defect repair
+        // (paris_hip_air_normalize_rows). A frame with fewer than min_pixels (0 = half the rectangle) of them, or whose value exceeds
+        // limit_abs (0 = no limit), stays as it is; air_stats() counts both.
+        inline auto set_air_region(std::uint32_t x0, std::uint32_t y0, std::uint32_t width, std::uint32_t height, std::uint32_t n_row,
+                                   std::uint32_t n_col, std::uint32_t min_pixels = 0u, float limit_abs = 0.f,
+                                   const std::uint8_t* mask = nullptr) -> void
+        {
+            const auto setting = paris_hip_air_region{x0, y0, width, height, min_pixels, limit_abs};
+            detail::runtime_check(paris_hip_set_air_region(current_ctx(), &setting, mask, n_row, n_col), "set_air_region()");
+            detail::state().air_regions.insert(current_ctx());
+        }
+
+        inline auto clear_air_region() -> void
+        {
+            detail::runtime_check(paris_hip_clear_air_region(current_ctx()), "clear_air_region()");
+            detail::state().air_regions.erase(current_ctx());
+        }
+
+        // what paris::weight() has counted since set_air_region() or the last reset; waits for the device
+        inline auto air_stats(bool reset = false) -> paris_hip_air_counts
+        {
+            auto out = paris_hip_air_counts{};
+            detail::runtime_check(paris_hip_air_stats(current_ctx(), &out, reset ? 1 : 0), "air_stats()");
+            return out;
+        }
+
+        namespace detail
+        {
+            inline auto has_air_region(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().air_regions;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

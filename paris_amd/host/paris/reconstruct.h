@@ -118,6 +118,13 @@ namespace paris
         float zinger_abs = 0.f, zinger_rel = 0.f;
         int zinger_polarity = 2;      // +1 bright, -1 dark, 0 both; 2: the default, resolved by run()
         std::size_t zinger_bytes = 0; // filled by run(): what the setting occupies on a device
+        // normalisation of every frame to an air region (extension): --air-region X0:Y0:W:H[:LIMIT], a rectangle
+        // of the frame the reconstruction sees (the binned frame with --bin) that sees only air in every view, checked by run()
+        // before any device work (detail::check_air_region). Every device ctx gets the setting, with the defect map's mask if there
+        // is one, and each frame has the rectangle's mean line integral subtracted directly after the correction
+        bool air = false;
+        paris_hip_air_region air_region{};
+        std::size_t air_bytes = 0; // filled by run(): what the setting occupies on a device
         // removal of ring artefacts (extension): --rings H[:FLOOR[:LIMIT]], checked by run() before any device
         // work (detail::check_rings). run() then reads the scan once on the first device (detail::ring_prepass): every frame goes
         // through the chain the reconstruction uses -- correction, repair, zinger filter -- into the profile, and the rule's correction
@@ -275,6 +282,8 @@ namespace paris
         paris_hip_defect_stats defects{};
         bool zinger_filter = false; // --zingers: a zinger filter was set; its counts over this device's tasks:
         paris_hip_zinger_counts zingers{};
+        bool air_region = false; // --air-region: the setting was made; its counts over this device's tasks:
+        paris_hip_air_counts air{};
         bool row_extension = false; // --extend-rows: the setting was made on this device's ctx
         paris_hip_volume_counts voxels{}; // --voxel-type: the counts of this device's drain ctx
         std::vector<std::string> skipped;
@@ -307,7 +316,7 @@ namespace paris
         inline double since(clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); }
 
         // the settings of the frame chain in front of the weights, the same for every device ctx of a run: --bin, --flat / --dark,
-        // --defects / --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
+        // --air-region, --defects / --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
         inline void set_frame_chain(paris_hip_ctx* ctx, const program_options& po, device_report& rep)
         {
             if(po.binning()) // --bin: the source detector's setting; everything below is at binned size
@@ -318,10 +327,11 @@ namespace paris
             if(po.flat)
                 rt(paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row, po.det_geo.n_col,
                                             po.t_min), "set_flat_field()");
+            auto mask = std::vector<std::uint8_t>{}; // the defect map's, which the air region leaves out as well
             if(po.defect_mask || po.defects_from_flat)
             {
                 const auto n_px = static_cast<std::size_t>(po.det_geo.n_row) * po.det_geo.n_col;
-                auto mask = po.defect_mask ? *po.defect_mask : std::vector<std::uint8_t>(n_px, 0u);
+                mask = po.defect_mask ? *po.defect_mask : std::vector<std::uint8_t>(n_px, 0u);
                 int rc = PARIS_HIP_SUCCESS;
                 if(po.defects_from_flat)
                 {
@@ -337,12 +347,26 @@ namespace paris
                 rt(rc, "set_defect_map()");
                 rep.defect_map = true;
             }
+            if(po.air)
+            {
+                rt(paris_hip_set_air_region(ctx, &po.air_region, mask.empty() ? nullptr : mask.data(), po.det_geo.n_row, po.det_geo.n_col),
+                   "set_air_region()");
+                rep.air_region = true;
+            }
             if(po.zingers)
             {
                 const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
                 rt(paris_hip_set_zinger_filter(ctx, &setting, po.det_geo.n_row, po.det_geo.n_col), "set_zinger_filter()");
                 rep.zinger_filter = true;
             }
+        }
+
+        // [first, first + count) becomes the smallest range that also holds [y0, y0 + height)
+        inline void hull_rows(std::uint32_t y0, std::uint32_t height, std::uint32_t& first, std::uint32_t& count)
+        {
+            const auto lo = std::min(first, y0), hi = std::max(first + count, y0 + height);
+            first = lo;
+            count = hi - lo;
         }
 
         // frames per group and groups, as reconstruct() lays its slots out
@@ -368,7 +392,7 @@ namespace paris
             // with --bin, every slot's full-width source frame as well, and the source-size mask
             const auto src_row = (static_cast<std::size_t>(po.src_row) * sizeof(float) + 255u) / 256u * 256u;
             const auto binning = po.binning() ? slots * po.src_col * src_row + (po.bin_mask ? po.bin_mask->size() : 0u) : 0u;
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes
+            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -878,12 +902,19 @@ namespace paris
                     first = band_first - std::min(band_first, by);
                     count = std::min(n_col - (band_first + band_count), by) + band_first + band_count - first;
                 };
+                // With --air-region every frame's value comes from the rectangle's rows, whatever the band: the rows read, uploaded and
+                // corrected become ONE range that holds the widened band and the rectangle's rows (the rows between them travel too:
+                // next_raw reads one contiguous range), and the value is subtracted from the widened band (air), the rows the repair
+                // and the zinger filter read. Every slab and every device reads the same rectangle and gets the same value.
                 std::uint32_t up_first = band_first, up_count = band_count, fix_first = band_first, fix_count = band_count;
                 if(band_count != 0)
                 {
                     widened((repair ? reach_rows : 0u) + zinger_rows, up_first, up_count);
                     widened(zinger_rows, fix_first, fix_count);
                 }
+                const std::uint32_t air_first = up_first, air_count = up_count;
+                if(band_count != 0 && po.air)
+                    hull_rows(po.air_region.y0, po.air_region.height, up_first, up_count);
                 // --bin: the source rows the uploaded band is binned from (the band itself without it)
                 const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
 
@@ -907,6 +938,9 @@ namespace paris
                     if(filled == 0)
                         return;
                     const auto t1 = clock::now();
+                    if(filter_by_group && band_count != 0 && po.air) // the frames' own flux drift first, one call for the group
+                        rt(paris_hip_air_normalize_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, air_first, air_count),
+                           "air normalisation");
                     if(filter_by_group && band_count != 0 && repair) // the repair before every weight, one launch for the group
                         rt(paris_hip_defect_repair_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count),
                            "defect repair");
@@ -1005,6 +1039,8 @@ namespace paris
                                                                n_row, up_count, p.pixel), "load()");
                         rep.h2d_bytes += static_cast<std::uint64_t>(src_count) * sn_row * px;
                         angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                        if(po.air && !filter_by_group) // the frame's own flux drift, straight after the correction
+                            rt(paris_hip_air_normalize_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, air_first, air_count), "air normalisation");
                         if(repair && !filter_by_group) // the band's defective pixels, before every weight
                             rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, fix_first, fix_count), "defect repair");
                         if(po.zingers && !filter_by_group) // then the band's outlier pixels
@@ -1058,6 +1094,8 @@ namespace paris
             rep.drain_wait_s += since(t_end);
             if(po.zingers)
                 rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
+            if(po.air)
+                rt(paris_hip_air_stats(ctx, &rep.air, 0), "air stats");
             rep.drain_s = drain->drain_seconds();
             rep.save_s = drain->save_seconds();
             rep.voxels = drain->voxel_counts();
@@ -1086,6 +1124,10 @@ namespace paris
         paris_hip_defect_stats defects{};
         bool zinger_filter = false;                     // --zingers: the filter was on; its counts over all devices and slabs (a
         paris_hip_zinger_counts zingers{};              // frame counts once per slab: each slab filters its own row band)
+        bool air_region = false;                        // --air-region: the setting was on; its counts over all devices and slabs (a
+        paris_hip_air_counts air{};                     // frame counts once per slab), and with --rings / --find-axis the pre-pass's
+        paris_hip_air_counts air_prepass{};
+        std::uint32_t air_row = 0, air_col = 0;         // the frame the rectangle was checked against (binned with --bin)
         bool row_extension = false;                     // --extend-rows: every device filtered with the setting
         bool ring_filter = false;                       // --rings: the pre-pass ran; what the rule did to the scan's mean frame, and
         paris_hip_ring_stats rings{};                   // how long the pre-pass took (reading the scan included)
@@ -1430,6 +1472,56 @@ namespace paris
                                                + ":" + std::to_string(po.voxels.hi) + ")"};
         }
 
+        // --air-region X0:Y0:W:H[:LIMIT] as typed; refuses anything but four unsigned integers and an optional number
+        inline auto parse_air_region(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--air-region X0:Y0:W:H[:LIMIT]: cannot read '" + v + "'"}; };
+            auto parts = std::vector<std::string>{};
+            for(std::size_t at = 0;;)
+            {
+                const auto colon = v.find(':', at);
+                parts.push_back(v.substr(at, colon == std::string::npos ? colon : colon - at));
+                if(colon == std::string::npos)
+                    break;
+                at = colon + 1u;
+            }
+            if(parts.size() != 4u && parts.size() != 5u)
+                throw bad();
+            std::uint32_t field[4] = {0, 0, 0, 0};
+            for(int k = 0; k < 4; ++k)
+            {
+                if(parts[k].empty() || parts[k].size() > 9u || parts[k].find_first_not_of("0123456789") != std::string::npos)
+                    throw bad();
+                field[k] = static_cast<std::uint32_t>(std::stoul(parts[k]));
+            }
+            float limit = 0.f;
+            if(parts.size() == 5u)
+            {
+                char* end = nullptr;
+                limit = std::strtof(parts[4].c_str(), &end);
+                if(parts[4].empty() || end == nullptr || *end != '\0')
+                    throw bad();
+            }
+            po.air_region = paris_hip_air_region{field[0], field[1], field[2], field[3], 0u, limit};
+            po.air = true;
+        }
+
+        // --air-region: the rectangle is checked against the detector the reconstruction sees (binned with --bin) here, before any
+        // device work
+        inline auto check_air_region(program_options& po, run_report& r) -> void
+        {
+            if(!po.air)
+                return;
+            r.air_row = po.det_geo.n_row;
+            r.air_col = po.det_geo.n_col;
+            if(paris_hip_air_region_check(&po.air_region, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.air_bytes) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--air-region X0:Y0:W:H[:LIMIT]: W and H at least 1, the rectangle inside the " + std::to_string(po.det_geo.n_row)
+                                               + " x " + std::to_string(po.det_geo.n_col) + " frame, at most 2^20 pixels, LIMIT finite and not negative (got "
+                                               + std::to_string(po.air_region.x0) + ":" + std::to_string(po.air_region.y0) + ":"
+                                               + std::to_string(po.air_region.width) + ":" + std::to_string(po.air_region.height) + ":"
+                                               + std::to_string(po.air_region.limit_abs) + ")"};
+        }
+
         // --zingers ABS[:REL] as typed; refuses anything that is not one or two numbers
         inline auto parse_zingers(const std::string& v, program_options& po) -> void
         {
@@ -1527,7 +1619,7 @@ namespace paris
         }
 
         // --rings and --find-axis: the pre-pass. Every projection the run uses is read once on the first device and goes through the
-        // chain the reconstruction uses -- the raw upload (corrected with --flat), the defect repair, the zinger filter -- into the ring
+        // chain the reconstruction uses -- the raw upload (corrected with --flat), the air normalisation, the defect repair, the zinger filter -- into the ring
         // profile (rings), into the axis search's sinogram (axis), or into both: a group of po.batch frames per call as the main loop
         // groups them. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by the reach
         // of the repair and of the zinger filter as a slab's band is in reconstruct(). Then the ring rule makes the correction frame,
@@ -1591,6 +1683,9 @@ namespace paris
                 std::uint32_t up_first = 0, up_count = 0, fix_first = 0, fix_count = 0;
                 widened((rep.defect_map ? rep.defects.reach_rows : 0u) + zinger_rows, up_first, up_count);
                 widened(zinger_rows, fix_first, fix_count);
+                const std::uint32_t air_first = up_first, air_count = up_count; // --air-region: as in reconstruct()
+                if(po.air)
+                    hull_rows(po.air_region.y0, po.air_region.height, up_first, up_count);
                 const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
                 if(rings)
                     rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
@@ -1634,6 +1729,8 @@ namespace paris
                         break;
                     if(axis && filled > po.axis_frames - frames)
                         throw stage_runtime_error{"--find-axis: the input holds more frames than were counted"};
+                    if(po.air)
+                        rt(paris_hip_air_normalize_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, air_first, air_count), "air normalisation");
                     if(rep.defect_map)
                         rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count), "defect repair");
                     if(po.zingers)
@@ -1645,6 +1742,8 @@ namespace paris
                     rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
                     frames += filled;
                 }
+                if(po.air)
+                    rt(paris_hip_air_stats(ctx, &r.air_prepass, 0), "air stats");
                 if(rings)
                 {
                     auto c = std::make_shared<std::vector<float>>(static_cast<std::size_t>(n_row) * n_col);
@@ -1774,6 +1873,7 @@ namespace paris
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         detail::load_defects(po);
         detail::apply_binning(po, r); // from here on po.det_geo is the binned detector
+        detail::check_air_region(po, r);
         detail::check_zingers(po);
         detail::check_extend_rows(po);
         detail::check_rings(po);
@@ -1902,6 +2002,13 @@ namespace paris
         {
             r.row_extension = r.row_extension || d.row_extension;
             r.zinger_filter = r.zinger_filter || d.zinger_filter;
+            r.air_region = r.air_region || d.air_region;
+            r.air.frames += d.air.frames;
+            r.air.normalised += d.air.normalised;
+            r.air.too_few += d.air.too_few;
+            r.air.above_limit += d.air.above_limit;
+            r.air.min_a = &d == &r.devices.front() ? d.air.min_a : std::min(r.air.min_a, d.air.min_a);
+            r.air.max_a = &d == &r.devices.front() ? d.air.max_a : std::max(r.air.max_a, d.air.max_a);
             r.zingers.frames += d.zingers.frames;
             r.zingers.replaced += d.zingers.replaced;
             r.zingers.saturated_frames += d.zingers.saturated_frames;

@@ -30,12 +30,16 @@ namespace paris
 
     namespace detail
     {
-        // the part of the chain that makes the line integrals the ring profile sums: correction, repair, zinger filter
+        // the part of the chain that makes the line integrals the ring profile sums: correction, air normalisation, repair, zinger
+        // filter
         inline auto line_integrals(backend::projection_device_type& p, const char* what) -> void
         {
             if(backend::detail::has_flat_field(backend::current_ctx()))
                 backend::detail::runtime_check(paris_hip_flat_field_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y,
                                                                          0u, p.dim_y), what);
+            if(backend::detail::has_air_region(backend::current_ctx()))
+                backend::detail::runtime_check(paris_hip_air_normalize_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                            p.dim_y, 0u, p.dim_y), what);
             if(backend::detail::has_defect_map(backend::current_ctx()))
                 backend::detail::runtime_check(paris_hip_defect_repair_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                             p.dim_y, 0u, p.dim_y), what);
@@ -63,7 +67,10 @@ namespace paris
         backend::axis_search_add(p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y, frame);
     }
 
-    // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with a defect map
+    // with a dark / flat setting (backend::set_flat_field), the correction to line integrals comes first, then with an air region
+    // (backend::set_air_region) the subtraction of the frame's own flux drift, measured where the detector sees only air (a constant
+    // over the frame, so it must be gone before the repair averages pixels, before the zinger filter compares them with thresholds
+    // and before the ring profile sums the frames), then with a defect map
     // (backend::set_defect_map) the repair of the defective pixels, then with a zinger filter (backend::set_zinger_filter) the removal
     // of the frame's outlier pixels, then with a ring correction (backend::set_ring_correction) the subtraction of the detector's
     // stationary offsets (additive in line integrals, so before every weight), then with an offset detector
