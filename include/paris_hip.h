@@ -40,6 +40,10 @@ extern "C" {
 #define PARIS_HIP_ERROR_INVALID_ARGUMENT 10001
 #define PARIS_HIP_ERROR_NO_DEVICE 10002
 #define PARIS_HIP_ERROR_UNSUPPORTED 10003
+/* what paris_hip_bh_solve refuses (the beam-hardening fit below) */
+#define PARIS_HIP_ERROR_BH_TOO_FEW_VOXELS 10004 /* fewer object or air voxels than the caller's minimum */
+#define PARIS_HIP_ERROR_BH_NOT_POSITIVE 10005   /* a Cholesky pivot of the normal equations is not positive */
+#define PARIS_HIP_ERROR_BH_NOT_FINITE 10006     /* a coefficient is not a finite float */
 
 /* ctx flags */
 #define PARIS_HIP_CTX_DEFAULT 0u
@@ -940,6 +944,110 @@ int paris_hip_air_measure(paris_hip_ctx* ctx, const float* d_p, size_t pitch, si
 /* The counts of the normalise calls since the setting was made or last reset: runs what is pending, waits for the ctx stream and
  * reads them; reset != 0 zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
 int paris_hip_air_stats(paris_hip_ctx* ctx, paris_hip_air_counts* out, int reset);
+/* Extension (no reference counterpart): beam-hardening correction -- a polychromatic tube makes the line integral
+ * p = -ln(sum s_E exp(-mu_E L)) concave in the path length L, and FDK turns that into cupping. The correction is a polynomial of the
+ * line integral without a constant term, q = c_1 p + c_2 p^2 + ... + c_N p^N, and its coefficients can be fitted from the scan itself
+ * (empirical cupping correction, Kachelriess et al. 2006). One definition of every piece; where the device and
+ * the host both implement one they give the same bits.
+ * Setting paris_hip_beam_hardening { uint32_t degree; float c[PARIS_HIP_BH_DEGREE_MAX]; }: 1 <= degree <= 4, every c_k finite, c[0] is
+ *   c_1. Air (p = 0) stays 0.
+ * Rule, per pixel, in fp32, N = degree:
+ *   p >= 0, or p is NaN: acc = c_N; acc = fmaf(acc, p, c_k) for k = N-1 ... 1; q = acc * p -- the last step is one multiplication.
+ *   p < 0 (noise in air): q = c_1 * p; the higher terms would bias air.
+ *   Explicit fused multiply-adds, no contraction elsewhere. A NaN pixel gives a NaN whose payload is unspecified.
+ * Order. The pass runs on line integrals, after the ring correction and before every weight (short-scan, offset-detector, cosine).
+ * Fit, on a slab of dim_x x dim_y x dim_z voxels (a volume or a run of whole slices of it), from the basis volumes f_k = FDK(p^k):
+ *   (a) Threshold (paris_hip_bh_threshold_from_histogram, host, the single implementation): Otsu's rule in double on the histogram
+ *       paris_hip_volume_stats returns for f_1 over [min, max]. T = sum of the bins, width = ((double)h_hi - h_lo) / n_bins. For the
+ *       inclusive cumulative split at bin b: w0 = C(b) / T, mu0 = (sum_{k <= b} k h_k) / C(b), mu1 = (sum_{k > b} k h_k) / (T - C(b));
+ *       score(b) = w0 (1 - w0) (mu0 - mu1)^2, and 0 where either side is empty. b is the smallest bin with the largest score;
+ *       thr = (float)(h_lo + (b + 1) width).
+ *   (b) Labels (paris_hip_bh_classify, device): the class of a voxel is object if v > thr, air if v <= thr, none if v is not finite.
+ *       A voxel gets the label 2 (object) or 1 (air) iff every voxel within Chebyshev distance `margin` of it, along all three axes,
+ *       has its class -- positions outside the slab count as differing -- and it lies inside the field of view,
+ *       (2x - dim_x + 1)^2 + (2y - dim_y + 1)^2 <= (min(dim_x, dim_y) - 2)^2 in integers. Every other voxel gets 0. Voxels outside
+ *       the field of view still lend their class to their neighbours. 0 <= margin <= PARIS_HIP_BH_MARGIN_MAX.
+ *   (c) Gram matrix (paris_hip_bh_gram on the device, paris_hip_bh_gram_host): per labelled voxel g = (f_1 ... f_N, m), m = 1 for
+ *       label 2 and 0 for label 1; G = sum g g^T, the upper triangle row by row: (N + 1)(N + 2) / 2 doubles, G[a][b] (a <= b) at
+ *       a (N + 1) - a (a - 1) / 2 + (b - a). A labelled voxel where any f_k is not finite is skipped and counted. The order of the
+ *       additions is fixed. With L = 65536 partial sums, voxel i (its 64-bit linear index) belongs to partial l = i mod L; within a
+ *       partial voxels are taken in ascending i; each term is (double)a * (double)b, exact for two floats, added in double to an
+ *       accumulator that starts at +0; then B_j = sum_m acc_{j + 256 m}, m ascending, for j = 0 ... 255, and G = sum_j B_j, j ascending.
+ *       Counts: n_object and n_air are the voxels summed, n_not_finite those skipped, n_ignored the voxels with another label.
+ *   (d) Solve (paris_hip_bh_solve, host): T = G[f_1][m] / n_object -- the mean of f_1 over the object's core, the FIXED template
+ *       level. Minimise sum (sum c_k f_k - T m)^2 over c_1 ... c_N: A = G[1..N][1..N], b_i = T G[f_i][m], by Cholesky in double, each
+ *       coefficient rounded once to float and used as solved (no normalisation by c_1). The rms residual relative to T,
+ *       sqrt(max(0, c^T A c - 2 T c^T G[f][m] + T^2 n_object) / (n_object + n_air)) / |T|, is reported for c = e_1 (before) and for
+ *       the rounded coefficients (after).
+ * Limits: one material; no metal. */
+#define PARIS_HIP_BH_DEGREE_MAX 4
+#define PARIS_HIP_BH_MARGIN_MAX 4
+#define PARIS_HIP_BH_HISTOGRAM_BINS 4096 /* what the fit asks paris_hip_volume_stats for */
+#define PARIS_HIP_BH_PARTIALS 65536      /* L of the Gram sum */
+#define PARIS_HIP_BH_MIN_VOXELS_DEFAULT 64
+typedef struct paris_hip_beam_hardening {
+    uint32_t degree;                  /* N: 1 .. PARIS_HIP_BH_DEGREE_MAX */
+    float c[PARIS_HIP_BH_DEGREE_MAX]; /* c[0] = c_1 ... c[N - 1] = c_N, each finite; the rest is ignored */
+} paris_hip_beam_hardening;
+/* what paris_hip_bh_gram counts */
+typedef struct paris_hip_bh_counts {
+    uint64_t n_object;     /* voxels with label 2 that were summed */
+    uint64_t n_air;        /* voxels with label 1 that were summed */
+    uint64_t n_ignored;    /* voxels with any other label */
+    uint64_t n_not_finite; /* labelled voxels skipped because an f_k is not finite */
+} paris_hip_bh_counts;
+/* what paris_hip_bh_solve returns */
+typedef struct paris_hip_bh_fit {
+    paris_hip_beam_hardening setting; /* the coefficients as solved */
+    double level;                     /* T */
+    double residual_before;           /* rms residual / |T| for c = e_1 */
+    double residual_after;            /* the same for the fitted coefficients */
+} paris_hip_bh_fit;
+/* Host only, no ctx and no device. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a degree outside 1 .. 4 or a c_k (k <= degree)
+ * that is not finite. */
+int paris_hip_beam_hardening_check(const paris_hip_beam_hardening* setting);
+/* Host only: the rule on n dense pixels, src to dst (which may be the same array) -- the second implementation of the one definition.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL src or dst with n != 0. */
+int paris_hip_beam_hardening_host(const paris_hip_beam_hardening* setting, const float* src, float* dst, uint64_t n);
+/* paris_hip_set_beam_hardening runs the check and keeps the setting for dim_x x dim_y frames (both >= 1); it travels to the kernel by
+ * value, so work queued before a replacement keeps the old one and nothing lives on the device. Without a setting nothing else
+ * changes. */
+int paris_hip_set_beam_hardening(paris_hip_ctx* ctx, const paris_hip_beam_hardening* setting, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_beam_hardening(paris_hip_ctx* ctx);
+/* In place on float frames, asynchronous: every pixel of rows [row_first, row_first + row_count) of n_frames frames frame_stride bytes
+ * apart, d_p the first frame's row 0, becomes q. 16-byte vectors are used where the base, the pitch, the stride (n_frames > 1) and
+ * dim_x allow, single pixels otherwise. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when dim_x / dim_y differ from the
+ * setting's, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_beam_hardening_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                  uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* The same with the setting as an argument (the ctx's, if any, is neither used nor changed): the fit forms p^k with the unit
+ * settings e_k. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a band, pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_beam_hardening_rows_with(paris_hip_ctx* ctx, const paris_hip_beam_hardening* setting, float* d_p, size_t pitch,
+                                       size_t frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y, uint32_t row_first,
+                                       uint32_t row_count);
+/* Host only: (a). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer, n_bins == 0, a range paris_hip_volume_window_check's rules
+ * refuse, or an empty histogram. */
+int paris_hip_bh_threshold_from_histogram(const uint64_t* hist, uint32_t n_bins, float h_lo, float h_hi, float* thr);
+/* (b), asynchronous on the ctx stream; what is deferred runs first. d_v: dim_x * dim_y * dim_z floats, 4-byte aligned; d_labels: as
+ * many bytes, which must not overlap them and are treated as paris_hip_volume_mark_dirty treats a range.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer, a zero dimension, a thr that is not finite, margin > PARIS_HIP_BH_MARGIN_MAX or
+ * overlapping ranges; PARIS_HIP_ERROR_UNSUPPORTED for a slab beyond the grid's limits (more than 65535 tiles of 16 rows or of 8 slices). */
+int paris_hip_bh_classify(paris_hip_ctx* ctx, const float* d_v, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, float thr, uint32_t margin,
+                          uint8_t* d_labels);
+/* (c), synchronous; what is deferred runs first. d_f: a host array of `degree` device pointers, f_1 first, each n_voxels floats;
+ * d_labels: n_voxels bytes on the device; gram receives (degree + 1)(degree + 2) / 2 doubles. The partial sums live in device
+ * memory the call allocates and frees. n_voxels == 0 gives zeros. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer, a degree
+ * outside 1 .. 4 or a misaligned f_k. */
+int paris_hip_bh_gram(paris_hip_ctx* ctx, const float* const* d_f, uint32_t degree, const uint8_t* d_labels, uint64_t n_voxels, double* gram,
+                      paris_hip_bh_counts* counts);
+/* Host only: the same definition on host arrays -- the second implementation. */
+int paris_hip_bh_gram_host(const float* const* f, uint32_t degree, const uint8_t* labels, uint64_t n_voxels, double* gram,
+                           paris_hip_bh_counts* counts);
+/* Host only: (d). min_voxels == 0 stands for PARIS_HIP_BH_MIN_VOXELS_DEFAULT. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer or a
+ * degree outside 1 .. 4; PARIS_HIP_ERROR_BH_TOO_FEW_VOXELS when n_object or n_air is below min_voxels;
+ * PARIS_HIP_ERROR_BH_NOT_POSITIVE when a pivot is not positive (NaN included); PARIS_HIP_ERROR_BH_NOT_FINITE when T is zero or not
+ * finite or a coefficient is not a finite float. *out is written on success only. */
+int paris_hip_bh_solve(const double* gram, uint32_t degree, const paris_hip_bh_counts* counts, uint64_t min_voxels, paris_hip_bh_fit* out);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

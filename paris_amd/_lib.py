@@ -130,6 +130,31 @@ class AirCounts(C.Structure):
 
 AIR_FRAMES_MAX = 64  # PARIS_HIP_AIR_FRAMES_MAX
 
+# what paris_hip_bh_solve refuses
+ERROR_BH_TOO_FEW_VOXELS = 10004
+ERROR_BH_NOT_POSITIVE = 10005
+ERROR_BH_NOT_FINITE = 10006
+BH_DEGREE_MAX = 4  # PARIS_HIP_BH_DEGREE_MAX
+BH_MARGIN_MAX = 4  # PARIS_HIP_BH_MARGIN_MAX
+BH_HISTOGRAM_BINS = 4096  # PARIS_HIP_BH_HISTOGRAM_BINS
+BH_PARTIALS = 65536  # PARIS_HIP_BH_PARTIALS
+BH_MIN_VOXELS_DEFAULT = 64  # PARIS_HIP_BH_MIN_VOXELS_DEFAULT
+
+
+class BeamHardening(C.Structure):
+    """paris_hip_beam_hardening: the polynomial q = c_1 p + ... + c_N p^N of the line integral (extension)"""
+    _fields_ = [("degree", C.c_uint32), ("c", C.c_float * BH_DEGREE_MAX)]
+
+
+class BhCounts(C.Structure):
+    """paris_hip_bh_counts: what paris_hip_bh_gram counts (extension)"""
+    _fields_ = [("n_object", C.c_uint64), ("n_air", C.c_uint64), ("n_ignored", C.c_uint64), ("n_not_finite", C.c_uint64)]
+
+
+class BhFit(C.Structure):
+    """paris_hip_bh_fit: what paris_hip_bh_solve returns (extension)"""
+    _fields_ = [("setting", BeamHardening), ("level", C.c_double), ("residual_before", C.c_double), ("residual_after", C.c_double)]
+
 
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
@@ -236,6 +261,17 @@ SIGNATURES = {
     "paris_hip_air_normalize_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_air_measure": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _vp, _vp]),
     "paris_hip_air_stats": (C.c_int, [_vp, _P(AirCounts), C.c_int]),
+    "paris_hip_beam_hardening_check": (C.c_int, [_P(BeamHardening)]),
+    "paris_hip_beam_hardening_host": (C.c_int, [_P(BeamHardening), _vp, _vp, C.c_uint64]),
+    "paris_hip_set_beam_hardening": (C.c_int, [_vp, _P(BeamHardening), _u32, _u32]),
+    "paris_hip_clear_beam_hardening": (C.c_int, [_vp]),
+    "paris_hip_beam_hardening_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_beam_hardening_rows_with": (C.c_int, [_vp, _P(BeamHardening), _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_bh_threshold_from_histogram": (C.c_int, [_vp, _u32, _f, _f, _P(_f)]),
+    "paris_hip_bh_classify": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _f, _u32, _vp]),
+    "paris_hip_bh_gram": (C.c_int, [_vp, _P(_vp), _u32, _vp, C.c_uint64, _vp, _P(BhCounts)]),
+    "paris_hip_bh_gram_host": (C.c_int, [_P(_vp), _u32, _vp, C.c_uint64, _vp, _P(BhCounts)]),
+    "paris_hip_bh_solve": (C.c_int, [_vp, _u32, _P(BhCounts), C.c_uint64, _P(BhFit)]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

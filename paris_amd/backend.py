@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (BeamHardening, BhCounts, BhFit, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -23,7 +23,9 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
            "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean", "VolumeWindow", "VolumeCounts",
            "VolumeStatistics", "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
-           "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host"]
+           "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host",
+           "BeamHardening", "BhCounts", "BhFit", "Labels", "BeamHardeningFit", "beam_hardening_check", "beam_hardening_host",
+           "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve"]
 
 
 class Projection:
@@ -273,6 +275,111 @@ def air_value_host(x0, y0, width, height, frame, mask=None, min_pixels=0, limit_
     check(_lib.load().paris_hip_air_value_host(C.byref(ar), None if m is None else m.ctypes.data, f.ctypes.data, f.shape[1], f.shape[0],
                                                C.byref(a), C.byref(n)), "paris_hip_air_value_host")
     return np.float32(a.value), n.value
+
+
+def _bh_setting(c):
+    """the setting for a sequence of coefficients c_1 ... c_N; a length outside 1 .. 4 gets the degree as it is, which the library
+    refuses"""
+    c = [float(x) for x in np.atleast_1d(np.asarray(c, np.float64))]
+    s = BeamHardening()
+    s.degree = len(c)
+    for k, x in enumerate(c[:_lib.BH_DEGREE_MAX]):
+        s.c[k] = x
+    return s
+
+
+def beam_hardening_check(c):
+    """Host only, no device (paris_hip_beam_hardening_check): raises ParisHipError unless c holds 1 to 4 finite coefficients
+    c_1 ... c_N of q = c_1 p + ... + c_N p^N."""
+    s = _bh_setting(c)
+    check(_lib.load().paris_hip_beam_hardening_check(C.byref(s)), "paris_hip_beam_hardening_check")
+
+
+def beam_hardening_host(c, frame):
+    """Host only, no device (paris_hip_beam_hardening_host): the beam-hardening rule on an array of line integrals, taken as float32
+    -- Horner with fused multiply-adds and a final multiplication for p >= 0 or NaN, c_1 p for p < 0.
+    Returns a float32 array of the same shape."""
+    f = np.ascontiguousarray(frame, np.float32)
+    out = np.empty_like(f)
+    s = _bh_setting(c)
+    check(_lib.load().paris_hip_beam_hardening_host(C.byref(s), f.ctypes.data if f.size else None, out.ctypes.data if f.size else None,
+                                                    f.size), "paris_hip_beam_hardening_host")
+    return out
+
+
+def bh_threshold_from_histogram(hist, h_lo, h_hi):
+    """Host only, no device (paris_hip_bh_threshold_from_histogram): Otsu's threshold of a linear histogram over [h_lo, h_hi] -- the
+    upper edge of the smallest bin that maximises the between-class variance -- as np.float32."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    if h.ndim != 1:
+        raise ValueError("bh_threshold_from_histogram: the histogram must be a 1-D array")
+    thr = C.c_float(0)
+    check(_lib.load().paris_hip_bh_threshold_from_histogram(h.ctypes.data if h.size else None, h.size, h_lo, h_hi, C.byref(thr)),
+          "paris_hip_bh_threshold_from_histogram")
+    return np.float32(thr.value)
+
+
+def _bh_terms(degree):
+    return (degree + 1) * (degree + 2) // 2
+
+
+def bh_gram_host(basis, labels):
+    """Host only, no device (paris_hip_bh_gram_host): the Gram sums of g = (f_1 ... f_N, m) over the labelled voxels in the order
+    DESIGN.md section 4.17 fixes. basis: N arrays of one shape, taken as float32; labels: uint8 of that shape. Returns
+    (float64[(N + 1)(N + 2) / 2], BhCounts)."""
+    fs = [np.ascontiguousarray(f, np.float32) for f in basis]
+    lab = np.ascontiguousarray(labels, np.uint8)
+    if any(f.shape != lab.shape for f in fs):
+        raise ValueError("bh_gram_host: the basis volumes and the labels differ in shape")
+    ptrs = (C.c_void_p * max(len(fs), 1))(*[f.ctypes.data for f in fs])
+    g, cnt = np.zeros(_bh_terms(len(fs)), np.float64), BhCounts()
+    check(_lib.load().paris_hip_bh_gram_host(ptrs, len(fs), lab.ctypes.data, lab.size, g.ctypes.data, C.byref(cnt)), "paris_hip_bh_gram_host")
+    return g, cnt
+
+
+def bh_gram_matrix(gram, degree):
+    """the packed upper triangle paris_hip_bh_gram returns as the full symmetric (degree + 1) x (degree + 1) float64 matrix"""
+    n = degree + 1
+    m = np.zeros((n, n), np.float64)
+    m[np.triu_indices(n)] = np.asarray(gram, np.float64)
+    return m + np.triu(m, 1).T
+
+
+def bh_solve(gram, degree, counts, min_voxels=0):
+    """Host only, no device (paris_hip_bh_solve): the coefficients that make sum c_k f_k as close as possible, in the least-squares
+    sense over the labelled voxels, to the two-level template T m, with T the mean of f_1 over the object's core -- by Cholesky in
+    double. Returns the BhFit: .setting (degree, c), .level, .residual_before, .residual_after. Raises ParisHipError with the status
+    ERROR_BH_TOO_FEW_VOXELS, ERROR_BH_NOT_POSITIVE or ERROR_BH_NOT_FINITE for a fit the library refuses."""
+    g = np.ascontiguousarray(gram, np.float64)
+    if g.size != _bh_terms(degree):
+        raise ValueError("bh_solve: %d Gram sums do not belong to degree %d" % (g.size, degree))
+    fit = BhFit()
+    check(_lib.load().paris_hip_bh_solve(g.ctypes.data, degree, C.byref(counts), min_voxels, C.byref(fit)), "paris_hip_bh_solve")
+    return fit
+
+
+class Labels:
+    """one byte per voxel of a dim_x x dim_y x dim_z slab on the device (Backend.bh_classify / Backend.labels_from_host)"""
+
+    def __init__(self, store, dim_x, dim_y, dim_z):
+        self._store = store  # the device allocation that holds the bytes
+        self.dim_x, self.dim_y, self.dim_z = dim_x, dim_y, dim_z
+
+    @property
+    def ptr(self):
+        return self._store.ptr
+
+    @property
+    def size(self):
+        return self.dim_x * self.dim_y * self.dim_z
+
+
+class BeamHardeningFit:
+    """What Backend.fit_beam_hardening returns: c (float32[N], as solved), level, residual_before, residual_after, threshold,
+    counts (BhCounts), gram (float64, packed), labels (uint8 (dim_z, dim_y, dim_x) of the fitted slab) and slices (first, count)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
 
 
 def row_extension_check(edge_pixels, taper_pixels, dim_x):
@@ -821,6 +928,136 @@ class Backend:
         st = AirCounts()
         check(self._L.paris_hip_air_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_air_stats")
         return st
+
+    # ---- beam hardening ------------------------------------------------------------
+    beam_hardening_check = staticmethod(beam_hardening_check)
+    beam_hardening_host = staticmethod(beam_hardening_host)
+    bh_threshold_from_histogram = staticmethod(bh_threshold_from_histogram)
+    bh_gram_host = staticmethod(bh_gram_host)
+    bh_solve = staticmethod(bh_solve)
+
+    def set_beam_hardening(self, c, dim_x, dim_y):
+        """paris_hip_set_beam_hardening for dim_x x dim_y frames: beam_hardening() then turns every line integral p into
+        q = c_1 p + ... + c_N p^N (c: 1 to 4 finite coefficients, c_1 first). Replaces an earlier setting; work already queued keeps
+        the old one."""
+        s = _bh_setting(c)
+        check(self._L.paris_hip_set_beam_hardening(self._ctx, C.byref(s), dim_x, dim_y), "paris_hip_set_beam_hardening")
+
+    def clear_beam_hardening(self):
+        """paris_hip_clear_beam_hardening: no beam-hardening correction from here on"""
+        check(self._L.paris_hip_clear_beam_hardening(self._ctx), "paris_hip_clear_beam_hardening")
+
+    def beam_hardening(self, p, frame_stride=0, n_frames=1, rows=None, c=None):
+        """The rule of set_beam_hardening() in place on float frames (paris_hip_beam_hardening_rows): rows (first, count) -- None:
+        every row -- of the n_frames frames frame_stride bytes apart starting at p. With c the coefficients are taken from the
+        argument and the backend's setting is neither used nor changed (paris_hip_beam_hardening_rows_with). Call it on line
+        integrals, after the ring correction and before every weight."""
+        first, count = (0, p.dim_y) if rows is None else rows
+        if c is None:
+            check(self._L.paris_hip_beam_hardening_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, first, count),
+                  "paris_hip_beam_hardening_rows")
+            return
+        s = _bh_setting(c)
+        check(self._L.paris_hip_beam_hardening_rows_with(self._ctx, C.byref(s), p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y,
+                                                         first, count), "paris_hip_beam_hardening_rows_with")
+
+    def make_labels_device(self, dim_x, dim_y, dim_z):
+        """one byte per voxel of a slab, uninitialised; free() takes it"""
+        return Labels(self.make_volume_device((dim_x * dim_y * dim_z + 3) // 4, 1, 1), dim_x, dim_y, dim_z)
+
+    def labels_from_host(self, labels):
+        """a uint8 array (dim_z, dim_y, dim_x) as Labels on the device"""
+        h = np.ascontiguousarray(labels, np.uint8)
+        if h.ndim != 3:
+            raise ValueError("labels_from_host: the labels must be a 3-D array (dim_z, dim_y, dim_x)")
+        d = self.make_labels_device(h.shape[2], h.shape[1], h.shape[0])
+        words = np.zeros(d._store.dim_x, np.float32)
+        words.view(np.uint8)[:h.size] = h.ravel()
+        check(self._L.paris_hip_memcpy_volume_h2d(self._ctx, d.ptr, words.ctypes.data, d._store.dim_x, 1, 1), "paris_hip_memcpy_volume_h2d")
+        self.synchronize()
+        return d
+
+    def labels_to_host(self, labels):
+        """the Labels as a uint8 array (dim_z, dim_y, dim_x); waits for the ctx stream"""
+        words = np.empty(labels._store.dim_x, np.float32)
+        check(self._L.paris_hip_memcpy_volume_d2h(self._ctx, words.ctypes.data, labels.ptr, labels._store.dim_x, 1, 1),
+              "paris_hip_memcpy_volume_d2h")
+        self.synchronize()
+        return words.view(np.uint8)[:labels.size].reshape(labels.dim_z, labels.dim_y, labels.dim_x).copy()
+
+    def bh_classify(self, v, thr, margin, labels=None):
+        """paris_hip_bh_classify of the device slab v: label 2 (object, v > thr) or 1 (air, v <= thr) for every voxel whose whole
+        neighbourhood of Chebyshev radius margin (0 .. 4) lies in the slab and has its class and which lies inside the field of
+        view, 0 otherwise. Returns the Labels (made here unless given). Runs what is deferred first; does not wait."""
+        out = labels if labels is not None else self.make_labels_device(v.dim_x, v.dim_y, v.dim_z)
+        if (out.dim_x, out.dim_y, out.dim_z) != (v.dim_x, v.dim_y, v.dim_z):
+            raise ValueError("bh_classify: the labels and the slab differ in size")
+        status = self._L.paris_hip_bh_classify(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z, thr, margin, out.ptr)
+        if status != _lib.SUCCESS and labels is None:
+            self.free(out)
+        check(status, "paris_hip_bh_classify")
+        return out
+
+    def bh_gram(self, basis, labels):
+        """paris_hip_bh_gram: the Gram sums of (f_1 ... f_N, m) over the labelled voxels of the device slabs basis[0 .. N) -- bit for
+        bit bh_gram_host() of the same data. Returns (float64[(N + 1)(N + 2) / 2], BhCounts). Waits for the result."""
+        n = len(basis)
+        if any((f.dim_x, f.dim_y, f.dim_z) != (labels.dim_x, labels.dim_y, labels.dim_z) for f in basis):
+            raise ValueError("bh_gram: the basis slabs and the labels differ in size")
+        ptrs = (C.c_void_p * max(n, 1))(*[f.ptr for f in basis])
+        g, cnt = np.zeros(_bh_terms(n), np.float64), BhCounts()
+        check(self._L.paris_hip_bh_gram(self._ctx, ptrs, n, labels.ptr, labels.size, g.ctypes.data, C.byref(cnt)), "paris_hip_bh_gram")
+        return g, cnt
+
+    def fit_beam_hardening(self, frames, det_geo, degree=2, margin=2, slices=None, vol_geo=None, min_voxels=0, prepare=None,
+                           enable_angles=False, angles=None):
+        """Empirical cupping correction: fits the coefficients of set_beam_hardening() from the scan itself. frames: the scan's line
+        integrals, one 2-D float32 array (n_col, n_row) per view, in view order, as they are after the ring correction. For each view
+        and each k = 1 .. degree the frame is uploaded, turned into p^k by the pass with the unit setting e_k, handed to
+        prepare(backend, projection) if given (the redundancy weights of a short or offset scan), weighted, filtered and
+        backprojected into the k-th basis slab: slices (first, count) of vol_geo's volume -- None: every slice; vol_geo None: the
+        natural volume of det_geo. Then Otsu's threshold of f_1, the labels with the given margin, the Gram sums and the solve
+        (DESIGN.md section 4.17). Returns a BeamHardeningFit; raises ParisHipError where the library refuses. The backend's own
+        beam-hardening setting is neither used nor changed; every device buffer made here is freed before the call returns."""
+        vg = vol_geo if vol_geo is not None else calculate_volume_geometry(det_geo)
+        first, count = (0, vg.dim_z) if slices is None else slices
+        if degree < 1 or degree > _lib.BH_DEGREE_MAX or count < 1 or first < 0 or first + count > vg.dim_z:
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "fit_beam_hardening")
+        slabs, labels = [], None
+        try:
+            for _ in range(degree):
+                slabs.append(self.make_volume_device(vg.dim_x, vg.dim_y, count))
+                self.memset_volume(slabs[-1])
+            for i, frame in enumerate(frames):
+                f = np.ascontiguousarray(frame, np.float32)
+                for k in range(degree):
+                    h = Projection(f, det_geo.n_row, det_geo.n_col, idx=i, phi=0.0 if angles is None else float(angles[i]))
+                    d_p = load(self, h)
+                    try:
+                        self.beam_hardening(d_p, c=[0.0] * k + [1.0])
+                        if prepare is not None:
+                            prepare(self, d_p)
+                        weight(self, d_p, det_geo)
+                        filter(self, d_p, det_geo)
+                        backproject(self, d_p, slabs[k], first, det_geo, vg, enable_angles, False, None)
+                    finally:
+                        self.free(d_p)
+            st, _ = self.volume_stats(slabs[0])
+            st, hist = self.volume_stats(slabs[0], st.min, st.max, _lib.BH_HISTOGRAM_BINS)
+            thr = bh_threshold_from_histogram(hist, st.min, st.max)
+            labels = self.bh_classify(slabs[0], thr, margin)
+            gram, counts = self.bh_gram(slabs, labels)
+            fit = bh_solve(gram, degree, counts, min_voxels)
+            return BeamHardeningFit(c=np.array(fit.setting.c[:degree], np.float32), level=fit.level, residual_before=fit.residual_before,
+                                    residual_after=fit.residual_after, threshold=thr, counts=counts, gram=gram,
+                                    labels=self.labels_to_host(labels), slices=(first, count))
+        finally:
+            self.flush()
+            self.synchronize()
+            for v in slabs:
+                self.free(v)
+            if labels is not None:
+                self.free(labels._store)
 
     # ---- row extension (DESIGN.md section 4.11) -----------------------------------------------------------
     row_extension_check = staticmethod(row_extension_check)

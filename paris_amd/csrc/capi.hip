@@ -116,6 +116,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_binning();
             paris_hip_warm_axis_search();
             paris_hip_warm_air_region();
+            paris_hip_warm_beam_hardening();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -1500,6 +1501,9 @@ extern "C" const char* paris_hip_strerror(int status)
         case PARIS_HIP_ERROR_INVALID_ARGUMENT: return "paris_hip: invalid argument";
         case PARIS_HIP_ERROR_NO_DEVICE: return "paris_hip: no HIP device";
         case PARIS_HIP_ERROR_UNSUPPORTED: return "paris_hip: unsupported size";
+        case PARIS_HIP_ERROR_BH_TOO_FEW_VOXELS: return "paris_hip: beam-hardening fit: too few object or air voxels were labelled";
+        case PARIS_HIP_ERROR_BH_NOT_POSITIVE: return "paris_hip: beam-hardening fit: the normal equations are not positive definite";
+        case PARIS_HIP_ERROR_BH_NOT_FINITE: return "paris_hip: beam-hardening fit: a coefficient is not finite";
         default: return hipGetErrorString(static_cast<hipError_t>(status));
     }
 }

@@ -199,6 +199,14 @@ struct paris_hip_ctx
         size_t device_bytes = 0;
         char* d_mem = nullptr;
     } air;
+    // Beam hardening (paris_hip_set_beam_hardening): the setting and the frame size it was made for. It
+    // travels to the kernel by value: nothing on the device, nothing to retire.
+    struct beam_hardening_t
+    {
+        bool set = false;
+        paris_hip_beam_hardening rule{};
+        uint32_t dim_x = 0, dim_y = 0;
+    } beam_hardening;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -479,6 +487,7 @@ void paris_hip_warm_volume_window();
 void paris_hip_warm_binning();
 void paris_hip_warm_axis_search();
 void paris_hip_warm_air_region();
+void paris_hip_warm_beam_hardening();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the

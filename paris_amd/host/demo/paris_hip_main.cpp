@@ -9,6 +9,7 @@
 //             [--defects mask.raw] [--defects-from-flat] [--zingers ABS[:REL] [--zinger-polarity bright|dark|both]] [--rings H[:FLOOR[:LIMIT]]]
 //             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]
 //             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]
+//             [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -86,6 +87,7 @@ int main(int argc, char** argv)
                             "          [--rings H[:FLOOR[:LIMIT]]]\n"
                             "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]\n"
                             "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]\n"
+                            "          [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -127,7 +129,15 @@ int main(int argc, char** argv)
                             "mean line integral of the rectangle's pixels (those --defects marks and values that are not finite left out) is\n"
                             "subtracted from the whole frame on the device, directly after the correction and before the repair. A frame with\n"
                             "fewer than half the rectangle's pixels left, or whose mean exceeds LIMIT in size (0, the default: no limit), stays\n"
-                            "as it is and is counted.\n");
+                            "as it is and is counted.\n"
+                            "--beam-hardening: a polychromatic tube makes the line integral concave in the path length, and the volume of a\n"
+                            "homogeneous part comes out cupped. Every line integral p >= 0 becomes C1 p + C2 p^2 [+ C3 p^3 [+ C4 p^4]] on the\n"
+                            "device, after the ring correction and before every weight; a negative p (noise in air) becomes C1 p.\n"
+                            "--fit-beam-hardening: the coefficients C1 .. CN (N in 1 .. 4) are found from the scan itself. The scan is read once\n"
+                            "before the reconstruction (after the pre-pass of --rings and --find-axis, whose results it uses): p, p^2 .. p^N are\n"
+                            "each reconstructed into the central SLICES slices of the volume (default 32), the slices are split into object and\n"
+                            "air by Otsu's threshold, leaving out every voxel within MARGIN voxels (0 .. 4, default 2) of the other class, and the\n"
+                            "combination that is flattest over both is solved for. One material only; not with --bin or --beam-hardening.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -162,6 +172,8 @@ int main(int argc, char** argv)
             else if(k == "--axis-rows") paris::detail::parse_axis_rows(val(), po);
             else if(k == "--axis-only") po.axis_only = true;
             else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
+            else if(k == "--beam-hardening") paris::detail::parse_beam_hardening(val(), po);
+            else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -245,6 +257,19 @@ int main(int argc, char** argv)
                             "widen the range of --find-axis\n");
             if(po.axis_only)
                 return 0;
+        }
+        if(r.beam_hardening)
+        {
+            if(r.bh_fitted)
+                std::printf("beam-hardening fit on: degree %u, %u frame(s) into slices %u .. %u in the pre-pass (%.3f s), threshold %.9g, %llu object and "
+                            "%llu air voxel(s), %llu not finite, level %.9g, residual %.6g before and %.6g after\n", r.bh.degree, r.bh_frames, r.bh_slice_first,
+                            r.bh_slice_first + r.bh_slices - 1u, r.bh_prepass_s, static_cast<double>(r.bh_threshold),
+                            static_cast<unsigned long long>(r.bh_counts.n_object), static_cast<unsigned long long>(r.bh_counts.n_air),
+                            static_cast<unsigned long long>(r.bh_counts.n_not_finite), r.bh_fit.level, r.bh_fit.residual_before, r.bh_fit.residual_after);
+            std::printf("beam hardening on: coefficients");
+            for(std::uint32_t k = 0; k < r.bh.degree; ++k)
+                std::printf("%s%.9g", k == 0u ? " " : ":", static_cast<double>(r.bh.c[k]));
+            std::printf("\n");
         }
         if(r.voxel_type != 0)
             std::printf("%llu voxel(s) written as %s over [%.9g, %.9g]: %llu below, %llu above, %llu not finite\n",

@@ -131,6 +131,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> zinger_filters; // set_zinger_filter(), per device of this thread
                 std::set<const paris_hip_ctx*> ring_corrections; // set_ring_correction(), per device of this thread
                 std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
+                std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -319,6 +320,66 @@ namespace paris
             inline auto has_air_region(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().air_regions;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the tube is polychromatic, so the line integrals of this thread's current device's
+        // frames (n_row x n_col pixels) are concave in the path length. Until clear_beam_hardening(),
+        // paris::weight() turns every line integral p >= 0 into c[0] p + c[1] p^2 + ... (degree coefficients, 1 .. 4, each finite) and a
+        // negative one into c[0] p, after the ring correction and before every weight (paris_hip_beam_hardening_rows).
+        inline auto set_beam_hardening(const float* c, std::uint32_t degree, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            auto setting = paris_hip_beam_hardening{};
+            setting.degree = degree;
+            for(std::uint32_t k = 0; c != nullptr && k < degree && k < PARIS_HIP_BH_DEGREE_MAX; ++k)
+                setting.c[k] = c[k];
+            detail::runtime_check(c == nullptr ? PARIS_HIP_ERROR_INVALID_ARGUMENT : paris_hip_set_beam_hardening(current_ctx(), &setting, n_row, n_col),
+                                  "set_beam_hardening()");
+            detail::state().beam_hardenings.insert(current_ctx());
+        }
+
+        inline auto clear_beam_hardening() -> void
+        {
+            detail::runtime_check(paris_hip_clear_beam_hardening(current_ctx()), "clear_beam_hardening()");
+            detail::state().beam_hardenings.erase(current_ctx());
+        }
+
+        // The pieces of the fit on this thread's current device, thin wrappers over the C calls: the labels of a slab of f_1, the
+        // Gram sums of the basis slabs over them (waits for the device), and -- host only -- the threshold and the solve.
+        inline auto bh_threshold_from_histogram(const std::uint64_t* hist, std::uint32_t n_bins, float h_lo, float h_hi) -> float
+        {
+            float thr = 0.f;
+            detail::runtime_check(paris_hip_bh_threshold_from_histogram(hist, n_bins, h_lo, h_hi, &thr), "bh_threshold_from_histogram()");
+            return thr;
+        }
+
+        inline auto bh_classify(const float* d_v, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t dim_z, float thr, std::uint32_t margin,
+                                std::uint8_t* d_labels) -> void
+        {
+            detail::runtime_check(paris_hip_bh_classify(current_ctx(), d_v, dim_x, dim_y, dim_z, thr, margin, d_labels), "bh_classify()");
+        }
+
+        inline auto bh_gram(const float* const* d_f, std::uint32_t degree, const std::uint8_t* d_labels, std::uint64_t n_voxels, double* gram)
+            -> paris_hip_bh_counts
+        {
+            auto counts = paris_hip_bh_counts{};
+            detail::runtime_check(paris_hip_bh_gram(current_ctx(), d_f, degree, d_labels, n_voxels, gram, &counts), "bh_gram()");
+            return counts;
+        }
+
+        inline auto bh_solve(const double* gram, std::uint32_t degree, const paris_hip_bh_counts& counts, std::uint64_t min_voxels = 0u) -> paris_hip_bh_fit
+        {
+            auto fit = paris_hip_bh_fit{};
+            detail::runtime_check(paris_hip_bh_solve(gram, degree, &counts, min_voxels, &fit), "bh_solve()");
+            return fit;
+        }
+
+        namespace detail
+        {
+            inline auto has_beam_hardening(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().beam_hardenings;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

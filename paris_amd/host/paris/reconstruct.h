@@ -143,6 +143,13 @@ namespace paris
         std::uint32_t axis_rows = 2;
         bool axis_rows_given = false;
         std::uint32_t axis_count = 0, axis_frames = 0;          // filled by run(): the candidates, and the frames of the circle
+        // beam-hardening correction (extension): --beam-hardening C1:C2[:C3[:C4]] gives the polynomial of the
+        // line integral, --fit-beam-hardening N[:SLICES[:MARGIN]] has run() fit it from the scan itself (detail::bh_prepass, after the
+        // ring pre-pass and the axis search): both checked by run() before any device work (detail::check_beam_hardening). Every
+        // device ctx gets the setting, and each frame is corrected after the ring correction and before every weight
+        bool beam_hardening = false, fit_beam_hardening = false;
+        paris_hip_beam_hardening bh{};                          // as given, or filled by run() with the fitted coefficients
+        std::uint32_t bh_slices = 32, bh_margin = 2;            // the fit's slab -- the central slices of the volume -- and its margin
         // detector binning (extension): --bin BX[:BY], each 1, 2, 4 or 8; 1 x 1 is no binning. run() checks the
         // setting before any device work and replaces det_geo by the binned geometry (detail::apply_binning), so that everything
         // derived from it follows; the dark and flat means and the defect mask are binned on the host, the frames on the device, each
@@ -746,6 +753,8 @@ namespace paris
             reach_rows = rep.defects.reach_rows;
             if(po.ring_c) // --rings: the correction frame of run()'s pre-pass, the same for every device
                 rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
+            if(po.beam_hardening) // --beam-hardening, or the coefficients run()'s fit found: the same on every device
+                rt(paris_hip_set_beam_hardening(ctx, &po.bh, po.det_geo.n_row, po.det_geo.n_col), "set_beam_hardening()");
         }
         catch(...)
         {
@@ -950,6 +959,9 @@ namespace paris
                     if(filter_by_group && band_count != 0 && po.ring_c) // then the detector's stationary offsets, on the band itself
                         rt(paris_hip_ring_correct_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
                            "ring correction");
+                    if(filter_by_group && band_count != 0 && po.beam_hardening) // then the linearisation, before every weight
+                        rt(paris_hip_beam_hardening_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
+                           "beam hardening");
                     if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
                         rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
                                                                  band_count, &t.det_geo), "offset-detector weight()");
@@ -1047,6 +1059,8 @@ namespace paris
                             rt(paris_hip_zinger_filter_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "zinger filter");
                         if(po.ring_c && !filter_by_group) // then the detector's stationary offsets
                             rt(paris_hip_ring_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "ring correction");
+                        if(po.beam_hardening && !filter_by_group) // then the linearisation, before every weight
+                            rt(paris_hip_beam_hardening_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "beam hardening");
                         if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
                             rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
                                                                      &t.det_geo), "offset-detector weight()");
@@ -1138,6 +1152,14 @@ namespace paris
         std::uint32_t axis_frames = 0, axis_count = 0;  // pre-pass took (reading the scan included; with --rings the same pre-pass)
         float axis_given = 0.f;
         double axis_prepass_s = 0;
+        bool beam_hardening = false;                    // --beam-hardening / --fit-beam-hardening: every frame went through this
+        paris_hip_beam_hardening bh{};                  // setting; with the fit: what it found -- coefficients, template level and the
+        bool bh_fitted = false;                         // two residuals --, the threshold, the counts, the frames and the slab
+        paris_hip_bh_fit bh_fit{};                      // (slices from bh_slice_first) of its pre-pass, and how long that took
+        paris_hip_bh_counts bh_counts{};                // (reading the scan included)
+        float bh_threshold = 0.f;
+        std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
+        double bh_prepass_s = 0;
         bool binning = false;                           // --bin: the factors, the source and the binned detector, and how many binned
         std::uint32_t bin_x = 1, bin_y = 1;             // pixels have no good source pixel (they join the defect map)
         std::uint32_t src_row = 0, src_col = 0, binned_row = 0, binned_col = 0;
@@ -1779,6 +1801,235 @@ namespace paris
                 r.axis_prepass_s = since(t_start);
         }
 
+        // the fields of a colon-separated option value; an empty field stays in as an empty string
+        inline auto colon_fields(const std::string& v) -> std::vector<std::string>
+        {
+            auto out = std::vector<std::string>{};
+            std::size_t at = 0;
+            for(;;)
+            {
+                const auto next = v.find(':', at);
+                out.push_back(v.substr(at, next == std::string::npos ? next : next - at));
+                if(next == std::string::npos)
+                    return out;
+                at = next + 1u;
+            }
+        }
+
+        // --beam-hardening C1:C2[:C3[:C4]] as typed; refuses anything but two to four numbers
+        inline auto parse_beam_hardening(const std::string& v, program_options& po) -> void
+        {
+            const auto field = colon_fields(v);
+            if(field.size() < 2u || field.size() > PARIS_HIP_BH_DEGREE_MAX)
+                throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: cannot read '" + v + "'"};
+            po.bh = paris_hip_beam_hardening{};
+            po.bh.degree = static_cast<std::uint32_t>(field.size());
+            for(std::size_t k = 0; k < field.size(); ++k)
+            {
+                char* end = nullptr;
+                po.bh.c[k] = std::strtof(field[k].c_str(), &end);
+                if(field[k].empty() || end == nullptr || *end != '\0')
+                    throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: cannot read '" + v + "'"};
+            }
+            po.beam_hardening = true;
+        }
+
+        // --fit-beam-hardening N[:SLICES[:MARGIN]] as typed; refuses anything but one to three unsigned numbers
+        inline auto parse_fit_beam_hardening(const std::string& v, program_options& po) -> void
+        {
+            const auto field = colon_fields(v);
+            std::uint32_t value[3] = {0u, 32u, 2u};
+            if(field.empty() || field.size() > 3u)
+                throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: cannot read '" + v + "'"};
+            for(std::size_t k = 0; k < field.size(); ++k)
+            {
+                if(field[k].empty() || field[k].size() > 9u || field[k].find_first_not_of("0123456789") != std::string::npos)
+                    throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: cannot read '" + v + "'"};
+                value[k] = static_cast<std::uint32_t>(std::stoul(field[k]));
+            }
+            po.bh = paris_hip_beam_hardening{};
+            po.bh.degree = value[0];
+            po.bh_slices = value[1];
+            po.bh_margin = value[2];
+            po.fit_beam_hardening = true;
+        }
+
+        // --beam-hardening / --fit-beam-hardening: checked here, before any device work. The fit's pre-pass reads whole frames of the
+        // detector the reconstruction sees: it has no full-width slots to bin from, so --bin is refused with it.
+        inline auto check_beam_hardening(const program_options& po) -> void
+        {
+            if(po.beam_hardening && po.fit_beam_hardening)
+                throw stage_construction_error{"--beam-hardening and --fit-beam-hardening cannot be combined: give the coefficients or have them fitted"};
+            if(po.beam_hardening && paris_hip_beam_hardening_check(&po.bh) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: every coefficient must be finite"};
+            if(!po.fit_beam_hardening)
+                return;
+            if(po.bh.degree < 1u || po.bh.degree > PARIS_HIP_BH_DEGREE_MAX || po.bh_slices < 1u || po.bh_margin > PARIS_HIP_BH_MARGIN_MAX)
+                throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: N must lie in 1 .. 4, SLICES must be at least 1 and MARGIN in 0 .. 4 (got "
+                                               + std::to_string(po.bh.degree) + ":" + std::to_string(po.bh_slices) + ":" + std::to_string(po.bh_margin) + ")"};
+            if(po.bh_slices < 2u * po.bh_margin + 1u)
+                throw stage_construction_error{"--fit-beam-hardening: " + std::to_string(po.bh_slices) + " slice(s) hold no voxel with a margin of "
+                                               + std::to_string(po.bh_margin) + " on both sides"};
+            if(po.binning())
+                throw stage_construction_error{"--fit-beam-hardening cannot be combined with --bin: its pre-pass reads the frames at the detector's size"};
+            if(po.axis_only)
+                throw stage_construction_error{"--fit-beam-hardening cannot be combined with --axis-only: nothing would be fitted"};
+        }
+
+        // --fit-beam-hardening: the pre-pass, after the ring pre-pass and the axis search, whose results it uses. Every projection the
+        // run uses is read once on the first device, whole, in groups of po.batch frames as the main loop groups them; each group goes
+        // N times through the main loop's frame stages -- the raw upload (corrected with --flat), the air normalisation, the defect
+        // repair, the zinger filter, the ring correction -- then, the k-th time, through the pass with the unit setting e_k, the
+        // redundancy weights, weight + filter and the backprojection into the k-th basis slab: the central po.bh_slices slices of the
+        // whole volume. (The group is uploaded again for each k from the pinned frames, which are read once: no device copy of it is
+        // kept.) Then threshold, labels, Gram sums and the solve. Everything allocated here is freed before it
+        // returns: run() plans the slabs afterwards.
+        inline auto bh_prepass(const program_options& po, run_report& r) -> void
+        {
+            const auto t_start = clock::now();
+            const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+            const auto& vg = r.vol_geo;
+            const std::uint32_t degree = po.bh.degree, slices = po.bh_slices, z_first = (vg.dim_z - slices) / 2u;
+            const std::uint32_t batch = slot_shape(po).first;
+            if(static_cast<std::uint64_t>(n_col) * batch > 0xffffffffull)
+                throw stage_construction_error{"too many projection slots for this detector"};
+            paris_hip_ctx* ctx = nullptr;
+            rt(paris_hip_ctx_create(0, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
+            auto h_buf = std::vector<float*>(batch, nullptr);
+            auto infos = std::vector<frame_info>(batch);
+            float* d_all = nullptr;
+            float* d_slab[PARIS_HIP_BH_DEGREE_MAX] = {nullptr, nullptr, nullptr, nullptr};
+            std::uint8_t* d_labels = nullptr;
+            const auto cleanup = [&] {
+                for(auto h : h_buf)
+                    paris_hip_free_host(ctx, h);
+                paris_hip_free(ctx, d_all);
+                for(auto d : d_slab)
+                    paris_hip_free(ctx, d);
+                paris_hip_free(ctx, d_labels);
+                paris_hip_ctx_destroy(ctx);
+            };
+            try
+            {
+                auto rep = device_report{};
+                set_frame_chain(ctx, po, rep);
+                if(po.ring_c)
+                    rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), n_row, n_col), "set_ring_correction()");
+                if(po.extend_rows)
+                {
+                    const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
+                    rt(paris_hip_set_row_extension(ctx, &setting), "set_row_extension()");
+                }
+                rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
+                std::size_t d_pitch = 0;
+                rt(paris_hip_malloc_projection(ctx, n_row, n_col * batch, &d_all, &d_pitch), "make_projection_device()");
+                const auto d_stride = d_pitch * n_col;
+                for(auto& h : h_buf)
+                {
+                    void* p = nullptr;
+                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(n_row) * n_col * sizeof(float), &p), "make_projection_host()");
+                    h = static_cast<float*>(p);
+                }
+                for(std::uint32_t k = 0; k < degree; ++k)
+                    rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, slices, &d_slab[k]), "make_volume()");
+                {
+                    float* words = nullptr; // the labels: one byte per voxel, in memory of the volume allocator
+                    const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
+                    if((voxels + 3u) / 4u > 0xffffffffull)
+                        throw stage_construction_error{"--fit-beam-hardening: the slab holds too many voxels"};
+                    rt(paris_hip_malloc_volume(ctx, static_cast<std::uint32_t>((voxels + 3u) / 4u), 1u, 1u, &words), "make_volume()");
+                    d_labels = reinterpret_cast<std::uint8_t*>(words);
+                }
+                const bool repair = rep.defect_map;
+                const float delta_s = po.det_geo.delta_s * po.det_geo.l_px_row, delta_t = po.det_geo.delta_t * po.det_geo.l_px_col;
+                const auto no_roi = region_of_interest{};
+                auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
+                std::uint32_t frames = 0;
+                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
+                for(bool more = true; more;)
+                {
+                    std::uint32_t filled = 0;
+                    for(; filled < batch; ++filled)
+                    {
+                        infos[filled] = source.next_raw(h_buf[filled], n_row, n_col, 0u, n_col);
+                        const auto& p = infos[filled];
+                        if(!p.valid())
+                        {
+                            more = false;
+                            break;
+                        }
+                        if(p.dim_x != n_row || p.dim_y != n_col)
+                            throw stage_runtime_error{"projection size does not match the detector geometry"};
+                        angles[filled] = po.enable_angles ? p.phi : static_cast<float>(p.idx) * po.det_geo.delta_phi;
+                        rt(paris_hip_stage_angle(&po.det_geo, p.idx, po.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle");
+                    }
+                    if(filled == 0)
+                        break;
+                    for(std::uint32_t k = 0; k < degree; ++k)
+                    {
+                        for(std::uint32_t f = 0; f < filled; ++f)
+                        {
+                            auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * f);
+                            const auto px = his::pixel_size(infos[f].pixel);
+                            if(po.flat)
+                                rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, 0u, n_col,
+                                                                             infos[f].pixel), "load()");
+                            else
+                                rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, infos[f].pixel), "load()");
+                        }
+                        if(po.air)
+                            rt(paris_hip_air_normalize_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "air normalisation");
+                        if(repair)
+                            rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "defect repair");
+                        if(po.zingers)
+                            rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "zinger filter");
+                        if(po.ring_c)
+                            rt(paris_hip_ring_correct_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring correction");
+                        auto unit = paris_hip_beam_hardening{};
+                        unit.degree = k + 1u;
+                        unit.c[k] = 1.f;
+                        rt(paris_hip_beam_hardening_rows_with(ctx, &unit, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "beam hardening");
+                        if(po.offset_detector)
+                            rt(paris_hip_offset_detector_weight_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo),
+                               "offset-detector weight()");
+                        if(po.short_scan)
+                            rt(paris_hip_short_scan_weight_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo, &po.scan,
+                                                                angles.data()), "short-scan weight()");
+                        rt(paris_hip_stage_weight_filter_batch(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo, nullptr, 0u, 0u),
+                           "weight() + filter()");
+                        rt(paris_hip_backproject_batch(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, d_slab[k], vg.dim_x, vg.dim_y, slices, z_first,
+                                                       &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
+                        rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the device frames are free for the next basis or group
+                    }
+                    frames += filled;
+                }
+                if(frames == 0u)
+                    throw stage_runtime_error{"--fit-beam-hardening: the input holds no projection"};
+                const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
+                auto stats = paris_hip_volume_statistics{};
+                rt(paris_hip_volume_stats(ctx, d_slab[0], voxels, 0.f, 0.f, 0u, nullptr, &stats), "volume_stats()");
+                auto hist = std::vector<std::uint64_t>(PARIS_HIP_BH_HISTOGRAM_BINS);
+                if(paris_hip_volume_stats(ctx, d_slab[0], voxels, stats.min, stats.max, PARIS_HIP_BH_HISTOGRAM_BINS, hist.data(), &stats) != PARIS_HIP_SUCCESS
+                   || paris_hip_bh_threshold_from_histogram(hist.data(), PARIS_HIP_BH_HISTOGRAM_BINS, stats.min, stats.max, &r.bh_threshold) != PARIS_HIP_SUCCESS)
+                    throw stage_runtime_error{"--fit-beam-hardening: the reconstruction of the scan has no range of values to take a threshold from"};
+                rt(paris_hip_bh_classify(ctx, d_slab[0], vg.dim_x, vg.dim_y, slices, r.bh_threshold, po.bh_margin, d_labels), "bh_classify()");
+                double gram[(PARIS_HIP_BH_DEGREE_MAX + 1) * (PARIS_HIP_BH_DEGREE_MAX + 2) / 2];
+                rt(paris_hip_bh_gram(ctx, d_slab, degree, d_labels, voxels, gram, &r.bh_counts), "bh_gram()");
+                rt(paris_hip_bh_solve(gram, degree, &r.bh_counts, 0u, &r.bh_fit), "--fit-beam-hardening: bh_solve()");
+                r.bh_fitted = true;
+                r.bh_frames = frames;
+                r.bh_slice_first = z_first;
+                r.bh_slices = slices;
+            }
+            catch(...)
+            {
+                cleanup();
+                throw;
+            }
+            cleanup();
+            r.bh_prepass_s = since(t_start);
+        }
+
         // --find-axis LO:HI[:STEP] as typed; refuses anything but two or three numbers
         inline auto parse_find_axis(const std::string& v, program_options& po) -> void
         {
@@ -1879,6 +2130,7 @@ namespace paris
         detail::check_rings(po);
         detail::check_voxels(po);
         detail::check_axis(po);
+        detail::check_beam_hardening(po);
         if(po.find_axis)
         {
             // before anything is derived from delta_s: the offset-detector check, the short-scan check and the volume geometry below
@@ -1906,6 +2158,9 @@ namespace paris
         r.roi_geo = r.vol_geo;
         if(po.enable_roi)                                  // :124-130
             r.roi_geo = apply_roi(r.vol_geo, po.roi.x1, po.roi.x2, po.roi.y1, po.roi.y2, po.roi.z1, po.roi.z2);
+        if(po.fit_beam_hardening && po.bh_slices > r.vol_geo.dim_z)
+            throw stage_construction_error{"--fit-beam-hardening: the volume has " + std::to_string(r.vol_geo.dim_z) + " slice(s), fewer than the "
+                                           + std::to_string(po.bh_slices) + " asked for"};
 
         int n_dev = 0;
         detail::rt(paris_hip_device_count(&n_dev), "get_devices()"); // :145
@@ -1920,6 +2175,14 @@ namespace paris
         r.batch = po.batch;
         if(po.rings && !po.find_axis) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
             detail::prepass(po, r, true, false);
+        if(po.fit_beam_hardening) // after the ring pre-pass and the axis search, whose results it uses; its slabs are gone before the run's are planned
+        {
+            detail::bh_prepass(po, r);
+            po.bh = r.bh_fit.setting;
+            po.beam_hardening = true;
+        }
+        r.beam_hardening = po.beam_hardening;
+        r.bh = po.bh;
 
         if(po.slabs > 0) // fixed split (src/cuda/subvolume_information.cpp:112-116 with a given count)
         {

@@ -84,6 +84,11 @@ namespace paris
         if(backend::detail::has_ring_correction(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_ring_correct_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                        p.dim_y, 0u, p.dim_y), "weight()");
+        // then with a beam-hardening setting (backend::set_beam_hardening) the polynomial of the line integral: the last step that is
+        // not linear in it, so before every weight
+        if(backend::detail::has_beam_hardening(backend::current_ctx()))
+            backend::detail::runtime_check(paris_hip_beam_hardening_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
+                                                                         p.dim_y, 0u, p.dim_y), "weight()");
         if(backend::detail::has_offset_detector(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_stage_offset_detector_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                                                   p.dim_y, &det_geo), "weight()");
