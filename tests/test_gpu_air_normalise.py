@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import air_rule as A
+import grid_cap_rule as G
 from paris_amd import _lib
 from paris_amd import backend as B
 from test_gpu_ring_correction import LAYOUTS, ORD_GEO, Stack, bits, pending, read, volume_to_host
@@ -110,6 +111,34 @@ def test_vector_and_single_pixel_subtraction_over_more_than_one_block(be, dim_x)
     frames = A.scan(dim_x, 70, 3, seed=dim_x)
     for layout in LAYOUTS:
         assert_measure_and_normalise(be, frames, rect, layout, what=(dim_x, layout))
+
+
+@pytest.mark.parametrize("dim_x", G.DIM_XS)
+def test_a_band_past_the_grid_cap(be, dim_x):
+    """1024 rows of 1025 pixels, or of 4100 in groups of four: 1 049 600 lanes against the subtraction's cap of 4096 blocks of 256,
+    so four blocks come round again and split their lane index a second time, into the band's final row. Two frames a stride larger
+    than the frame apart, a small rectangle in a corner; rows 0 .. 2 and 1027 .. 1029, the pitch padding and the gap keep their bits"""
+    assert G.lanes(dim_x, dim_x % 4 == 0) > G.CAP_LANES
+    rect = (dim_x - 9, 1, 8, 5)
+    frames = A.scan(dim_x, G.DIM_Y, 2, seed=dim_x)
+    a, cnt, whys = A.values(frames, rect)
+    assert whys == ["normalised"] * 2 and (np.abs(a) > 1e-3).all() and a[0] != a[1]
+    first, count = G.BAND
+    s = G.Canvas(be, frames)
+    be.set_air_region(*rect, dim_x, G.DIM_Y)
+    try:
+        got_a, got_n = be.air_measure(s.first, frame_stride=s.stride, n_frames=2)
+        assert A.same_bits(got_a, a) and np.array_equal(got_n, cnt)
+        be.air_normalize(s.first, frame_stride=s.stride, n_frames=2, rows=G.BAND)
+        got = s.read()
+        G.assert_canvas(s, got, s.expected([A.subtract(f, v, G.BAND)[first:first + count] for f, v in zip(frames, a)]), dim_x)
+        for k in range(2):   # the second visit wrote
+            tail_got, tail_was = G.second_visit(s, got, k), G.second_visit(s, s.before, k)
+            assert np.count_nonzero(bits(tail_got) != bits(tail_was)) > 0.99 * tail_was.size
+        assert A.stats_of(be.air_stats()) == A.counts_of(whys, a)
+    finally:
+        be.clear_air_region()
+        s.free()
 
 
 @pytest.mark.parametrize("rows,inside", [((0, 7), False), ((12, 8), False), ((5, 9), True), ((0, 20), True), ((6, 6), True),

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import beam_hardening_rule as R
+import grid_cap_rule as G
 from paris_amd import _lib
 from paris_amd import backend as B
 from test_gpu_ring_correction import read
@@ -104,6 +105,35 @@ def test_whole_frames_over_more_than_one_block(be, dim_x):
     frames = [R.special_pixels((70, dim_x), seed=dim_x + k) for k in range(5)]
     assert_pass(be, frames, 0, R.COEFFICIENTS[3], (0, 70), True, dim_x)
     assert_pass(be, frames[:2], 0, R.COEFFICIENTS[4], (69, 1), False, dim_x)
+
+
+@pytest.mark.parametrize("dim_x", G.DIM_XS)
+def test_a_band_past_the_grid_cap(be, dim_x):
+    """1024 rows of 1025 pixels, or of 4100 in groups of four: 1 049 600 lanes against the cap of 4096 blocks of 256, so four blocks
+    come round again and split their lane index a second time, into the band's final row. Two frames a stride larger than the frame
+    apart; rows 0 .. 2 and 1027 .. 1029, the pitch padding and the gap keep their bits. The setting form, then the argument form on
+    what it left."""
+    assert G.lanes(dim_x, dim_x % 4 == 0) > G.CAP_LANES
+    frames = [R.special_pixels((G.DIM_Y, dim_x), seed=dim_x + k) for k in range(2)]
+    first, count = G.BAND
+    s = G.Canvas(be, frames)
+    try:
+        assert s.first.ptr % 16 == 0 and s.stride % 16 == 0 and s.stride > s.pitch * G.DIM_Y   # dim_x alone decides the path
+        c = R.COEFFICIENTS[3]
+        be.set_beam_hardening(c, dim_x, G.DIM_Y)
+        be.beam_hardening(s.first, frame_stride=s.stride, n_frames=2, rows=G.BAND)
+        once = [B.beam_hardening_host(c, f[first:first + count]) for f in frames]
+        got = s.read()
+        G.assert_canvas(s, got, s.expected(once), (dim_x, "setting"))
+        for k in range(2):   # the second visit wrote: nearly every pixel there differs from what it was
+            tail_got, tail_was = G.second_visit(s, got, k), G.second_visit(s, s.before, k)
+            assert np.count_nonzero(R.bits(tail_got) != R.bits(tail_was)) > 0.9 * tail_was.size
+        be.beam_hardening(s.first, frame_stride=s.stride, n_frames=2, rows=G.BAND, c=R.COEFFICIENTS[2])
+        twice = [B.beam_hardening_host(R.COEFFICIENTS[2], q) for q in once]
+        G.assert_canvas(s, s.read(), s.expected(twice), (dim_x, "argument"))
+    finally:
+        be.clear_beam_hardening()
+        s.free()
 
 
 def test_an_empty_band_and_no_frame_do_nothing(be):

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_cap_rule as G
 import phantom
 import test_gpu_paris_hip as P
 from oracle import formats as F
@@ -165,6 +166,46 @@ def test_fused_upload_equals_raw_upload_and_in_place_pass_on_row_bands(be, dtype
                 assert_formula(ga, expected(full[r0:r0 + n], dark[r0:r0 + n], flat[r0:r0 + n], 1e-5), (tight, r0))
                 be.free(oa)
                 be.free(ob)
+    finally:
+        be.clear_flat_field()
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.float32])
+@pytest.mark.parametrize("dim_x", G.WIDEN_DIM_XS)
+def test_fused_upload_of_more_rows_than_the_widening_grid_has_blocks(be, dtype, dim_x):
+    """4100 rows from detector row 3 on against WIDEN_MAX_BLOCKS = 2048: every block comes round for a second row, four of them for a
+    third, and reads the references of that row. 5 pixels a row: one per lane; 8: whole 16-byte vectors. The contract in float64
+    rounded once, bit for bit (as tests/test_gpu_binning.py holds its chain: on these seeded pixels the device's double logarithm
+    rounds to the fp32 value numpy's does); the in-place pass on a raw upload gives the same bits; rows 0 .. 2 and the padding of every row are not written"""
+    r0, n = 3, G.WIDEN_ROWS
+    dim_y = n + r0
+    top = {np.uint8: 255.0, np.uint16: 65535.0, np.uint32: 4e9, np.float32: 1e4}[dtype]
+    rng = np.random.default_rng(dim_x)
+    dark = (0.02 * top * (1 + rng.random((dim_y, dim_x)))).astype(np.float32)
+    flat = (dark + 0.8 * top * (0.6 + 0.5 * rng.random((dim_y, dim_x)))).astype(np.float32)
+    flat[dim_y - 1, dim_x - 1] = dark[dim_y - 1, dim_x - 1]          # a dead pixel at the very end: 0
+    t_min = 1e-5 if dtype != np.uint8 else 0.01
+    full = counts(dtype, dark, flat, 4, t_min)
+    want = expected(full[r0:], dark[r0:], flat[r0:], t_min)
+    assert want[-1, -1] == 0 and np.count_nonzero(want) > 0.9 * want.size
+    sentinel = np.uint32(0x7FC0BEEF)
+    be.set_flat_field(dark, flat, t_min)
+    try:
+        a, b = be.make_projection_device(dim_x, dim_y), be.make_projection_device(dim_x, dim_y)
+        wide = B.Projection(a.ptr, a.pitch // 4, dim_y, pitch=a.pitch, on_device=True)
+        assert a.pitch > 4 * dim_x
+        be.copy_h2d(B.Projection(np.full((dim_y, a.pitch // 4), sentinel, np.uint32).view(np.float32), a.pitch // 4, dim_y), wide)
+        be.upload_raw(full[r0:], a, row_first=r0, corrected=True)
+        be.upload_raw(full[r0:], b, row_first=r0)
+        be.flat_field_rows(b, row_first=r0, row_count=n)
+        h = be.make_projection_host(a.pitch // 4, dim_y)
+        be.copy_d2h(wide, h)
+        got = bits(h.buf)
+        assert np.array_equal(got[r0:, :dim_x], bits(want))
+        assert np.array_equal(bits(read(be, b)[r0:]), got[r0:, :dim_x])
+        assert np.all(got[:r0] == sentinel) and np.all(got[:, dim_x:] == sentinel)
+        be.free(a)
+        be.free(b)
     finally:
         be.clear_flat_field()
 

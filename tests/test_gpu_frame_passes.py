@@ -1,7 +1,8 @@
 """The ordering contract every in-place frame pass obeys, pinned once per pass: the
-Parker weight, the offset-detector weight, the flat-field rows pass and the defect repair. A held-back weighting runs first, a frame of
-the pending by-reference group is backprojected as it was, a call with nothing to launch launches nothing, and the common argument
-rule refuses the same frame and band descriptions everywhere. Shapes and geometry are those of tests/test_gpu_defect_map.py."""
+Parker weight, the offset-detector weight, the flat-field rows pass, the defect repair and both forms of the beam-hardening pass (its
+setting, and the rule as an argument). A held-back weighting runs first, a frame of the pending by-reference group is backprojected
+as it was, a call with nothing to launch launches nothing, and the common argument rule refuses the same frame and band descriptions
+everywhere. Shapes and geometry are those of tests/test_gpu_defect_map.py."""
 import ctypes as C
 
 import numpy as np
@@ -62,11 +63,25 @@ def _defect_raw(be, ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count):
     return be._L.paris_hip_defect_repair_rows(be._ctx, ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count)
 
 
+BH_C = [0.93, 0.11]              # q = 0.93 p + 0.11 p^2: changes every pixel that is not zero
+
+
+def _bh_raw(be, ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count):
+    return be._L.paris_hip_beam_hardening_rows(be._ctx, ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count)
+
+
+def _bh_with_raw(be, ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count):
+    rule = B._bh_setting(BH_C)
+    return be._L.paris_hip_beam_hardening_rows_with(be._ctx, C.byref(rule), ptr, pitch, stride, n, dim_x, dim_y, row_first, row_count)
+
+
 PASSES = [
     Pass("parker", lambda be: None, lambda be, d: be.short_scan_weight(d, _det(), SCAN, PHI), _parker_raw),
     Pass("offset_detector", lambda be: None, lambda be, d: be.offset_detector_weight(d, _det()), _offset_raw),
     Pass("flat_field", lambda be: be.set_flat_field(DARK, FLAT), lambda be, d: be.flat_field_rows(d), _flat_raw),
     Pass("defect_repair", lambda be: be.set_defect_map(MASK), lambda be, d: be.defect_repair_rows(d), _defect_raw),
+    Pass("beam_hardening", lambda be: be.set_beam_hardening(BH_C, DIM_X, DIM_Y), lambda be, d: be.beam_hardening(d), _bh_raw),
+    Pass("beam_hardening_with", lambda be: None, lambda be, d: be.beam_hardening(d, c=BH_C), _bh_with_raw),
 ]
 each_pass = pytest.mark.parametrize("p", PASSES, ids=repr)
 

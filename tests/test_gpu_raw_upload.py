@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_cap_rule as G
 import test_gpu_paris_hip as P
 from oracle import formats as F
 from paris_amd import _lib
@@ -95,6 +96,24 @@ def test_bit_exact_widening(be, dtype, dim_x, wrapped, padded):
     be.free(d)
     if wrapped:
         be.free(v)
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.float32])
+@pytest.mark.parametrize("dim_x", G.WIDEN_DIM_XS)
+def test_more_rows_than_the_widening_grid_has_blocks(be, dtype, dim_x):
+    """4100 rows against WIDEN_MAX_BLOCKS = 2048: every block comes round for a second row, four of them for a third. 5 pixels a row:
+    one per lane; 8: whole 16-byte vectors of every stored type. Rows 0 .. 2 of the buffer and the padding of every row are not written"""
+    assert G.WIDEN_ROWS > 2 * 2048
+    r0, dim_y = 3, G.WIDEN_ROWS + 3
+    h = values(dtype, G.WIDEN_ROWS, dim_x, dim_x)
+    d = be.make_projection_device(dim_x, dim_y)
+    assert d.pitch > 4 * dim_x
+    fill(be, d.ptr, d.pitch, dim_y)
+    be.upload_raw(h, d, row_first=r0)
+    got = read_rows(be, d.ptr, d.pitch, dim_y)
+    assert np.array_equal(got[r0:, :dim_x], bits(h.astype(np.float32)))
+    assert np.all(got[:r0] == SENTINEL) and np.all(got[:, dim_x:] == SENTINEL)
+    be.free(d)
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32])

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_cap_rule as G
 import ring_rule as R
 import test_gpu_flat_field as FF
 import test_gpu_paris_hip as P
@@ -106,6 +107,31 @@ def test_more_than_one_block(be, dim_x):
         be.ring_profile_begin(dim_x, 70)
         be.ring_profile_add_rows(s.first, frame_stride=s.stride, n_frames=2)
         assert_finish_equals_rule(be, frames, 2, what=(dim_x, layout))
+        s.free()
+
+
+@pytest.mark.parametrize("dim_x", G.DIM_XS)
+def test_sums_of_a_band_past_the_grid_cap(be, dim_x):
+    """1024 rows of 1025 pixels, or of 4100 in groups of four: 1 049 600 lanes against the cap of 4096 blocks of 256, so four blocks
+    come round again and split their lane index a second time, into the band's final row. Two frames a stride larger than the frame
+    apart; the frames, the rows around the band, the pitch padding and the gap are only read"""
+    assert G.lanes(dim_x, dim_x % 4 == 0) > G.CAP_LANES
+    frames = R.scan(dim_x, G.DIM_Y, 2, seed=dim_x)
+    first, count = G.BAND
+    counts = np.zeros(G.DIM_Y, np.uint32)
+    counts[first:first + count] = 2
+    s = G.Canvas(be, frames)
+    try:
+        be.ring_profile_begin(dim_x, G.DIM_Y)
+        be.ring_profile_add_rows(s.first, row_first=first, row_count=count, frame_stride=s.stride, n_frames=2)
+        c, mean, st = assert_finish_equals_rule(be, frames, counts, what=dim_x)
+        assert (st.frames_min, st.frames_max) == (0, 2)
+        assert not mean[:first].any() and not mean[first + count:].any()      # no sum landed in a row outside the band
+        last = mean[first + count - 1]
+        assert (last > 1).all() and c[first + count - 1, dim_x // 3] != 0      # the second visit added, up to the final column
+        assert np.array_equal(G.bits(s.read()), G.bits(s.before))
+    finally:
+        be.ring_profile_discard()
         s.free()
 
 
@@ -247,6 +273,37 @@ def test_correct_rows_equals_p_minus_c_and_leaves_the_rest_alone(be, dim_x, dim_
         s.free()
     finally:
         be.clear_ring_correction()
+
+
+@pytest.mark.parametrize("dim_x", G.DIM_XS)
+def test_correct_rows_of_a_band_past_the_grid_cap(be, dim_x):
+    """the shapes of test_sums_of_a_band_past_the_grid_cap: the correction is non-zero in the lanes of the second visit as well -- in
+    the band's final row up to the final columns, as a whole group of four and as single pixels of a group -- and in the rows around the
+    band, which must not be written"""
+    frames, c = scan_correction(dim_x, G.DIM_Y, n=2, seed=dim_x)
+    first, count = G.BAND
+    last = first + count - 1
+    c[last, dim_x - 4:] = [0.5, -0.25, 0.125, 1.0]          # the final group of four: the 16-byte store
+    c[last, dim_x - 8:dim_x - 4] = [0.375, 0, 0, -0.375]    # a group with two corrections: single stores
+    c[last, dim_x - 1024] = -0.5                             # the first pixel every shape's second visit serves
+    assert c[:first].any() and c[last + 1:].any() and np.count_nonzero(c[last, dim_x - 1024:]) >= 7
+    quiet = np.argwhere(c[first:last + 1] == 0)[::100003]    # pixels of the band without a correction keep every bit
+    for k, (y, x) in enumerate(quiet):
+        frames[k % 2].view(np.uint32)[first + y, x] = R.NAN_PAYLOAD + k
+    be.set_ring_correction(c)
+    s = G.Canvas(be, frames)
+    try:
+        be.ring_correct_rows(s.first, row_first=first, row_count=count, frame_stride=s.stride, n_frames=2)
+        got = s.read()
+        G.assert_canvas(s, got, s.expected([R.subtract(f, c)[first:last + 1] for f in frames]), dim_x)
+        for k in range(2):
+            band_got, band_was = s.frame_of(got, k)[first:last + 1], frames[k][first:last + 1]
+            assert np.array_equal(bits(band_got)[c[first:last + 1] == 0], bits(band_was)[c[first:last + 1] == 0]), "NaN payloads included"
+            tail = bits(band_got[-1, dim_x - 1024:]) != bits(band_was[-1, dim_x - 1024:])
+            assert np.array_equal(tail, c[last, dim_x - 1024:] != 0)      # the second visit wrote exactly the corrected pixels
+    finally:
+        be.clear_ring_correction()
+        s.free()
 
 
 def pending(be):
