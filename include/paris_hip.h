@@ -743,8 +743,8 @@ int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, si
  *   off = (1/2) (J[m-1] - J[m+1]) / q, clamped to [-1/2, 1/2], and delta_s = (float)(c_m + off step), in double.
  *   Otherwise delta_s = c_m and at_edge = 1.
  *   The median reported is the lower one: the ((s - 1) / 2 + 1)-th smallest of the s scored J.
- * Limits: the mid-plane only -- the cone angle across the R rows is ignored; a full equidistant circle; detector tilt and in-plane
- * rotation are not estimated. */
+ * Limits: the mid-plane only -- the cone angle across the R rows is ignored; a full equidistant circle; detector tilt is not
+ * estimated. The detector's in-plane rotation is found by a search of its own, paris_hip_roll_search_run below. */
 typedef struct paris_hip_axis_search {
     float lo;             /* the first candidate [px] */
     float step;           /* the distance between candidates [px], > 0 */
@@ -867,6 +867,113 @@ int paris_hip_clear_binning(paris_hip_ctx* ctx);
 int paris_hip_bin_frames(paris_hip_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
                          size_t dst_frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y, uint32_t row_first,
                          uint32_t row_count);
+/* Extension (no reference counterpart): correction of the detector's in-plane rotation ("roll", eta) about its normal -- every
+ * frame is resampled onto a detector whose rows are perpendicular to the projected rotation axis, after every correction that is
+ * stationary in detector coordinates and before the redundancy weights and the row filter. One definition;
+ * the device (paris_hip_detector_roll_rows) and the host (paris_hip_detector_roll_host) both implement it and give the same bits.
+ * Setting paris_hip_detector_roll { float eta_deg; }. eta_deg is finite, nonzero and |eta_deg| <= 10; "no roll" is no setting.
+ *   The detector needs n_row >= 2 and n_col >= 2, l_px_row, l_px_col > 0 and finite, delta_s and delta_t finite.
+ * Constants, each computed on the host in double and rounded to float once: eta = eta_deg pi / 180, rho = l_px_col / l_px_row,
+ *   cx = n_row / 2 + delta_s - 1/2, cy = n_col / 2 + delta_t - 1/2 (the axis column of the axis search and its band's centre row),
+ *   a = cos eta, b = -sin eta rho, c = sin eta / rho, d = cos eta: a rotation in millimetres about (cx, cy).
+ * Output pixel (i, j) -- column i, row j -- of a frame p, all in fp32, each operation rounded once, no contraction:
+ *   di = (float)i - cx, dj = (float)j - cy;
+ *   x = (a di + b dj) + cx, y = (c di + d dj) + cy (two products, their sum, then the centre);
+ *   x is clamped to [0, n_row - 1] and y to [0, n_col - 1] (x < 0 becomes 0, x > n_row - 1 becomes n_row - 1): the edge is replicated;
+ *   i0 = min((int)floor(x), n_row - 2), wx = x - (float)i0; j0 = min((int)floor(y), n_col - 2), wy = y - (float)j0;
+ *   top = p[j0][i0] + wx (p[j0][i0 + 1] - p[j0][i0]); bot is the same on row j0 + 1; out = top + wy (bot - top).
+ *   A tap that is not finite propagates by this arithmetic alone.
+ * Source rows of a destination band. Every step is monotone in i and in j, so the extremes of y over a band lie at its four
+ *   corner pixels: the band reads rows min j0 .. max j0 + 1 over the corners (paris_hip_detector_roll_source_rows), exactly. */
+typedef struct paris_hip_detector_roll {
+    float eta_deg; /* the detector's in-plane rotation [deg], nonzero, |eta_deg| <= 10 */
+} paris_hip_detector_roll;
+/* Host only, no ctx and no device. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting or geometry or for what the rule excludes. */
+int paris_hip_detector_roll_check(const paris_hip_detector_roll* setting, const paris_detector_geometry* det_geo);
+/* Host only: the rule on one dense frame -- src and dst n_col rows of n_row floats, which must not overlap. The single host
+ * implementation. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL src or dst. */
+int paris_hip_detector_roll_host(const paris_hip_detector_roll* setting, const paris_detector_geometry* det_geo, const float* src,
+                                 float* dst);
+/* Host only: the source rows [*src_first, *src_first + *src_count) that destination rows [row_first, row_first + row_count) read.
+ * An empty band gives (row_first clamped to n_col - 1, 0). PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, for a band outside n_col or
+ * a NULL pointer. */
+int paris_hip_detector_roll_source_rows(const paris_hip_detector_roll* setting, const paris_detector_geometry* det_geo, uint32_t row_first,
+                                        uint32_t row_count, uint32_t* src_first, uint32_t* src_count);
+/* paris_hip_set_detector_roll runs the check and stores the setting with the geometry; nothing lives on the device.
+ * paris_hip_clear_detector_roll removes it (no error without one). Without a setting nothing else changes. */
+int paris_hip_set_detector_roll(paris_hip_ctx* ctx, const paris_hip_detector_roll* setting, const paris_detector_geometry* det_geo);
+int paris_hip_clear_detector_roll(paris_hip_ctx* ctx);
+/* Writes rows [row_first, row_first + row_count) of n_frames destination frames (dim_x x dim_y, rows dst_pitch bytes apart, frames
+ * dst_frame_stride bytes apart, d_dst the first frame's row 0) from source frames of the same size (src_pitch, src_frame_stride,
+ * d_src the first frame's row 0), of which only the rows paris_hip_detector_roll_source_rows names are read. Nothing else is
+ * written, bytes of a row past 4 dim_x included. A lane owns four adjacent pixels and stores them as one 16-byte vector where the
+ * destination's base, pitch and (n_frames > 1) stride are multiples of 16, single pixels otherwise and in a row's ragged last
+ * segment. A held-back weighting runs first; a source or destination frame of the pending by-reference group has that group
+ * launched first, and both bands are noted as used. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when dim_x / dim_y differ
+ * from the setting's n_row / n_col, for a band outside dim_y, for a pitch or stride paris_hip_flat_field_rows would refuse, or when
+ * the source and destination ranges overlap. _with takes the setting and the geometry as arguments; the ctx's own setting is neither
+ * used nor changed. */
+int paris_hip_detector_roll_rows(paris_hip_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
+                                 size_t dst_pitch, size_t dst_frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y,
+                                 uint32_t row_first, uint32_t row_count);
+int paris_hip_detector_roll_rows_with(paris_hip_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
+                                      size_t dst_pitch, size_t dst_frame_stride, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y,
+                                      uint32_t row_first, uint32_t row_count, const paris_hip_detector_roll* setting,
+                                      const paris_detector_geometry* det_geo);
+/* Finding the roll from the scan itself. Over a full circle a point at cylinder coordinates (r, phi0, z)
+ * is seen at detector position (t, v) in view phi0 - psi and at (-t, v) in view phi0 + psi: the scan mean of the line integrals is
+ * mirror-symmetric about the projected axis column in every detector row, whatever the object and the cone angle. A rolled detector
+ * tilts that line by eta; the cost of a candidate is the mean squared asymmetry of the mean frame rolled back by it.
+ * Setting paris_hip_roll_search { float lo_deg; float step_deg; uint32_t count; uint32_t min_pixels; }.
+ *   Candidates are eta_k = (float)((double)lo_deg + k (double)step_deg), k = 0 .. count - 1; 1 <= count <= 256; lo_deg finite;
+ *   step_deg > 0 and finite. Every candidate passes paris_hip_detector_roll_check or is exactly 0; a candidate of exactly 0 is
+ *   scored on the mean itself. min_pixels = 0 stands for n_row n_col / 16.
+ * Input. The scan mean M, n_col rows of n_row floats, of a full equidistant circle of line integrals on a centred detector: the
+ *   h_mean of paris_hip_ring_profile_finish.
+ * Margins keep replicated pixels out of the score. With the constants of candidate k as the pixel rule rounds them,
+ *   m_x = ceil(max_k(|b_k| max(cy, n_col - 1 - cy) + |1 - a_k| max(cx, n_row - 1 - cx))) + 1, in double, and m_y the same with c_k,
+ *   d_k and cx and cy exchanged. The rows scored are [m_y, n_col - m_y). 2 m_x >= n_row or 2 m_y >= n_col is refused.
+ * Mirror plan, on the host in double, once per search, with cx = n_row / 2 + delta_s - 1/2 in double: for column i,
+ *   ip = 2 cx - i, i0 = floor(ip), w = (float)(ip - i0); the column is valid iff m_x <= i <= n_row - 1 - m_x, m_x <= i0 and
+ *   i0 + 1 <= n_row - 1 - m_x.
+ * Score (device). R_k is M rolled by eta_k, by the kernel of paris_hip_detector_roll_rows. For every scored row j and valid column
+ *   i, in fp32, each operation rounded once: mir = R[j][i0] + w (R[j][i0 + 1] - R[j][i0]), dd = R[j][i] - mir. A dd that is not
+ *   finite is skipped and counted. J[k] = the sum of (double)dd (double)dd divided by the integer number of pairs summed. Every
+ *   partial sum has one owner and the partial sums are combined in a fixed order: two runs give the same bits. A candidate with
+ *   fewer than min_pixels pairs, or none, is unscored: J = +inf.
+ * Estimate: the rule of paris_hip_axis_estimate_from_costs -- both call one implementation.
+ * Limits: a full equidistant circle on a centred detector (not short or offset scans); out-of-plane tilts are not estimated. */
+typedef struct paris_hip_roll_search {
+    float lo_deg;        /* the first candidate [deg] */
+    float step_deg;      /* the distance between candidates [deg], > 0 */
+    uint32_t count;      /* candidates, 1 .. 256 */
+    uint32_t min_pixels; /* a candidate with fewer pairs is unscored; 0 = n_row n_col / 16 */
+} paris_hip_roll_search;
+typedef struct paris_hip_roll_result {
+    float eta_deg;      /* the estimate [deg] */
+    uint32_t best;      /* m: the index of the smallest scored J */
+    double cost_min;    /* J[m] */
+    double cost_median; /* the lower median of the scored J */
+    uint32_t scored;    /* candidates with a finite J */
+    uint32_t at_edge;   /* 1: no parabola -- the minimum is at an end, beside an unscored candidate, or not convex */
+    uint64_t skipped;   /* pairs whose difference was not finite, over all candidates (paris_hip_roll_search_run only) */
+    uint32_t margin_x;  /* m_x (paris_hip_roll_search_run only) */
+    uint32_t margin_y;  /* m_y (paris_hip_roll_search_run only) */
+} paris_hip_roll_result;
+/* Host only, no ctx and no device: checks a search for a detector and reports the margins and what the search occupies on the
+ * device while it runs (any pointer may be NULL). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting or geometry or for what the
+ * rule above excludes. */
+int paris_hip_roll_search_check(const paris_hip_roll_search* setting, const paris_detector_geometry* det_geo, uint32_t* margin_x,
+                                uint32_t* margin_y, size_t* device_bytes);
+/* Host only: the estimate from the `count` costs. Only lo_deg, step_deg and count are read; skipped and the margins are set to 0.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer, a count outside 1 .. 256, a lo_deg or step_deg the rule excludes, or when no
+ * candidate is scored (the result then has scored = 0). */
+int paris_hip_roll_estimate_from_costs(const paris_hip_roll_search* setting, const double* cost, paris_hip_roll_result* result);
+/* The search (paris_hip_roll_search_run; the setting has the plain name): runs the check, uploads h_mean into memory of its own, scores every candidate on the ctx stream, waits for it, fills
+ * cost[count] and pairs[count] (may be NULL), runs the estimate and frees its memory, whatever the estimate answers. The ctx's
+ * own roll setting is neither used nor changed. */
+int paris_hip_roll_search_run(paris_hip_ctx* ctx, const paris_hip_roll_search* setting, const paris_detector_geometry* det_geo,
+                              const float* h_mean, double* cost, uint64_t* pairs, paris_hip_roll_result* result);
 /* Extension (no reference counterpart): normalisation of every frame to an air region -- the flat is taken once, but the source's
  * output drifts from frame to frame; a frame taken at (1 + e) of the flat's flux comes out of the dark / flat correction as
  * p - ln(1 + e), a constant over the frame, which FDK turns into shading and streaks. A rectangle of the

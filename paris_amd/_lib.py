@@ -116,6 +116,23 @@ class AxisResult(C.Structure):
 AXIS_FRAMES_MAX = 64  # PARIS_HIP_AXIS_FRAMES_MAX
 
 
+class DetectorRoll(C.Structure):
+    """paris_hip_detector_roll: the detector's in-plane rotation [deg] (extension)"""
+    _fields_ = [("eta_deg", C.c_float)]
+
+
+class RollSearch(C.Structure):
+    """paris_hip_roll_search: the candidates of the roll search (extension)"""
+    _fields_ = [("lo_deg", C.c_float), ("step_deg", C.c_float), ("count", C.c_uint32), ("min_pixels", C.c_uint32)]
+
+
+class RollResult(C.Structure):
+    """paris_hip_roll_result: the estimate of the roll search (extension)"""
+    _fields_ = [("eta_deg", C.c_float), ("best", C.c_uint32), ("cost_min", C.c_double), ("cost_median", C.c_double),
+                ("scored", C.c_uint32), ("at_edge", C.c_uint32), ("skipped", C.c_uint64), ("margin_x", C.c_uint32),
+                ("margin_y", C.c_uint32)]
+
+
 class AirRegion(C.Structure):
     """paris_hip_air_region: the rectangle of the detector that sees only air, and when a frame is not normalised (extension)"""
     _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("min_pixels", C.c_uint32),
@@ -254,6 +271,17 @@ SIGNATURES = {
     "paris_hip_set_binning": (C.c_int, [_vp, _P(Binning), _vp, _u32, _u32]),
     "paris_hip_clear_binning": (C.c_int, [_vp]),
     "paris_hip_bin_frames": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_detector_roll_check": (C.c_int, [_P(DetectorRoll), _P(DetectorGeometry)]),
+    "paris_hip_detector_roll_host": (C.c_int, [_P(DetectorRoll), _P(DetectorGeometry), _vp, _vp]),
+    "paris_hip_detector_roll_source_rows": (C.c_int, [_P(DetectorRoll), _P(DetectorGeometry), _u32, _u32, _P(_u32), _P(_u32)]),
+    "paris_hip_set_detector_roll": (C.c_int, [_vp, _P(DetectorRoll), _P(DetectorGeometry)]),
+    "paris_hip_clear_detector_roll": (C.c_int, [_vp]),
+    "paris_hip_detector_roll_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_detector_roll_rows_with": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32, _P(DetectorRoll),
+                                                    _P(DetectorGeometry)]),
+    "paris_hip_roll_search_check": (C.c_int, [_P(RollSearch), _P(DetectorGeometry), _P(_u32), _P(_u32), _P(_sz)]),
+    "paris_hip_roll_estimate_from_costs": (C.c_int, [_P(RollSearch), _vp, _P(RollResult)]),
+    "paris_hip_roll_search_run": (C.c_int, [_vp, _P(RollSearch), _P(DetectorGeometry), _vp, _vp, _vp, _P(RollResult)]),
     "paris_hip_air_region_check": (C.c_int, [_P(AirRegion), _u32, _u32, _P(_u32), _P(_sz)]),
     "paris_hip_air_value_host": (C.c_int, [_P(AirRegion), _vp, _vp, _u32, _u32, _P(_f), _P(_u32)]),
     "paris_hip_set_air_region": (C.c_int, [_vp, _P(AirRegion), _vp, _u32, _u32]),

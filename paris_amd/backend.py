@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BeamHardening, BhCounts, BhFit, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (BeamHardening, BhCounts, BhFit, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -25,7 +25,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "VolumeStatistics", "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
            "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host",
            "BeamHardening", "BhCounts", "BhFit", "Labels", "BeamHardeningFit", "beam_hardening_check", "beam_hardening_host",
-           "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve"]
+           "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve", "DetectorRoll", "RollSearch", "RollResult",
+           "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs"]
 
 
 class Projection:
@@ -245,6 +246,52 @@ def bin_mask(bin_x, bin_y, mask):
     ox, oy = binning_check(bin_x, bin_y, m.shape[1], m.shape[0])
     bn, out = Binning(bin_x, bin_y), np.empty((oy, ox), np.uint8)
     check(_lib.load().paris_hip_bin_mask(C.byref(bn), m.ctypes.data, m.shape[1], m.shape[0], out.ctypes.data), "paris_hip_bin_mask")
+    return out
+
+
+def detector_roll_check(eta_deg, det_geo):
+    """Host only, no device (paris_hip_detector_roll_check): raises ParisHipError unless eta_deg is finite, nonzero and at most 10 in
+    magnitude and det_geo describes a detector of at least 2 x 2 pixels with positive pixel sizes and finite offsets."""
+    s = DetectorRoll(eta_deg)
+    check(_lib.load().paris_hip_detector_roll_check(C.byref(s), C.byref(det_geo)), "paris_hip_detector_roll_check")
+
+
+def detector_roll_host(eta_deg, det_geo, frame):
+    """Host only, no device (paris_hip_detector_roll_host): the roll rule on a 2-D array of the detector's size (n_col, n_row), taken
+    as float32 -- the frame resampled bilinearly, edge replicated, onto a detector rotated back by eta_deg about the projected axis
+    (DESIGN.md section 4.19). Returns a float32 array of the same shape."""
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.shape != (det_geo.n_col, det_geo.n_row):
+        raise ValueError("detector_roll_host: the frame must have the detector's size (n_col, n_row)")
+    s, out = DetectorRoll(eta_deg), np.empty_like(f)
+    check(_lib.load().paris_hip_detector_roll_host(C.byref(s), C.byref(det_geo), f.ctypes.data, out.ctypes.data), "paris_hip_detector_roll_host")
+    return out
+
+
+def detector_roll_source_rows(eta_deg, det_geo, row_first, row_count):
+    """Host only, no device (paris_hip_detector_roll_source_rows): (first, count) of the source rows that destination rows
+    [row_first, row_first + row_count) read."""
+    s, first, count = DetectorRoll(eta_deg), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().paris_hip_detector_roll_source_rows(C.byref(s), C.byref(det_geo), row_first, row_count, C.byref(first), C.byref(count)),
+          "paris_hip_detector_roll_source_rows")
+    return first.value, count.value
+
+
+def roll_search_check(lo, step, count, det_geo, min_pixels=0):
+    """Host only, no device (paris_hip_roll_search_check): checks a roll search -- candidates (float)(lo + k step) degrees, k < count
+    <= 256, each nonzero one a valid roll -- for det_geo's detector and returns (margin_x, margin_y, device_bytes)."""
+    s, mx, my, nbytes = RollSearch(lo, step, count, min_pixels), C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    check(_lib.load().paris_hip_roll_search_check(C.byref(s), C.byref(det_geo), C.byref(mx), C.byref(my), C.byref(nbytes)),
+          "paris_hip_roll_search_check")
+    return mx.value, my.value, nbytes.value
+
+
+def roll_estimate_from_costs(lo, step, cost):
+    """Host only, no device (paris_hip_roll_estimate_from_costs): the estimate from one cost per candidate -- the smallest scored
+    (finite) one, refined by the parabola through its neighbours; the rule of the axis search. Returns the RollResult."""
+    j = np.ascontiguousarray(cost, np.float64)
+    s, out = RollSearch(lo, step, j.size, 0), RollResult()
+    check(_lib.load().paris_hip_roll_estimate_from_costs(C.byref(s), j.ctypes.data, C.byref(out)), "paris_hip_roll_estimate_from_costs")
     return out
 
 
@@ -883,6 +930,53 @@ class Backend:
         count = dst.dim_y - row_first if row_count is None else row_count
         check(self._L.paris_hip_bin_frames(self._ctx, src.ptr, src.pitch, src_frame_stride, dst.ptr, dst.pitch, dst_frame_stride, n_frames,
                                            src.dim_x, src.dim_y, row_first, count), "paris_hip_bin_frames")
+
+    # ---- detector roll -----------------------------------------------------------
+    detector_roll_check = staticmethod(detector_roll_check)
+    detector_roll_host = staticmethod(detector_roll_host)
+    detector_roll_source_rows = staticmethod(detector_roll_source_rows)
+    roll_search_check = staticmethod(roll_search_check)
+    roll_estimate_from_costs = staticmethod(roll_estimate_from_costs)
+
+    def set_detector_roll(self, eta_deg, det_geo):
+        """paris_hip_set_detector_roll for det_geo's detector: detector_roll() then resamples every frame onto a detector rotated back
+        by eta_deg degrees about the projected rotation axis. Replaces an earlier setting; work already queued keeps the old one."""
+        s = DetectorRoll(eta_deg)
+        check(self._L.paris_hip_set_detector_roll(self._ctx, C.byref(s), C.byref(det_geo)), "paris_hip_set_detector_roll")
+
+    def clear_detector_roll(self):
+        """paris_hip_clear_detector_roll: no detector roll from here on"""
+        check(self._L.paris_hip_clear_detector_roll(self._ctx), "paris_hip_clear_detector_roll")
+
+    def detector_roll(self, src, dst, rows=None, src_frame_stride=0, dst_frame_stride=0, n_frames=1, eta_deg=None, det_geo=None):
+        """The rule of set_detector_roll() from float frames into frames of the same size (paris_hip_detector_roll_rows): rows
+        (first, count) -- None: every row -- of the n_frames frames dst_frame_stride bytes apart starting at dst, from the frames
+        src_frame_stride bytes apart starting at src, of which only the rows detector_roll_source_rows() names are read. With eta_deg
+        and det_geo the setting is taken from the arguments and the backend's is neither used nor changed
+        (paris_hip_detector_roll_rows_with). Call it on line integrals, after the beam-hardening correction and before every weight."""
+        first, count = (0, dst.dim_y) if rows is None else rows
+        if eta_deg is None:
+            check(self._L.paris_hip_detector_roll_rows(self._ctx, src.ptr, src.pitch, src_frame_stride, dst.ptr, dst.pitch, dst_frame_stride,
+                                                       n_frames, src.dim_x, src.dim_y, first, count), "paris_hip_detector_roll_rows")
+            return
+        s = DetectorRoll(eta_deg)
+        check(self._L.paris_hip_detector_roll_rows_with(self._ctx, src.ptr, src.pitch, src_frame_stride, dst.ptr, dst.pitch, dst_frame_stride,
+                                                        n_frames, src.dim_x, src.dim_y, first, count, C.byref(s), C.byref(det_geo)),
+              "paris_hip_detector_roll_rows_with")
+
+    def find_detector_roll(self, mean, lo, step, count, det_geo, min_pixels=0):
+        """paris_hip_roll_search_run: finds the detector roll from the scan mean of a full equidistant circle of line integrals on a
+        centred detector -- mean: (n_col, n_row), what ring_profile_finish() returns -- by the mirror symmetry of that mean about the
+        projected axis. Candidates (float)(lo + k step) degrees, k < count. Returns (RollResult, cost, pairs): float64 costs (+inf:
+        unscored) and the pairs summed per candidate. Waits for the ctx stream."""
+        m = np.ascontiguousarray(mean, np.float32)
+        if m.shape != (det_geo.n_col, det_geo.n_row):
+            raise ValueError("find_detector_roll: the mean must have the detector's size (n_col, n_row)")
+        n = max(int(count), 0)
+        s, out, cost, pairs = RollSearch(lo, step, n, min_pixels), RollResult(), np.empty(n, np.float64), np.empty(n, np.uint64)
+        check(self._L.paris_hip_roll_search_run(self._ctx, C.byref(s), C.byref(det_geo), m.ctypes.data, cost.ctypes.data, pairs.ctypes.data,
+                                                C.byref(out)), "paris_hip_roll_search_run")
+        return out, cost, pairs
 
     # ---- air region (DESIGN.md section 4.16) --------------------------------------------------------------
     air_region_check = staticmethod(air_region_check)

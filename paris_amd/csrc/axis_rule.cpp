@@ -83,15 +83,12 @@ extern "C" int paris_hip_axis_search_plan(const paris_hip_axis_search* s, const 
     return PARIS_HIP_SUCCESS;
 }
 
-extern "C" int paris_hip_axis_estimate_from_costs(const paris_hip_axis_search* s, const double* cost, const uint32_t* columns,
-                                                  paris_hip_axis_result* result)
+int paris_hip_estimate_from_costs(double lo, double step, uint32_t count, const double* cost, paris_hip_cost_estimate* out)
 {
-    if(!axis_candidates_valid(s) || cost == nullptr || result == nullptr)
-        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    paris_hip_axis_result r{};
+    paris_hip_cost_estimate r{};
     std::vector<double> scored;
     uint32_t m = 0;
-    for(uint32_t k = 0; k < s->count; ++k)
+    for(uint32_t k = 0; k < count; ++k)
         if(std::isfinite(cost[k]))
         {
             if(scored.empty() || cost[k] < cost[m])
@@ -101,27 +98,48 @@ extern "C" int paris_hip_axis_estimate_from_costs(const paris_hip_axis_search* s
     r.scored = static_cast<uint32_t>(scored.size());
     if(scored.empty())
     {
-        *result = r;
+        *out = r;
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     }
     std::nth_element(scored.begin(), scored.begin() + (scored.size() - 1u) / 2u, scored.end());
     r.cost_median = scored[(scored.size() - 1u) / 2u];
     r.best = m;
     r.cost_min = cost[m];
-    r.columns = columns != nullptr ? columns[m] : 0u;
-    const double c_m = axis_candidate(*s, m);
-    r.delta_s = static_cast<float>(c_m);
+    const double c_m = static_cast<double>(static_cast<float>(lo + m * step));
+    r.value = static_cast<float>(c_m);
     r.at_edge = 1u;
-    if(m >= 1u && m + 1u < s->count && std::isfinite(cost[m - 1u]) && std::isfinite(cost[m + 1u]))
+    if(m >= 1u && m + 1u < count && std::isfinite(cost[m - 1u]) && std::isfinite(cost[m + 1u]))
     {
         const double q = cost[m - 1u] - 2.0 * cost[m] + cost[m + 1u];
         if(q > 0.0)
         {
             const double off = std::min(std::max(0.5 * (cost[m - 1u] - cost[m + 1u]) / q, -0.5), 0.5);
-            r.delta_s = static_cast<float>(c_m + off * static_cast<double>(s->step));
+            r.value = static_cast<float>(c_m + off * step);
             r.at_edge = 0u;
         }
     }
-    *result = r;
+    *out = r;
     return PARIS_HIP_SUCCESS;
+}
+
+extern "C" int paris_hip_axis_estimate_from_costs(const paris_hip_axis_search* s, const double* cost, const uint32_t* columns,
+                                                  paris_hip_axis_result* result)
+{
+    if(!axis_candidates_valid(s) || cost == nullptr || result == nullptr)
+        return PARIS_HIP_ERROR_INVALID_ARGUMENT;
+    paris_hip_cost_estimate e{};
+    const int rc = paris_hip_estimate_from_costs(static_cast<double>(s->lo), static_cast<double>(s->step), s->count, cost, &e);
+    paris_hip_axis_result r{};
+    r.scored = e.scored;
+    if(rc == PARIS_HIP_SUCCESS)
+    {
+        r.cost_median = e.cost_median;
+        r.best = e.best;
+        r.cost_min = e.cost_min;
+        r.columns = columns != nullptr ? columns[e.best] : 0u;
+        r.delta_s = e.value;
+        r.at_edge = e.at_edge;
+    }
+    *result = r;
+    return rc;
 }

@@ -207,6 +207,14 @@ struct paris_hip_ctx
         paris_hip_beam_hardening rule{};
         uint32_t dim_x = 0, dim_y = 0;
     } beam_hardening;
+    // Detector roll (paris_hip_set_detector_roll): the setting and the geometry it was made for. The six
+    // constants are made per call and travel to the kernel by value: nothing on the device, nothing to retire.
+    struct detector_roll_t
+    {
+        bool set = false;
+        paris_hip_detector_roll rule{};
+        paris_detector_geometry geo{};
+    } detector_roll;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -488,6 +496,7 @@ void paris_hip_warm_binning();
 void paris_hip_warm_axis_search();
 void paris_hip_warm_air_region();
 void paris_hip_warm_beam_hardening();
+void paris_hip_warm_detector_roll();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -523,7 +532,64 @@ void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying);
 // air_region.hip: the same for the air region's memory
 void paris_hip_air_region_release(paris_hip_ctx* ctx, bool destroying);
+
+// axis_rule.cpp: the estimate both searches share (the rule is stated with paris_hip_axis_search in include/paris_hip.h). Candidates
+// are (float)(lo + k step), k < count; a candidate is scored iff its cost is finite. PARIS_HIP_ERROR_INVALID_ARGUMENT when none is
+// (out->scored = 0 then). The callers have checked lo, step, count and the pointers.
+struct paris_hip_cost_estimate
+{
+    float value;                  // the estimate
+    uint32_t best, scored, at_edge;
+    double cost_min, cost_median; // J[best], the lower median of the scored J
+};
+int paris_hip_estimate_from_costs(double lo, double step, uint32_t count, const double* cost, paris_hip_cost_estimate* out);
+
+// roll_rule.cpp: the six constants of the detector roll's rule, each computed in double and rounded to float once (the setting and
+// the geometry have passed paris_hip_detector_roll_check, or eta_deg is exactly 0: the identity)
+struct paris_hip_roll_constants
+{
+    float a, b, c, d, cx, cy;
+};
+paris_hip_roll_constants paris_hip_roll_constants_of(float eta_deg, const paris_detector_geometry& g);
+// roll_rule.cpp: the mirror plan of the roll search and its margins (setting and geometry have passed paris_hip_roll_search_check)
+struct paris_hip_roll_mirror
+{
+    int32_t i0; // the mirror column's left tap; -1: the column is not scored
+    float w;    // the weight of column i0 + 1
+};
+void paris_hip_roll_search_plan(const paris_hip_roll_search& s, const paris_detector_geometry& g, uint32_t* margin_x, uint32_t* margin_y,
+                                paris_hip_roll_mirror* columns);
+// detector_roll.hip: enqueues the roll kernel on ctx->stream for a destination band and constants that have been checked
+struct paris_hip_frame_band;
+void paris_hip_detector_roll_launch(paris_hip_ctx* ctx, const paris_hip_frame_band& src, const paris_hip_frame_band& dst,
+                                    const paris_hip_roll_constants& k);
 #pragma GCC visibility pop
+
+// Where the pieces of a roll search's one allocation lie (detector_roll.hip); roll_rule.cpp reports the total. In this order: the
+// mean M and the rolled scratch frame R (n_col rows of n_row floats each, the row length padded to 16 bytes), the mirror plan (n_row
+// 8-byte entries), the score kernel's partial sums (16 bytes per candidate and tile of 256 columns x 32 rows) and the totals (24
+// bytes per candidate).
+constexpr uint32_t PARIS_HIP_ROLL_TILE_COLUMNS = 256u, PARIS_HIP_ROLL_TILE_ROWS = 32u;
+struct paris_hip_roll_layout
+{
+    size_t pitch, mean, rolled, plan, partial, total_of, bytes;
+    uint32_t col_tiles, row_tiles;
+};
+inline paris_hip_roll_layout paris_hip_roll_layout_of(uint32_t n_row, uint32_t n_col, uint32_t count)
+{
+    paris_hip_roll_layout l{};
+    const auto pad = [](size_t b) { return (b + 255u) / 256u * 256u; };
+    l.pitch = (static_cast<size_t>(n_row) * sizeof(float) + 15u) / 16u * 16u;
+    l.col_tiles = (n_row + PARIS_HIP_ROLL_TILE_COLUMNS - 1u) / PARIS_HIP_ROLL_TILE_COLUMNS;
+    l.row_tiles = (n_col + PARIS_HIP_ROLL_TILE_ROWS - 1u) / PARIS_HIP_ROLL_TILE_ROWS;
+    l.mean = 0u;
+    l.rolled = l.mean + pad(l.pitch * n_col);
+    l.plan = l.rolled + pad(l.pitch * n_col);
+    l.partial = l.plan + pad(static_cast<size_t>(n_row) * 8u);
+    l.total_of = l.partial + pad(static_cast<size_t>(count) * l.col_tiles * l.row_tiles * 16u);
+    l.bytes = l.total_of + pad(static_cast<size_t>(count) * 24u);
+    return l;
+}
 
 // Where the pieces of an air region's one allocation lie (air_region.hip); air_rule.cpp reports the total. The counters: four 64-bit
 // counts (frames, normalised, too_few, above_limit), then the smallest and the largest value as ordered 32-bit keys, padded to 64 bytes.

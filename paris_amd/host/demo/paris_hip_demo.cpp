@@ -7,7 +7,7 @@
 //                       [--short-scan start_deg range_deg] [--offset-detector] [--flat dark.raw|none flat.raw t_min]
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
 //                       [--rings half_width floor limit] [--find-axis lo step count rows]
-//                       [--extend-rows W M] [--bin BX BY mask.raw|none] [--air-region x0 y0 width height limit]
+//                       [--extend-rows W M] [--bin BX BY mask.raw|none] [--air-region x0 y0 width height limit] [--detector-roll deg]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -32,6 +32,8 @@
 // "axis: delta_s = ..." and replaces the geometry's delta_s in the loops. The volume grid stays the one of the geometry given.
 // --extend-rows: the taper length W and the number of edge pixels M of the row extension for truncated projections.
 // set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
+// --detector-roll: the detector's in-plane rotation in degrees. set_detector_roll() before the loops (with the binned geometry under
+// --bin), so that paris::weight() resamples each frame after the beam-hardening correction and before every weight.
 // --bin: the geometry on the command line is the SOURCE detector's and in.raw holds frames of that size; each loaded frame is binned
 // into a buffer of the binned detector (set_binning() before the loops, bin_frame() after paris::load()) and everything downstream runs
 // with binned_geometry(). mask.raw: n_col x n_row bytes at source size, nonzero = left out of its bin. --flat, --defects and the other
@@ -107,6 +109,8 @@ int main(int argc, char** argv)
         auto axis = paris_hip_axis_search{};
         bool extend_rows = false;
         std::uint32_t extend_taper = 0, extend_edge = 0;
+        bool detector_roll = false;
+        float roll_deg = 0.f;
         std::uint32_t bin_x = 1, bin_y = 1;
         std::string bin_mask_path;
         bool vol_given = false;
@@ -182,6 +186,12 @@ int main(int argc, char** argv)
                 extend_taper = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
                 extend_edge = static_cast<std::uint32_t>(std::strtoul(argv[a + 2], nullptr, 10));
                 a += 2;
+            }
+            else if(!std::strcmp(argv[a], "--detector-roll") && a + 1 < argc)
+            {
+                detector_roll = true;
+                roll_deg = std::strtof(argv[a + 1], nullptr);
+                a += 1;
             }
             else if(!std::strcmp(argv[a], "--bin") && a + 3 < argc)
             {
@@ -297,6 +307,8 @@ int main(int argc, char** argv)
             paris::backend::set_zinger_filter(zinger_abs, zinger_rel, zinger_polarity, det.n_row, det.n_col);
         if(extend_rows)
             paris::backend::set_row_extension(extend_edge, extend_taper);
+        if(detector_roll)
+            paris::backend::set_detector_roll(roll_deg, det);
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 

@@ -88,6 +88,7 @@ int main(int argc, char** argv)
                             "          [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]\n"
                             "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]\n"
                             "          [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]\n"
+                            "          [--detector-roll DEG | --find-roll LO:HI[:STEP] [--roll-only]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -137,7 +138,18 @@ int main(int argc, char** argv)
                             "before the reconstruction (after the pre-pass of --rings and --find-axis, whose results it uses): p, p^2 .. p^N are\n"
                             "each reconstructed into the central SLICES slices of the volume (default 32), the slices are split into object and\n"
                             "air by Otsu's threshold, leaving out every voxel within MARGIN voxels (0 .. 4, default 2) of the other class, and the\n"
-                            "combination that is flattest over both is solved for. One material only; not with --bin or --beam-hardening.\n");
+                            "combination that is flattest over both is solved for. One material only; not with --bin or --beam-hardening.\n"
+                            "--detector-roll: the detector is rotated in its own plane by DEG degrees (not 0, at most 10 in size). Every frame is\n"
+                            "resampled on the device, bilinearly with the edge replicated, onto a detector whose rows are perpendicular to the\n"
+                            "projected rotation axis -- a rotation in millimetres about the axis column and the centre row -- after the\n"
+                            "beam-hardening correction and before every weight.\n"
+                            "--find-roll: DEG is found from the scan itself. The projections must form a full circle at equal steps on a centred\n"
+                            "detector (no --short-scan, no --offset-detector, no --angles). The scan is read once before the reconstruction\n"
+                            "(together with --rings and --find-axis when given, after the axis search, whose delta_s it uses): the mean of all\n"
+                            "frames is mirror-symmetric about the projected axis in every detector row, and each candidate LO, LO + STEP .. HI\n"
+                            "[degrees; STEP defaults to 0.25, at most 256 candidates] is scored on the device by the mean squared asymmetry of\n"
+                            "the mean frame rolled back by it. The estimate is the minimum of a parabola through the best candidate and its\n"
+                            "neighbours. --roll-only prints it and stops. Not with --fit-beam-hardening.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -171,6 +183,9 @@ int main(int argc, char** argv)
             else if(k == "--find-axis") paris::detail::parse_find_axis(val(), po);
             else if(k == "--axis-rows") paris::detail::parse_axis_rows(val(), po);
             else if(k == "--axis-only") po.axis_only = true;
+            else if(k == "--detector-roll") paris::detail::parse_detector_roll(val(), po);
+            else if(k == "--find-roll") paris::detail::parse_find_roll(val(), po);
+            else if(k == "--roll-only") po.roll_only = true;
             else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
             else if(k == "--beam-hardening") paris::detail::parse_beam_hardening(val(), po);
             else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
@@ -258,6 +273,21 @@ int main(int argc, char** argv)
             if(po.axis_only)
                 return 0;
         }
+        if(r.roll_search)
+        {
+            std::printf("roll search on: eta = %.4f deg, candidate %u of %u at step %g, J_min = %.6g, J_median = %.6g, J_min / J_median = %.3g, "
+                        "%u candidate(s) scored, %llu pair(s) skipped, margins %u x %u, %u frame(s) in the pre-pass (%.3f s)\n",
+                        static_cast<double>(r.roll.eta_deg), r.roll.best, r.roll_count, static_cast<double>(po.roll_step), r.roll.cost_min, r.roll.cost_median,
+                        r.roll.cost_median > 0.0 ? r.roll.cost_min / r.roll.cost_median : 0.0, r.roll.scored,
+                        static_cast<unsigned long long>(r.roll.skipped), r.roll.margin_x, r.roll.margin_y, r.roll_frames, r.roll_prepass_s);
+            if(r.roll.at_edge != 0u)
+                std::printf("warning: the roll search's minimum has no scored neighbour on both sides or is not convex: eta is the best candidate itself; "
+                            "widen the range of --find-roll\n");
+            if(po.roll_only)
+                return 0;
+        }
+        if(r.detector_roll)
+            std::printf("detector roll on: %.9g deg\n", static_cast<double>(r.roll_deg));
         if(r.beam_hardening)
         {
             if(r.bh_fitted)

@@ -132,6 +132,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> ring_corrections; // set_ring_correction(), per device of this thread
                 std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
                 std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
+                std::set<const paris_hip_ctx*> detector_rolls; // set_detector_roll(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -380,6 +381,32 @@ namespace paris
             inline auto has_beam_hardening(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().beam_hardenings;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the detector of this thread's current device's frames is rotated in its own plane by
+        // eta_deg degrees. Until clear_detector_roll(), paris::weight() resamples every frame onto a detector
+        // whose rows are perpendicular to the projected rotation axis, after the beam-hardening correction and before every weight
+        // (paris_hip_detector_roll_rows): the projection's buffer is exchanged for the resampled one. Off unless called.
+        inline auto set_detector_roll(float eta_deg, const detector_geometry& det_geo) -> void
+        {
+            const auto setting = paris_hip_detector_roll{eta_deg};
+            detail::runtime_check(paris_hip_set_detector_roll(current_ctx(), &setting, detail::as_c<paris_detector_geometry>(det_geo)), "set_detector_roll()");
+            detail::state().detector_rolls.insert(current_ctx());
+        }
+
+        inline auto clear_detector_roll() -> void
+        {
+            detail::runtime_check(paris_hip_clear_detector_roll(current_ctx()), "clear_detector_roll()");
+            detail::state().detector_rolls.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_detector_roll(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().detector_rolls;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

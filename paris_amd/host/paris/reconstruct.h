@@ -150,6 +150,15 @@ namespace paris
         bool beam_hardening = false, fit_beam_hardening = false;
         paris_hip_beam_hardening bh{};                          // as given, or filled by run() with the fitted coefficients
         std::uint32_t bh_slices = 32, bh_margin = 2;            // the fit's slab -- the central slices of the volume -- and its margin
+        // correction of the detector's in-plane rotation (extension): --detector-roll DEG gives the angle,
+        // --find-roll LO:HI[:STEP] [--roll-only] has run() find it from the scan mean of the ring profile pre-pass (detail::prepass,
+        // after the axis search, whose delta_s it uses): both checked by run() before any device work (detail::check_roll). Every
+        // device ctx gets the setting, and each frame is resampled into a second buffer of its slot after the beam-hardening
+        // correction and before every weight; everything after reads that buffer
+        bool roll = false, find_roll = false, roll_only = false;
+        float roll_deg = 0.f;                                   // as given, or filled by run() with the estimate
+        float roll_lo = 0.f, roll_hi = 0.f, roll_step = 0.25f;
+        std::uint32_t roll_count = 0;                           // filled by run(): the candidates
         // detector binning (extension): --bin BX[:BY], each 1, 2, 4 or 8; 1 x 1 is no binning. run() checks the
         // setting before any device work and replaces det_geo by the binned geometry (detail::apply_binning), so that everything
         // derived from it follows; the dark and flat means and the defect mask are binned on the host, the frames on the device, each
@@ -399,7 +408,9 @@ namespace paris
             // with --bin, every slot's full-width source frame as well, and the source-size mask
             const auto src_row = (static_cast<std::size_t>(po.src_row) * sizeof(float) + 255u) / 256u * 256u;
             const auto binning = po.binning() ? slots * po.src_col * src_row + (po.bin_mask ? po.bin_mask->size() : 0u) : 0u;
-            return slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
+            // with --detector-roll / --find-roll, every slot's rolled frame as well
+            const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
+            return rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -755,6 +766,11 @@ namespace paris
                 rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
             if(po.beam_hardening) // --beam-hardening, or the coefficients run()'s fit found: the same on every device
                 rt(paris_hip_set_beam_hardening(ctx, &po.bh, po.det_geo.n_row, po.det_geo.n_col), "set_beam_hardening()");
+            if(po.roll) // --detector-roll, or the angle run()'s search found: the same on every device
+            {
+                const auto setting = paris_hip_detector_roll{po.roll_deg};
+                rt(paris_hip_set_detector_roll(ctx, &setting, &po.det_geo), "set_detector_roll()");
+            }
         }
         catch(...)
         {
@@ -793,6 +809,10 @@ namespace paris
         auto d_src = std::vector<float*>(slots, nullptr);
         float* d_src_all = nullptr; // --bin: the full-width frames of all slots, one under the other like d_all
         std::size_t s_pitch = 0;
+        // --detector-roll: the rolled frames of all slots, laid out as d_all (same pitch, same stride). d_out[s] is the frame of slot s
+        // that the weights, the filter and the backprojection read: the rolled one with a roll, d_buf[s] without
+        auto d_out = std::vector<float*>(slots, nullptr);
+        float* d_roll_all = nullptr;
         auto fence = std::vector<paris_hip_fence*>(groups, nullptr);
         float* d_all = nullptr; // the device frames of all slots, one under the other: slot s starts at row s * n_col
         std::size_t d_pitch = 0, h16_pitch = 0, h16_stride = 0;
@@ -812,6 +832,7 @@ namespace paris
                 paris_hip_free_host(ctx, h_buf[s]);
             paris_hip_free(ctx, d_all);
             paris_hip_free(ctx, d_src_all);
+            paris_hip_free(ctx, d_roll_all);
             paris_hip_free(ctx, d_half);
             for(int s = 0; s < 2; ++s)
             {
@@ -832,12 +853,20 @@ namespace paris
                     throw stage_construction_error{"too many projection slots for this detector"};
                 rt(paris_hip_malloc_projection(ctx, sn_row, sn_col * static_cast<std::uint32_t>(slots), &d_src_all, &s_pitch), "make_projection_device()");
             }
+            if(po.roll)
+            {
+                std::size_t r_pitch = 0;
+                rt(paris_hip_malloc_projection(ctx, n_row, n_col * static_cast<std::uint32_t>(slots), &d_roll_all, &r_pitch), "make_projection_device()");
+                if(r_pitch != d_pitch)
+                    throw stage_runtime_error{"the rolled frames' pitch differs from the frames'"};
+            }
             for(int s = 0; s < slots; ++s)
             {
                 void* p = nullptr;
                 rt(paris_hip_malloc_host(ctx, frame_bytes, &p), "make_projection_host()");
                 h_buf[s] = static_cast<float*>(p);
                 d_buf[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * static_cast<std::size_t>(s));
+                d_out[s] = po.roll ? reinterpret_cast<float*>(reinterpret_cast<char*>(d_roll_all) + d_stride * static_cast<std::size_t>(s)) : d_buf[s];
                 if(binning)
                     d_src[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * static_cast<std::size_t>(s));
             }
@@ -899,6 +928,15 @@ namespace paris
                     rt(paris_hip_slab_row_band(&t.det_geo, &t.vol_geo, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, t.enable_roi,
                                                &t.roi, &band_first, &band_count), "slab_row_band()");
                 rep.band_rows += band_count;
+                // With a roll the slab's band is what the roll WRITES and everything after it reads (out_first, out_count); the rows
+                // every earlier pass covers become the roll's source range of that band (paris_hip_detector_roll_source_rows), which
+                // is widened further below as any band is. Every slab's volume then equals the whole-detector run's, bit for bit.
+                const std::uint32_t out_first = band_first, out_count = band_count;
+                if(po.roll && band_count != 0)
+                {
+                    const auto setting = paris_hip_detector_roll{po.roll_deg};
+                    rt(paris_hip_detector_roll_source_rows(&setting, &t.det_geo, out_first, out_count, &band_first, &band_count), "detector_roll_source_rows()");
+                }
                 // With a defect map the repair of a band's defects reads good pixels up to reach_rows rows beyond it: those rows are
                 // read, uploaded and corrected as well (clipped to the detector), and nothing else is done to them -- the band itself
                 // is repaired, weighted and filtered. Every slab's volume then equals the whole-detector run's, bit for bit.
@@ -962,14 +1000,17 @@ namespace paris
                     if(filter_by_group && band_count != 0 && po.beam_hardening) // then the linearisation, before every weight
                         rt(paris_hip_beam_hardening_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
                            "beam hardening");
+                    if(filter_by_group && band_count != 0 && po.roll) // then the roll, the last frame pass: one call for the group
+                        rt(paris_hip_detector_roll_rows(ctx, d_buf[group * batch], d_pitch, d_stride, d_out[group * batch], d_pitch, d_stride, filled, n_row,
+                                                        n_col, out_first, out_count), "detector roll");
                     if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
-                        rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first,
-                                                                 band_count, &t.det_geo), "offset-detector weight()");
+                        rt(paris_hip_offset_detector_weight_rows(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first,
+                                                                 out_count, &t.det_geo), "offset-detector weight()");
                     if(filter_by_group && band_count != 0 && po.short_scan) // the redundancy weight first, one launch for the group
-                        rt(paris_hip_short_scan_weight_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count,
+                        rt(paris_hip_short_scan_weight_rows(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first, out_count,
                                                             &t.det_geo, &po.scan, angles.data()), "short-scan weight()");
                     if(filter_by_group && band_count != 0)
-                        rt(paris_hip_stage_weight_filter_batch(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count,
+                        rt(paris_hip_stage_weight_filter_batch(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first, out_count,
                                                                &t.det_geo,
                                                                po.f16 ? reinterpret_cast<std::uint16_t*>(reinterpret_cast<char*>(d_half) + h16_stride * group * batch) : nullptr,
                                                                h16_pitch, h16_stride), "weight() + filter()");
@@ -979,7 +1020,7 @@ namespace paris
                                                            offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi, sines.data(), cosines.data(), delta_s,
                                                            delta_t), "backproject()");
                     else
-                        rt(paris_hip_backproject_batch(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, d_v, t.subvol_geo.dim_x,
+                        rt(paris_hip_backproject_batch(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, d_v, t.subvol_geo.dim_x,
                                                        t.subvol_geo.dim_y, dim_z, offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi, sines.data(),
                                                        cosines.data(), delta_s, delta_t), "backproject()"); // :104
                     rt(paris_hip_fence_record(ctx, fence[group]), "fence record"); // the group's slots are free once this has run
@@ -1061,18 +1102,21 @@ namespace paris
                             rt(paris_hip_ring_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "ring correction");
                         if(po.beam_hardening && !filter_by_group) // then the linearisation, before every weight
                             rt(paris_hip_beam_hardening_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "beam hardening");
+                        if(po.roll && !filter_by_group) // then the roll into the slot's second frame, which everything below reads
+                            rt(paris_hip_detector_roll_rows(ctx, d_buf[slot], d_pitch, 0u, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count),
+                               "detector roll");
                         if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
-                            rt(paris_hip_offset_detector_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count,
+                            rt(paris_hip_offset_detector_weight_rows(ctx, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count,
                                                                      &t.det_geo), "offset-detector weight()");
                         if(po.short_scan && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
-                            rt(paris_hip_short_scan_weight_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count, &t.det_geo,
+                            rt(paris_hip_short_scan_weight_rows(ctx, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count, &t.det_geo,
                                                                 &po.scan, &angles[filled]), "short-scan weight()");
                         // :102-103 in one launch: the weight rides along in the row filter's load; with --f16 (BASELINE config 5) the
                         // filtered band is stored as IEEE half straight into the slot's half frame
                         // (small frames: the whole group by one launch when it is flushed -- a launch per 512^2 frame is mostly latency)
                         auto* half_frame = po.f16 ? reinterpret_cast<std::uint16_t*>(reinterpret_cast<char*>(d_half) + h16_stride * static_cast<std::size_t>(slot)) : nullptr;
                         if(!filter_by_group)
-                            rt(paris_hip_stage_weight_filter_rows(ctx, d_buf[slot], d_pitch, n_row, n_col, band_first, band_count, &t.det_geo, half_frame,
+                            rt(paris_hip_stage_weight_filter_rows(ctx, d_out[slot], d_pitch, n_row, n_col, out_first, out_count, &t.det_geo, half_frame,
                                                                   h16_pitch), "weight() + filter()");
                     }
                     rt(paris_hip_stage_angle(&t.det_geo, p.idx, t.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle"); // src/backprojection.cpp:52-63
@@ -1160,6 +1204,12 @@ namespace paris
         float bh_threshold = 0.f;
         std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
         double bh_prepass_s = 0;
+        bool detector_roll = false;                     // --detector-roll / --find-roll: every frame was resampled by roll_deg;
+        float roll_deg = 0.f;                           // with the search: the estimate and its costs' summary, the frames of its
+        bool roll_search = false;                       // pre-pass, the candidates, and how long the pre-pass took (reading the
+        paris_hip_roll_result roll{};                   // scan included; with --rings / --find-axis the same pre-pass)
+        std::uint32_t roll_frames = 0, roll_count = 0;
+        double roll_prepass_s = 0;
         bool binning = false;                           // --bin: the factors, the source and the binned detector, and how many binned
         std::uint32_t bin_x = 1, bin_y = 1;             // pixels have no good source pixel (they join the defect map)
         std::uint32_t src_row = 0, src_col = 0, binned_row = 0, binned_col = 0;
@@ -1647,8 +1697,9 @@ namespace paris
         // of the repair and of the zinger filter as a slab's band is in reconstruct(). Then the ring rule makes the correction frame,
         // which is kept in po, and the search gives its estimate, which is kept in r. Everything allocated here is freed before it
         // returns: run() plans the slabs afterwards.
-        inline auto prepass(program_options& po, run_report& r, bool rings, bool axis) -> void
+        inline auto prepass(program_options& po, run_report& r, bool rings, bool axis, bool roll = false) -> void
         {
+            const bool profile = rings || roll; // --find-roll scores the scan mean, which the ring profile makes
             const auto t_start = clock::now();
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
             const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
@@ -1692,7 +1743,7 @@ namespace paris
                 }
                 // the rows of every frame that are read, uploaded and corrected (up), repaired (fix) and filtered and consumed (band)
                 std::uint32_t band_first = 0, band_count = n_col;
-                if(axis && !rings)
+                if(axis && !profile)
                 {
                     rt(paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, &band_first, nullptr), "axis_search_check()");
                     band_count = po.axis_rows;
@@ -1709,7 +1760,7 @@ namespace paris
                 if(po.air)
                     hull_rows(po.air_region.y0, po.air_region.height, up_first, up_count);
                 const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
-                if(rings)
+                if(profile)
                     rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
                 if(axis)
                     rt(paris_hip_axis_search_begin(ctx, &search, &po.det_geo, po.axis_frames), "axis_search_begin()");
@@ -1757,7 +1808,7 @@ namespace paris
                         rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count), "defect repair");
                     if(po.zingers)
                         rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, band_first, band_count), "zinger filter");
-                    if(rings)
+                    if(profile)
                         rt(paris_hip_ring_profile_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
                     if(axis)
                         rt(paris_hip_axis_search_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, frames), "axis_search_add_rows()");
@@ -1766,14 +1817,22 @@ namespace paris
                 }
                 if(po.air)
                     rt(paris_hip_air_stats(ctx, &r.air_prepass, 0), "air stats");
-                if(rings)
+                auto mean = std::vector<float>(roll ? static_cast<std::size_t>(n_row) * n_col : 0u); // --find-roll: the scan mean
+                if(profile)
                 {
                     auto c = std::make_shared<std::vector<float>>(static_cast<std::size_t>(n_row) * n_col);
-                    const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
-                    rt(paris_hip_ring_profile_finish(ctx, &setting, c->data(), nullptr, &r.rings), "ring_profile_finish()");
-                    po.ring_c = std::move(c);
-                    r.ring_filter = true;
-                    r.ring_frames = frames;
+                    // (without --rings the profile is closed with the smallest valid setting and its correction frame is dropped)
+                    const auto setting = rings ? paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit} : paris_hip_ring_filter{1u, 0.f, 0.f};
+                    auto unused = paris_hip_ring_stats{};
+                    rt(paris_hip_ring_profile_finish(ctx, &setting, c->data(), roll ? mean.data() : nullptr, rings ? &r.rings : &unused), "ring_profile_finish()");
+                    if(rings)
+                    {
+                        for(std::size_t k = 0; k < mean.size(); ++k) // the search sees the mean as the corrected frames will give it
+                            mean[k] = mean[k] - (*c)[k];
+                        po.ring_c = std::move(c);
+                        r.ring_filter = true;
+                        r.ring_frames = frames;
+                    }
                 }
                 if(axis)
                 {
@@ -1788,6 +1847,21 @@ namespace paris
                     r.axis_frames = frames;
                     r.axis_count = po.axis_count;
                 }
+                if(roll) // after the axis search: the mirror line is the axis just found
+                {
+                    auto geo = po.det_geo;
+                    if(axis)
+                        geo.delta_s = r.axis.delta_s;
+                    const auto roll_search = paris_hip_roll_search{po.roll_lo, po.roll_step, po.roll_count, 0u};
+                    auto cost = std::vector<double>(po.roll_count);
+                    const int rc = paris_hip_roll_search_run(ctx, &roll_search, &geo, mean.data(), cost.data(), nullptr, &r.roll);
+                    if(rc == PARIS_HIP_ERROR_INVALID_ARGUMENT && r.roll.scored == 0u)
+                        throw stage_runtime_error{"--find-roll: no candidate has enough finite pixel pairs inside the margins"};
+                    rt(rc, "roll_search()");
+                    r.roll_search = true;
+                    r.roll_frames = frames;
+                    r.roll_count = po.roll_count;
+                }
             }
             catch(...)
             {
@@ -1795,6 +1869,8 @@ namespace paris
                 throw;
             }
             cleanup();
+            if(roll)
+                r.roll_prepass_s = since(t_start);
             if(rings)
                 r.ring_prepass_s = since(t_start);
             if(axis)
@@ -2104,6 +2180,87 @@ namespace paris
                                                + std::to_string(po.axis_rows) + ")"};
         }
 
+        // --detector-roll DEG as typed
+        inline auto parse_detector_roll(const std::string& v, program_options& po) -> void
+        {
+            char* end = nullptr;
+            po.roll_deg = std::strtof(v.c_str(), &end);
+            if(v.empty() || end == nullptr || *end != '\0')
+                throw stage_construction_error{"--detector-roll DEG: cannot read '" + v + "'"};
+            po.roll = true;
+        }
+
+        // --find-roll LO:HI[:STEP] as typed; refuses anything but two or three numbers
+        inline auto parse_find_roll(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--find-roll LO:HI[:STEP]: cannot read '" + v + "'"}; };
+            const auto f = colon_fields(v);
+            if(f.size() < 2u || f.size() > 3u)
+                throw bad();
+            float num[3] = {0.f, 0.f, 0.25f};
+            for(std::size_t k = 0; k < f.size(); ++k)
+            {
+                char* end = nullptr;
+                num[k] = std::strtof(f[k].c_str(), &end);
+                if(f[k].empty() || end == nullptr || *end != '\0')
+                    throw bad();
+            }
+            po.roll_lo = num[0];
+            po.roll_hi = num[1];
+            po.roll_step = num[2];
+            po.find_roll = true;
+        }
+
+        // --detector-roll / --find-roll: the angle, the candidates and the scan are checked for this detector here, before any device
+        // work. The search needs a full, equidistant circle on a centred detector: it is refused with --short-scan, with
+        // --offset-detector, with an angle file, and for frames (after the quality stride) that do not cover 360 degrees
+        inline auto check_roll(program_options& po) -> void
+        {
+            if(po.roll_only && !po.find_roll)
+                throw stage_construction_error{"--roll-only needs --find-roll"};
+            if(po.roll && po.find_roll)
+                throw stage_construction_error{"--detector-roll and --find-roll cannot be combined: give the angle or have it found"};
+            if((po.roll || po.find_roll) && po.fit_beam_hardening)
+                throw stage_construction_error{"--detector-roll / --find-roll cannot be combined with --fit-beam-hardening: its pre-pass does not resample the frames"};
+            if(po.roll)
+            {
+                const auto setting = paris_hip_detector_roll{po.roll_deg};
+                if(paris_hip_detector_roll_check(&setting, &po.det_geo) != PARIS_HIP_SUCCESS)
+                    throw stage_construction_error{"--detector-roll DEG: DEG must be finite, not 0 and at most 10 in size, on a detector of at least 2 x 2 pixels "
+                                                   "with positive pixel sizes (got " + std::to_string(po.roll_deg) + ")"};
+            }
+            if(!po.find_roll)
+                return;
+            if(po.short_scan)
+                throw stage_construction_error{"--find-roll needs a full circle: it cannot be combined with --short-scan"};
+            if(po.offset_detector)
+                throw stage_construction_error{"--find-roll needs a centred detector: it cannot be combined with --offset-detector"};
+            if(po.enable_angles)
+                throw stage_construction_error{"--find-roll needs equidistant projections: it cannot be combined with an angle file (--angles)"};
+            if(po.roll_only && po.axis_only)
+                throw stage_construction_error{"--roll-only cannot be combined with --axis-only: the run would stop before the roll search"};
+            const double span = static_cast<double>(po.roll_hi) - static_cast<double>(po.roll_lo);
+            if(!std::isfinite(po.roll_lo) || !std::isfinite(po.roll_hi) || !std::isfinite(po.roll_step) || !(po.roll_step > 0.f) || !(span >= 0.0)
+               || span / static_cast<double>(po.roll_step) > 255.0)
+                throw stage_construction_error{"--find-roll LO:HI[:STEP]: LO <= HI and STEP > 0, all finite, and at most 256 candidates (got "
+                                               + std::to_string(po.roll_lo) + ":" + std::to_string(po.roll_hi) + ":" + std::to_string(po.roll_step) + ")"};
+            po.roll_count = static_cast<std::uint32_t>(std::floor(span / static_cast<double>(po.roll_step) + 0.5)) + 1u;
+            const auto a = frame_angles(po.input_path, false, po.angle_path, po.quality, po.det_geo.delta_phi);
+            const double step = a.size() >= 2u ? static_cast<double>(a[1]) - static_cast<double>(a[0]) : 0.0;
+            if(a.size() < 4u || !(step > 0.0) || std::abs(static_cast<double>(a.size()) * step - 360.0) > 0.5 * step)
+            {
+                char msg[256];
+                std::snprintf(msg, sizeof msg, "--find-roll needs a full circle of at least 4 projections at a positive angle step: %zu projection(s) "
+                              "%.6g degrees apart cover %.6g degrees", a.size(), step, static_cast<double>(a.size()) * step);
+                throw stage_construction_error{msg};
+            }
+            const auto search = paris_hip_roll_search{po.roll_lo, po.roll_step, po.roll_count, 0u};
+            if(paris_hip_roll_search_check(&search, &po.det_geo, nullptr, nullptr, nullptr) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--find-roll LO:HI[:STEP]: every candidate must lie within 10 degrees of 0 and leave pixels inside the margins "
+                                               "of the detector (got " + std::to_string(po.roll_lo) + ":" + std::to_string(po.roll_hi) + ":"
+                                               + std::to_string(po.roll_step) + ")"};
+        }
+
         inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
         {
             if(v == "bright") po.zinger_polarity = 1;
@@ -2131,6 +2288,12 @@ namespace paris
         detail::check_voxels(po);
         detail::check_axis(po);
         detail::check_beam_hardening(po);
+        detail::check_roll(po);
+        // --find-roll: the estimate becomes the run's roll (an estimate of exactly 0 is no roll)
+        const auto adopt_roll = [&] {
+            po.roll_deg = r.roll.eta_deg;
+            po.roll = po.roll_deg != 0.f;
+        };
         if(po.find_axis)
         {
             // before anything is derived from delta_s: the offset-detector check, the short-scan check and the volume geometry below
@@ -2140,11 +2303,13 @@ namespace paris
             if(n_pre == 0)
                 throw stage_construction_error{"no HIP device"};
             auto pre = detail::fit_batch(po, po.devices > 0 && po.devices < n_pre ? po.devices : n_pre);
-            detail::prepass(pre, r, po.rings, true);
+            detail::prepass(pre, r, po.rings, true, po.find_roll);
             po.ring_c = pre.ring_c;
+            if(po.find_roll)
+                adopt_roll();
             r.axis_given = po.det_geo.delta_s;
             po.det_geo.delta_s = r.axis.delta_s;
-            if(po.axis_only)
+            if(po.axis_only || po.roll_only)
             {
                 r.wall_s = detail::since(start);
                 return r;
@@ -2173,8 +2338,17 @@ namespace paris
                                            + " devices would be used)"};
         po = detail::fit_batch(po, n_dev);
         r.batch = po.batch;
-        if(po.rings && !po.find_axis) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
-            detail::prepass(po, r, true, false);
+        if((po.rings || po.find_roll) && !po.find_axis) // before the slabs are planned: the pre-pass's buffers are gone by then, the correction frame is in the reserve
+        {
+            detail::prepass(po, r, po.rings, false, po.find_roll);
+            if(po.find_roll)
+                adopt_roll();
+            if(po.roll_only)
+            {
+                r.wall_s = detail::since(start);
+                return r;
+            }
+        }
         if(po.fit_beam_hardening) // after the ring pre-pass and the axis search, whose results it uses; its slabs are gone before the run's are planned
         {
             detail::bh_prepass(po, r);
@@ -2183,6 +2357,8 @@ namespace paris
         }
         r.beam_hardening = po.beam_hardening;
         r.bh = po.bh;
+        r.detector_roll = po.roll;
+        r.roll_deg = po.roll_deg;
 
         if(po.slabs > 0) // fixed split (src/cuda/subvolume_information.cpp:112-116 with a given count)
         {

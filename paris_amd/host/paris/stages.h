@@ -89,6 +89,15 @@ namespace paris
         if(backend::detail::has_beam_hardening(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_beam_hardening_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                          p.dim_y, 0u, p.dim_y), "weight()");
+        // then with a detector roll (backend::set_detector_roll) the resampling, the last frame pass: it reads one buffer and writes
+        // another, so the projection takes the resampled buffer and lets go of its own
+        if(backend::detail::has_detector_roll(backend::current_ctx()))
+        {
+            auto rolled = backend::make_projection_device(p.dim_x, p.dim_y);
+            backend::detail::runtime_check(paris_hip_detector_roll_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, rolled.buf.get(),
+                                                                        rolled.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y, 0u, p.dim_y), "weight()");
+            std::swap(p.buf, rolled.buf);
+        }
         if(backend::detail::has_offset_detector(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_stage_offset_detector_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                                                   p.dim_y, &det_geo), "weight()");
