@@ -1155,6 +1155,75 @@ int paris_hip_bh_gram_host(const float* const* f, uint32_t degree, const uint8_t
  * PARIS_HIP_ERROR_BH_NOT_POSITIVE when a pivot is not positive (NaN included); PARIS_HIP_ERROR_BH_NOT_FINITE when T is zero or not
  * finite or a coefficient is not a finite float. *out is written on success only. */
 int paris_hip_bh_solve(const double* gram, uint32_t degree, const paris_hip_bh_counts* counts, uint64_t min_voxels, paris_hip_bh_fit* out);
+/* Extension (no reference counterpart): detector lag -- an a-Si flat panel carries a few per cent of every frame's signal over into
+ * the following frames (afterglow), which blurs the volume azimuthally and draws tails behind dense edges. The correction is the
+ * recursive deconvolution of a multi-exponential impulse response (Hsieh et al. 2000; for flat panels Starman et al. 2011; DESIGN.md
+ * section 4.20). It is the one pass that carries per-pixel STATE from frame to frame: the frames of one pass over the scan form an
+ * ordered sequence. One definition; the host function and the device give the same bits.
+ * Setting paris_hip_lag_model { uint32_t terms; float b[4]; float a[4]; int start; }: N = terms in 1 .. 4, term n with the weight
+ *   b_n > 0 and the decay rate per frame a_n > 0, both finite. The impulse response is h(k) = b_0 delta(k) + sum_n b_n exp(-a_n k),
+ *   k >= 0, normalised to unit DC gain: b_0 = 1 - sum_n b_n / (1 - exp(-a_n)), and b_0 > 0 is required (in double). With every b_n > 0
+ *   and b_0 > 0 the poles of the inverse filter lie in (0, 1) on the real axis.
+ *   With B = b_0 + sum b_n and the state S_n,k = x_(k-1) + exp(-a_n) S_n,(k-1) the detector's forward model is
+ *   y_k = B x_k + sum_n b_n exp(-a_n) S_n,k; the correction is its exact algebraic inverse.
+ * Coefficients (paris_hip_lag_coefficients, the single implementation), each computed in double and rounded once to fp32:
+ *   g_n = exp(-a_n), c_n = b_n g_n / B, invB = 1 / B, w_n = 1 / (1 - g_n).
+ * Rule, per pixel and frame, in fp32, in this order, explicit fused multiply-adds and no contraction elsewhere:
+ *   y = i - d             d: the ctx's dark pixel at the frame's absolute row and column when a flat-field setting is in force, else 0
+ *                         (the host function: the caller's dark array, or 0 without one)
+ *   first frame of a sequence, start = PARIS_HIP_LAG_START_STEADY: S_n = w_n * y for every n   (PARIS_HIP_LAG_START_REST: S_n = 0)
+ *   acc = y * invB;  for n = 0 .. N-1: acc = fmaf(-c_n, S_n, acc);  x = acc
+ *   for n = 0 .. N-1: S_n = fmaf(g_n, S_n, x)
+ *   store x + d
+ *   A pixel whose y is not finite is stored unchanged and its state advances with x = 0 (on a sequence's first frame from S_n = 0):
+ *   one bad sample does not poison a pixel for the rest of the scan.
+ *   STEADY: the beam was on and the first view had been seen for a long time -- how scans are taken.
+ * Order. The pass runs on COUNTS: after the raw upload and the binning, before the dark / flat correction, which afterwards sees
+ * x + d where it saw i. Every later pass is as it was. */
+#define PARIS_HIP_LAG_TERMS_MAX 4
+#define PARIS_HIP_LAG_START_REST 0
+#define PARIS_HIP_LAG_START_STEADY 1
+typedef struct paris_hip_lag_model {
+    uint32_t terms;                   /* N: 1 .. PARIS_HIP_LAG_TERMS_MAX */
+    float b[PARIS_HIP_LAG_TERMS_MAX]; /* the weights b_n > 0; the rest is ignored */
+    float a[PARIS_HIP_LAG_TERMS_MAX]; /* the decay rates per frame a_n > 0; the rest is ignored */
+    int start;                        /* PARIS_HIP_LAG_START_REST or PARIS_HIP_LAG_START_STEADY */
+} paris_hip_lag_model;
+/* Host only, no ctx and no device. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL model, terms outside 1 .. 4, a b_n or a_n (n < terms)
+ * that is not finite or not > 0, b_0 <= 0, or an unknown start. */
+int paris_hip_lag_model_check(const paris_hip_lag_model* model);
+/* Host only: the one place the coefficients are derived (the device path calls it too). g, c and w receive 4 floats each, those
+ * from `terms` on are 0; inv_b and b0 (the latter in double) may be NULL. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL
+ * g, c or w. */
+int paris_hip_lag_coefficients(const paris_hip_lag_model* model, float g[4], float c[4], float w[4], float* inv_b, double* b0);
+/* Host only: the rule on n_frames dense frames of n_pixels pixels each, in time order, in place -- the second implementation of the
+ * one definition. dark: n_pixels floats or NULL (zero). state: terms x n_pixels floats, planar per term, which the caller keeps
+ * between calls; *started: 0 before frame 0 of the sequence (the state's contents are then ignored), set to 1 by the first frame.
+ * Calls that split a sequence anywhere give the bits of one call. PARIS_HIP_ERROR_INVALID_ARGUMENT as the check, or for a NULL
+ * frames, state or started with work to do. */
+int paris_hip_lag_correct_host(const paris_hip_lag_model* model, const float* dark_or_null, float* frames, float* state, int* started,
+                               uint64_t n_pixels, uint32_t n_frames);
+/* Both run the check, then whatever is deferred, and close an open sequence. The model travels to the kernel by value. Without a
+ * setting nothing else changes. */
+int paris_hip_set_lag_correction(paris_hip_ctx* ctx, const paris_hip_lag_model* model);
+int paris_hip_clear_lag_correction(paris_hip_ctx* ctx);
+/* Opens the sequence of one band, rows [row_first, row_first + row_count) of dim_x x dim_y frames: one open sequence per ctx. The
+ * band's state -- terms x row_count x dim_x floats, planar per term, rows dense -- is allocated, zeroed on the compute stream and
+ * counts towards paris_hip_projection_reserve_bytes while the sequence is open; the frame counter starts at 0.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when a flat-field setting has other dimensions than dim_x x dim_y, for a zero or
+ * out-of-frame band, or while a sequence is open. */
+int paris_hip_lag_begin(paris_hip_ctx* ctx, uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* Closes the sequence; its state is freed once no queued work can touch it. Without an open sequence: no error. */
+int paris_hip_lag_end(paris_hip_ctx* ctx);
+/* In place on float frames of counts, asynchronous: the rule on the band's rows of n_frames frames frame_stride bytes apart, d_p the
+ * first frame's row 0. The call's frames are consecutive in time and follow the previous call's; the frame counter advances by
+ * n_frames. 16-byte vectors are used where the base, the pitch, the stride (n_frames > 1) and dim_x allow, single pixels otherwise.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT without an open sequence, when dim_x, dim_y or the band differ from the begun ones (a pass over other
+ * rows would leave their state stale), or for a pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_lag_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                               uint32_t dim_y, uint32_t row_first, uint32_t row_count);
+/* The open sequence's frame counter (0 without one). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL argument. */
+int paris_hip_lag_frames(paris_hip_ctx* ctx, uint64_t* frames);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

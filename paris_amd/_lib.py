@@ -173,6 +173,16 @@ class BhFit(C.Structure):
     _fields_ = [("setting", BeamHardening), ("level", C.c_double), ("residual_before", C.c_double), ("residual_after", C.c_double)]
 
 
+LAG_TERMS_MAX = 4  # PARIS_HIP_LAG_TERMS_MAX
+LAG_START_REST = 0  # PARIS_HIP_LAG_START_REST
+LAG_START_STEADY = 1  # PARIS_HIP_LAG_START_STEADY
+
+
+class LagModel(C.Structure):
+    """paris_hip_lag_model: the multi-exponential impulse response of the detector's lag (extension)"""
+    _fields_ = [("terms", C.c_uint32), ("b", C.c_float * LAG_TERMS_MAX), ("a", C.c_float * LAG_TERMS_MAX), ("start", C.c_int)]
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -300,6 +310,15 @@ SIGNATURES = {
     "paris_hip_bh_gram": (C.c_int, [_vp, _P(_vp), _u32, _vp, C.c_uint64, _vp, _P(BhCounts)]),
     "paris_hip_bh_gram_host": (C.c_int, [_P(_vp), _u32, _vp, C.c_uint64, _vp, _P(BhCounts)]),
     "paris_hip_bh_solve": (C.c_int, [_vp, _u32, _P(BhCounts), C.c_uint64, _P(BhFit)]),
+    "paris_hip_lag_model_check": (C.c_int, [_P(LagModel)]),
+    "paris_hip_lag_coefficients": (C.c_int, [_P(LagModel), _vp, _vp, _vp, _P(_f), _P(C.c_double)]),
+    "paris_hip_lag_correct_host": (C.c_int, [_P(LagModel), _vp, _vp, _vp, _P(C.c_int), C.c_uint64, _u32]),
+    "paris_hip_set_lag_correction": (C.c_int, [_vp, _P(LagModel)]),
+    "paris_hip_clear_lag_correction": (C.c_int, [_vp]),
+    "paris_hip_lag_begin": (C.c_int, [_vp, _u32, _u32, _u32, _u32]),
+    "paris_hip_lag_end": (C.c_int, [_vp]),
+    "paris_hip_lag_correct_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
+    "paris_hip_lag_frames": (C.c_int, [_vp, _P(C.c_uint64)]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BeamHardening, BhCounts, BhFit, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (BeamHardening, BhCounts, BhFit, LagModel, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -26,7 +26,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host",
            "BeamHardening", "BhCounts", "BhFit", "Labels", "BeamHardeningFit", "beam_hardening_check", "beam_hardening_host",
            "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve", "DetectorRoll", "RollSearch", "RollResult",
-           "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs"]
+           "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs",
+           "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host"]
 
 
 class Projection:
@@ -352,6 +353,62 @@ def beam_hardening_host(c, frame):
     check(_lib.load().paris_hip_beam_hardening_host(C.byref(s), f.ctypes.data if f.size else None, out.ctypes.data if f.size else None,
                                                     f.size), "paris_hip_beam_hardening_host")
     return out
+
+
+_LAG_STARTS = {"rest": _lib.LAG_START_REST, "steady": _lib.LAG_START_STEADY}
+
+
+def _lag_setting(terms, start):
+    """the model for a sequence of (b_n, a_n) pairs and start "steady" / "rest"; a length outside 1 .. 4 gets the term count as it is
+    and an unknown start the value -1, both of which the library refuses"""
+    pairs = [(float(b), float(a)) for b, a in terms]
+    m = LagModel()
+    m.terms = len(pairs)
+    for n, (b, a) in enumerate(pairs[:_lib.LAG_TERMS_MAX]):
+        m.b[n], m.a[n] = b, a
+    m.start = _LAG_STARTS.get(start, start if isinstance(start, int) else -1)
+    return m
+
+
+def lag_model_check(terms, start="steady"):
+    """Host only, no device (paris_hip_lag_model_check): raises ParisHipError unless terms holds 1 to 4 pairs (b_n, a_n), each finite
+    and > 0, with b_0 = 1 - sum b_n / (1 - exp(-a_n)) > 0, and start is "steady" or "rest" (DESIGN.md section 4.20)."""
+    m = _lag_setting(terms, start)
+    check(_lib.load().paris_hip_lag_model_check(C.byref(m)), "paris_hip_lag_model_check")
+
+
+def lag_coefficients(terms, start="steady"):
+    """Host only, no device (paris_hip_lag_coefficients): (g, c, w, inv_b, b0) of the model -- g_n = exp(-a_n), c_n = b_n g_n / B,
+    w_n = 1 / (1 - g_n) as float32[N], inv_b = 1 / B as np.float32, each computed in double and rounded once, and b0 as a float."""
+    m = _lag_setting(terms, start)
+    g, c, w = (np.zeros(_lib.LAG_TERMS_MAX, np.float32) for _ in range(3))
+    inv_b, b0 = C.c_float(0.0), C.c_double(0.0)
+    check(_lib.load().paris_hip_lag_coefficients(C.byref(m), g.ctypes.data, c.ctypes.data, w.ctypes.data, C.byref(inv_b), C.byref(b0)),
+          "paris_hip_lag_coefficients")
+    n = m.terms
+    return g[:n].copy(), c[:n].copy(), w[:n].copy(), np.float32(inv_b.value), b0.value
+
+
+def lag_correct_host(terms, frames, dark=None, start="steady", state=None, started=False):
+    """Host only, no device (paris_hip_lag_correct_host): the lag rule on frames[f] (float32 counts, f in time order, every frame of
+    one shape), with the dark frame `dark` (None: zero). state: None opens a sequence; otherwise the (N, *frame shape) float32 array
+    and the `started` flag an earlier call returned. Returns (corrected frames, state, started): the inputs are not written."""
+    f = np.array(frames, np.float32, order="C")
+    if f.ndim < 1:
+        raise ValueError("lag_correct_host: frames must hold a leading frame axis")
+    m = _lag_setting(terms, start)
+    n_frames, n_pixels = f.shape[0], int(np.prod(f.shape[1:], dtype=np.int64))
+    d = None if dark is None else np.ascontiguousarray(dark, np.float32)
+    if d is not None and d.size != n_pixels:
+        raise ValueError("lag_correct_host: the dark frame and the frames differ in size")
+    st = np.zeros((max(m.terms, 0),) + f.shape[1:], np.float32) if state is None else np.array(state, np.float32, order="C")
+    if st.size != m.terms * n_pixels:
+        raise ValueError("lag_correct_host: the state does not belong to these frames and terms")
+    flag = C.c_int(1 if (started and state is not None) else 0)
+    check(_lib.load().paris_hip_lag_correct_host(C.byref(m), None if d is None else d.ctypes.data, f.ctypes.data if f.size else None,
+                                                 st.ctypes.data if st.size else None, C.byref(flag), n_pixels, n_frames),
+          "paris_hip_lag_correct_host")
+    return f, st, bool(flag.value)
 
 
 def bh_threshold_from_histogram(hist, h_lo, h_hi):
@@ -1054,6 +1111,46 @@ class Backend:
         s = _bh_setting(c)
         check(self._L.paris_hip_beam_hardening_rows_with(self._ctx, C.byref(s), p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y,
                                                          first, count), "paris_hip_beam_hardening_rows_with")
+
+    # ---- detector lag ---------------------------------------------------------------
+    lag_model_check = staticmethod(lag_model_check)
+    lag_coefficients = staticmethod(lag_coefficients)
+    lag_correct_host = staticmethod(lag_correct_host)
+
+    def set_lag_correction(self, terms, start="steady"):
+        """paris_hip_set_lag_correction: terms is 1 to 4 pairs (b_n, a_n) of the detector's multi-exponential impulse response, start
+        "steady" (the beam was on before the first frame: the default) or "rest". Runs what is deferred first; replaces an earlier
+        setting and closes an open sequence."""
+        m = _lag_setting(terms, start)
+        check(self._L.paris_hip_set_lag_correction(self._ctx, C.byref(m)), "paris_hip_set_lag_correction")
+
+    def clear_lag_correction(self):
+        """paris_hip_clear_lag_correction: no lag correction from here on; an open sequence is closed"""
+        check(self._L.paris_hip_clear_lag_correction(self._ctx), "paris_hip_clear_lag_correction")
+
+    def lag_begin(self, dim_x, dim_y, row_first=0, row_count=None):
+        """paris_hip_lag_begin: opens the sequence of rows [row_first, row_first + row_count) -- None: to the last row -- of dim_x x
+        dim_y frames: the band's zeroed state on the device, frame counter 0. One open sequence per backend."""
+        count = dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_lag_begin(self._ctx, dim_x, dim_y, row_first, count), "paris_hip_lag_begin")
+
+    def lag_correct(self, p, frame_stride=0, n_frames=1, row_first=0, row_count=None):
+        """The lag rule in place on float frames of counts (paris_hip_lag_correct_rows): the begun band of the n_frames frames
+        frame_stride bytes apart starting at p, which follow the previous call's frames in time. Call it after the raw upload and
+        the binning, before flat_field_rows()."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        check(self._L.paris_hip_lag_correct_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count),
+              "paris_hip_lag_correct_rows")
+
+    def lag_end(self):
+        """paris_hip_lag_end: closes the open sequence (none open: nothing happens)"""
+        check(self._L.paris_hip_lag_end(self._ctx), "paris_hip_lag_end")
+
+    def lag_frames(self):
+        """paris_hip_lag_frames: how many frames the open sequence has seen (0 without one)"""
+        n = C.c_uint64(0)
+        check(self._L.paris_hip_lag_frames(self._ctx, C.byref(n)), "paris_hip_lag_frames")
+        return int(n.value)
 
     def make_labels_device(self, dim_x, dim_y, dim_z):
         """one byte per voxel of a slab, uninitialised; free() takes it"""

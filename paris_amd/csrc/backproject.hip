@@ -1028,6 +1028,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
         total += static_cast<size_t>(ctx->binning.dim_x) * ctx->binning.dim_y;
     if(ctx->air.set) // the mask bytes, values and counters of paris_hip_set_air_region
         total += ctx->air.device_bytes;
+    if(ctx->lag.d_state != nullptr) // the state of the sequence paris_hip_lag_begin opened
+        total += ctx->lag.state_bytes;
     if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached
         total += ctx->row_extension.device_bytes;
     if(ctx->volume_window.d_acc != nullptr) // the volume export's counters

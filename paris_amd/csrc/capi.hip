@@ -118,6 +118,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_air_region();
             paris_hip_warm_beam_hardening();
             paris_hip_warm_detector_roll();
+            paris_hip_warm_lag();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -337,6 +338,7 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     paris_hip_binning_release(ctx, true);
     paris_hip_axis_search_release(ctx, true);
     paris_hip_air_region_release(ctx, true);
+    paris_hip_lag_release(ctx, true);
     if(ctx->defer_count != 0)
     {
         // Projections still deferred belong to key_v. Every library entry point that reads or frees a volume has flushed them

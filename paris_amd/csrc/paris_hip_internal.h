@@ -215,6 +215,21 @@ struct paris_hip_ctx
         paris_hip_detector_roll rule{};
         paris_detector_geometry geo{};
     } detector_roll;
+    // Detector lag (paris_hip_set_lag_correction): the model and the coefficients made from it, which travel
+    // to the kernel by value. The open sequence (paris_hip_lag_begin): the band it was begun for, how many frames it has seen, and
+    // the band's state on the device -- model.terms planes of row_count x dim_x floats -- read and written by lag_kernel on the
+    // compute stream only (and zeroed there), so it is retired and freed as the ring profile's sums are.
+    struct lag_t
+    {
+        bool set = false;
+        paris_hip_lag_model model{};
+        float g[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, c[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f},
+              w[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, inv_b = 0.f;
+        float* d_state = nullptr; // != nullptr: a sequence is open
+        size_t state_bytes = 0;
+        uint32_t dim_x = 0, dim_y = 0, row_first = 0, row_count = 0;
+        uint64_t frames = 0;
+    } lag;
     // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
     // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
     // retired and freed as the defect plan is.
@@ -497,6 +512,7 @@ void paris_hip_warm_axis_search();
 void paris_hip_warm_air_region();
 void paris_hip_warm_beam_hardening();
 void paris_hip_warm_detector_roll();
+void paris_hip_warm_lag();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -532,6 +548,8 @@ void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
 void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying);
 // air_region.hip: the same for the air region's memory
 void paris_hip_air_region_release(paris_hip_ctx* ctx, bool destroying);
+// lag.hip: the same for an open lag sequence's state
+void paris_hip_lag_release(paris_hip_ctx* ctx, bool destroying);
 
 // axis_rule.cpp: the estimate both searches share (the rule is stated with paris_hip_axis_search in include/paris_hip.h). Candidates
 // are (float)(lo + k step), k < count; a candidate is scored iff its cost is finite. PARIS_HIP_ERROR_INVALID_ARGUMENT when none is

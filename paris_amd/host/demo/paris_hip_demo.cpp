@@ -8,6 +8,7 @@
 //                       [--reproject frames.raw] [--defects mask.raw] [--zingers abs rel polarity]
 //                       [--rings half_width floor limit] [--find-axis lo step count rows]
 //                       [--extend-rows W M] [--bin BX BY mask.raw|none] [--air-region x0 y0 width height limit] [--detector-roll deg]
+//                       [--lag steady|rest B1:A1[:B2:A2[:B3:A3[:B4:A4]]]]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -34,6 +35,10 @@
 // set_row_extension() before the loops, so that paris::filter() adds the extension's response at its store.
 // --detector-roll: the detector's in-plane rotation in degrees. set_detector_roll() before the loops (with the binned geometry under
 // --bin), so that paris::weight() resamples each frame after the beam-hardening correction and before every weight.
+// --lag: the frames are counts of a detector with lag (needs --flat). set_lag_correction() before the loops; this loop knows where a
+// scan begins, so each slab's pass over the frames opens a sequence for whole frames (lag_begin()), corrects every loaded (and binned)
+// frame in time order before paris::weight() corrects it to line integrals (lag_correct()), and closes it (lag_end()). Refused with
+// --rings and --find-axis, whose pre-pass here does not run it.
 // --bin: the geometry on the command line is the SOURCE detector's and in.raw holds frames of that size; each loaded frame is binned
 // into a buffer of the binned detector (set_binning() before the loops, bin_frame() after paris::load()) and everything downstream runs
 // with binned_geometry(). mask.raw: n_col x n_row bytes at source size, nonzero = left out of its bin. --flat, --defects and the other
@@ -111,6 +116,10 @@ int main(int argc, char** argv)
         std::uint32_t extend_taper = 0, extend_edge = 0;
         bool detector_roll = false;
         float roll_deg = 0.f;
+        bool lag = false;
+        int lag_start = PARIS_HIP_LAG_START_STEADY;
+        std::uint32_t lag_terms = 0;
+        float lag_b[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, lag_a[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f};
         std::uint32_t bin_x = 1, bin_y = 1;
         std::string bin_mask_path;
         bool vol_given = false;
@@ -193,6 +202,22 @@ int main(int argc, char** argv)
                 roll_deg = std::strtof(argv[a + 1], nullptr);
                 a += 1;
             }
+            else if(!std::strcmp(argv[a], "--lag") && a + 2 < argc)
+            {
+                lag = true;
+                lag_start = !std::strcmp(argv[a + 1], "rest") ? PARIS_HIP_LAG_START_REST : PARIS_HIP_LAG_START_STEADY;
+                const char* at = argv[a + 2];
+                for(std::uint32_t k = 0; k < 2u * PARIS_HIP_LAG_TERMS_MAX && *at != '\0'; ++k)
+                {
+                    char* end = nullptr;
+                    (k % 2u == 0u ? lag_b : lag_a)[k / 2u] = std::strtof(at, &end);
+                    lag_terms = k / 2u + 1u;
+                    at = *end == ':' ? end + 1 : end;
+                    if(end == at)
+                        break;
+                }
+                a += 2;
+            }
             else if(!std::strcmp(argv[a], "--bin") && a + 3 < argc)
             {
                 bin_x = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
@@ -230,6 +255,11 @@ int main(int argc, char** argv)
         if(binning && (rings || find_axis || !reproject_path.empty()))
         {
             std::fprintf(stderr, "--bin cannot be combined with --rings, --find-axis or --reproject\n");
+            return 2;
+        }
+        if(lag && (rings || find_axis))
+        {
+            std::fprintf(stderr, "--lag cannot be combined with --rings or --find-axis\n");
             return 2;
         }
         const auto src_det = det; // the detector the frames of in.raw come from
@@ -309,6 +339,8 @@ int main(int argc, char** argv)
             paris::backend::set_row_extension(extend_edge, extend_taper);
         if(detector_roll)
             paris::backend::set_detector_roll(roll_deg, det);
+        if(lag)
+            paris::backend::set_lag_correction(lag_b, lag_a, lag_terms, lag_start);
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 
@@ -384,6 +416,8 @@ int main(int argc, char** argv)
             auto v = paris::make_volume(info.geo, last);
             const auto offset = static_cast<std::uint32_t>(id) * info.geo.dim_z;
             const auto t_start = std::chrono::steady_clock::now();
+            if(lag) // this pass over the scan is a sequence of its own, from frame 0
+                paris::backend::lag_begin(det.n_row, det.n_col, 0u, det.n_col);
             for(std::uint32_t i = 0; i < n_proj; ++i)
             {
                 // every call of one iteration of src/main.cpp:98-105 between two clock reads (~20 ns each)
@@ -403,6 +437,8 @@ int main(int argc, char** argv)
                     paris::backend::bin_frame(d_p.buf.get(), d_p.buf.pitch(), d_b.buf.get(), d_b.buf.pitch(), src_det.n_row, src_det.n_col, det.n_col);
                     d_p = std::move(d_b);
                 }
+                if(lag) // on the counts, before paris::weight() corrects them to line integrals
+                    paris::backend::lag_correct(d_p.buf.get(), d_p.buf.pitch(), det.n_row, det.n_col, 0u, det.n_col);
                 const auto c3 = clock::now();
                 if(do_weight) paris::weight(d_p, det);
                 const auto c4 = clock::now();
@@ -418,6 +454,8 @@ int main(int argc, char** argv)
                 for(int k = 0; k < 8; ++k)
                     split_s[k] += std::chrono::duration<double>(c[k + 1] - c[k]).count();
             }
+            if(lag)
+                paris::backend::lag_end();
             fill_s = split_s[1];
             const auto t_tail = std::chrono::steady_clock::now();
             paris::backend::synchronize(); // the timed region ends when the GPU has finished, not when the last call returned

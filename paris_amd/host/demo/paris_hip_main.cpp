@@ -10,6 +10,7 @@
 //             [--extend-rows W[:M]] [--voxel-type u8|u16 --voxel-range LO:HI|auto[:P_LO:P_HI]] [--bin BX[:BY]]
 //             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]
 //             [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]
+//             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -89,6 +90,7 @@ int main(int argc, char** argv)
                             "          [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]\n"
                             "          [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]\n"
                             "          [--detector-roll DEG | --find-roll LO:HI[:STEP] [--roll-only]]\n"
+                            "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -149,7 +151,14 @@ int main(int argc, char** argv)
                             "frames is mirror-symmetric about the projected axis in every detector row, and each candidate LO, LO + STEP .. HI\n"
                             "[degrees; STEP defaults to 0.25, at most 256 candidates] is scored on the device by the mean squared asymmetry of\n"
                             "the mean frame rolled back by it. The estimate is the minimum of a parabola through the best candidate and its\n"
-                            "neighbours. --roll-only prints it and stops. Not with --fit-beam-hardening.\n");
+                            "neighbours. --roll-only prints it and stops. Not with --fit-beam-hardening.\n"
+                            "--lag: an a-Si flat panel carries a few per cent of every frame's signal over into the following frames. Its impulse\n"
+                            "response is b_0 at once plus one to four terms B_n exp(-A_n k), k frames later (B_n, A_n > 0; b_0 = 1 - sum B_n /\n"
+                            "(1 - exp(-A_n)) must stay above 0). Every frame's counts are deconvolved recursively on the device, in the order of the\n"
+                            "files, after the upload (and --bin) and before the dark / flat correction; each pass over the scan starts from frame 0.\n"
+                            "--lag-start steady (the default): the beam was on and the first view had been seen for a long time; rest: the detector\n"
+                            "had seen nothing. Needs --flat (the frames must be counts); not with --quality above 1 (the skipped frames still fed\n"
+                            "the detector's memory).\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -189,6 +198,8 @@ int main(int argc, char** argv)
             else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
             else if(k == "--beam-hardening") paris::detail::parse_beam_hardening(val(), po);
             else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
+            else if(k == "--lag") paris::detail::parse_lag(val(), po);
+            else if(k == "--lag-start") paris::detail::parse_lag_start(val(), po);
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -229,6 +240,14 @@ int main(int argc, char** argv)
         if(r.flat_frames != 0)
             std::printf("dark / flat correction on: %u flat frame(s), %u dark frame(s)%s, min transmission %g\n", r.flat_frames, r.dark_frames,
                         r.dark_frames == 0 ? " (zero dark)" : "", static_cast<double>(po.t_min));
+        if(r.lag)
+        {
+            std::printf("lag correction on: %u term(s)", r.lag_model.terms);
+            for(std::uint32_t n = 0; n < r.lag_model.terms; ++n)
+                std::printf(" %.9g:%.9g", static_cast<double>(r.lag_model.b[n]), static_cast<double>(r.lag_model.a[n]));
+            std::printf(", b_0 = %.6g, every pass over the scan starts %s\n", r.lag_b0,
+                        r.lag_model.start == PARIS_HIP_LAG_START_STEADY ? "steady" : "at rest");
+        }
         if(r.defect_map)
             std::printf("defect map on: %llu defective pixel(s), %llu unrepairable (no good pixel within %d)\n",
                         static_cast<unsigned long long>(r.defects.defects), static_cast<unsigned long long>(r.defects.unrepairable), PARIS_HIP_DEFECT_R_MAX);

@@ -578,6 +578,49 @@ namespace paris
                                   "bin_frame()");
         }
 
+        // Extension (no reference counterpart): the detector of this thread's current device carries part of every frame's signal
+        // over into the following frames (lag). b and a hold `terms` weights and decay rates per frame of
+        // its impulse response (1 .. 4 terms), start is PARIS_HIP_LAG_START_STEADY or _REST. The pass carries state from frame to
+        // frame, so a caller that knows where a scan begins drives it itself: lag_begin() for the rows it will upload, then
+        // lag_correct() on every frame of counts in time order -- after the raw upload and bin_frame(), before the dark / flat
+        // correction -- then lag_end(). PARIS's per-projection stage loop (stages.h) has no notion of where a scan begins and does not
+        // apply it.
+        inline auto set_lag_correction(const float* b, const float* a, std::uint32_t terms, int start = PARIS_HIP_LAG_START_STEADY) -> void
+        {
+            auto model = paris_hip_lag_model{};
+            model.terms = terms;
+            model.start = start;
+            for(std::uint32_t n = 0; b != nullptr && a != nullptr && n < terms && n < PARIS_HIP_LAG_TERMS_MAX; ++n)
+            {
+                model.b[n] = b[n];
+                model.a[n] = a[n];
+            }
+            detail::runtime_check(b == nullptr || a == nullptr ? PARIS_HIP_ERROR_INVALID_ARGUMENT : paris_hip_set_lag_correction(current_ctx(), &model),
+                                  "set_lag_correction()");
+        }
+
+        inline auto clear_lag_correction() -> void
+        {
+            detail::runtime_check(paris_hip_clear_lag_correction(current_ctx()), "clear_lag_correction()");
+        }
+
+        inline auto lag_begin(std::uint32_t n_row, std::uint32_t n_col, std::uint32_t row_first, std::uint32_t row_count) -> void
+        {
+            detail::runtime_check(paris_hip_lag_begin(current_ctx(), n_row, n_col, row_first, row_count), "lag_begin()");
+        }
+
+        // the begun rows of one n_row x n_col frame of counts at d_p, the next in time
+        inline auto lag_correct(float* d_p, std::size_t pitch, std::uint32_t n_row, std::uint32_t n_col, std::uint32_t row_first, std::uint32_t row_count)
+            -> void
+        {
+            detail::runtime_check(paris_hip_lag_correct_rows(current_ctx(), d_p, pitch, 0u, 1u, n_row, n_col, row_first, row_count), "lag_correct()");
+        }
+
+        inline auto lag_end() -> void
+        {
+            detail::runtime_check(paris_hip_lag_end(current_ctx()), "lag_end()");
+        }
+
         // ---- buffers ------------------------------------------------------------------------------------------
         struct device_free { void operator()(float* p) const noexcept { paris_hip_free(current_ctx(), p); } };
         struct host_free { void operator()(float* p) const noexcept { paris_hip_free_host(current_ctx(), p); } };

@@ -167,6 +167,14 @@ namespace paris
         std::uint32_t src_row = 0, src_col = 0;                         // filled by run() with binning: the source detector (0: no binning)
         std::shared_ptr<const std::vector<std::uint8_t>> bin_mask;      // filled by run(): the bad source pixels left out of their bins (may be empty)
         bool binning() const { return src_row != 0; }
+        // correction of the detector's lag (extension): --lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] gives the weights and
+        // decay rates per frame of the panel's impulse response, --lag-start rest|steady how a pass over the scan starts (steady: the
+        // beam was on before the first frame, the default), checked by run() before any device work (detail::check_lag): it needs
+        // --flat, because the frames must be counts, and every frame of the scan (no --quality above 1). Every device ctx gets the
+        // setting; each pass over the scan opens a sequence for the rows it uploads, corrects every frame between its raw upload (and
+        // binning) and the dark / flat correction, which then runs as a pass of its own, and closes the sequence after the last frame
+        bool lag = false, lag_start_given = false;
+        paris_hip_lag_model lag_model{0u, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, PARIS_HIP_LAG_START_STEADY};
         // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
         // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
         // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
@@ -343,6 +351,8 @@ namespace paris
             if(po.flat)
                 rt(paris_hip_set_flat_field(ctx, po.dark ? po.dark->pixels.data() : nullptr, po.flat->pixels.data(), po.det_geo.n_row, po.det_geo.n_col,
                                             po.t_min), "set_flat_field()");
+            if(po.lag)
+                rt(paris_hip_set_lag_correction(ctx, &po.lag_model), "set_lag_correction()");
             auto mask = std::vector<std::uint8_t>{}; // the defect map's, which the air region leaves out as well
             if(po.defect_mask || po.defects_from_flat)
             {
@@ -410,7 +420,9 @@ namespace paris
             const auto binning = po.binning() ? slots * po.src_col * src_row + (po.bin_mask ? po.bin_mask->size() : 0u) : 0u;
             // with --detector-roll / --find-roll, every slot's rolled frame as well
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
-            return rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
+            // with --lag, the state of a whole-detector sequence at most
+            const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -965,6 +977,10 @@ namespace paris
                 // --bin: the source rows the uploaded band is binned from (the band itself without it)
                 const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
 
+                // --lag: this pass over the scan is a sequence of its own, from frame 0 of the file, for the rows it uploads
+                if(po.lag && band_count != 0)
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, up_first, up_count), "lag_begin()");
+
                 t0 = clock::now();
                 // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
                 auto shared = pool != nullptr ? pool->get(t) : std::shared_ptr<shared_frames>{};
@@ -1081,8 +1097,19 @@ namespace paris
                             rt(paris_hip_upload_projection_raw(ctx, d_src_band, s_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, sn_row * px,
                                                                sn_row, src_count, p.pixel), "load()");
                             rt(paris_hip_bin_frames(ctx, d_src[slot], s_pitch, 0u, d_buf[slot], d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
+                            if(po.lag) // the detector's memory of the frames before, on the binned counts
+                                rt(paris_hip_lag_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
                             if(po.flat)
                                 rt(paris_hip_flat_field_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
+                        }
+                        else if(po.lag)
+                        {
+                            // the unfused route binning takes: the counts as stored, the lag correction on them, then the dark / flat
+                            // correction as a pass of its own -- the same bits as the corrected upload of the corrected counts
+                            rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
+                                                               n_row, up_count, p.pixel), "load()");
+                            rt(paris_hip_lag_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
+                            rt(paris_hip_flat_field_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
                         }
                         else if(po.flat)
                             rt(paris_hip_upload_projection_raw_corrected(ctx, d_buf[slot], d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off,
@@ -1126,6 +1153,8 @@ namespace paris
                     ++rep.projections;
                 }
                 flush(); // the last, possibly partial group
+                if(po.lag)
+                    rt(paris_hip_lag_end(ctx), "lag_end()");
                 if(feed)
                 {
                     rep.source_s += feed->read_seconds();
@@ -1214,6 +1243,9 @@ namespace paris
         std::uint32_t bin_x = 1, bin_y = 1;             // pixels have no good source pixel (they join the defect map)
         std::uint32_t src_row = 0, src_col = 0, binned_row = 0, binned_col = 0;
         std::uint64_t binned_defective = 0;
+        bool lag = false;                               // --lag: every pass over the scan corrected the frames' counts with this model,
+        paris_hip_lag_model lag_model{};                // whose instantaneous weight is lag_b0
+        double lag_b0 = 0.0;
         int voxel_type = 0;                             // --voxel-type: the voxels were quantised over [voxel_lo, voxel_hi] (with
         float voxel_lo = 0.f, voxel_hi = 0.f;           // --voxel-range auto: the window chosen); the counts of every drain ctx, added
         paris_hip_volume_counts voxels{};
@@ -1764,6 +1796,8 @@ namespace paris
                     rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
                 if(axis)
                     rt(paris_hip_axis_search_begin(ctx, &search, &po.det_geo, po.axis_frames), "axis_search_begin()");
+                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, up_first, up_count), "lag_begin()");
                 std::uint32_t frames = 0;
                 auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
                 for(bool more = true; more;)
@@ -1788,8 +1822,17 @@ namespace paris
                             auto* d_full_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_full) + static_cast<std::size_t>(src_first) * s_pitch);
                             rt(paris_hip_upload_projection_raw(ctx, d_full_band, s_pitch, h_band, sn_row * px, sn_row, src_count, p.pixel), "load()");
                             rt(paris_hip_bin_frames(ctx, d_full, s_pitch, 0u, d_frame, d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
+                            if(po.lag)
+                                rt(paris_hip_lag_correct_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
                             if(po.flat)
                                 rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
+                        }
+                        else if(po.lag) // the unfused route, as in reconstruct()
+                        {
+                            rt(paris_hip_upload_projection_raw(ctx, reinterpret_cast<float*>(reinterpret_cast<char*>(d_frame) + static_cast<std::size_t>(up_first) * d_pitch),
+                                                               d_pitch, h_band, n_row * px, n_row, up_count, p.pixel), "load()");
+                            rt(paris_hip_lag_correct_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
+                            rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
                         }
                         else if(po.flat)
                             rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_band, n_row * px, n_row, n_col, up_first, up_count, p.pixel),
@@ -1815,6 +1858,8 @@ namespace paris
                     rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
                     frames += filled;
                 }
+                if(po.lag)
+                    rt(paris_hip_lag_end(ctx), "lag_end()");
                 if(po.air)
                     rt(paris_hip_air_stats(ctx, &r.air_prepass, 0), "air stats");
                 auto mean = std::vector<float>(roll ? static_cast<std::size_t>(n_row) * n_col : 0u); // --find-roll: the scan mean
@@ -2022,6 +2067,8 @@ namespace paris
                 auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
                 std::uint32_t frames = 0;
                 auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
+                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file, on whole frames
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, 0u, n_col), "lag_begin()");
                 for(bool more = true; more;)
                 {
                     std::uint32_t filled = 0;
@@ -2041,13 +2088,38 @@ namespace paris
                     }
                     if(filled == 0)
                         break;
+                    if(po.lag)
+                    {
+                        // The group goes through the stages once per basis, but the sequence's state must see every frame once: the
+                        // counts are corrected once, in time order, and the pinned frames (a slot holds 4 bytes per pixel) are replaced
+                        // by the corrected counts as f32, which every basis then uploads.
+                        for(std::uint32_t f = 0; f < filled; ++f)
+                        {
+                            auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * f);
+                            rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * his::pixel_size(infos[f].pixel), n_row, n_col,
+                                                               infos[f].pixel), "load()");
+                        }
+                        rt(paris_hip_lag_correct_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "lag correction");
+                        for(std::uint32_t f = 0; f < filled; ++f)
+                        {
+                            rt(paris_hip_memcpy_projection_d2h(ctx, h_buf[f], n_row * sizeof(float), reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_all) + d_stride * f),
+                                                               d_pitch, n_row, n_col), "copy_d2h()");
+                            infos[f].pixel = his::pixel_f32;
+                        }
+                        rt(paris_hip_ctx_synchronize(ctx), "synchronize");
+                    }
                     for(std::uint32_t k = 0; k < degree; ++k)
                     {
                         for(std::uint32_t f = 0; f < filled; ++f)
                         {
                             auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * f);
                             const auto px = his::pixel_size(infos[f].pixel);
-                            if(po.flat)
+                            if(po.lag) // the unfused route: the corrected counts, then the dark / flat correction as a pass of its own
+                            {
+                                rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, infos[f].pixel), "load()");
+                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, 0u, n_col), "flat field");
+                            }
+                            else if(po.flat)
                                 rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, 0u, n_col,
                                                                              infos[f].pixel), "load()");
                             else
@@ -2079,6 +2151,8 @@ namespace paris
                     }
                     frames += filled;
                 }
+                if(po.lag)
+                    rt(paris_hip_lag_end(ctx), "lag_end()");
                 if(frames == 0u)
                     throw stage_runtime_error{"--fit-beam-hardening: the input holds no projection"};
                 const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
@@ -2261,6 +2335,53 @@ namespace paris
                                                + std::to_string(po.roll_step) + ")"};
         }
 
+        // --lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] as typed; refuses anything but one to four pairs of numbers
+        inline auto parse_lag(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]]: cannot read '" + v + "'"}; };
+            const auto field = colon_fields(v);
+            if(field.size() < 2u || field.size() % 2u != 0u || field.size() > 2u * PARIS_HIP_LAG_TERMS_MAX)
+                throw bad();
+            po.lag_model.terms = static_cast<std::uint32_t>(field.size() / 2u);
+            for(std::size_t k = 0; k < field.size(); ++k)
+            {
+                char* end = nullptr;
+                const float x = std::strtof(field[k].c_str(), &end);
+                if(field[k].empty() || end == nullptr || *end != '\0')
+                    throw bad();
+                (k % 2u == 0u ? po.lag_model.b : po.lag_model.a)[k / 2u] = x;
+            }
+            po.lag = true;
+        }
+
+        inline auto parse_lag_start(const std::string& v, program_options& po) -> void
+        {
+            if(v == "rest") po.lag_model.start = PARIS_HIP_LAG_START_REST;
+            else if(v == "steady") po.lag_model.start = PARIS_HIP_LAG_START_STEADY;
+            else throw stage_construction_error{"--lag-start rest|steady: unknown start " + v};
+            po.lag_start_given = true;
+        }
+
+        // --lag / --lag-start: checked here, before any device work. The correction works on counts, so it needs --flat; and on every
+        // frame the detector took, so --quality above 1 is refused: the skipped frames still fed the detector's memory.
+        inline auto check_lag(const program_options& po) -> void
+        {
+            if(!po.lag)
+            {
+                if(po.lag_start_given)
+                    throw stage_construction_error{"--lag-start needs --lag"};
+                return;
+            }
+            if(po.flat_path.empty())
+                throw stage_construction_error{"--lag needs --flat: the lag correction works on detector counts, before the dark / flat correction"};
+            if(po.quality > 1u)
+                throw stage_construction_error{"--lag cannot be combined with --quality " + std::to_string(po.quality)
+                                               + ": the skipped frames still fed the detector's memory"};
+            if(paris_hip_lag_model_check(&po.lag_model) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]]: every weight B and decay rate per frame A must be finite and above 0, "
+                                               "and b_0 = 1 - sum B / (1 - exp(-A)) must be above 0"};
+        }
+
         inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
         {
             if(v == "bright") po.zinger_polarity = 1;
@@ -2276,6 +2397,7 @@ namespace paris
         auto po = requested; // batch may shrink to fit the devices' memory (detail::fit_batch)
         auto r = run_report{};
         const auto start = detail::clock::now();
+        detail::check_lag(po);
         detail::load_flat_field(po);
         r.flat_frames = po.flat ? po.flat->n_frames : 0u;
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
@@ -2359,6 +2481,13 @@ namespace paris
         r.bh = po.bh;
         r.detector_roll = po.roll;
         r.roll_deg = po.roll_deg;
+        r.lag = po.lag;
+        r.lag_model = po.lag_model;
+        if(po.lag)
+        {
+            float g[4], c[4], w[4];
+            detail::rt(paris_hip_lag_coefficients(&po.lag_model, g, c, w, nullptr, &r.lag_b0), "lag_coefficients()");
+        }
 
         if(po.slabs > 0) // fixed split (src/cuda/subvolume_information.cpp:112-116 with a given count)
         {
