@@ -37,3 +37,16 @@ def test_variant_tests_against_the_experiments_build():
     r = subprocess.run([sys.executable, "-c", "from paris_amd import _lib; print(_lib.has_experiments(), _lib.LIB_PATH)"], capture_output=True,
                        text=True, timeout=300, env=env, cwd=ROOT)
     assert r.stdout.split()[0] == "True" and r.stdout.split()[1].endswith("libparis_hip_experiments.so"), r.stdout + r.stderr
+
+
+def test_filter_bins_against_the_experiments_build():
+    """tests/test_gpu_filter_bins.py once more with the other library: its variant 2 cases run there instead of being refused, and a K
+    the ctx did not make is served by the first radix-16 kernel"""
+    assert os.path.exists(_lib.EXPERIMENTS_LIB_PATH), "build it: make -C paris_amd/csrc EXPERIMENTS=1 (__graft_entry__.build() does)"
+    env = dict(os.environ, PARIS_HIP_LIBRARY=_lib.EXPERIMENTS_LIB_PATH)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_filter_bins.py"), "-x", "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    tail = r.stdout[-3000:] + r.stderr[-1500:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) >= 54 and "skipped" not in r.stdout.splitlines()[-1], tail
