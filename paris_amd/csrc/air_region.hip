@@ -176,10 +176,11 @@ namespace
     {
         const paris_hip_ctx::air_t& s = ctx->air;
         const paris_hip_air_layout lay = paris_hip_air_layout_of(s.rule.width, s.rule.height);
+        char* d_mem = s.mem.as<char>();
         hipLaunchKernelGGL(air_value_kernel, dim3(nf), dim3(AIR_THREADS), 0, ctx->stream, b.frame(f0), b.frame_stride, b.pitch / sizeof(float),
                            s.rule.x0, s.rule.y0, s.rule.width, s.rule.height, s.rule.min_pixels, s.rule.limit_abs,
-                           reinterpret_cast<const uint8_t*>(s.d_mem + lay.mask), reinterpret_cast<float*>(s.d_mem + lay.value),
-                           reinterpret_cast<uint32_t*>(s.d_mem + lay.count), counted ? reinterpret_cast<air_counters*>(s.d_mem) : nullptr);
+                           reinterpret_cast<const uint8_t*>(d_mem + lay.mask), reinterpret_cast<float*>(d_mem + lay.value),
+                           reinterpret_cast<uint32_t*>(d_mem + lay.count), counted ? reinterpret_cast<air_counters*>(d_mem) : nullptr);
     }
 
     int air_refuse(const paris_hip_ctx* ctx, uint32_t dim_x, uint32_t dim_y)
@@ -187,13 +188,6 @@ namespace
         const paris_hip_ctx::air_t& s = ctx->air;
         return !s.set || dim_x != s.dim_x || dim_y != s.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
     }
-}
-
-void paris_hip_air_region_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->air.d_mem, destroying);
-    ctx->air = paris_hip_ctx::air_t{};
-    paris_hip_sweep_retired(ctx, destroying);
 }
 
 extern "C" int paris_hip_set_air_region(paris_hip_ctx* ctx, const paris_hip_air_region* ar, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y)
@@ -213,33 +207,17 @@ extern "C" int paris_hip_set_air_region(paris_hip_ctx* ctx, const paris_hip_air_
         for(uint32_t y = 0; y < ar->height; ++y)
             for(uint32_t x = 0; x < ar->width; ++x)
                 init[lay.mask + static_cast<size_t>(y) * ar->width + x] = mask[static_cast<size_t>(ar->y0 + y) * dim_x + ar->x0 + x] != 0u ? 1 : 0;
-    char* d = nullptr;
-    int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), bytes);
-    // copied on the ctx's auxiliary stream and waited for there, as the zinger filter's accumulators are zeroed: in place before any
-    // kernel of the compute stream uses it, without waiting for the work queued there, which still uses the old setting
-    if(rc == PARIS_HIP_SUCCESS)
-        rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        const hipError_t err = hipMemcpyAsync(d, init.data(), bytes, hipMemcpyHostToDevice, ctx->aux_stream);
-        const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err != hipSuccess ? err : waited);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        if(d != nullptr)
-            (void)hipFree(d);
+    paris_hip_device_buffer mem;
+    if(int rc = paris_hip_install(ctx, bytes, {{0u, init.data(), bytes}}, &mem))
         return rc;
-    }
-    paris_hip_air_region_release(ctx, false);
     paris_hip_ctx::air_t& s = ctx->air;
+    paris_hip_release(ctx, s);
     s.set = true;
     s.rule = *ar;
     s.rule.min_pixels = min_pixels;
     s.dim_x = dim_x;
     s.dim_y = dim_y;
-    s.device_bytes = bytes;
-    s.d_mem = d;
+    s.mem = mem;
     return PARIS_HIP_SUCCESS;
 }
 
@@ -247,7 +225,7 @@ extern "C" int paris_hip_clear_air_region(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_air_region_release(ctx, false);
+    paris_hip_release(ctx, ctx->air);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -257,7 +235,7 @@ extern "C" int paris_hip_air_normalize_rows(paris_hip_ctx* ctx, float* d_p, size
     const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     const auto launch = [&] {
         const paris_hip_ctx::air_t& s = ctx->air;
-        const float* value = reinterpret_cast<const float*>(s.d_mem + paris_hip_air_layout_of(s.rule.width, s.rule.height).value);
+        const float* value = reinterpret_cast<const float*>(s.mem.as<char>() + paris_hip_air_layout_of(s.rule.width, s.rule.height).value);
         const bool vec = air_vector_rows(band);
         const uint32_t groups_x = vec ? dim_x / 4u : dim_x;
         const uint64_t lanes = static_cast<uint64_t>(groups_x) * row_count;
@@ -295,9 +273,9 @@ extern "C" int paris_hip_air_measure(paris_hip_ctx* ctx, const float* d_p, size_
             const uint32_t nf = std::min<uint32_t>(PARIS_HIP_AIR_FRAMES_MAX, n_frames - f0);
             air_launch_values(ctx, band, f0, nf, false);
             if(h_a != nullptr)
-                copy_rc = static_cast<int>(hipMemcpyAsync(h_a + f0, s.d_mem + lay.value, nf * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+                copy_rc = static_cast<int>(hipMemcpyAsync(h_a + f0, s.mem.as<char>() + lay.value, nf * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
             if(h_n != nullptr && copy_rc == PARIS_HIP_SUCCESS)
-                copy_rc = static_cast<int>(hipMemcpyAsync(h_n + f0, s.d_mem + lay.count, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                copy_rc = static_cast<int>(hipMemcpyAsync(h_n + f0, s.mem.as<char>() + lay.count, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             if(copy_rc == PARIS_HIP_SUCCESS) // (the host arrays may be pageable: each copy is complete before the slots are reused)
                 copy_rc = static_cast<int>(hipStreamSynchronize(ctx->stream));
         }
@@ -325,9 +303,9 @@ extern "C" int paris_hip_air_stats(paris_hip_ctx* ctx, paris_hip_air_counts* out
         return rc;
     air_counters acc{};
     const air_counters empty = air_counters_empty();
-    PARIS_HIP_TRY(hipMemcpyAsync(&acc, ctx->air.d_mem, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
+    PARIS_HIP_TRY(hipMemcpyAsync(&acc, ctx->air.mem.d, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
     if(reset)
-        PARIS_HIP_TRY(hipMemcpyAsync(ctx->air.d_mem, &empty, sizeof(empty), hipMemcpyHostToDevice, ctx->stream));
+        PARIS_HIP_TRY(hipMemcpyAsync(ctx->air.mem.d, &empty, sizeof(empty), hipMemcpyHostToDevice, ctx->stream));
     PARIS_HIP_TRY(hipStreamSynchronize(ctx->stream));
     out->frames = acc.frames;
     out->normalised = acc.normalised;

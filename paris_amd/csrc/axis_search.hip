@@ -196,16 +196,8 @@ namespace
 
     float* axis_sinogram(const paris_hip_ctx::axis_t& a)
     {
-        return reinterpret_cast<float*>(a.d_mem);
+        return a.mem.as<float>();
     }
-}
-
-void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_ctx::axis_t& a = ctx->axis;
-    paris_hip_retire_device_buffer(ctx, a.d_mem, destroying);
-    a = paris_hip_ctx::axis_t{};
-    paris_hip_sweep_retired(ctx, destroying);
 }
 
 extern "C" int paris_hip_axis_search_begin(paris_hip_ctx* ctx, const paris_hip_axis_search* setting, const paris_detector_geometry* det_geo,
@@ -214,7 +206,7 @@ extern "C" int paris_hip_axis_search_begin(paris_hip_ctx* ctx, const paris_hip_a
     if(int rc = paris_hip_bind(ctx))
         return rc;
     paris_hip_ctx::axis_t next;
-    if(int rc = paris_hip_axis_search_check(setting, det_geo, n_frames, &next.row_first, &next.device_bytes))
+    if(int rc = paris_hip_axis_search_check(setting, det_geo, n_frames, &next.row_first, nullptr))
         return rc;
     const uint32_t n = det_geo->n_row, count = setting->count;
     const paris_hip_axis_layout lay = paris_hip_axis_layout_of(n, n_frames, count);
@@ -227,26 +219,9 @@ extern "C" int paris_hip_axis_search_begin(paris_hip_ctx* ctx, const paris_hip_a
             return rc;
         next.columns[k] = static_cast<uint32_t>(std::count_if(row, row + n, [](const paris_hip_axis_entry& e) { return e.i0 >= 0; }));
     }
-    char* d = nullptr;
-    int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), lay.bytes);
-    // the plan is copied on the ctx's auxiliary stream and waited for there, as the ring correction is: in place before any kernel of
-    // the compute stream reads it, without waiting for the work queued there, which still belongs to the old search
-    if(rc == PARIS_HIP_SUCCESS)
-        rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        hipError_t err = hipMemcpyAsync(d + lay.plan, plan.data(), plan.size() * sizeof(paris_hip_axis_entry), hipMemcpyHostToDevice, ctx->aux_stream);
-        const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err != hipSuccess ? err : waited);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        if(d != nullptr)
-            (void)hipFree(d);
+    if(int rc = paris_hip_install(ctx, lay.bytes, {{lay.plan, plan.data(), plan.size() * sizeof(paris_hip_axis_entry)}}, &next.mem))
         return rc;
-    }
-    paris_hip_axis_search_release(ctx, false);
-    next.d_mem = d;
+    paris_hip_release(ctx, ctx->axis);
     next.setting = *setting;
     next.n = n;
     next.n_col = det_geo->n_col;
@@ -261,7 +236,7 @@ extern "C" int paris_hip_axis_search_add_rows(paris_hip_ctx* ctx, const float* d
 {
     if(ctx == nullptr)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    const bool open = ctx->axis.d_mem != nullptr && dim_x == ctx->axis.n && dim_y == ctx->axis.n_col;
+    const bool open = ctx->axis.mem.d != nullptr && dim_x == ctx->axis.n && dim_y == ctx->axis.n_col;
     const paris_hip_frame_band band{const_cast<float*>(d_p), pitch,   frame_stride, n_frames, dim_x, dim_y, open ? ctx->axis.row_first : 0u,
                                     open ? ctx->axis.setting.rows : 0u};
     const auto refuse = [&]() -> int {
@@ -298,17 +273,18 @@ extern "C" int paris_hip_axis_search_finish(paris_hip_ctx* ctx, double* cost, ui
     if(int rc = paris_hip_bind(ctx))
         return rc;
     paris_hip_ctx::axis_t& a = ctx->axis;
-    if(a.d_mem == nullptr || cost == nullptr || result == nullptr || a.missing != 0u)
+    if(a.mem.d == nullptr || cost == nullptr || result == nullptr || a.missing != 0u)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     if(int rc = paris_hip_flush_pending_weight(ctx))
         return rc;
     const uint32_t count = a.setting.count;
     const paris_hip_axis_layout lay = paris_hip_axis_layout_of(a.n, a.n_frames, count);
     const uint32_t tiles = lay.col_tiles * lay.view_tiles;
-    axis_partial* d_partial = reinterpret_cast<axis_partial*>(a.d_mem + lay.partial);
-    axis_total* d_total = reinterpret_cast<axis_total*>(a.d_mem + lay.total_of);
+    char* d_mem = a.mem.as<char>();
+    axis_partial* d_partial = reinterpret_cast<axis_partial*>(d_mem + lay.partial);
+    axis_total* d_total = reinterpret_cast<axis_total*>(d_mem + lay.total_of);
     hipLaunchKernelGGL(axis_score_kernel, dim3(tiles, count), dim3(AXIS_THREADS), 0, ctx->stream, axis_sinogram(a),
-                       reinterpret_cast<const paris_hip_axis_entry*>(a.d_mem + lay.plan), a.n, a.n_frames, lay.col_tiles, d_partial);
+                       reinterpret_cast<const paris_hip_axis_entry*>(d_mem + lay.plan), a.n, a.n_frames, lay.col_tiles, d_partial);
     hipLaunchKernelGGL(axis_total_kernel, dim3(count), dim3(AXIS_THREADS), 0, ctx->stream, d_partial, tiles, d_total);
     PARIS_HIP_TRY(hipGetLastError());
     std::vector<axis_total> total(count);
@@ -329,7 +305,7 @@ extern "C" int paris_hip_axis_search_finish(paris_hip_ctx* ctx, double* cost, ui
     const int rc = paris_hip_axis_estimate_from_costs(&a.setting, cost, a.columns.data(), result);
     result->skipped = skipped;
     result->row_first = a.row_first;
-    paris_hip_axis_search_release(ctx, false);
+    paris_hip_release(ctx, a);
     return rc;
 }
 
@@ -337,7 +313,7 @@ extern "C" int paris_hip_axis_search_discard(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_axis_search_release(ctx, false);
+    paris_hip_release(ctx, ctx->axis);
     return PARIS_HIP_SUCCESS;
 }
 

@@ -1012,29 +1012,8 @@ extern "C" int paris_hip_projection_reserve_bytes(paris_hip_ctx* ctx, uint32_t d
     size_t total = std::min(ctx->device_pool_capacity(frame) * frame, paris_hip_ctx::PARKED_DEVICE_LIMIT + frame);
     if(ctx->defer_depth > 1u)
         total += (ctx->defer_refs != 0 ? 1u : 2u) * static_cast<size_t>(ctx->defer_depth) * frame; // the pending group by reference, or the ring's two halves
-    if(ctx->flat_field.d_ref != nullptr) // the dark and flat frames of paris_hip_set_flat_field
-        total += 2u * sizeof(float) * static_cast<size_t>(ctx->flat_field.dim_x) * ctx->flat_field.dim_y;
-    if(ctx->defect_map.set) // the plan of paris_hip_set_defect_map
-        total += static_cast<size_t>(ctx->defect_map.stats.device_bytes);
-    if(ctx->zinger.set) // the scratch of paris_hip_set_zinger_filter
-        total += ctx->zinger.device_bytes;
-    if(ctx->ring.d_sum != nullptr) // the open profile of paris_hip_ring_profile_begin
-        total += sizeof(double) * static_cast<size_t>(ctx->ring.sum_dim_x) * ctx->ring.sum_dim_y;
-    if(ctx->ring.set) // the correction frame of paris_hip_set_ring_correction
-        total += sizeof(float) * static_cast<size_t>(ctx->ring.dim_x) * ctx->ring.dim_y;
-    if(ctx->axis.d_mem != nullptr) // the sinogram, plan and partial sums of paris_hip_axis_search_begin
-        total += ctx->axis.device_bytes;
-    if(ctx->binning.d_mask != nullptr) // the mask of paris_hip_set_binning
-        total += static_cast<size_t>(ctx->binning.dim_x) * ctx->binning.dim_y;
-    if(ctx->air.set) // the mask bytes, values and counters of paris_hip_set_air_region
-        total += ctx->air.device_bytes;
-    if(ctx->lag.d_state != nullptr) // the state of the sequence paris_hip_lag_begin opened
-        total += ctx->lag.state_bytes;
-    if(ctx->row_extension.set) // the responses paris_hip_set_row_extension's filter calls have cached
-        total += ctx->row_extension.device_bytes;
-    if(ctx->volume_window.d_acc != nullptr) // the volume export's counters
-        total += PARIS_HIP_VOLUME_WINDOW_ACC_BYTES;
-    total += ctx->volume_window.stage_bytes; // the staging buffer of paris_hip_volume_quantize_d2h
+    // and the device memory of every setting
+    ctx->each_setting([&total](auto& setting) { paris_hip_each_buffer(setting, [&total](const paris_hip_device_buffer& b) { total += b.bytes; }); });
     *bytes = total;
     return PARIS_HIP_SUCCESS;
 }

@@ -205,13 +205,6 @@ namespace
     }
 }
 
-void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->binning.d_mask, destroying);
-    ctx->binning = paris_hip_ctx::binning_t{};
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 extern "C" int paris_hip_set_binning(paris_hip_ctx* ctx, const paris_hip_binning* setting, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y)
 {
     if(int rc = paris_hip_bind(ctx))
@@ -219,32 +212,18 @@ extern "C" int paris_hip_set_binning(paris_hip_ctx* ctx, const paris_hip_binning
     uint32_t out_x = 0, out_y = 0;
     if(int rc = paris_hip_binning_check(setting, dim_x, dim_y, &out_x, &out_y))
         return rc;
-    uint8_t* d = nullptr;
+    paris_hip_device_buffer mem; // (none without a mask)
     if(mask != nullptr)
     {
         const size_t n = static_cast<size_t>(dim_x) * dim_y;
-        if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), n))
+        if(int rc = paris_hip_install(ctx, n, {{0u, mask, n}}, &mem))
             return rc;
-        // copied on the ctx's auxiliary stream and waited for there, as the flat-field frames are
-        int rc = paris_hip_ensure_aux(ctx);
-        if(rc == PARIS_HIP_SUCCESS)
-        {
-            hipError_t err = hipMemcpyAsync(d, mask, n, hipMemcpyHostToDevice, ctx->aux_stream);
-            if(err == hipSuccess)
-                err = hipStreamSynchronize(ctx->aux_stream);
-            rc = static_cast<int>(err);
-        }
-        if(rc != PARIS_HIP_SUCCESS)
-        {
-            (void)hipFree(d);
-            return rc;
-        }
     }
-    paris_hip_binning_release(ctx, false);
     paris_hip_ctx::binning_t& bn = ctx->binning;
+    paris_hip_release(ctx, bn);
     bn.set = true;
     bn.rule = *setting;
-    bn.d_mask = d;
+    bn.mem = mem;
     bn.dim_x = dim_x;
     bn.dim_y = dim_y;
     bn.out_x = out_x;
@@ -256,7 +235,7 @@ extern "C" int paris_hip_clear_binning(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_binning_release(ctx, false);
+    paris_hip_release(ctx, ctx->binning);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -286,14 +265,14 @@ extern "C" int paris_hip_bin_frames(paris_hip_ctx* ctx, const float* d_src, size
         a.src_stride = src_frame_stride;
         a.dst_pitch = dst_pitch;
         a.dst_stride = dst_frame_stride;
-        a.mask = bn.d_mask;
+        a.mask = bn.mem.as<uint8_t>();
         a.n_frames = n_frames;
         a.dim_x = dim_x;
         a.out_x = bn.out_x;
         a.row_first = row_first;
         a.row_end = row_first + row_count;
         a.mask_words = dim_x % 4u == 0 ? 1u : 0u;
-        hipLaunchKernelGGL(bin_kernel_for(bn.rule.bin_x, by, bn.d_mask != nullptr, vec), dim3(gx, gy, gz), dim3(BIN_THREADS), 0, ctx->stream, a);
+        hipLaunchKernelGGL(bin_kernel_for(bn.rule.bin_x, by, bn.mem.d != nullptr, vec), dim3(gx, gy, gz), dim3(BIN_THREADS), 0, ctx->stream, a);
     };
     return paris_hip_frame_pass(ctx, src, dst, [] { return PARIS_HIP_SUCCESS; }, launch);
 }

@@ -329,16 +329,6 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     if(ctx->upload_stream != nullptr)
         (void)hipStreamSynchronize(ctx->upload_stream);
     ctx->pending_weight.active = false; // a weighting nobody filtered or read: dropped with the ctx
-    paris_hip_flat_field_release(ctx, true); // (nothing reads the reference frames but the compute stream, drained above)
-    paris_hip_defect_map_release(ctx, true);
-    paris_hip_zinger_release(ctx, true);
-    paris_hip_ring_profile_release(ctx, true);
-    paris_hip_ring_correction_release(ctx, true);
-    paris_hip_volume_window_release(ctx, true);
-    paris_hip_binning_release(ctx, true);
-    paris_hip_axis_search_release(ctx, true);
-    paris_hip_air_region_release(ctx, true);
-    paris_hip_lag_release(ctx, true);
     if(ctx->defer_count != 0)
     {
         // Projections still deferred belong to key_v. Every library entry point that reads or frees a volume has flushed them
@@ -368,7 +358,9 @@ extern "C" int paris_hip_ctx_destroy(paris_hip_ctx* ctx)
     }
     if(ctx->bp_stream != nullptr)
         (void)hipStreamSynchronize(ctx->bp_stream);
-    paris_hip_row_extension_release(ctx, true); // (after the deferred group above: its filter launch reads the responses)
+    // every setting's device memory, freed at once: only the compute stream (drained above) and the deferred group that has just run --
+    // its filter launch reads the row extension's responses -- read any of it
+    ctx->each_setting([ctx](auto& setting) { paris_hip_release(ctx, setting, true); });
     if(ctx->bp_stream != nullptr)
     {
         (void)hipStreamSynchronize(ctx->bp_stream); // fused launches the caller never joined (it never looked at the volume again)
@@ -778,6 +770,37 @@ void paris_hip_sweep_retired(paris_hip_ctx* ctx, bool all)
         else
             ++k;
     }
+}
+
+int paris_hip_install(paris_hip_ctx* ctx, size_t bytes, std::initializer_list<paris_hip_fill> fills, paris_hip_device_buffer* out)
+{
+    *out = paris_hip_device_buffer{};
+    char* d = nullptr;
+    int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), bytes);
+    // The fills run on the ctx's own auxiliary stream and are waited for there: the caller's arrays are pageable memory they may
+    // reuse at once, and the new setting must be in place before any kernel of the compute stream reads it -- without waiting for
+    // the work queued there, which still uses the old setting.
+    if(rc == PARIS_HIP_SUCCESS)
+        rc = paris_hip_ensure_aux(ctx);
+    if(rc == PARIS_HIP_SUCCESS)
+    {
+        hipError_t err = hipSuccess;
+        for(const paris_hip_fill& f : fills)
+            if(err == hipSuccess && f.bytes != 0u)
+                err = f.h_src != nullptr ? hipMemcpyAsync(d + f.offset, f.h_src, f.bytes, hipMemcpyHostToDevice, ctx->aux_stream)
+                                         : hipMemsetAsync(d + f.offset, 0, f.bytes, ctx->aux_stream);
+        // (waited for even after a failed fill: the earlier ones still read the caller's arrays and write the buffer)
+        const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
+        rc = static_cast<int>(err != hipSuccess ? err : waited);
+    }
+    if(rc != PARIS_HIP_SUCCESS)
+    {
+        if(d != nullptr)
+            (void)hipFree(d);
+        return rc;
+    }
+    *out = paris_hip_device_buffer{d, bytes};
+    return PARIS_HIP_SUCCESS;
 }
 
 int paris_hip_release_group_references(paris_hip_ctx* ctx, uint64_t group)
@@ -1340,7 +1363,7 @@ extern "C" int paris_hip_upload_projection_raw_corrected(paris_hip_ctx* ctx, flo
     }
     const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
     if(d_frame == nullptr || h_src == nullptr || d_pitch < static_cast<size_t>(dim_x) * sizeof(float) || d_pitch % sizeof(float) != 0
-       || h_pitch < static_cast<size_t>(dim_x) * px || row_first > dim_y || row_count > dim_y - row_first || ff.d_ref == nullptr
+       || h_pitch < static_cast<size_t>(dim_x) * px || row_first > dim_y || row_count > dim_y - row_first || ff.mem.d == nullptr
        || dim_x != ff.dim_x || dim_y != ff.dim_y)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     if(int rc = paris_hip_flush_pending_weight(ctx))

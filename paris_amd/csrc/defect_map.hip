@@ -41,13 +41,6 @@ namespace
     }
 }
 
-void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->defect_map.d_plan, destroying);
-    ctx->defect_map = paris_hip_ctx::defect_map_t{};
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask, uint32_t dim_x, uint32_t dim_y)
 {
     if(int rc = paris_hip_bind(ctx))
@@ -58,41 +51,25 @@ extern "C" int paris_hip_set_defect_map(paris_hip_ctx* ctx, const uint8_t* mask,
     if(int rc = paris_hip_defect_plan_create(mask, dim_x, dim_y, &plan))
         return rc;
     const size_t n = plan->defect.size(), m = plan->source.size();
-    uint32_t* d = nullptr;
-    int rc = PARIS_HIP_SUCCESS;
+    paris_hip_device_buffer mem; // (none for a plan without a repairable defect)
     if(n != 0)
     {
-        rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), static_cast<size_t>(plan->stats.device_bytes));
-        // The copies run on the ctx's own auxiliary stream and are waited for there: the plan's host arrays go with this call, and
-        // the new plan must be in place before any kernel of the compute stream reads it -- without waiting for the work queued
-        // there, which may still read the old setting.
-        if(rc == PARIS_HIP_SUCCESS)
-            rc = paris_hip_ensure_aux(ctx);
-        if(rc == PARIS_HIP_SUCCESS)
+        const size_t w = sizeof(uint32_t); // of every entry, the float weights too
+        if(int rc = paris_hip_install(ctx, static_cast<size_t>(plan->stats.device_bytes),
+                                      {{0u, plan->defect.data(), n * w},
+                                       {n * w, plan->first_source.data(), (n + 1u) * w},
+                                       {(2u * n + 1u) * w, plan->source.data(), m * w},
+                                       {(2u * n + 1u + m) * w, plan->weight.data(), m * w}},
+                                      &mem))
         {
-            hipError_t err = hipMemcpyAsync(d, plan->defect.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
-            if(err == hipSuccess)
-                err = hipMemcpyAsync(d + n, plan->first_source.data(), (n + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
-            if(err == hipSuccess)
-                err = hipMemcpyAsync(d + 2u * n + 1u, plan->source.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux_stream);
-            if(err == hipSuccess)
-                err = hipMemcpyAsync(d + 2u * n + 1u + m, plan->weight.data(), m * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream);
-            // (waited for even after a failed copy: the earlier ones still read the plan's arrays)
-            const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-            rc = static_cast<int>(err != hipSuccess ? err : waited);
-        }
-        if(rc != PARIS_HIP_SUCCESS)
-        {
-            if(d != nullptr)
-                (void)hipFree(d);
             paris_hip_defect_plan_destroy(plan);
             return rc;
         }
     }
-    paris_hip_defect_map_release(ctx, false);
     paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
+    paris_hip_release(ctx, dm);
     dm.set = true;
-    dm.d_plan = d;
+    dm.mem = mem;
     dm.dim_x = dim_x;
     dm.dim_y = dim_y;
     dm.n = static_cast<uint32_t>(n);
@@ -107,7 +84,7 @@ extern "C" int paris_hip_clear_defect_map(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_defect_map_release(ctx, false);
+    paris_hip_release(ctx, ctx->defect_map);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -135,7 +112,7 @@ extern "C" int paris_hip_defect_repair_rows(paris_hip_ctx* ctx, float* d_p, size
     };
     const auto launch = [&] {
         const paris_hip_ctx::defect_map_t& dm = ctx->defect_map;
-        const uint32_t* defect = dm.d_plan;
+        const uint32_t* defect = dm.mem.as<uint32_t>();
         const uint32_t* first_source = defect + dm.n;
         const uint32_t* source = first_source + dm.n + 1u;
         const float* weight = reinterpret_cast<const float*>(source + dm.m);

@@ -356,14 +356,6 @@ static const paris_hip_filter_info* fused_filter_of(paris_hip_ctx* ctx, const fl
 }
 
 // ---- row extension (include/paris_hip.h) ----------------------------------------------------------------
-void paris_hip_row_extension_release(paris_hip_ctx* ctx, bool destroying)
-{
-    for(auto& kv : ctx->row_extension.cache)
-        paris_hip_retire_device_buffer(ctx, kv.second, destroying);
-    ctx->row_extension = paris_hip_ctx::row_extension_t{};
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 static int row_extension_device(paris_hip_ctx* ctx, float tau, uint32_t dim_x, const float** d_c, uint32_t* m)
 {
     auto& re = ctx->row_extension;
@@ -378,28 +370,13 @@ static int row_extension_device(paris_hip_ctx* ctx, float tau, uint32_t dim_x, c
         std::vector<float> c(dim_x);
         if(int rc = paris_hip_row_extension_response(&re.rule, dim_x, tau, c.data()))
             return rc;
-        float* d = nullptr;
         const size_t bytes = static_cast<size_t>(dim_x) * sizeof(float);
-        if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), bytes))
+        paris_hip_device_buffer mem;
+        if(int rc = paris_hip_install(ctx, bytes, {{0u, c.data(), bytes}}, &mem))
             return rc;
-        // copied on the ctx's auxiliary stream and waited for there (as the defect plan is): in place before the launch that follows
-        // reads it, without waiting for the work queued on the compute stream
-        int rc = paris_hip_ensure_aux(ctx);
-        if(rc == PARIS_HIP_SUCCESS)
-        {
-            const hipError_t err = hipMemcpyAsync(d, c.data(), bytes, hipMemcpyHostToDevice, ctx->aux_stream);
-            const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-            rc = static_cast<int>(err != hipSuccess ? err : waited);
-        }
-        if(rc != PARIS_HIP_SUCCESS)
-        {
-            (void)hipFree(d);
-            return rc;
-        }
-        it = re.cache.emplace(key, d).first;
-        re.device_bytes += bytes;
+        it = re.cache.emplace(key, mem).first;
     }
-    *d_c = it->second;
+    *d_c = it->second.as<float>();
     *m = re.rule.edge_pixels;
     return PARIS_HIP_SUCCESS;
 }
@@ -436,7 +413,7 @@ extern "C" int paris_hip_set_row_extension(paris_hip_ctx* ctx, const paris_hip_r
         return rc;
     if(int rc = paris_hip_flush_deferred(ctx)) // (runs a held-back weighting / filter as well): no queued row sees the change
         return rc;
-    paris_hip_row_extension_release(ctx, false);
+    paris_hip_release(ctx, ctx->row_extension);
     ctx->row_extension.set = true;
     ctx->row_extension.rule = *setting;
     return PARIS_HIP_SUCCESS;
@@ -448,7 +425,7 @@ extern "C" int paris_hip_clear_row_extension(paris_hip_ctx* ctx)
         return rc;
     if(int rc = paris_hip_flush_deferred(ctx))
         return rc;
-    paris_hip_row_extension_release(ctx, false);
+    paris_hip_release(ctx, ctx->row_extension);
     return PARIS_HIP_SUCCESS;
 }
 

@@ -58,13 +58,6 @@ namespace
     }
 }
 
-void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->flat_field.d_ref, destroying);
-    ctx->flat_field = paris_hip_ctx::flat_field_t{};
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark, const float* h_flat, uint32_t dim_x, uint32_t dim_y,
                                         float t_min)
 {
@@ -82,31 +75,12 @@ extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark,
         const double den = static_cast<double>(h_flat[k]) - dk;
         dead[k] = (!(den > 0.0) || !std::isfinite(dk) || !std::isfinite(static_cast<double>(h_flat[k]))) ? 1u : 0u;
     }
-    float* d = nullptr;
-    if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), 2u * n * sizeof(float)))
+    paris_hip_device_buffer mem; // the dark (zeros without one), the flat right behind it
+    if(int rc = paris_hip_install(ctx, 2u * n * sizeof(float), {{0u, h_dark, n * sizeof(float)}, {n * sizeof(float), h_flat, n * sizeof(float)}}, &mem))
         return rc;
-    // The copies run on the ctx's own auxiliary stream and are waited for there: the caller's arrays are pageable memory they may
-    // reuse at once, and the new frames must be in place before any kernel of the compute stream reads them -- without waiting for
-    // the work queued there, which may still read the old setting.
-    int rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        hipError_t err = h_dark != nullptr ? hipMemcpyAsync(d, h_dark, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream)
-                                           : hipMemsetAsync(d, 0, n * sizeof(float), ctx->aux_stream);
-        if(err == hipSuccess)
-            err = hipMemcpyAsync(d + n, h_flat, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream);
-        if(err == hipSuccess)
-            err = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        (void)hipFree(d);
-        return rc;
-    }
-    paris_hip_flat_field_release(ctx, false);
     paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-    ff.d_ref = d;
+    paris_hip_release(ctx, ff);
+    ff.mem = mem;
     ff.dim_x = dim_x;
     ff.dim_y = dim_y;
     ff.t_min = t_min;
@@ -116,7 +90,7 @@ extern "C" int paris_hip_set_flat_field(paris_hip_ctx* ctx, const float* h_dark,
 
 extern "C" int paris_hip_flat_field_dead_pixels(paris_hip_ctx* ctx, uint8_t* mask)
 {
-    if(ctx == nullptr || mask == nullptr || ctx->flat_field.d_ref == nullptr)
+    if(ctx == nullptr || mask == nullptr || ctx->flat_field.mem.d == nullptr)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     std::copy(ctx->flat_field.dead.begin(), ctx->flat_field.dead.end(), mask);
     return PARIS_HIP_SUCCESS;
@@ -126,7 +100,7 @@ extern "C" int paris_hip_clear_flat_field(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_flat_field_release(ctx, false);
+    paris_hip_release(ctx, ctx->flat_field);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -136,7 +110,7 @@ extern "C" int paris_hip_flat_field_rows(paris_hip_ctx* ctx, float* d_p, size_t 
     const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     const auto refuse = [&]() -> int {
         const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-        return ff.d_ref == nullptr || dim_x != ff.dim_x || dim_y != ff.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
+        return ff.mem.d == nullptr || dim_x != ff.dim_x || dim_y != ff.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
     };
     const auto launch = [&] {
         const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
@@ -147,8 +121,8 @@ extern "C" int paris_hip_flat_field_rows(paris_hip_ctx* ctx, float* d_p, size_t 
         const uint32_t gz = std::min(n_frames, FF_MAX_FRAMES);
         const uint32_t slices = (row_count + FF_ROWS_PER_THREAD - 1u) / FF_ROWS_PER_THREAD;
         const uint32_t gy = std::max(1u, std::min({slices, 65535u, FF_MAX_BLOCKS / std::max(1u, gx * gz)}));
-        const float* dark = ff.d_ref;
-        const float* flat = ff.d_ref + static_cast<size_t>(ff.dim_x) * ff.dim_y;
+        const float* dark = ff.mem.as<float>();
+        const float* flat = dark + static_cast<size_t>(ff.dim_x) * ff.dim_y;
         const dim3 grid(gx, gy, gz);
         if(vec)
             hipLaunchKernelGGL(flat_field_kernel<true>, grid, dim3(FF_THREADS), 0, ctx->stream, band.frame(0), frame_stride, n_frames,

@@ -168,11 +168,11 @@ namespace
     void lag_launch_terms(paris_hip_ctx* ctx, const paris_hip_frame_band& b, bool vec, uint32_t blocks, uint32_t groups_x, uint64_t lanes,
                           const float* dark, const lag_setting& k)
     {
-        const paris_hip_ctx::lag_t& l = ctx->lag;
-        const uint64_t plane = static_cast<uint64_t>(l.row_count) * l.dim_x;
+        const paris_hip_ctx::lag_t::sequence_t& q = ctx->lag.seq;
+        const uint64_t plane = static_cast<uint64_t>(q.row_count) * q.dim_x;
         const auto kernel = vec ? &lag_kernel<TERMS, true> : &lag_kernel<TERMS, false>;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(LAG_THREADS), 0, ctx->stream, b.frame(0), b.frame_stride, b.n_frames, b.pitch / sizeof(float),
-                           b.dim_x, b.row_first, groups_x, lanes, dark, l.d_state, plane, l.frames == 0u ? 1 : 0, k);
+                           b.dim_x, b.row_first, groups_x, lanes, dark, q.mem.as<float>(), plane, q.frames == 0u ? 1 : 0, k);
     }
 
     void lag_launch(paris_hip_ctx* ctx, const paris_hip_frame_band& b)
@@ -187,7 +187,7 @@ namespace
         const uint32_t groups_x = vec ? b.dim_x / 4u : b.dim_x;
         const uint64_t lanes = static_cast<uint64_t>(groups_x) * b.row_count;
         const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(LAG_MAX_BLOCKS, (lanes + LAG_THREADS - 1u) / LAG_THREADS));
-        const float* dark = ctx->flat_field.d_ref; // (nullptr without a flat-field setting: d = 0)
+        const float* dark = ctx->flat_field.mem.as<float>(); // (nullptr without a flat-field setting: d = 0)
         switch(l.model.terms)
         {
         case 1u: lag_launch_terms<1u>(ctx, b, vec, blocks, groups_x, lanes, dark, k); break;
@@ -196,17 +196,6 @@ namespace
         default: lag_launch_terms<4u>(ctx, b, vec, blocks, groups_x, lanes, dark, k); break;
         }
     }
-}
-
-void paris_hip_lag_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_ctx::lag_t& l = ctx->lag;
-    paris_hip_retire_device_buffer(ctx, l.d_state, destroying);
-    l.d_state = nullptr;
-    l.state_bytes = 0;
-    l.dim_x = l.dim_y = l.row_first = l.row_count = 0;
-    l.frames = 0;
-    paris_hip_sweep_retired(ctx, destroying);
 }
 
 extern "C" int paris_hip_set_lag_correction(paris_hip_ctx* ctx, const paris_hip_lag_model* model)
@@ -220,7 +209,7 @@ extern "C" int paris_hip_set_lag_correction(paris_hip_ctx* ctx, const paris_hip_
         return rc;
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_lag_release(ctx, false); // a replaced setting closes the sequence
+    paris_hip_release(ctx, ctx->lag.seq); // a replaced setting closes the sequence
     fresh.set = true;
     fresh.model = *model;
     ctx->lag = fresh;
@@ -235,7 +224,7 @@ extern "C" int paris_hip_clear_lag_correction(paris_hip_ctx* ctx)
         return rc;
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_lag_release(ctx, false);
+    paris_hip_release(ctx, ctx->lag.seq);
     ctx->lag = paris_hip_ctx::lag_t{};
     return PARIS_HIP_SUCCESS;
 }
@@ -246,8 +235,8 @@ extern "C" int paris_hip_lag_begin(paris_hip_ctx* ctx, uint32_t dim_x, uint32_t 
         return rc;
     paris_hip_ctx::lag_t& l = ctx->lag;
     const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-    if(!l.set || l.d_state != nullptr || dim_x == 0u || row_count == 0u || row_first > dim_y || row_count > dim_y - row_first
-       || (ff.d_ref != nullptr && (ff.dim_x != dim_x || ff.dim_y != dim_y)))
+    if(!l.set || l.seq.mem.d != nullptr || dim_x == 0u || row_count == 0u || row_first > dim_y || row_count > dim_y - row_first
+       || (ff.mem.d != nullptr && (ff.dim_x != dim_x || ff.dim_y != dim_y)))
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     const size_t bytes = static_cast<size_t>(l.model.terms) * row_count * dim_x * sizeof(float);
     float* d = nullptr;
@@ -261,13 +250,12 @@ extern "C" int paris_hip_lag_begin(paris_hip_ctx* ctx, uint32_t dim_x, uint32_t 
         (void)hipFree(d);
         return static_cast<int>(err);
     }
-    l.d_state = d;
-    l.state_bytes = bytes;
-    l.dim_x = dim_x;
-    l.dim_y = dim_y;
-    l.row_first = row_first;
-    l.row_count = row_count;
-    l.frames = 0;
+    l.seq.mem = paris_hip_device_buffer{d, bytes};
+    l.seq.dim_x = dim_x;
+    l.seq.dim_y = dim_y;
+    l.seq.row_first = row_first;
+    l.seq.row_count = row_count;
+    l.seq.frames = 0;
     return paris_hip_finish(ctx);
 }
 
@@ -275,7 +263,7 @@ extern "C" int paris_hip_lag_end(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_lag_release(ctx, false);
+    paris_hip_release(ctx, ctx->lag.seq);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -284,14 +272,14 @@ extern "C" int paris_hip_lag_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t
 {
     const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     const auto refuse = [&]() -> int {
-        const paris_hip_ctx::lag_t& l = ctx->lag;
+        const paris_hip_ctx::lag_t::sequence_t& q = ctx->lag.seq;
         const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-        const bool same = l.set && l.d_state != nullptr && dim_x == l.dim_x && dim_y == l.dim_y && row_first == l.row_first && row_count == l.row_count;
-        return !same || (ff.d_ref != nullptr && (ff.dim_x != dim_x || ff.dim_y != dim_y)) ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
+        const bool same = ctx->lag.set && q.mem.d != nullptr && dim_x == q.dim_x && dim_y == q.dim_y && row_first == q.row_first && row_count == q.row_count;
+        return !same || (ff.mem.d != nullptr && (ff.dim_x != dim_x || ff.dim_y != dim_y)) ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
     };
     return paris_hip_frame_pass(ctx, band, refuse, [&] {
         lag_launch(ctx, band);
-        ctx->lag.frames += n_frames;
+        ctx->lag.seq.frames += n_frames;
     });
 }
 
@@ -299,7 +287,7 @@ extern "C" int paris_hip_lag_frames(paris_hip_ctx* ctx, uint64_t* frames)
 {
     if(ctx == nullptr || frames == nullptr)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    *frames = ctx->lag.d_state != nullptr ? ctx->lag.frames : 0u;
+    *frames = ctx->lag.seq.mem.d != nullptr ? ctx->lag.seq.frames : 0u;
     return PARIS_HIP_SUCCESS;
 }
 

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <array>
 #include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <vector>
 
@@ -40,7 +41,19 @@ struct paris_hip_filter_info
     float tau = 0.f; // the pixel pitch K was made for (the row extension's response needs it)
 };
 
-// what paris_hip_ctx::volume_window_t::d_acc occupies: 32 bytes of quantise counters, 32 bytes of stats results, the 64-bit bins
+// device memory a ctx setting owns: `bytes` is what paris_hip_projection_reserve_bytes counts for it
+struct paris_hip_device_buffer
+{
+    void* d = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T* as() const
+    {
+        return static_cast<T*>(d);
+    }
+};
+
+// what paris_hip_ctx::volume_window_t::mem occupies: 32 bytes of quantise counters, 32 bytes of stats results, the 64-bit bins
 constexpr size_t PARIS_HIP_VOLUME_WINDOW_ACC_BYTES = 64u + 8u * PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX;
 
 struct paris_hip_ctx
@@ -115,89 +128,83 @@ struct paris_hip_ctx
         size_t bytes = 0; // extent of the buffer as uploaded (pitch x rows): stage calls on a row band pass interior pointers
     };
     std::map<const void*, upload_target> upload_targets;
-    // Dark / flat correction (paris_hip_set_flat_field): the reference frames on the device, the dark at d_ref, the flat right behind
-    // it (each dim_x x dim_y, rows dim_x floats apart). Only kernels on the compute stream read them, so a replaced or cleared
-    // setting's buffer is retired (`retired` below).
+    // Settings that own device memory (DESIGN.md section 1.1 gives the one rule they all follow). Each keeps its memory in a
+    // paris_hip_device_buffer `mem`; what is said below is what is particular to the setting.
+    // Dark / flat correction (paris_hip_set_flat_field): the dark frame, the flat right behind it (each dim_x x dim_y, rows dim_x
+    // floats apart).
     struct flat_field_t
     {
-        float* d_ref = nullptr;
+        paris_hip_device_buffer mem;
         uint32_t dim_x = 0, dim_y = 0;
         double t_min = 1.0;
         std::vector<uint8_t> dead; // host: 1 where D or F is not finite or F - D <= 0 (paris_hip_flat_field_dead_pixels)
     } flat_field;
-    // Defect map (paris_hip_set_defect_map): the plan of defect_plan.cpp in one device buffer -- defect[n], first_source[n + 1],
-    // source[m], weight[m], 4 bytes each -- read by the repair kernel on the compute stream only, so it is replaced, retired and freed
-    // as the flat-field frames are. A plan without a repairable defect has no buffer (d_plan == nullptr while set).
+    // Defect map (paris_hip_set_defect_map): the plan of defect_plan.cpp -- defect[n], first_source[n + 1], source[m], weight[m], 4
+    // bytes each. A plan without a repairable defect has no buffer (mem.d == nullptr while set).
     struct defect_map_t
     {
         bool set = false;
-        uint32_t* d_plan = nullptr;
+        paris_hip_device_buffer mem;
         uint32_t dim_x = 0, dim_y = 0;
         uint32_t n = 0, m = 0; // repairable defects, sources
         paris_hip_defect_stats stats{};
         std::vector<uint32_t> row_start; // host, dim_y + 1: the sorted defect list's range per detector row
     } defect_map;
-    // Zinger filter (paris_hip_set_zinger_filter): the rule with max_hits resolved, and one device buffer -- three 64-bit accumulators
-    // (padded to 32 bytes), `frames` x max_hits (index, value) pairs, `frames` hit counters -- read and written by the kernels of
-    // zinger.hip on the compute stream only, so it is replaced, retired and freed as the defect plan is.
+    // Zinger filter (paris_hip_set_zinger_filter): the rule with max_hits resolved; three 64-bit accumulators (padded to 32 bytes),
+    // `frames` x max_hits (index, value) pairs, `frames` hit counters.
     struct zinger_t
     {
         bool set = false;
         paris_hip_zinger_filter rule{};
         uint32_t dim_x = 0, dim_y = 0;
         uint32_t frames = 0; // frames one launch serves
-        size_t device_bytes = 0;
-        char* d_scratch = nullptr;
+        paris_hip_device_buffer mem;
     } zinger;
-    // Ring filter. The open profile (paris_hip_ring_profile_begin): the double sums on the device, rows
-    // sum_dim_x doubles apart, and on the host how many frames each row has received. The correction frame
-    // (paris_hip_set_ring_correction): rows dim_x floats apart; `zero`: it holds no pixel to correct, paris_hip_ring_correct_rows is
-    // idle. Both are touched by the kernels of ring.hip on the compute stream only (the sums by the copy of finish as well, on the same
-    // stream), so they are replaced, retired and freed as the defect plan is.
-    struct ring_t
+    // Ring filter. The open profile (paris_hip_ring_profile_begin): the double sums, rows dim_x doubles
+    // apart (the copy of finish reads them too, on the compute stream), and on the host how many frames each row has received.
+    struct ring_profile_t
     {
-        double* d_sum = nullptr;
-        uint32_t sum_dim_x = 0, sum_dim_y = 0;
-        std::vector<uint32_t> count;
-        bool set = false, zero = false;
-        float* d_c = nullptr;
+        paris_hip_device_buffer mem;
         uint32_t dim_x = 0, dim_y = 0;
-    } ring;
-    // Axis search (paris_hip_axis_search_begin): ONE device allocation that holds, in this order, the
-    // sinogram (n_frames rows of n floats), the plan (count rows of n 16-byte entries), the score kernel's partial sums and the
-    // per-candidate totals (paris_hip_axis_layout). On the host: which sinogram rows have been added and every candidate's valid
-    // columns. Touched by the kernels of axis_search.hip and the copies of finish on the compute stream only (the plan's upload
-    // runs on the auxiliary stream and is waited for in begin), so it is replaced, retired and freed as the ring profile is.
+        std::vector<uint32_t> count;
+    } ring_profile;
+    // The correction frame (paris_hip_set_ring_correction): rows dim_x floats apart; `zero`: it holds no pixel to correct,
+    // paris_hip_ring_correct_rows is idle.
+    struct ring_correction_t
+    {
+        bool set = false, zero = false;
+        paris_hip_device_buffer mem;
+        uint32_t dim_x = 0, dim_y = 0;
+    } ring_correction;
+    // Axis search (paris_hip_axis_search_begin): in this order the sinogram (n_frames rows of n floats), the
+    // plan (count rows of n 16-byte entries), the score kernel's partial sums and the per-candidate totals (paris_hip_axis_layout);
+    // finish copies from it on the compute stream. On the host: which sinogram rows have been added and every candidate's valid columns.
     struct axis_t
     {
-        char* d_mem = nullptr;
-        size_t device_bytes = 0;
+        paris_hip_device_buffer mem;
         paris_hip_axis_search setting{};
         uint32_t n = 0, n_col = 0, n_frames = 0, row_first = 0, missing = 0;
         std::vector<uint8_t> seen;
         std::vector<uint32_t> columns;
     } axis;
     // Detector binning (paris_hip_set_binning): the setting for one source detector, the binned size, and the
-    // device copy of the optional source-size mask (nullptr: every pixel good) -- read by the kernels of bin_frames.hip on the compute
-    // stream only, so it is replaced, retired and freed as the defect plan is.
+    // optional source-size mask (mem.d == nullptr: every pixel good).
     struct binning_t
     {
         bool set = false;
         paris_hip_binning rule{};
-        uint8_t* d_mask = nullptr;
+        paris_hip_device_buffer mem;
         uint32_t dim_x = 0, dim_y = 0, out_x = 0, out_y = 0;
     } binning;
-    // Air region (paris_hip_set_air_region): the rule with min_pixels resolved, and one device buffer laid
-    // out by paris_hip_air_layout_of -- the counters, the values and counts of one launch, the rectangle's mask bytes -- read and
-    // written by the kernels of air_region.hip (and the copies of measure and stats) on the compute stream only, so it is replaced,
-    // retired and freed as the zinger filter's scratch is.
+    // Air region (paris_hip_set_air_region): the rule with min_pixels resolved; the buffer is laid out by
+    // paris_hip_air_layout_of -- the counters, the values and counts of one launch, the rectangle's mask bytes (measure and stats copy
+    // from it on the compute stream).
     struct air_t
     {
         bool set = false;
         paris_hip_air_region rule{};
         uint32_t dim_x = 0, dim_y = 0;
-        size_t device_bytes = 0;
-        char* d_mem = nullptr;
+        paris_hip_device_buffer mem;
     } air;
     // Beam hardening (paris_hip_set_beam_hardening): the setting and the frame size it was made for. It
     // travels to the kernel by value: nothing on the device, nothing to retire.
@@ -216,42 +223,47 @@ struct paris_hip_ctx
         paris_detector_geometry geo{};
     } detector_roll;
     // Detector lag (paris_hip_set_lag_correction): the model and the coefficients made from it, which travel
-    // to the kernel by value. The open sequence (paris_hip_lag_begin): the band it was begun for, how many frames it has seen, and
-    // the band's state on the device -- model.terms planes of row_count x dim_x floats -- read and written by lag_kernel on the
-    // compute stream only (and zeroed there), so it is retired and freed as the ring profile's sums are.
+    // to the kernel by value. `seq` is the open sequence (paris_hip_lag_begin), which ends without the model: the band it was begun
+    // for, how many frames it has seen, and the band's state -- model.terms planes of row_count x dim_x floats, zeroed on the compute
+    // stream.
     struct lag_t
     {
         bool set = false;
         paris_hip_lag_model model{};
         float g[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, c[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f},
               w[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, inv_b = 0.f;
-        float* d_state = nullptr; // != nullptr: a sequence is open
-        size_t state_bytes = 0;
-        uint32_t dim_x = 0, dim_y = 0, row_first = 0, row_count = 0;
-        uint64_t frames = 0;
+        struct sequence_t
+        {
+            paris_hip_device_buffer mem; // mem.d != nullptr: a sequence is open
+            uint32_t dim_x = 0, dim_y = 0, row_first = 0, row_count = 0;
+            uint64_t frames = 0;
+        } seq;
     } lag;
-    // Row extension (paris_hip_set_row_extension): the rule, and the device copies of the response c made so far, one per
-    // (dim_x, tau bits, W) -- read by the filter kernels on the compute stream (or the second stream, behind a join) only, so they are
-    // retired and freed as the defect plan is.
+    // Row extension (paris_hip_set_row_extension): the rule, and the responses c made so far, one buffer per (dim_x, tau bits, W) --
+    // the second stream reads them too, behind a join.
     struct row_extension_t
     {
         bool set = false;
         paris_hip_row_extension rule{};
-        std::map<std::array<uint32_t, 3>, float*> cache;
-        size_t device_bytes = 0;
+        std::map<std::array<uint32_t, 3>, paris_hip_device_buffer> cache;
     } row_extension;
-    // Volume export (volume_window.hip), both made on first use. d_acc: the three 64-bit counters of the
+    // Volume export (volume_window.hip), both made on first use. mem: the three 64-bit counters of the
     // quantise calls (padded to 32 bytes), then the stats kernel's results -- two 32-bit extremes, three 64-bit counters (32 bytes) --
-    // and its PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX 64-bit bins. d_stage: where paris_hip_volume_quantize_d2h quantises to before its
-    // copy to the host; grows on demand, the outgrown one is retired. Touched on the compute stream only. `voxels` is kept here: it
-    // is the sum of the calls' n_voxels.
+    // and its PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX 64-bit bins; zeroed on the compute stream. stage: where
+    // paris_hip_volume_quantize_d2h quantises to before its copy to the host; grows on demand, the outgrown one is retired. `voxels`
+    // is kept here: it is the sum of the calls' n_voxels.
     struct volume_window_t
     {
-        char* d_acc = nullptr;
-        char* d_stage = nullptr;
-        size_t stage_bytes = 0;
+        paris_hip_device_buffer mem, stage;
         uint64_t voxels = 0;
     } volume_window;
+    // every setting above that owns device memory: what paris_hip_ctx_destroy releases and paris_hip_projection_reserve_bytes counts
+    template <class F>
+    void each_setting(F&& f)
+    {
+        f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
+        f(row_extension), f(volume_window);
+    }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
     std::vector<std::pair<void*, hipEvent_t>> retired;
@@ -467,6 +479,41 @@ int paris_hip_device_malloc(paris_hip_ctx* ctx, void** out, size_t bytes);
 void paris_hip_retire_device_buffer(paris_hip_ctx* ctx, void* d, bool now);
 // capi.hip: frees the retired buffers no queued work can read any more (all = true: every one -- the streams have been drained)
 void paris_hip_sweep_retired(paris_hip_ctx* ctx, bool all);
+// capi.hip: makes the memory of a new setting: `bytes` from paris_hip_device_malloc, every fill enqueued on the ctx's auxiliary
+// stream, and that stream waited for whether or not a copy failed. *out is the buffer, or empty with the first error returned.
+struct paris_hip_fill
+{
+    size_t offset;
+    const void* h_src; // nullptr: zeros
+    size_t bytes;
+};
+int paris_hip_install(paris_hip_ctx* ctx, size_t bytes, std::initializer_list<paris_hip_fill> fills, paris_hip_device_buffer* out);
+// the buffers of one setting (a member of paris_hip_ctx::each_setting)
+template <class S, class F>
+void paris_hip_each_buffer(S& s, F&& f)
+{
+    f(s.mem);
+}
+template <class F>
+void paris_hip_each_buffer(paris_hip_ctx::row_extension_t& s, F&& f)
+{
+    for(auto& kv : s.cache)
+        f(kv.second);
+}
+template <class F>
+void paris_hip_each_buffer(paris_hip_ctx::volume_window_t& s, F&& f)
+{
+    f(s.mem), f(s.stage);
+}
+// A setting is replaced, cleared or ended: its buffers are retired (destroying = true: freed at once), the setting is as a new ctx
+// has it, and the retired buffers no queued work can read any more are freed.
+template <class S>
+void paris_hip_release(paris_hip_ctx* ctx, S& s, bool destroying = false)
+{
+    paris_hip_each_buffer(s, [&](paris_hip_device_buffer& b) { paris_hip_retire_device_buffer(ctx, b.d, destroying); });
+    s = S{};
+    paris_hip_sweep_retired(ctx, destroying);
+}
 #pragma GCC visibility pop
 // capi.hip: the pending group has been launched as `group` (0: dropped) -- buffers freed meanwhile are parked behind it, the others
 // remember it as their last reader
@@ -523,33 +570,12 @@ int paris_hip_widen_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint3
 // another dim_x or rows outside the setting's.
 int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitch, uint32_t dim_x, uint32_t dim_y, int pixel_type,
                                  uint32_t row0);
-// flat_field.hip: the ctx's reference frames go, their memory freed as soon as no queued work can read them (ctx destroy: at once)
-void paris_hip_flat_field_release(paris_hip_ctx* ctx, bool destroying);
-// defect_map.hip: the same for the ctx's defect plan
-void paris_hip_defect_map_release(paris_hip_ctx* ctx, bool destroying);
 #pragma GCC visibility push(hidden)
-// filter.hip: the same for the row extension's cached responses
-void paris_hip_row_extension_release(paris_hip_ctx* ctx, bool destroying);
 // filter.hip: what a filter launch of rows of dim_x pixels with the K whose permuted copy is d_kp (d_k: the K itself) adds at its
 // store: *d_c = nullptr without a setting, else the device copy of c (made and cached on first use) and *m = edge_pixels.
 // PARIS_HIP_ERROR_INVALID_ARGUMENT for dim_x < m, PARIS_HIP_ERROR_UNSUPPORTED for a K this ctx did not make.
 int paris_hip_row_extension_for(paris_hip_ctx* ctx, const float* d_kp, uint32_t dim_x, const float** d_c, uint32_t* m);
 int paris_hip_row_extension_for_k(paris_hip_ctx* ctx, const float* d_k, uint32_t dim_x, const float** d_c, uint32_t* m);
-// zinger.hip: the same for the zinger filter's scratch
-void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying);
-// ring.hip: the same for the ring filter's open profile and for its correction frame
-void paris_hip_ring_profile_release(paris_hip_ctx* ctx, bool destroying);
-void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying);
-// volume_window.hip: the same for the volume export's counters and its staging buffer
-void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying);
-// bin_frames.hip: the same for the binning's mask
-void paris_hip_binning_release(paris_hip_ctx* ctx, bool destroying);
-// axis_search.hip: the same for an open axis search
-void paris_hip_axis_search_release(paris_hip_ctx* ctx, bool destroying);
-// air_region.hip: the same for the air region's memory
-void paris_hip_air_region_release(paris_hip_ctx* ctx, bool destroying);
-// lag.hip: the same for an open lag sequence's state
-void paris_hip_lag_release(paris_hip_ctx* ctx, bool destroying);
 
 // axis_rule.cpp: the estimate both searches share (the rule is stated with paris_hip_axis_search in include/paris_hip.h). Candidates
 // are (float)(lo + k step), k < count; a candidate is scored iff its cost is finite. PARIS_HIP_ERROR_INVALID_ARGUMENT when none is

@@ -131,26 +131,6 @@ namespace
     }
 }
 
-void paris_hip_ring_profile_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_ctx::ring_t& r = ctx->ring;
-    paris_hip_retire_device_buffer(ctx, r.d_sum, destroying);
-    r.d_sum = nullptr;
-    r.sum_dim_x = r.sum_dim_y = 0;
-    r.count.clear();
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
-void paris_hip_ring_correction_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_ctx::ring_t& r = ctx->ring;
-    paris_hip_retire_device_buffer(ctx, r.d_c, destroying);
-    r.d_c = nullptr;
-    r.set = r.zero = false;
-    r.dim_x = r.dim_y = 0;
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 extern "C" int paris_hip_ring_profile_begin(paris_hip_ctx* ctx, uint32_t dim_x, uint32_t dim_y)
 {
     if(int rc = paris_hip_bind(ctx))
@@ -160,29 +140,15 @@ extern "C" int paris_hip_ring_profile_begin(paris_hip_ctx* ctx, uint32_t dim_x, 
     const uint64_t n = static_cast<uint64_t>(dim_x) * dim_y;
     if(n > 0xffffffffull)
         return PARIS_HIP_ERROR_UNSUPPORTED;
-    double* d = nullptr;
-    int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), static_cast<size_t>(n) * sizeof(double));
-    // The sums are zeroed on the ctx's auxiliary stream and waited for there, as the zinger filter's accumulators are: in place before
-    // any kernel of the compute stream adds to them, without waiting for the work queued there, which still adds to the old profile.
-    if(rc == PARIS_HIP_SUCCESS)
-        rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        const hipError_t err = hipMemsetAsync(d, 0, static_cast<size_t>(n) * sizeof(double), ctx->aux_stream);
-        const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err != hipSuccess ? err : waited);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        if(d != nullptr)
-            (void)hipFree(d);
+    const size_t bytes = static_cast<size_t>(n) * sizeof(double);
+    paris_hip_device_buffer mem; // the sums start at zero
+    if(int rc = paris_hip_install(ctx, bytes, {{0u, nullptr, bytes}}, &mem))
         return rc;
-    }
-    paris_hip_ring_profile_release(ctx, false);
-    paris_hip_ctx::ring_t& r = ctx->ring;
-    r.d_sum = d;
-    r.sum_dim_x = dim_x;
-    r.sum_dim_y = dim_y;
+    paris_hip_ctx::ring_profile_t& r = ctx->ring_profile;
+    paris_hip_release(ctx, r);
+    r.mem = mem;
+    r.dim_x = dim_x;
+    r.dim_y = dim_y;
     r.count.assign(dim_y, 0u);
     return PARIS_HIP_SUCCESS;
 }
@@ -192,11 +158,11 @@ extern "C" int paris_hip_ring_profile_add_rows(paris_hip_ctx* ctx, const float* 
 {
     const paris_hip_frame_band band{const_cast<float*>(d_p), pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     const auto refuse = [&]() -> int {
-        const paris_hip_ctx::ring_t& r = ctx->ring;
-        return r.d_sum == nullptr || dim_x != r.sum_dim_x || dim_y != r.sum_dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
+        const paris_hip_ctx::ring_profile_t& r = ctx->ring_profile;
+        return r.mem.d == nullptr || dim_x != r.dim_x || dim_y != r.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
     };
     const auto launch = [&] {
-        paris_hip_ctx::ring_t& r = ctx->ring;
+        paris_hip_ctx::ring_profile_t& r = ctx->ring_profile;
         const bool vec = ring_vector_rows(band);
         const ring_dealing d = ring_deal(band, vec);
         const auto kernel = vec ? &ring_accumulate_kernel<true> : &ring_accumulate_kernel<false>;
@@ -204,7 +170,7 @@ extern "C" int paris_hip_ring_profile_add_rows(paris_hip_ctx* ctx, const float* 
         for(uint32_t f0 = 0; f0 < n_frames; f0 += PARIS_HIP_RING_FRAMES_MAX)
             hipLaunchKernelGGL(kernel, dim3(d.blocks), dim3(RING_THREADS), 0, ctx->stream, band.frame(f0), frame_stride,
                                std::min<uint32_t>(PARIS_HIP_RING_FRAMES_MAX, n_frames - f0), pitch / sizeof(float), dim_x, row_first, d.groups_x,
-                               d.lanes, r.d_sum);
+                               d.lanes, r.mem.as<double>());
         for(uint32_t y = row_first; y < row_first + row_count; ++y)
             r.count[y] += n_frames;
     };
@@ -216,17 +182,17 @@ extern "C" int paris_hip_ring_profile_finish(paris_hip_ctx* ctx, const paris_hip
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_ctx::ring_t& r = ctx->ring;
-    if(r.d_sum == nullptr || h_c == nullptr)
+    paris_hip_ctx::ring_profile_t& r = ctx->ring_profile;
+    if(r.mem.d == nullptr || h_c == nullptr)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
-    const uint32_t dim_x = r.sum_dim_x, dim_y = r.sum_dim_y;
+    const uint32_t dim_x = r.dim_x, dim_y = r.dim_y;
     if(int rc = paris_hip_ring_filter_check(setting, dim_x, dim_y, nullptr, nullptr))
         return rc;
     if(int rc = paris_hip_flush_pending_weight(ctx))
         return rc;
     const size_t n = static_cast<size_t>(dim_x) * dim_y;
     std::vector<double> sum(n);
-    PARIS_HIP_TRY(hipMemcpyAsync(sum.data(), r.d_sum, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PARIS_HIP_TRY(hipMemcpyAsync(sum.data(), r.mem.d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PARIS_HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::vector<float> mean_own(h_mean == nullptr ? n : 0u);
     float* mean = h_mean != nullptr ? h_mean : mean_own.data();
@@ -237,7 +203,7 @@ extern "C" int paris_hip_ring_profile_finish(paris_hip_ctx* ctx, const paris_hip
             mean[k] = r.count[y] != 0u ? static_cast<float>(sum[k] / frames) : 0.f;
     }
     const int rc = paris_hip_ring_correction_from_mean(setting, mean, r.count.data(), dim_x, dim_y, h_c, out);
-    paris_hip_ring_profile_release(ctx, false);
+    paris_hip_release(ctx, r);
     return rc;
 }
 
@@ -245,7 +211,7 @@ extern "C" int paris_hip_ring_profile_discard(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_ring_profile_release(ctx, false);
+    paris_hip_release(ctx, ctx->ring_profile);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -263,28 +229,14 @@ extern "C" int paris_hip_set_ring_correction(paris_hip_ctx* ctx, const float* h_
             return PARIS_HIP_ERROR_INVALID_ARGUMENT;
         zero = zero && h_c[k] == 0.f;
     }
-    float* d = nullptr;
-    if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), n * sizeof(float)))
+    paris_hip_device_buffer mem;
+    if(int rc = paris_hip_install(ctx, n * sizeof(float), {{0u, h_c, n * sizeof(float)}}, &mem))
         return rc;
-    // copied on the ctx's auxiliary stream and waited for there, as the flat-field frames are
-    int rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        hipError_t err = hipMemcpyAsync(d, h_c, n * sizeof(float), hipMemcpyHostToDevice, ctx->aux_stream);
-        if(err == hipSuccess)
-            err = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        (void)hipFree(d);
-        return rc;
-    }
-    paris_hip_ring_correction_release(ctx, false);
-    paris_hip_ctx::ring_t& r = ctx->ring;
+    paris_hip_ctx::ring_correction_t& r = ctx->ring_correction;
+    paris_hip_release(ctx, r);
     r.set = true;
     r.zero = zero;
-    r.d_c = d;
+    r.mem = mem;
     r.dim_x = dim_x;
     r.dim_y = dim_y;
     return PARIS_HIP_SUCCESS;
@@ -294,7 +246,7 @@ extern "C" int paris_hip_clear_ring_correction(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_ring_correction_release(ctx, false);
+    paris_hip_release(ctx, ctx->ring_correction);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -303,7 +255,7 @@ extern "C" int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_
 {
     const paris_hip_frame_band band{d_p, pitch, frame_stride, n_frames, dim_x, dim_y, row_first, row_count};
     const auto refuse = [&]() -> int {
-        const paris_hip_ctx::ring_t& r = ctx->ring;
+        const paris_hip_ctx::ring_correction_t& r = ctx->ring_correction;
         return !r.set || dim_x != r.dim_x || dim_y != r.dim_y ? PARIS_HIP_ERROR_INVALID_ARGUMENT : PARIS_HIP_SUCCESS;
     };
     const auto launch = [&] {
@@ -311,9 +263,9 @@ extern "C" int paris_hip_ring_correct_rows(paris_hip_ctx* ctx, float* d_p, size_
         const ring_dealing d = ring_deal(band, vec);
         const auto kernel = vec ? &ring_subtract_kernel<true> : &ring_subtract_kernel<false>;
         hipLaunchKernelGGL(kernel, dim3(d.blocks, std::min(n_frames, 65535u)), dim3(RING_THREADS), 0, ctx->stream, band.frame(0), frame_stride, n_frames,
-                           pitch / sizeof(float), dim_x, row_first, d.groups_x, d.lanes, ctx->ring.d_c);
+                           pitch / sizeof(float), dim_x, row_first, d.groups_x, d.lanes, ctx->ring_correction.mem.as<float>());
     };
-    return paris_hip_frame_pass(ctx, band, refuse, [&] { return ctx->ring.zero; }, launch, [&band] { return band.rows(); });
+    return paris_hip_frame_pass(ctx, band, refuse, [&] { return ctx->ring_correction.zero; }, launch, [&band] { return band.rows(); });
 }
 
 void paris_hip_warm_ring()

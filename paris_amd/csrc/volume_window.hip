@@ -27,7 +27,7 @@ namespace
     // per SIMD on 256 CUs. Twice the blocks made the u16 kernel 7 % SLOWER (reads and writes mix in HBM) and the read-only stats kernel
     // 14 to 27 % faster (profiles/r16_volume_window.txt): the stats grid is capped where every SIMD holds its 8 waves.
     constexpr uint32_t VW_QUANT_GRID_MAX = 1024u, VW_STATS_GRID_MAX = 2048u;
-    constexpr size_t VW_QUANT_OFFSET = 0u, VW_STATS_OFFSET = 32u, VW_BINS_OFFSET = 64u; // within paris_hip_ctx::volume_window_t::d_acc
+    constexpr size_t VW_QUANT_OFFSET = 0u, VW_STATS_OFFSET = 32u, VW_BINS_OFFSET = 64u; // within paris_hip_ctx::volume_window_t::mem
 
     struct vw_tally
     {
@@ -289,7 +289,7 @@ namespace
     // the ctx's counters, made and zeroed in stream order before their first use
     int vw_ensure_acc(paris_hip_ctx* ctx)
     {
-        if(ctx->volume_window.d_acc != nullptr)
+        if(ctx->volume_window.mem.d != nullptr)
             return PARIS_HIP_SUCCESS;
         char* d = nullptr;
         if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), PARIS_HIP_VOLUME_WINDOW_ACC_BYTES))
@@ -300,7 +300,7 @@ namespace
             (void)hipFree(d);
             return static_cast<int>(err);
         }
-        ctx->volume_window.d_acc = d;
+        ctx->volume_window.mem = paris_hip_device_buffer{d, PARIS_HIP_VOLUME_WINDOW_ACC_BYTES};
         return PARIS_HIP_SUCCESS;
     }
 
@@ -309,7 +309,7 @@ namespace
     {
         if(int rc = vw_ensure_acc(ctx))
             return rc;
-        unsigned long long* acc = reinterpret_cast<unsigned long long*>(ctx->volume_window.d_acc + VW_QUANT_OFFSET);
+        unsigned long long* acc = reinterpret_cast<unsigned long long*>(ctx->volume_window.mem.as<char>() + VW_QUANT_OFFSET);
         const uint32_t per = 16u / elem;
         const uint32_t head = ((16u - static_cast<uint32_t>(reinterpret_cast<uintptr_t>(d_v) & 15u)) & 15u) / 4u;
         const bool vec = n >= static_cast<uint64_t>(head) + per && (reinterpret_cast<uintptr_t>(d_q) + head * elem) % 16u == 0u;
@@ -424,21 +424,20 @@ extern "C" int paris_hip_volume_quantize_d2h(paris_hip_ctx* ctx, const float* d_
     if(n_voxels == 0u)
         return PARIS_HIP_SUCCESS;
     paris_hip_ctx::volume_window_t& vw = ctx->volume_window;
-    if(bytes > vw.stage_bytes)
+    if(bytes > vw.stage.bytes)
     {
         // work already queued still copies out of the old scratch: it is retired, not freed
         const size_t want = (bytes + 255u) & ~static_cast<size_t>(255u);
         char* d = nullptr;
         if(int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), want))
             return rc;
-        paris_hip_retire_device_buffer(ctx, vw.d_stage, false);
+        paris_hip_retire_device_buffer(ctx, vw.stage.d, false);
         paris_hip_sweep_retired(ctx, false);
-        vw.d_stage = d;
-        vw.stage_bytes = want;
+        vw.stage = paris_hip_device_buffer{d, want};
     }
-    if(int rc = vw_launch_quantize(ctx, d_v, n_voxels, setting, scale, elem, vw.d_stage))
+    if(int rc = vw_launch_quantize(ctx, d_v, n_voxels, setting, scale, elem, vw.stage.d))
         return rc;
-    PARIS_HIP_TRY(hipMemcpyAsync(h_q, vw.d_stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PARIS_HIP_TRY(hipMemcpyAsync(h_q, vw.stage.d, bytes, hipMemcpyDeviceToHost, ctx->stream));
     paris_hip_note_host_use(ctx, h_q, paris_hip_ctx::USED_COMPUTE);
     return paris_hip_finish(ctx);
 }
@@ -453,11 +452,11 @@ extern "C" int paris_hip_volume_quantize_counts(paris_hip_ctx* ctx, paris_hip_vo
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     paris_hip_ctx::volume_window_t& vw = ctx->volume_window;
     unsigned long long acc[3] = {0, 0, 0};
-    if(vw.d_acc != nullptr)
+    if(vw.mem.d != nullptr)
     {
-        PARIS_HIP_TRY(hipMemcpyAsync(acc, vw.d_acc + VW_QUANT_OFFSET, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
+        PARIS_HIP_TRY(hipMemcpyAsync(acc, vw.mem.as<char>() + VW_QUANT_OFFSET, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
         if(reset)
-            PARIS_HIP_TRY(hipMemsetAsync(vw.d_acc + VW_QUANT_OFFSET, 0, VW_STATS_OFFSET - VW_QUANT_OFFSET, ctx->stream));
+            PARIS_HIP_TRY(hipMemsetAsync(vw.mem.as<char>() + VW_QUANT_OFFSET, 0, VW_STATS_OFFSET - VW_QUANT_OFFSET, ctx->stream));
     }
     PARIS_HIP_TRY(hipStreamSynchronize(ctx->stream));
     out->voxels = vw.voxels;
@@ -492,7 +491,7 @@ extern "C" int paris_hip_volume_stats(paris_hip_ctx* ctx, const float* d_v, uint
     {
         if(int rc = vw_ensure_acc(ctx))
             return rc;
-        char* d = ctx->volume_window.d_acc;
+        char* d = ctx->volume_window.mem.as<char>();
         PARIS_HIP_TRY(hipMemsetAsync(d + VW_STATS_OFFSET, 0, sizeof(head) + sizeof(uint64_t) * n_bins, ctx->stream));
         const uint64_t items = std::max<uint64_t>(1u, n_voxels / 4u);
         const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(VW_STATS_GRID_MAX, (items + VW_THREADS - 1u) / VW_THREADS));
@@ -516,14 +515,6 @@ extern "C" int paris_hip_volume_stats(paris_hip_ctx* ctx, const float* d_v, uint
     out->not_finite = head.cnt[2];
     out->voxels = n_voxels;
     return PARIS_HIP_SUCCESS;
-}
-
-void paris_hip_volume_window_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->volume_window.d_acc, destroying);
-    paris_hip_retire_device_buffer(ctx, ctx->volume_window.d_stage, destroying);
-    ctx->volume_window = paris_hip_ctx::volume_window_t{};
-    paris_hip_sweep_retired(ctx, destroying);
 }
 
 void paris_hip_warm_volume_window()

@@ -143,13 +143,13 @@ int paris_hip_widen_correct_rows(paris_hip_ctx* ctx, float* d_dst, size_t d_pitc
                                  uint32_t row0)
 {
     const paris_hip_ctx::flat_field_t& ff = ctx->flat_field;
-    if(ff.d_ref == nullptr || dim_x != ff.dim_x || row0 > ff.dim_y || dim_y > ff.dim_y - row0)
+    if(ff.mem.d == nullptr || dim_x != ff.dim_x || row0 > ff.dim_y || dim_y > ff.dim_y - row0)
         return PARIS_HIP_ERROR_INVALID_ARGUMENT;
     if(dim_x == 0 || dim_y == 0)
         return PARIS_HIP_SUCCESS;
     correction c;
-    c.dark = ff.d_ref;
-    c.flat = ff.d_ref + static_cast<size_t>(ff.dim_x) * ff.dim_y;
+    c.dark = ff.mem.as<float>();
+    c.flat = c.dark + static_cast<size_t>(ff.dim_x) * ff.dim_y;
     c.row0 = row0;
     c.t_min = ff.t_min;
     switch(pixel_type)

@@ -215,13 +215,6 @@ extern "C" int paris_hip_zinger_filter_check(const paris_hip_zinger_filter* zf, 
     return PARIS_HIP_SUCCESS;
 }
 
-void paris_hip_zinger_release(paris_hip_ctx* ctx, bool destroying)
-{
-    paris_hip_retire_device_buffer(ctx, ctx->zinger.d_scratch, destroying);
-    ctx->zinger = paris_hip_ctx::zinger_t{};
-    paris_hip_sweep_retired(ctx, destroying);
-}
-
 extern "C" int paris_hip_set_zinger_filter(paris_hip_ctx* ctx, const paris_hip_zinger_filter* zf, uint32_t dim_x, uint32_t dim_y)
 {
     if(int rc = paris_hip_bind(ctx))
@@ -230,34 +223,18 @@ extern "C" int paris_hip_set_zinger_filter(paris_hip_ctx* ctx, const paris_hip_z
     size_t bytes = 0;
     if(int rc = paris_hip_zinger_filter_check(zf, dim_x, dim_y, &hits, &bytes))
         return rc;
-    char* d = nullptr;
-    int rc = paris_hip_device_malloc(ctx, reinterpret_cast<void**>(&d), bytes);
-    // The accumulators are zeroed on the ctx's auxiliary stream and waited for there, as the defect plan's copies are: in place before
-    // any kernel of the compute stream adds to them, without waiting for the work queued there, which still uses the old setting.
-    if(rc == PARIS_HIP_SUCCESS)
-        rc = paris_hip_ensure_aux(ctx);
-    if(rc == PARIS_HIP_SUCCESS)
-    {
-        const hipError_t err = hipMemsetAsync(d, 0, Z_ACC_BYTES, ctx->aux_stream);
-        const hipError_t waited = hipStreamSynchronize(ctx->aux_stream);
-        rc = static_cast<int>(err != hipSuccess ? err : waited);
-    }
-    if(rc != PARIS_HIP_SUCCESS)
-    {
-        if(d != nullptr)
-            (void)hipFree(d);
+    paris_hip_device_buffer mem; // the accumulators start at zero
+    if(int rc = paris_hip_install(ctx, bytes, {{0u, nullptr, Z_ACC_BYTES}}, &mem))
         return rc;
-    }
-    paris_hip_zinger_release(ctx, false);
     paris_hip_ctx::zinger_t& z = ctx->zinger;
+    paris_hip_release(ctx, z);
     z.set = true;
     z.rule = *zf;
     z.rule.max_hits = hits;
     z.dim_x = dim_x;
     z.dim_y = dim_y;
     z.frames = zinger_frames_per_launch(hits);
-    z.device_bytes = bytes;
-    z.d_scratch = d;
+    z.mem = mem;
     return PARIS_HIP_SUCCESS;
 }
 
@@ -265,7 +242,7 @@ extern "C" int paris_hip_clear_zinger_filter(paris_hip_ctx* ctx)
 {
     if(int rc = paris_hip_bind(ctx))
         return rc;
-    paris_hip_zinger_release(ctx, false);
+    paris_hip_release(ctx, ctx->zinger);
     return PARIS_HIP_SUCCESS;
 }
 
@@ -281,8 +258,8 @@ extern "C" int paris_hip_zinger_filter_rows(paris_hip_ctx* ctx, float* d_p, size
     const auto launch = [&] {
         const paris_hip_ctx::zinger_t& z = ctx->zinger;
         const uint32_t hits = z.rule.max_hits;
-        unsigned long long* acc = reinterpret_cast<unsigned long long*>(z.d_scratch);
-        uint2* pairs = reinterpret_cast<uint2*>(z.d_scratch + Z_ACC_BYTES);
+        unsigned long long* acc = z.mem.as<unsigned long long>();
+        uint2* pairs = reinterpret_cast<uint2*>(z.mem.as<char>() + Z_ACC_BYTES);
         uint32_t* count = reinterpret_cast<uint32_t*>(pairs + static_cast<size_t>(z.frames) * hits);
         const uint32_t strips = (row_count + ZD_ROWS - 1u) / ZD_ROWS;
         const bool vec = dim_x % ZD_PX == 0u && pitch % 16u == 0u && frame_stride % 16u == 0u && reinterpret_cast<uintptr_t>(d_p) % 16u == 0u;
@@ -321,9 +298,9 @@ extern "C" int paris_hip_zinger_stats(paris_hip_ctx* ctx, paris_hip_zinger_count
     if(int rc = paris_hip_flush_pending_weight(ctx))
         return rc;
     unsigned long long acc[3] = {0, 0, 0};
-    PARIS_HIP_TRY(hipMemcpyAsync(acc, ctx->zinger.d_scratch, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
+    PARIS_HIP_TRY(hipMemcpyAsync(acc, ctx->zinger.mem.d, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
     if(reset)
-        PARIS_HIP_TRY(hipMemsetAsync(ctx->zinger.d_scratch, 0, Z_ACC_BYTES, ctx->stream));
+        PARIS_HIP_TRY(hipMemsetAsync(ctx->zinger.mem.d, 0, Z_ACC_BYTES, ctx->stream));
     PARIS_HIP_TRY(hipStreamSynchronize(ctx->stream));
     out->frames = acc[0];
     out->replaced = acc[1];

@@ -211,6 +211,32 @@ def test_reserve_bytes_hold_the_state_while_a_sequence_is_open(be):
     be.clear_lag_correction()
 
 
+@pytest.mark.parametrize("start", R.STARTS)
+def test_a_sequence_ended_and_reopened_behind_queued_work(start):
+    """Four frames of 256 x 64 (16-byte vectors) are corrected, the sequence is ended and a new one begun at once, and four other
+    frames are corrected, with nothing waited for in between: the first four keep the ended sequence's state -- it is retired behind
+    them, not freed -- and the second four start from a state of their own."""
+    dim_x, dim_y, band = 256, 64, (0, 64)
+    model = R.MODELS[2]
+    sets = [R.special_frames((4, dim_y, dim_x), seed=70), R.special_frames((4, dim_y, dim_x), seed=71)]
+    with B.Backend(0, synchronous=False) as abe:
+        abe.set_lag_correction(model, start)
+        pools = [Pool(abe, frames) for frames in sets]
+        for pool in pools:
+            assert dim_x % 4 == 0 and pool.first.ptr % 16 == 0 and pool.pitch % 16 == 0 and pool.stride % 16 == 0
+        for pool in pools:
+            abe.lag_begin(dim_x, dim_y)
+            for k in range(4):
+                abe.lag_correct(pool.frame(k))
+            abe.lag_end()                                   # the four passes above may still be queued: they keep their state
+        for pool, frames in zip(pools, sets):
+            want, _, _ = B.lag_correct_host(model, frames, start=start)
+            assert not R.same_pixels(want, frames)
+            pool.assert_bands(pool.read(), want, band=band, what=start)
+        for pool in pools:
+            pool.free()
+
+
 def test_refusals_write_nothing(be):
     L = _lib.load()
     frames = scan_frames(64, seed=8)
