@@ -7,7 +7,11 @@ Fixtures are data only (inputs are regenerated from the LCG; expected outputs ar
   cube64.npz  64^3 / 8 projections: three central slices, sum and abs-sum
   mkl_fft.npz MKL's FFTW transforms (libmkl_rt.so) of the KAT geometry's filter and 8 weighted projections, keyed by the
               sha256 of their inputs (tests/mkl_fftw.py: Recorded); written only where libmkl_rt.so exists
+  fdk_model_bounds.json  the oracle's own error against the float64 model of tests/fdk_model.py on the cases of
+              tests/fdk_cases.py, per case and stage (CPU only; alone:  python tests/golden/make_golden.py fdk_model_bounds)
 """
+import json
+import math
 import os
 import sys
 
@@ -36,7 +40,8 @@ def main():
     v = O.reconstruct(d, g, 8)
     np.savez_compressed(os.path.join(HERE, "cube64.npz"), slices=v[31:34].copy(),
                         sum=np.float64(v.sum(dtype=np.float64)), abssum=np.float64(np.abs(v).sum(dtype=np.float64)))
-    files = ["kat.npz", "cube64.npz"]
+    record_fdk_model_bounds()
+    files = ["kat.npz", "cube64.npz", "fdk_model_bounds.json"]
     if mkl_fftw.available():
         record_mkl()
         files.append("mkl_fft.npz")
@@ -58,5 +63,25 @@ def record_mkl():
     mkl_fftw.save_log(log, os.path.join(HERE, "mkl_fft.npz"))
 
 
+def record_fdk_model_bounds():
+    """Per case and stage: the oracle's largest absolute error against the float64 model relative to the model's largest magnitude,
+    and the share of voxels that needed the boundary rule. The errors are rounded UP to three significant digits, so that another
+    BLAS's float64 summation order in the model cannot move a figure past its record."""
+    import fdk_cases
+
+    def up(x):
+        q = 10.0 ** (math.floor(math.log10(x)) - 2)
+        return float("%.2e" % (math.ceil(x / q) * q))
+
+    bounds = {case: {stage: {"error": up(err), "boundary_share": share} for stage, (err, share) in fdk_cases.oracle_errors(O, case).items()}
+              for case in fdk_cases.ORACLE_CASES}
+    with open(os.path.join(HERE, fdk_cases.BOUNDS_FILE), "w") as f:
+        json.dump(bounds, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["fdk_model_bounds"]:
+        record_fdk_model_bounds()
+    else:
+        main()

@@ -21,8 +21,11 @@ ELLIPSOIDS = [
 ]
 
 
-def projection(n_row, n_col, l_px_row, l_px_col, d_so, d_od, phi_deg, radius_mm, delta_s=0.0, delta_t=0.0):
-    """Line integrals (mm) for one view; returns float32 (n_col, n_row)."""
+def projection(n_row, n_col, l_px_row, l_px_col, d_so, d_od, phi_deg, radius_mm, delta_s=0.0, delta_t=0.0, ellipsoids=None):
+    """Line integrals (mm) for one view of the ellipsoids (a table like ELLIPSOIDS; None: the module's ELLIPSOIDS as it stands at the
+    call, which tests/beam_hardening_rule.py swaps for its own); returns float32 (n_col, n_row)."""
+    if ellipsoids is None:
+        ellipsoids = ELLIPSOIDS
     phi = np.deg2rad(phi_deg)
     c, s_ = np.cos(phi), np.sin(phi)
     t = (np.arange(n_row) + 0.5) * l_px_row - n_row * l_px_row / 2 - delta_s * l_px_row
@@ -36,7 +39,7 @@ def projection(n_row, n_col, l_px_row, l_px_col, d_so, d_od, phi_deg, radius_mm,
     Dz = D[..., 2]
     Sx, Sy, Sz = -d_so * c, -d_so * s_, 0.0
     out = np.zeros_like(T)
-    for val, a, b, cc, x0, y0, z0, rot in ELLIPSOIDS:
+    for val, a, b, cc, x0, y0, z0, rot in ellipsoids:
         r = np.deg2rad(rot)
         cr, sr = np.cos(r), np.sin(r)
         # into the ellipsoid's frame, scaled to a unit sphere
@@ -51,3 +54,20 @@ def projection(n_row, n_col, l_px_row, l_px_col, d_so, d_od, phi_deg, radius_mm,
         disc = Bq * Bq - A * Cq
         out += val * np.where(disc > 0, 2.0 * np.sqrt(np.maximum(disc, 0)) / A, 0.0)
     return out.astype(np.float32)
+
+
+def density(x, y, z, radius_mm, ellipsoids=None):
+    """The phantom itself at the points (x, y, z) in mm (arrays that broadcast): the sum of the values of the ellipsoids that
+    hold the point, float64."""
+    if ellipsoids is None:
+        ellipsoids = ELLIPSOIDS
+    x, y, z = (np.asarray(a, np.float64) for a in (x, y, z))
+    out = np.zeros(np.broadcast(x, y, z).shape, np.float64)
+    for val, a, b, cc, x0, y0, z0, rot in ellipsoids:
+        r = np.deg2rad(rot)
+        cr, sr = np.cos(r), np.sin(r)
+        px, py, pz = x - x0 * radius_mm, y - y0 * radius_mm, z - z0 * radius_mm
+        ox, oy = (px * cr + py * sr), (-px * sr + py * cr)
+        inside = (ox / (a * radius_mm)) ** 2 + (oy / (b * radius_mm)) ** 2 + (pz / (cc * radius_mm)) ** 2 < 1.0
+        out += np.where(inside, val, 0.0)
+    return out

@@ -50,3 +50,20 @@ def test_filter_bins_against_the_experiments_build():
     assert r.returncode == 0, tail
     m = re.search(r"(\d+) passed", r.stdout)
     assert m and int(m.group(1)) >= 54 and "skipped" not in r.stdout.splitlines()[-1], tail
+
+
+def test_fdk_model_variants_against_the_experiments_build():
+    """tests/test_gpu_fdk_model.py's slice kernel (backprojection variant 3) and first radix-16 filter (variant 2) cases, which the
+    product library only refuses: against the float64 model with the other library"""
+    assert os.path.exists(_lib.EXPERIMENTS_LIB_PATH), "build it: make -C paris_amd/csrc EXPERIMENTS=1 (__graft_entry__.build() does)"
+    env = dict(os.environ, PARIS_HIP_LIBRARY=_lib.EXPERIMENTS_LIB_PATH)
+    path = os.path.join(ROOT, "tests", "test_gpu_fdk_model.py")
+    ids = ["%s::test_backproject_kernel_variants_against_the_model[3-%s-%s]" % (path, d, v) for d in ("v61", "v64")
+           for v in ("natural", "overshoot", "roi_slab")]
+    ids += ["%s::test_filter_against_the_model[%s-2]" % (path, c) for c in ("v61", "v64", "f97", "w")]
+    r = subprocess.run([sys.executable, "-m", "pytest"] + ids + ["-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"], capture_output=True,
+                       text=True, timeout=600, env=env, cwd=ROOT)
+    tail = r.stdout[-3000:] + r.stderr[-1500:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == len(ids) and "skipped" not in r.stdout.splitlines()[-1], tail
