@@ -39,6 +39,7 @@
 #include <utility>
 #include <vector>
 
+#include "frame_rows.h"
 #include "sink.h"
 #include "source.h"
 #include "types.h"
@@ -98,7 +99,7 @@ namespace paris
         bool offset_detector = false;
         // dark / flat correction of intensity frames to line integrals (extension): --flat / --dark name HIS files whose frames are
         // averaged into one reference frame each by run(), before any device work (detail::load_flat_field); every device ctx gets
-        // them and uploads frames through paris_hip_upload_projection_raw_corrected
+        // them and uploads frames through the corrected upload (detail::frame_chain::upload)
         std::string flat_path, dark_path;
         float t_min = 1e-5f;
         std::shared_ptr<const his::mean> flat, dark; // filled by run(); dark may stay empty (a zero dark)
@@ -331,16 +332,25 @@ namespace paris
 
     namespace detail
     {
-        inline void rt(int rc, const char* what)
-        {
-            if(rc != PARIS_HIP_SUCCESS)
-                throw stage_runtime_error{std::string{what} + " failed: " + paris_hip_strerror(rc)};
-        }
         using clock = std::chrono::steady_clock;
         inline double since(clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); }
 
-        // the settings of the frame chain in front of the weights, the same for every device ctx of a run: --bin, --flat / --dark,
-        // --air-region, --defects / --defects-from-flat and --zingers. Throws; the caller destroys the ctx.
+        // a ctx of `device` for as long as the object lives. Declared before everything that lives in the ctx: destroyed after it
+        class device_ctx
+        {
+        public:
+            explicit device_ctx(int device) { rt(paris_hip_ctx_create(device, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx_), "set_device()"); }
+            device_ctx(const device_ctx&) = delete;
+            auto operator=(const device_ctx&) -> device_ctx& = delete;
+            ~device_ctx() { paris_hip_ctx_destroy(ctx_); }
+            operator paris_hip_ctx*() const { return ctx_; }
+
+        private:
+            paris_hip_ctx* ctx_ = nullptr;
+        };
+
+        // the settings of the frame chain up to the zinger filter, the same for every device ctx of a run and for the pre-passes: --bin,
+        // --flat / --dark, --lag, --air-region, --defects / --defects-from-flat and --zingers
         inline void set_frame_chain(paris_hip_ctx* ctx, const program_options& po, device_report& rep)
         {
             if(po.binning()) // --bin: the source detector's setting; everything below is at binned size
@@ -387,12 +397,29 @@ namespace paris
             }
         }
 
-        // [first, first + count) becomes the smallest range that also holds [y0, y0 + height)
-        inline void hull_rows(std::uint32_t y0, std::uint32_t height, std::uint32_t& first, std::uint32_t& count)
+        // the settings of the chain behind the zinger filter, the same for every device ctx of a run and for the fit pre-pass (which
+        // runs before there is a polynomial, and never with a roll): the correction frame of --rings from run()'s pre-pass,
+        // --beam-hardening or the coefficients run()'s fit found, --detector-roll or the angle run()'s search found, --extend-rows and
+        // the filter window. The ring / axis / roll pre-pass sets none of them: it stops in front of them, and a setting holds device
+        // memory that counts against the reserve.
+        inline void set_chain_back(paris_hip_ctx* ctx, const program_options& po, device_report& rep)
         {
-            const auto lo = std::min(first, y0), hi = std::max(first + count, y0 + height);
-            first = lo;
-            count = hi - lo;
+            if(po.ring_c)
+                rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
+            if(po.beam_hardening)
+                rt(paris_hip_set_beam_hardening(ctx, &po.bh, po.det_geo.n_row, po.det_geo.n_col), "set_beam_hardening()");
+            if(po.roll)
+            {
+                const auto setting = paris_hip_detector_roll{po.roll_deg};
+                rt(paris_hip_set_detector_roll(ctx, &setting, &po.det_geo), "set_detector_roll()");
+            }
+            if(po.extend_rows)
+            {
+                const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
+                rt(paris_hip_set_row_extension(ctx, &setting), "set_row_extension()");
+                rep.row_extension = true;
+            }
+            rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
         }
 
         // frames per group and groups, as reconstruct() lays its slots out
@@ -441,6 +468,206 @@ namespace paris
                 po.batch /= 2;
             return po;
         }
+
+        // The frame slots of a ctx, and their owner. A slot is a pinned host buffer with room for a frame as stored at 4 bytes per pixel,
+        // and a device frame at the detector's size; the device frames of all slots lie one under the other in one allocation (slot s
+        // starts at row s * n_col), so that a group of slots is n frames at a stride. With --bin a slot also has a full-width source
+        // frame, which the frame is binned from; with `rolled` a second frame, same pitch and stride, that the roll writes and
+        // everything after it reads; with `half` an IEEE half frame that the row filter writes. `fences` fences come with the slots,
+        // one per group of the main loop.
+        class frame_slots
+        {
+        public:
+            frame_slots(paris_hip_ctx* ctx, const program_options& po, std::uint32_t count, std::uint32_t fences, bool rolled, bool half)
+            : frame_slots{ctx} // the object is complete from here on: the destructor frees what was allocated before a throw
+            {
+                const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+                const auto sn_row = po.binning() ? po.src_row : n_row, sn_col = po.binning() ? po.src_col : n_col;
+                const auto frames = [&](std::uint32_t dim_x, std::uint32_t dim_y, float** d, std::size_t* d_pitch, const char* what) {
+                    if(static_cast<std::uint64_t>(dim_y) * count > 0xffffffffull)
+                        throw stage_construction_error{"too many projection slots for this detector"};
+                    rt(paris_hip_malloc_projection(ctx, dim_x, dim_y * count, d, d_pitch), what);
+                };
+                frames(n_row, n_col, &d_all_, &pitch, "make_projection_device()");
+                stride = pitch * n_col;
+                if(po.binning())
+                {
+                    frames(sn_row, sn_col, &d_src_all_, &src_pitch, "make_projection_device()");
+                    src_stride_ = src_pitch * sn_col;
+                }
+                if(rolled)
+                {
+                    std::size_t r_pitch = 0;
+                    frames(n_row, n_col, &d_roll_all_, &r_pitch, "make_projection_device()");
+                    if(r_pitch != pitch)
+                        throw stage_runtime_error{"the rolled frames' pitch differs from the frames'"};
+                }
+                host_.assign(count, nullptr);
+                for(auto& h : host_)
+                {
+                    void* p = nullptr;
+                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(sn_row) * sn_col * sizeof(float), &p), "make_projection_host()");
+                    h = static_cast<float*>(p);
+                }
+                fence_.assign(fences, nullptr);
+                for(auto& f : fence_)
+                    rt(paris_hip_fence_create(ctx, &f), "fence");
+                if(half)
+                {
+                    float* raw = nullptr;
+                    frames(static_cast<std::uint32_t>((static_cast<std::size_t>(n_row) * 2 + 255) / 256 * 256 / 4), n_col, &raw, &half_pitch, "half projection");
+                    d_half_ = reinterpret_cast<std::uint16_t*>(raw);
+                    half_stride = half_pitch * n_col;
+                }
+            }
+            frame_slots(const frame_slots&) = delete;
+            auto operator=(const frame_slots&) -> frame_slots& = delete;
+            ~frame_slots()
+            {
+                for(auto f : fence_)
+                    paris_hip_fence_destroy(ctx_, f);
+                for(auto h : host_)
+                    paris_hip_free_host(ctx_, h);
+                paris_hip_free(ctx_, d_all_);
+                paris_hip_free(ctx_, d_src_all_);
+                paris_hip_free(ctx_, d_roll_all_);
+                paris_hip_free(ctx_, d_half_);
+            }
+
+            auto host(std::uint32_t s) const -> float* { return host_[s]; }
+            auto frame(std::uint32_t s) const -> float* { return at(d_all_, stride, s); }
+            auto source(std::uint32_t s) const -> float* { return at(d_src_all_, src_stride_, s); } // --bin
+            // the frame of slot s that the weights, the filter and the backprojection read: the rolled one if there is one
+            auto out(std::uint32_t s) const -> float* { return d_roll_all_ != nullptr ? at(d_roll_all_, stride, s) : frame(s); }
+            auto half(std::uint32_t s) const -> std::uint16_t* { return d_half_ != nullptr ? at(d_half_, half_stride, s) : nullptr; }
+            auto hosts() const -> const std::vector<float*>& { return host_; }
+            auto fences() const -> const std::vector<paris_hip_fence*>& { return fence_; }
+
+            std::size_t pitch = 0, stride = 0;           // bytes from row to row of a frame, and from one slot's frame to the next
+            std::size_t src_pitch = 0;                   // --bin: of the full-width frames
+            std::size_t half_pitch = 0, half_stride = 0; // of the half frames (0 without them)
+
+        private:
+            explicit frame_slots(paris_hip_ctx* ctx) : ctx_{ctx} {}
+            template<class T>
+            static auto at(T* base, std::size_t bytes, std::uint32_t s) -> T* { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + bytes * s); }
+
+            paris_hip_ctx* ctx_;
+            std::vector<float*> host_;
+            std::vector<paris_hip_fence*> fence_;
+            float *d_all_ = nullptr, *d_src_all_ = nullptr, *d_roll_all_ = nullptr;
+            std::uint16_t* d_half_ = nullptr;
+            std::size_t src_stride_ = 0;
+        };
+
+        // The driver's frame chain, written once: from a frame as stored in a pinned slot to filtered rows, for one frame behind its
+        // upload (grouped = false: n = 1 at stride 0) or for n slots from `first` on in one call each (grouped: at the slots' stride).
+        // reconstruct() runs all of it either way; the ring / axis / roll pre-pass stops after clean(), the fit pre-pass puts its unit
+        // polynomial into linearise(). Every pass runs only where its setting was made, on the rows the plan gives it (frame_rows.h).
+        struct frame_chain
+        {
+            paris_hip_ctx* ctx;
+            const program_options& po;
+            const frame_slots& slots;
+            bool repair; // a defect map is set
+
+            // Slot s's pinned frame to corrected line integrals in its device frame, for the rows of `up`. The rows arrive as stored
+            // (u8 / u16 / u32 / f32; f64 as f32): the upload carries those bytes and the device widens them, bit for bit the host's
+            // conversion (:101 -- on the upload stream, overlapping the kernels of the previous projections). With --flat alone the
+            // same pass corrects them with the reference rows of their absolute detector rows. With --bin the source rows go as stored
+            // into the slot's full-width frame and are binned from there into the slot's frame; with --lag the detector's memory of
+            // the frames before is taken off the (binned) counts -- unless that was done already (lag_applied: the fit pre-pass, which
+            // uploads every group once per basis) --; either way the dark / flat correction then runs in place as a pass of its own:
+            // the same bits as the corrected upload of such counts.
+            void upload(std::uint32_t s, int pixel, const frame_rows& rows, bool lag_applied = false) const
+            {
+                const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+                const bool binning = po.binning();
+                const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
+                const auto px = his::pixel_size(pixel);
+                const auto* h_band = reinterpret_cast<const char*>(slots.host(s)) + static_cast<std::size_t>(rows.src.first) * sn_row * px;
+                auto* d_frame = slots.frame(s);
+                if(!binning && !po.lag && po.flat)
+                {
+                    rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, slots.pitch, h_band, n_row * px, n_row, n_col, rows.up.first, rows.up.count,
+                                                                 pixel), "load()");
+                    return;
+                }
+                auto* d_raw = binning ? slots.source(s) : d_frame;
+                const auto raw_pitch = binning ? slots.src_pitch : slots.pitch;
+                rt(paris_hip_upload_projection_raw(ctx, reinterpret_cast<float*>(reinterpret_cast<char*>(d_raw) + static_cast<std::size_t>(rows.src.first) * raw_pitch),
+                                                   raw_pitch, h_band, sn_row * px, sn_row, rows.src.count, pixel), "load()");
+                if(binning)
+                    rt(paris_hip_bin_frames(ctx, d_raw, raw_pitch, 0u, d_frame, slots.pitch, 0u, 1u, sn_row, sn_col, rows.up.first, rows.up.count), "bin()");
+                if(po.lag && !lag_applied)
+                    rt(paris_hip_lag_correct_rows(ctx, d_frame, slots.pitch, 0u, 1u, n_row, n_col, rows.up.first, rows.up.count), "lag correction");
+                if((binning || po.lag) && po.flat)
+                    rt(paris_hip_flat_field_rows(ctx, d_frame, slots.pitch, 0u, 1u, n_row, n_col, rows.up.first, rows.up.count), "flat field");
+            }
+
+            // the frames' own flux drift, straight after the correction; the band's defective pixels; then its outlier pixels
+            void clean(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows) const
+            {
+                const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+                const auto stride = grouped ? slots.stride : 0u;
+                auto* d = slots.frame(first);
+                if(po.air)
+                    rt(paris_hip_air_normalize_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.air.first, rows.air.count), "air normalisation");
+                if(repair)
+                    rt(paris_hip_defect_repair_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.fix.first, rows.fix.count), "defect repair");
+                if(po.zingers)
+                    rt(paris_hip_zinger_filter_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "zinger filter");
+            }
+
+            // the detector's stationary offsets, then the polynomial of the line integral: the run's, or `unit` in its place
+            void linearise(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const paris_hip_beam_hardening* unit = nullptr) const
+            {
+                const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+                const auto stride = grouped ? slots.stride : 0u;
+                auto* d = slots.frame(first);
+                if(po.ring_c)
+                    rt(paris_hip_ring_correct_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "ring correction");
+                if(unit != nullptr)
+                    rt(paris_hip_beam_hardening_rows_with(ctx, unit, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "beam hardening");
+                else if(po.beam_hardening)
+                    rt(paris_hip_beam_hardening_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "beam hardening");
+            }
+
+            // The roll, the last frame pass, into the slots' second frames, which everything after it reads; the redundancy weight of
+            // an offset detector or of a short scan (angles: one per frame, in degrees) on the raw band, before the cosine weight;
+            // then :102-103 in one launch: the weight rides along in the row filter's load, and with half frames the filtered band is
+            // stored as IEEE half straight into them. One frame goes through the entry point for a frame, a group -- of one frame
+            // too -- through the one for a batch.
+            void finish(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles) const
+            {
+                const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+                const auto stride = grouped ? slots.stride : 0u;
+                const auto out = rows.out;
+                auto* d = slots.out(first);
+                if(po.roll)
+                    rt(paris_hip_detector_roll_rows(ctx, slots.frame(first), slots.pitch, stride, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count),
+                       "detector roll");
+                if(po.offset_detector)
+                    rt(paris_hip_offset_detector_weight_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count, &po.det_geo),
+                       "offset-detector weight()");
+                if(po.short_scan)
+                    rt(paris_hip_short_scan_weight_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count, &po.det_geo, &po.scan, angles),
+                       "short-scan weight()");
+                if(grouped)
+                    rt(paris_hip_stage_weight_filter_batch(ctx, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count, &po.det_geo, slots.half(first),
+                                                           slots.half_pitch, slots.half_stride), "weight() + filter()");
+                else
+                    rt(paris_hip_stage_weight_filter_rows(ctx, d, slots.pitch, n_row, n_col, out.first, out.count, &po.det_geo, slots.half(first),
+                                                          slots.half_pitch), "weight() + filter()");
+            }
+
+            void run(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles) const
+            {
+                clean(first, n, grouped, rows);
+                linearise(first, n, grouped, rows);
+                finish(first, n, grouped, rows, angles);
+            }
+        };
     }
 
     namespace detail
@@ -765,434 +992,212 @@ namespace paris
         auto rep = device_report{};
         rep.device = device;
         const auto t_setup = clock::now();
-        paris_hip_ctx* ctx = nullptr;
-        rt(paris_hip_ctx_create(device, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()"); // :87
-        bool repair = false;
-        std::uint32_t reach_rows = 0; // how far beyond a band's rows the repair reads
-        try
-        {
-            set_frame_chain(ctx, po, rep);
-            repair = rep.defect_map;
-            reach_rows = rep.defects.reach_rows;
-            if(po.ring_c) // --rings: the correction frame of run()'s pre-pass, the same for every device
-                rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
-            if(po.beam_hardening) // --beam-hardening, or the coefficients run()'s fit found: the same on every device
-                rt(paris_hip_set_beam_hardening(ctx, &po.bh, po.det_geo.n_row, po.det_geo.n_col), "set_beam_hardening()");
-            if(po.roll) // --detector-roll, or the angle run()'s search found: the same on every device
-            {
-                const auto setting = paris_hip_detector_roll{po.roll_deg};
-                rt(paris_hip_set_detector_roll(ctx, &setting, &po.det_geo), "set_detector_roll()");
-            }
-        }
-        catch(...)
-        {
-            paris_hip_ctx_destroy(ctx);
-            throw;
-        }
-        // --extend-rows: the same setting on every device
-        if(po.extend_rows)
-        {
-            const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
-            const int rc = paris_hip_set_row_extension(ctx, &setting);
-            if(rc != PARIS_HIP_SUCCESS)
-            {
-                paris_hip_ctx_destroy(ctx);
-                rt(rc, "set_row_extension()");
-            }
-            rep.row_extension = true;
-        }
-        const std::uint32_t zinger_rows = po.zingers ? 1u : 0u; // how far beyond a band's rows the zinger filter reads
+        const device_ctx ctx{device}; // :87
+        set_frame_chain(ctx, po, rep);
+        set_chain_back(ctx, po, rep);
 
         // Projections travel in groups: a group of `batch` frames is converted, uploaded, weighted and filtered one by one,
         // then backprojected with ONE fused launch (paris_hip_backproject_batch[_f16]: bit-identical to the sequence, the slab
         // is read and written once per group). While the GPU works on one group the host fills the next. batch = 1 is the
         // reference's one launch per projection with `slots` single-frame groups.
         const std::uint32_t batch = slot_shape(po).first, groups = slot_shape(po).second;
-        rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
-        const int slots = static_cast<int>(batch * groups);
         const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
         // --bin: frames are read and uploaded at the source detector's size into full-width slots of their own and binned from there
         // into the slots everything downstream works on; without it the two sizes are one and there are no full-width slots
         const bool binning = po.binning();
         const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
-        const auto frame_bytes = static_cast<std::size_t>(sn_row) * sn_col * sizeof(float);
-        auto h_buf = std::vector<float*>(slots, nullptr);
-        auto d_buf = std::vector<float*>(slots, nullptr);
-        auto d_src = std::vector<float*>(slots, nullptr);
-        float* d_src_all = nullptr; // --bin: the full-width frames of all slots, one under the other like d_all
-        std::size_t s_pitch = 0;
-        // --detector-roll: the rolled frames of all slots, laid out as d_all (same pitch, same stride). d_out[s] is the frame of slot s
-        // that the weights, the filter and the backprojection read: the rolled one with a roll, d_buf[s] without
-        auto d_out = std::vector<float*>(slots, nullptr);
-        float* d_roll_all = nullptr;
-        auto fence = std::vector<paris_hip_fence*>(groups, nullptr);
-        float* d_all = nullptr; // the device frames of all slots, one under the other: slot s starts at row s * n_col
-        std::size_t d_pitch = 0, h16_pitch = 0, h16_stride = 0;
-        std::uint16_t* d_half = nullptr;
         // Two volume buffers when the device has room for them: the slab just finished is copied down and written by the drain
         // thread while the next one is reconstructed in the other buffer. The second buffer is allocated when (and if) this device
         // thread pops a second task and a slab's worth of memory is still free.
-        float* d_vol[2] = {nullptr, nullptr};
-        std::size_t v_cap[2] = {0, 0};
-        paris_hip_fence* slab_done[2] = {nullptr, nullptr};
-        std::unique_ptr<volume_drain> drain;
-        auto cleanup = [&] {
-            drain.reset(); // joins the drain thread: nothing reads the volumes or the fences after this
-            for(auto f : fence)
-                paris_hip_fence_destroy(ctx, f);
-            for(int s = 0; s < slots; ++s)
-                paris_hip_free_host(ctx, h_buf[s]);
-            paris_hip_free(ctx, d_all);
-            paris_hip_free(ctx, d_src_all);
-            paris_hip_free(ctx, d_roll_all);
-            paris_hip_free(ctx, d_half);
-            for(int s = 0; s < 2; ++s)
-            {
-                paris_hip_free(ctx, d_vol[s]);
-                paris_hip_fence_destroy(ctx, slab_done[s]);
-            }
-            paris_hip_ctx_destroy(ctx);
-        };
-        try
+        struct slab_buffers
         {
-            if(static_cast<std::uint64_t>(n_col) * static_cast<std::uint64_t>(slots) > 0xffffffffull)
-                throw stage_construction_error{"too many projection slots for this detector"};
-            rt(paris_hip_malloc_projection(ctx, n_row, n_col * static_cast<std::uint32_t>(slots), &d_all, &d_pitch), "make_projection_device()");
-            const auto d_stride = d_pitch * n_col; // bytes from one slot's frame to the next
-            if(binning)
+            paris_hip_ctx* ctx;
+            float* d_vol[2];
+            std::size_t cap[2];
+            paris_hip_fence* done[2];
+            ~slab_buffers()
             {
-                if(static_cast<std::uint64_t>(sn_col) * static_cast<std::uint64_t>(slots) > 0xffffffffull)
-                    throw stage_construction_error{"too many projection slots for this detector"};
-                rt(paris_hip_malloc_projection(ctx, sn_row, sn_col * static_cast<std::uint32_t>(slots), &d_src_all, &s_pitch), "make_projection_device()");
+                for(int s = 0; s < 2; ++s)
+                {
+                    paris_hip_free(ctx, d_vol[s]);
+                    paris_hip_fence_destroy(ctx, done[s]);
+                }
             }
-            if(po.roll)
+        } slab{ctx, {nullptr, nullptr}, {0, 0}, {nullptr, nullptr}};
+        const frame_slots slots{ctx, po, batch * groups, groups, po.roll, po.f16};
+        const frame_chain chain{ctx, po, slots, rep.defect_map};
+        for(auto& f : slab.done)
+            rt(paris_hip_fence_create(ctx, &f), "fence");
+        // (declared last: its destructor joins the drain thread before anything above is freed -- nothing reads the volumes or the
+        // fences after that --, and the ctx is destroyed last of all)
+        volume_drain drain{device, out, po.drain_chunk_bytes, po.voxels};
+        rep.setup_s = since(t_setup);
+        task t{};
+        bool two = false, decided = false;
+        while(queue.pop(t)) // :89-91
+        {
+            const bool last = (t.num - t.id) <= 1;                                    // :92
+            const auto dim_z = t.subvol_geo.dim_z + (last ? t.subvol_geo.remainder : 0u); // make_volume: src/make_volume.cpp:32-34
+            const auto offset = t.id * t.subvol_geo.dim_z;                             // :96
+            const auto voxels = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * dim_z;
+            if(rep.tasks == 1u && !decided) // a second slab for this device: is there room to keep the first while it is written?
             {
-                std::size_t r_pitch = 0;
-                rt(paris_hip_malloc_projection(ctx, n_row, n_col * static_cast<std::uint32_t>(slots), &d_roll_all, &r_pitch), "make_projection_device()");
-                if(r_pitch != d_pitch)
-                    throw stage_runtime_error{"the rolled frames' pitch differs from the frames'"};
+                std::size_t free_b = 0, total_b = 0;
+                rt(paris_hip_device_memory(device, &free_b, &total_b), "device memory");
+                // a slab the size of the largest of the run (the last one carries the remainder) plus slack for the runtime
+                const auto need = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * (t.subvol_geo.dim_z + t.subvol_geo.remainder) * sizeof(float);
+                two = po.two_volumes && free_b > need + need / 8u + (std::size_t{256} << 20);
+                decided = true;
+                rep.two_volumes = two;
             }
-            for(int s = 0; s < slots; ++s)
+            const int b = two ? static_cast<int>(rep.tasks & 1u) : 0;
+            auto t0 = clock::now();
+            drain.wait(b); // the slab that lived in this buffer is in the file
+            rep.drain_wait_s += since(t0);
+            float*& d_v = slab.d_vol[b];
+            if(voxels > slab.cap[b]) // slabs of one run have (almost) the same size: allocate once, re-zero per task
             {
-                void* p = nullptr;
-                rt(paris_hip_malloc_host(ctx, frame_bytes, &p), "make_projection_host()");
-                h_buf[s] = static_cast<float*>(p);
-                d_buf[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * static_cast<std::size_t>(s));
-                d_out[s] = po.roll ? reinterpret_cast<float*>(reinterpret_cast<char*>(d_roll_all) + d_stride * static_cast<std::size_t>(s)) : d_buf[s];
-                if(binning)
-                    d_src[s] = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * static_cast<std::size_t>(s));
+                rt(paris_hip_free(ctx, d_v), "free");
+                d_v = nullptr;
+                slab.cap[b] = 0;
+                rt(paris_hip_malloc_volume(ctx, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, &d_v), "make_volume()");
+                slab.cap[b] = voxels;
             }
-            for(auto& f : fence)
-                rt(paris_hip_fence_create(ctx, &f), "fence");
-            if(po.f16)
-            {
-                float* raw = nullptr;
-                h16_pitch = (static_cast<std::size_t>(n_row) * 2 + 255) / 256 * 256;
-                std::size_t got = 0;
-                // the half copies of all slots, one under the other like d_all
-                rt(paris_hip_malloc_projection(ctx, static_cast<std::uint32_t>(h16_pitch / 4), n_col * static_cast<std::uint32_t>(slots), &raw, &got),
-                   "half projection");
-                d_half = reinterpret_cast<std::uint16_t*>(raw);
-                h16_pitch = got;
-                h16_stride = h16_pitch * n_col;
-            }
+            else
+                rt(paris_hip_memset_volume(ctx, d_v, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z), "make_volume()");
 
-            for(auto& f : slab_done)
-                rt(paris_hip_fence_create(ctx, &f), "fence");
-            drain.reset(new volume_drain{device, out, po.drain_chunk_bytes, po.voxels});
-            rep.setup_s = since(t_setup);
-            task t{};
-            bool two = false, decided = false;
-            while(queue.pop(t)) // :89-91
-            {
-                const bool last = (t.num - t.id) <= 1;                                    // :92
-                const auto dim_z = t.subvol_geo.dim_z + (last ? t.subvol_geo.remainder : 0u); // make_volume: src/make_volume.cpp:32-34
-                const auto offset = t.id * t.subvol_geo.dim_z;                             // :96
-                const auto voxels = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * dim_z;
-                if(rep.tasks == 1u && !decided) // a second slab for this device: is there room to keep the first while it is written?
-                {
-                    std::size_t free_b = 0, total_b = 0;
-                    rt(paris_hip_device_memory(device, &free_b, &total_b), "device memory");
-                    // a slab the size of the largest of the run (the last one carries the remainder) plus slack for the runtime
-                    const auto need = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * (t.subvol_geo.dim_z + t.subvol_geo.remainder) * sizeof(float);
-                    two = po.two_volumes && free_b > need + need / 8u + (std::size_t{256} << 20);
-                    decided = true;
-                    rep.two_volumes = two;
-                }
-                const int b = two ? static_cast<int>(rep.tasks & 1u) : 0;
-                auto t0 = clock::now();
-                drain->wait(b); // the slab that lived in this buffer is in the file
-                rep.drain_wait_s += since(t0);
-                float*& d_v = d_vol[b];
-                if(voxels > v_cap[b]) // slabs of one run have (almost) the same size: allocate once, re-zero per task
-                {
-                    rt(paris_hip_free(ctx, d_v), "free");
-                    d_v = nullptr;
-                    v_cap[b] = 0;
-                    rt(paris_hip_malloc_volume(ctx, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, &d_v), "make_volume()");
-                    v_cap[b] = voxels;
-                }
+            auto band = row_range{0u, n_col};
+            if(po.row_band)
+                rt(paris_hip_slab_row_band(&t.det_geo, &t.vol_geo, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, t.enable_roi,
+                                           &t.roi, &band.first, &band.count), "slab_row_band()");
+            rep.band_rows += band.count;
+            // f4: only the detector rows this slab can read are converted, uploaded, weighted and filtered; the buffers keep
+            // their full size, rows outside the band are never read for a voxel of the slab. Which rows each pass covers: the plan
+            const auto roll = paris_hip_detector_roll{po.roll_deg};
+            const auto rows = plan_frame_rows(band, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr,
+                                              binning ? po.bin_y : 1u, po.roll ? &roll : nullptr, &t.det_geo);
+
+            // --lag: this pass over the scan is a sequence of its own, from frame 0 of the file, for the rows it uploads
+            if(po.lag && rows.band.count != 0)
+                rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
+
+            t0 = clock::now();
+            // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
+            auto shared = pool != nullptr ? pool->get(t) : std::shared_ptr<shared_frames>{};
+            auto cur = shared_frames::cursor{};
+            auto own = std::unique_ptr<frame_stream>{};
+            if(!shared)
+                own.reset(new frame_stream{t.input_path, t.enable_angles, t.angle_path, t.quality});
+            rep.source_s += since(t0);
+            std::uint32_t group = 0, filled = 0; // frames of the current group already enqueued
+            auto feed = std::unique_ptr<frame_feed>{};
+            auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch);
+            auto angles = std::vector<float>(batch); // --short-scan: each frame's angle [deg], resolved as paris_hip_stage_angle does
+            const float delta_s = t.det_geo.delta_s * t.det_geo.l_px_row, delta_t = t.det_geo.delta_t * t.det_geo.l_px_col; // src/backprojection.cpp:49-50
+            // frames of up to 1024 x 1024 are weighted and filtered group by group (one launch for up to `batch` frames when the
+            // group is flushed) instead of frame by frame behind each upload: their launches are mostly latency
+            const bool filter_by_group = batch > 1u && static_cast<std::uint64_t>(n_row) * n_col <= (1ull << 20);
+            const auto flush = [&] { // one fused launch for the frames of the current group, then on to the other group
+                if(filled == 0)
+                    return;
+                const auto t1 = clock::now();
+                if(filter_by_group && rows.band.count != 0) // the chain for the group: one call per pass
+                    chain.run(group * batch, filled, true, rows, angles.data());
+                if(po.f16)
+                    rt(paris_hip_backproject_batch_f16(ctx, slots.half(group * batch), slots.half_pitch, slots.half_stride, filled, n_row, n_col, d_v,
+                                                       t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi,
+                                                       sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
                 else
-                    rt(paris_hip_memset_volume(ctx, d_v, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z), "make_volume()");
-
-                std::uint32_t band_first = 0, band_count = n_col;
-                if(po.row_band)
-                    rt(paris_hip_slab_row_band(&t.det_geo, &t.vol_geo, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, t.enable_roi,
-                                               &t.roi, &band_first, &band_count), "slab_row_band()");
-                rep.band_rows += band_count;
-                // With a roll the slab's band is what the roll WRITES and everything after it reads (out_first, out_count); the rows
-                // every earlier pass covers become the roll's source range of that band (paris_hip_detector_roll_source_rows), which
-                // is widened further below as any band is. Every slab's volume then equals the whole-detector run's, bit for bit.
-                const std::uint32_t out_first = band_first, out_count = band_count;
-                if(po.roll && band_count != 0)
-                {
-                    const auto setting = paris_hip_detector_roll{po.roll_deg};
-                    rt(paris_hip_detector_roll_source_rows(&setting, &t.det_geo, out_first, out_count, &band_first, &band_count), "detector_roll_source_rows()");
-                }
-                // With a defect map the repair of a band's defects reads good pixels up to reach_rows rows beyond it: those rows are
-                // read, uploaded and corrected as well (clipped to the detector), and nothing else is done to them -- the band itself
-                // is repaired, weighted and filtered. Every slab's volume then equals the whole-detector run's, bit for bit.
-                // With --zingers the windows of the band's pixels reach one row beyond it: the rows read, uploaded and corrected are the
-                // band widened by 1 -- by reach_rows + 1 with a defect map, whose repair then covers the band widened by 1, so that a
-                // window on the band's edge sees the repaired pixels the whole-detector run sees -- and the zinger filter covers the band
-                // itself. The extra rows are never weighted or filtered. (Saturation is counted per band, against a max_hits made for
-                // the whole detector: the slabs' volumes equal the whole-detector run's only while no frame saturates in either.)
-                const auto widened = [&](std::uint32_t by, std::uint32_t& first, std::uint32_t& count) {
-                    first = band_first - std::min(band_first, by);
-                    count = std::min(n_col - (band_first + band_count), by) + band_first + band_count - first;
-                };
-                // With --air-region every frame's value comes from the rectangle's rows, whatever the band: the rows read, uploaded and
-                // corrected become ONE range that holds the widened band and the rectangle's rows (the rows between them travel too:
-                // next_raw reads one contiguous range), and the value is subtracted from the widened band (air), the rows the repair
-                // and the zinger filter read. Every slab and every device reads the same rectangle and gets the same value.
-                std::uint32_t up_first = band_first, up_count = band_count, fix_first = band_first, fix_count = band_count;
-                if(band_count != 0)
-                {
-                    widened((repair ? reach_rows : 0u) + zinger_rows, up_first, up_count);
-                    widened(zinger_rows, fix_first, fix_count);
-                }
-                const std::uint32_t air_first = up_first, air_count = up_count;
-                if(band_count != 0 && po.air)
-                    hull_rows(po.air_region.y0, po.air_region.height, up_first, up_count);
-                // --bin: the source rows the uploaded band is binned from (the band itself without it)
-                const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
-
-                // --lag: this pass over the scan is a sequence of its own, from frame 0 of the file, for the rows it uploads
-                if(po.lag && band_count != 0)
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, up_first, up_count), "lag_begin()");
-
-                t0 = clock::now();
-                // :93 (index restarts per task). Several devices: the frames come from the pass's read-once source
-                auto shared = pool != nullptr ? pool->get(t) : std::shared_ptr<shared_frames>{};
-                auto cur = shared_frames::cursor{};
-                auto own = std::unique_ptr<frame_stream>{};
-                if(!shared)
-                    own.reset(new frame_stream{t.input_path, t.enable_angles, t.angle_path, t.quality});
-                rep.source_s += since(t0);
-                std::uint32_t group = 0, filled = 0; // frames of the current group already enqueued
-                auto feed = std::unique_ptr<frame_feed>{};
-                auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch);
-                auto angles = std::vector<float>(batch); // --short-scan: each frame's angle [deg], resolved as paris_hip_stage_angle does
-                const float delta_s = t.det_geo.delta_s * t.det_geo.l_px_row, delta_t = t.det_geo.delta_t * t.det_geo.l_px_col; // src/backprojection.cpp:49-50
-                // frames of up to 1024 x 1024 are weighted and filtered group by group (one launch for up to `batch` frames when the
-                // group is flushed) instead of frame by frame behind each upload: their launches are mostly latency
-                const bool filter_by_group = batch > 1u && static_cast<std::uint64_t>(n_row) * n_col <= (1ull << 20);
-                const auto flush = [&] { // one fused launch for the frames of the current group, then on to the other group
-                    if(filled == 0)
-                        return;
-                    const auto t1 = clock::now();
-                    if(filter_by_group && band_count != 0 && po.air) // the frames' own flux drift first, one call for the group
-                        rt(paris_hip_air_normalize_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, air_first, air_count),
-                           "air normalisation");
-                    if(filter_by_group && band_count != 0 && repair) // the repair before every weight, one launch for the group
-                        rt(paris_hip_defect_repair_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count),
-                           "defect repair");
-                    if(filter_by_group && band_count != 0 && po.zingers) // then the zinger filter, one call for the group
-                        rt(paris_hip_zinger_filter_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
-                           "zinger filter");
-                    if(filter_by_group && band_count != 0 && po.ring_c) // then the detector's stationary offsets, on the band itself
-                        rt(paris_hip_ring_correct_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
-                           "ring correction");
-                    if(filter_by_group && band_count != 0 && po.beam_hardening) // then the linearisation, before every weight
-                        rt(paris_hip_beam_hardening_rows(ctx, d_buf[group * batch], d_pitch, d_stride, filled, n_row, n_col, band_first, band_count),
-                           "beam hardening");
-                    if(filter_by_group && band_count != 0 && po.roll) // then the roll, the last frame pass: one call for the group
-                        rt(paris_hip_detector_roll_rows(ctx, d_buf[group * batch], d_pitch, d_stride, d_out[group * batch], d_pitch, d_stride, filled, n_row,
-                                                        n_col, out_first, out_count), "detector roll");
-                    if(filter_by_group && band_count != 0 && po.offset_detector) // the redundancy weight first, one launch for the group
-                        rt(paris_hip_offset_detector_weight_rows(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first,
-                                                                 out_count, &t.det_geo), "offset-detector weight()");
-                    if(filter_by_group && band_count != 0 && po.short_scan) // the redundancy weight first, one launch for the group
-                        rt(paris_hip_short_scan_weight_rows(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first, out_count,
-                                                            &t.det_geo, &po.scan, angles.data()), "short-scan weight()");
-                    if(filter_by_group && band_count != 0)
-                        rt(paris_hip_stage_weight_filter_batch(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, out_first, out_count,
-                                                               &t.det_geo,
-                                                               po.f16 ? reinterpret_cast<std::uint16_t*>(reinterpret_cast<char*>(d_half) + h16_stride * group * batch) : nullptr,
-                                                               h16_pitch, h16_stride), "weight() + filter()");
-                    if(po.f16)
-                        rt(paris_hip_backproject_batch_f16(ctx, reinterpret_cast<const std::uint16_t*>(reinterpret_cast<const char*>(d_half) + h16_stride * group * batch),
-                                                           h16_pitch, h16_stride, filled, n_row, n_col, d_v, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z,
-                                                           offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi, sines.data(), cosines.data(), delta_s,
-                                                           delta_t), "backproject()");
-                    else
-                        rt(paris_hip_backproject_batch(ctx, d_out[group * batch], d_pitch, d_stride, filled, n_row, n_col, d_v, t.subvol_geo.dim_x,
-                                                       t.subvol_geo.dim_y, dim_z, offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi, sines.data(),
-                                                       cosines.data(), delta_s, delta_t), "backproject()"); // :104
-                    rt(paris_hip_fence_record(ctx, fence[group]), "fence record"); // the group's slots are free once this has run
-                    rep.enqueue_s += since(t1);
-                    group = (group + 1u) % groups;
-                    filled = 0;
-                    if(feed)
-                        feed->flushed();
-                };
-                // f4: only the detector rows this slab can read are converted, uploaded, weighted and filtered; the
-                // buffers keep their full size, rows outside the band are never read for a voxel of the slab
-                // The rows arrive as stored (u8 / u16 / u32 / f32; f64 as f32): the upload carries those bytes and the device widens them
-                // (paris_hip_upload_projection_raw, bit for bit the host's conversion). A slot keeps room for 4 bytes per pixel.
-                // With --flat the same pass corrects them to line integrals with the reference rows of their absolute detector rows
-                // (paris_hip_upload_projection_raw_corrected): the short-scan weight and the weight + filter see line integrals.
-                const auto next_frame = [&](float* dst) {
-                    return shared ? shared->next_raw(cur, dst, sn_row, sn_col, src_first, src_count)
-                                  : own->next_raw(dst, sn_row, sn_col, src_first, src_count); // :100, straight into pinned memory
-                };
-                if(po.read_ahead)
-                    feed.reset(new frame_feed{ctx, next_frame, h_buf, batch, fence});
-                for(;;) // :98
-                {
-                    const int slot = static_cast<int>(group * batch + filled);
-                    auto p = frame_info{};
-                    if(feed)
-                    {
-                        t0 = clock::now();
-                        p = feed->take(); // read by the feed thread, which also waited for the slot to be free
-                        rep.source_wait_s += since(t0);
-                    }
-                    else
-                    {
-                        t0 = clock::now();
-                        if(filled == 0)
-                            rt(paris_hip_fence_wait(ctx, fence[group]), "fence wait"); // everything that last used this group's slots is done
-                        rep.enqueue_s += since(t0);
-                        t0 = clock::now();
-                        p = next_frame(h_buf[slot]);
-                        rep.source_s += since(t0);
-                    }
-                    if(!p.valid())
-                        break;
-                    if(p.dim_x != sn_row || p.dim_y != sn_col)
-                        throw stage_runtime_error{"projection size does not match the detector geometry"};
-                    t0 = clock::now();
-                    const auto px = his::pixel_size(p.pixel);
-                    const auto band_off = static_cast<std::size_t>(src_first) * sn_row * px; // bytes
-                    auto* d_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_buf[slot]) + static_cast<std::size_t>(up_first) * d_pitch);
-                    if(band_count != 0)
-                    {
-                        // :101 -- on the upload stream, overlapping the kernels of the previous projections
-                        if(binning)
-                        {
-                            // the source rows as stored into the slot's full-width frame, binned from there into the slot's binned
-                            // frame, which is then corrected in place: the same bits as the corrected upload of a binned frame
-                            auto* d_src_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src[slot]) + static_cast<std::size_t>(src_first) * s_pitch);
-                            rt(paris_hip_upload_projection_raw(ctx, d_src_band, s_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, sn_row * px,
-                                                               sn_row, src_count, p.pixel), "load()");
-                            rt(paris_hip_bin_frames(ctx, d_src[slot], s_pitch, 0u, d_buf[slot], d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
-                            if(po.lag) // the detector's memory of the frames before, on the binned counts
-                                rt(paris_hip_lag_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
-                            if(po.flat)
-                                rt(paris_hip_flat_field_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
-                        }
-                        else if(po.lag)
-                        {
-                            // the unfused route binning takes: the counts as stored, the lag correction on them, then the dark / flat
-                            // correction as a pass of its own -- the same bits as the corrected upload of the corrected counts
-                            rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
-                                                               n_row, up_count, p.pixel), "load()");
-                            rt(paris_hip_lag_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
-                            rt(paris_hip_flat_field_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
-                        }
-                        else if(po.flat)
-                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_buf[slot], d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off,
-                                                                         n_row * px, n_row, n_col, up_first, up_count, p.pixel), "load()");
-                        else
-                            rt(paris_hip_upload_projection_raw(ctx, d_band, d_pitch, reinterpret_cast<const char*>(h_buf[slot]) + band_off, n_row * px,
-                                                               n_row, up_count, p.pixel), "load()");
-                        rep.h2d_bytes += static_cast<std::uint64_t>(src_count) * sn_row * px;
-                        angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
-                        if(po.air && !filter_by_group) // the frame's own flux drift, straight after the correction
-                            rt(paris_hip_air_normalize_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, air_first, air_count), "air normalisation");
-                        if(repair && !filter_by_group) // the band's defective pixels, before every weight
-                            rt(paris_hip_defect_repair_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, fix_first, fix_count), "defect repair");
-                        if(po.zingers && !filter_by_group) // then the band's outlier pixels
-                            rt(paris_hip_zinger_filter_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "zinger filter");
-                        if(po.ring_c && !filter_by_group) // then the detector's stationary offsets
-                            rt(paris_hip_ring_correct_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "ring correction");
-                        if(po.beam_hardening && !filter_by_group) // then the linearisation, before every weight
-                            rt(paris_hip_beam_hardening_rows(ctx, d_buf[slot], d_pitch, 0u, 1u, n_row, n_col, band_first, band_count), "beam hardening");
-                        if(po.roll && !filter_by_group) // then the roll into the slot's second frame, which everything below reads
-                            rt(paris_hip_detector_roll_rows(ctx, d_buf[slot], d_pitch, 0u, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count),
-                               "detector roll");
-                        if(po.offset_detector && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
-                            rt(paris_hip_offset_detector_weight_rows(ctx, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count,
-                                                                     &t.det_geo), "offset-detector weight()");
-                        if(po.short_scan && !filter_by_group) // the redundancy weight on the raw band, before the cosine weight
-                            rt(paris_hip_short_scan_weight_rows(ctx, d_out[slot], d_pitch, 0u, 1u, n_row, n_col, out_first, out_count, &t.det_geo,
-                                                                &po.scan, &angles[filled]), "short-scan weight()");
-                        // :102-103 in one launch: the weight rides along in the row filter's load; with --f16 (BASELINE config 5) the
-                        // filtered band is stored as IEEE half straight into the slot's half frame
-                        // (small frames: the whole group by one launch when it is flushed -- a launch per 512^2 frame is mostly latency)
-                        auto* half_frame = po.f16 ? reinterpret_cast<std::uint16_t*>(reinterpret_cast<char*>(d_half) + h16_stride * static_cast<std::size_t>(slot)) : nullptr;
-                        if(!filter_by_group)
-                            rt(paris_hip_stage_weight_filter_rows(ctx, d_out[slot], d_pitch, n_row, n_col, out_first, out_count, &t.det_geo, half_frame,
-                                                                  h16_pitch), "weight() + filter()");
-                    }
-                    rt(paris_hip_stage_angle(&t.det_geo, p.idx, t.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle"); // src/backprojection.cpp:52-63
-                    rep.enqueue_s += since(t0);
-                    if(++filled == batch)
-                        flush();
-                    ++rep.projections;
-                }
-                flush(); // the last, possibly partial group
-                if(po.lag)
-                    rt(paris_hip_lag_end(ctx), "lag_end()");
+                    rt(paris_hip_backproject_batch(ctx, slots.out(group * batch), slots.pitch, slots.stride, filled, n_row, n_col, d_v, t.subvol_geo.dim_x,
+                                                   t.subvol_geo.dim_y, dim_z, offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi, sines.data(),
+                                                   cosines.data(), delta_s, delta_t), "backproject()"); // :104
+                rt(paris_hip_fence_record(ctx, slots.fences()[group]), "fence record"); // the group's slots are free once this has run
+                rep.enqueue_s += since(t1);
+                group = (group + 1u) % groups;
+                filled = 0;
+                if(feed)
+                    feed->flushed();
+            };
+            const auto next_frame = [&](float* dst) {
+                return shared ? shared->next_raw(cur, dst, sn_row, sn_col, rows.src.first, rows.src.count)
+                              : own->next_raw(dst, sn_row, sn_col, rows.src.first, rows.src.count); // :100, straight into pinned memory
+            };
+            if(po.read_ahead)
+                feed.reset(new frame_feed{ctx, next_frame, slots.hosts(), batch, slots.fences()});
+            for(;;) // :98
+            {
+                const auto slot = group * batch + filled;
+                auto p = frame_info{};
                 if(feed)
                 {
-                    rep.source_s += feed->read_seconds();
-                    feed.reset(); // joins the feed thread: the source objects are this thread's again
+                    t0 = clock::now();
+                    p = feed->take(); // read by the feed thread, which also waited for the slot to be free
+                    rep.source_wait_s += since(t0);
                 }
-                for(const auto& s : (shared ? cur.skipped_files() : own->skipped_files())) // the shared source's list: run_report
-                    rep.skipped.push_back(s);
-
-                // src/sink.cpp:76-82: the slab is complete behind this fence; the drain thread takes it from there
-                rt(paris_hip_fence_record(ctx, slab_done[b]), "fence record");
-                auto j = volume_drain::job{};
-                j.d_v = d_v;
-                j.dim_x = t.subvol_geo.dim_x;
-                j.dim_y = t.subvol_geo.dim_y;
-                j.dim_z = dim_z;
-                j.first = offset;
-                j.ready = slab_done[b];
-                j.buffer = b;
-                drain->submit(j);
-                ++rep.tasks;
+                else
+                {
+                    t0 = clock::now();
+                    if(filled == 0)
+                        rt(paris_hip_fence_wait(ctx, slots.fences()[group]), "fence wait"); // everything that last used this group's slots is done
+                    rep.enqueue_s += since(t0);
+                    t0 = clock::now();
+                    p = next_frame(slots.host(slot));
+                    rep.source_s += since(t0);
+                }
+                if(!p.valid())
+                    break;
+                if(p.dim_x != sn_row || p.dim_y != sn_col)
+                    throw stage_runtime_error{"projection size does not match the detector geometry"};
+                t0 = clock::now();
+                if(rows.band.count != 0)
+                {
+                    chain.upload(slot, p.pixel, rows);
+                    rep.h2d_bytes += static_cast<std::uint64_t>(rows.src.count) * sn_row * his::pixel_size(p.pixel);
+                    angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                    // (small frames: the whole group by one call per pass when it is flushed -- a launch per 512^2 frame is mostly latency)
+                    if(!filter_by_group)
+                        chain.run(slot, 1u, false, rows, &angles[filled]);
+                }
+                rt(paris_hip_stage_angle(&t.det_geo, p.idx, t.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle"); // src/backprojection.cpp:52-63
+                rep.enqueue_s += since(t0);
+                if(++filled == batch)
+                    flush();
+                ++rep.projections;
             }
-            const auto t_end = clock::now();
-            drain->finish();
-            rep.drain_wait_s += since(t_end);
-            if(po.zingers)
-                rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
-            if(po.air)
-                rt(paris_hip_air_stats(ctx, &rep.air, 0), "air stats");
-            rep.drain_s = drain->drain_seconds();
-            rep.save_s = drain->save_seconds();
-            rep.voxels = drain->voxel_counts();
+            flush(); // the last, possibly partial group
+            if(po.lag)
+                rt(paris_hip_lag_end(ctx), "lag_end()");
+            if(feed)
+            {
+                rep.source_s += feed->read_seconds();
+                feed.reset(); // joins the feed thread: the source objects are this thread's again
+            }
+            for(const auto& s : (shared ? cur.skipped_files() : own->skipped_files())) // the shared source's list: run_report
+                rep.skipped.push_back(s);
+
+            // src/sink.cpp:76-82: the slab is complete behind this fence; the drain thread takes it from there
+            rt(paris_hip_fence_record(ctx, slab.done[b]), "fence record");
+            auto j = volume_drain::job{};
+            j.d_v = d_v;
+            j.dim_x = t.subvol_geo.dim_x;
+            j.dim_y = t.subvol_geo.dim_y;
+            j.dim_z = dim_z;
+            j.first = offset;
+            j.ready = slab.done[b];
+            j.buffer = b;
+            drain.submit(j);
+            ++rep.tasks;
         }
-        catch(...)
-        {
-            cleanup();
-            throw;
-        }
-        cleanup();
+        const auto t_end = clock::now();
+        drain.finish();
+        rep.drain_wait_s += since(t_end);
+        if(po.zingers)
+            rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
+        if(po.air)
+            rt(paris_hip_air_stats(ctx, &rep.air, 0), "air stats");
+        rep.drain_s = drain.drain_seconds();
+        rep.save_s = drain.save_seconds();
+        rep.voxels = drain.voxel_counts();
         return rep;
     }
 
@@ -1723,10 +1728,10 @@ namespace paris
         }
 
         // --rings and --find-axis: the pre-pass. Every projection the run uses is read once on the first device and goes through the
-        // chain the reconstruction uses -- the raw upload (corrected with --flat), the air normalisation, the defect repair, the zinger filter -- into the ring
+        // chain the reconstruction uses, as far as the zinger filter (frame_chain: upload() and clean()), into the ring
         // profile (rings), into the axis search's sinogram (axis), or into both: a group of po.batch frames per call as the main loop
-        // groups them. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by the reach
-        // of the repair and of the zinger filter as a slab's band is in reconstruct(). Then the ring rule makes the correction frame,
+        // groups them. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by the row
+        // plan as a slab's band is. Then the ring rule makes the correction frame,
         // which is kept in po, and the search gives its estimate, which is kept in r. Everything allocated here is freed before it
         // returns: run() plans the slabs afterwards.
         inline auto prepass(program_options& po, run_report& r, bool rings, bool axis, bool roll = false) -> void
@@ -1736,68 +1741,29 @@ namespace paris
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
             const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
             const std::uint32_t batch = slot_shape(po).first;
-            if(static_cast<std::uint64_t>(n_col) * batch > 0xffffffffull)
-                throw stage_construction_error{"too many projection slots for this detector"};
-            paris_hip_ctx* ctx = nullptr;
-            rt(paris_hip_ctx_create(0, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
-            auto h_buf = std::vector<float*>(batch, nullptr);
-            float* d_all = nullptr;
-            // --bin: the profile is taken on binned frames; the source frames go through full-width slots as in reconstruct()
+            // --bin: the profile is taken on binned frames; the source frames go through the slots' full-width frames
             const bool binning = po.binning();
             const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
-            float* d_src_all = nullptr;
-            const auto cleanup = [&] {
-                for(auto h : h_buf)
-                    paris_hip_free_host(ctx, h);
-                paris_hip_free(ctx, d_all);
-                paris_hip_free(ctx, d_src_all);
-                paris_hip_ctx_destroy(ctx);
-            };
-            try
             {
+                const device_ctx ctx{0};
                 auto rep = device_report{};
                 set_frame_chain(ctx, po, rep);
-                std::size_t d_pitch = 0;
-                rt(paris_hip_malloc_projection(ctx, n_row, n_col * batch, &d_all, &d_pitch), "make_projection_device()");
-                const auto d_stride = d_pitch * n_col;
-                std::size_t s_pitch = 0;
-                if(binning)
-                {
-                    if(static_cast<std::uint64_t>(sn_col) * batch > 0xffffffffull)
-                        throw stage_construction_error{"too many projection slots for this detector"};
-                    rt(paris_hip_malloc_projection(ctx, sn_row, sn_col * batch, &d_src_all, &s_pitch), "make_projection_device()");
-                }
-                for(auto& h : h_buf)
-                {
-                    void* p = nullptr;
-                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(sn_row) * sn_col * sizeof(float), &p), "make_projection_host()");
-                    h = static_cast<float*>(p);
-                }
-                // the rows of every frame that are read, uploaded and corrected (up), repaired (fix) and filtered and consumed (band)
-                std::uint32_t band_first = 0, band_count = n_col;
+                const frame_slots slots{ctx, po, batch, 0u, false, false};
+                const frame_chain chain{ctx, po, slots, rep.defect_map};
+                // the rows of every frame that are filtered and consumed: all of them, or the search's band; the plan widens them
+                auto band = row_range{0u, n_col};
                 if(axis && !profile)
                 {
-                    rt(paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, &band_first, nullptr), "axis_search_check()");
-                    band_count = po.axis_rows;
+                    rt(paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, &band.first, nullptr), "axis_search_check()");
+                    band.count = po.axis_rows;
                 }
-                const auto widened = [&](std::uint32_t by, std::uint32_t& first, std::uint32_t& count) {
-                    first = band_first - std::min(band_first, by);
-                    count = std::min(n_col - (band_first + band_count), by) + band_first + band_count - first;
-                };
-                const std::uint32_t zinger_rows = po.zingers ? 1u : 0u;
-                std::uint32_t up_first = 0, up_count = 0, fix_first = 0, fix_count = 0;
-                widened((rep.defect_map ? rep.defects.reach_rows : 0u) + zinger_rows, up_first, up_count);
-                widened(zinger_rows, fix_first, fix_count);
-                const std::uint32_t air_first = up_first, air_count = up_count; // --air-region: as in reconstruct()
-                if(po.air)
-                    hull_rows(po.air_region.y0, po.air_region.height, up_first, up_count);
-                const std::uint32_t src_first = binning ? po.bin_y * up_first : up_first, src_count = binning ? po.bin_y * up_count : up_count;
+                const auto rows = plan_frame_rows(band, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr, binning ? po.bin_y : 1u);
                 if(profile)
                     rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
                 if(axis)
                     rt(paris_hip_axis_search_begin(ctx, &search, &po.det_geo, po.axis_frames), "axis_search_begin()");
                 if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, up_first, up_count), "lag_begin()");
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
                 std::uint32_t frames = 0;
                 auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
                 for(bool more = true; more;)
@@ -1805,7 +1771,7 @@ namespace paris
                     std::uint32_t filled = 0;
                     for(; filled < batch; ++filled)
                     {
-                        const auto p = source.next_raw(h_buf[filled], sn_row, sn_col, src_first, src_count);
+                        const auto p = source.next_raw(slots.host(filled), sn_row, sn_col, rows.src.first, rows.src.count);
                         if(!p.valid())
                         {
                             more = false;
@@ -1813,48 +1779,17 @@ namespace paris
                         }
                         if(p.dim_x != sn_row || p.dim_y != sn_col)
                             throw stage_runtime_error{"projection size does not match the detector geometry"};
-                        auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * filled);
-                        const auto px = his::pixel_size(p.pixel);
-                        const auto* h_band = reinterpret_cast<const char*>(h_buf[filled]) + static_cast<std::size_t>(src_first) * sn_row * px;
-                        if(binning)
-                        {
-                            auto* d_full = reinterpret_cast<float*>(reinterpret_cast<char*>(d_src_all) + s_pitch * sn_col * filled);
-                            auto* d_full_band = reinterpret_cast<float*>(reinterpret_cast<char*>(d_full) + static_cast<std::size_t>(src_first) * s_pitch);
-                            rt(paris_hip_upload_projection_raw(ctx, d_full_band, s_pitch, h_band, sn_row * px, sn_row, src_count, p.pixel), "load()");
-                            rt(paris_hip_bin_frames(ctx, d_full, s_pitch, 0u, d_frame, d_pitch, 0u, 1u, sn_row, sn_col, up_first, up_count), "bin()");
-                            if(po.lag)
-                                rt(paris_hip_lag_correct_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
-                            if(po.flat)
-                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
-                        }
-                        else if(po.lag) // the unfused route, as in reconstruct()
-                        {
-                            rt(paris_hip_upload_projection_raw(ctx, reinterpret_cast<float*>(reinterpret_cast<char*>(d_frame) + static_cast<std::size_t>(up_first) * d_pitch),
-                                                               d_pitch, h_band, n_row * px, n_row, up_count, p.pixel), "load()");
-                            rt(paris_hip_lag_correct_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "lag correction");
-                            rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, up_first, up_count), "flat field");
-                        }
-                        else if(po.flat)
-                            rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_band, n_row * px, n_row, n_col, up_first, up_count, p.pixel),
-                               "load()");
-                        else
-                            rt(paris_hip_upload_projection_raw(ctx, reinterpret_cast<float*>(reinterpret_cast<char*>(d_frame) + static_cast<std::size_t>(up_first) * d_pitch),
-                                                               d_pitch, h_band, n_row * px, n_row, up_count, p.pixel), "load()");
+                        chain.upload(filled, p.pixel, rows);
                     }
                     if(filled == 0)
                         break;
                     if(axis && filled > po.axis_frames - frames)
                         throw stage_runtime_error{"--find-axis: the input holds more frames than were counted"};
-                    if(po.air)
-                        rt(paris_hip_air_normalize_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, air_first, air_count), "air normalisation");
-                    if(rep.defect_map)
-                        rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, fix_first, fix_count), "defect repair");
-                    if(po.zingers)
-                        rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, band_first, band_count), "zinger filter");
+                    chain.clean(0u, filled, true, rows);
                     if(profile)
-                        rt(paris_hip_ring_profile_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
+                        rt(paris_hip_ring_profile_add_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
                     if(axis)
-                        rt(paris_hip_axis_search_add_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, frames), "axis_search_add_rows()");
+                        rt(paris_hip_axis_search_add_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, frames), "axis_search_add_rows()");
                     rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
                     frames += filled;
                 }
@@ -1907,13 +1842,7 @@ namespace paris
                     r.roll_frames = frames;
                     r.roll_count = po.roll_count;
                 }
-            }
-            catch(...)
-            {
-                cleanup();
-                throw;
-            }
-            cleanup();
+            } // (the buffers and the ctx are gone: the times below include that)
             if(roll)
                 r.roll_prepass_s = since(t_start);
             if(rings)
@@ -2012,69 +1941,51 @@ namespace paris
             const auto& vg = r.vol_geo;
             const std::uint32_t degree = po.bh.degree, slices = po.bh_slices, z_first = (vg.dim_z - slices) / 2u;
             const std::uint32_t batch = slot_shape(po).first;
-            if(static_cast<std::uint64_t>(n_col) * batch > 0xffffffffull)
-                throw stage_construction_error{"too many projection slots for this detector"};
-            paris_hip_ctx* ctx = nullptr;
-            rt(paris_hip_ctx_create(0, nullptr, PARIS_HIP_CTX_DEFAULT, &ctx), "set_device()");
-            auto h_buf = std::vector<float*>(batch, nullptr);
             auto infos = std::vector<frame_info>(batch);
-            float* d_all = nullptr;
-            float* d_slab[PARIS_HIP_BH_DEGREE_MAX] = {nullptr, nullptr, nullptr, nullptr};
-            std::uint8_t* d_labels = nullptr;
-            const auto cleanup = [&] {
-                for(auto h : h_buf)
-                    paris_hip_free_host(ctx, h);
-                paris_hip_free(ctx, d_all);
-                for(auto d : d_slab)
-                    paris_hip_free(ctx, d);
-                paris_hip_free(ctx, d_labels);
-                paris_hip_ctx_destroy(ctx);
-            };
-            try
             {
+                const device_ctx ctx{0};
+                struct fit_buffers // the basis slabs and the labels
+                {
+                    paris_hip_ctx* ctx;
+                    float* d_slab[PARIS_HIP_BH_DEGREE_MAX];
+                    std::uint8_t* d_labels;
+                    ~fit_buffers()
+                    {
+                        for(auto d : d_slab)
+                            paris_hip_free(ctx, d);
+                        paris_hip_free(ctx, d_labels);
+                    }
+                } fit{ctx, {nullptr, nullptr, nullptr, nullptr}, nullptr};
                 auto rep = device_report{};
                 set_frame_chain(ctx, po, rep);
-                if(po.ring_c)
-                    rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), n_row, n_col), "set_ring_correction()");
-                if(po.extend_rows)
-                {
-                    const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
-                    rt(paris_hip_set_row_extension(ctx, &setting), "set_row_extension()");
-                }
-                rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
-                std::size_t d_pitch = 0;
-                rt(paris_hip_malloc_projection(ctx, n_row, n_col * batch, &d_all, &d_pitch), "make_projection_device()");
-                const auto d_stride = d_pitch * n_col;
-                for(auto& h : h_buf)
-                {
-                    void* p = nullptr;
-                    rt(paris_hip_malloc_host(ctx, static_cast<std::size_t>(n_row) * n_col * sizeof(float), &p), "make_projection_host()");
-                    h = static_cast<float*>(p);
-                }
+                set_chain_back(ctx, po, rep); // (no polynomial and no roll yet: check_beam_hardening, check_roll)
+                const frame_slots slots{ctx, po, batch, 0u, false, false};
+                const frame_chain chain{ctx, po, slots, rep.defect_map};
                 for(std::uint32_t k = 0; k < degree; ++k)
-                    rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, slices, &d_slab[k]), "make_volume()");
+                    rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, slices, &fit.d_slab[k]), "make_volume()");
                 {
                     float* words = nullptr; // the labels: one byte per voxel, in memory of the volume allocator
                     const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
                     if((voxels + 3u) / 4u > 0xffffffffull)
                         throw stage_construction_error{"--fit-beam-hardening: the slab holds too many voxels"};
                     rt(paris_hip_malloc_volume(ctx, static_cast<std::uint32_t>((voxels + 3u) / 4u), 1u, 1u, &words), "make_volume()");
-                    d_labels = reinterpret_cast<std::uint8_t*>(words);
+                    fit.d_labels = reinterpret_cast<std::uint8_t*>(words);
                 }
-                const bool repair = rep.defect_map;
+                // whole frames: every range of the plan is the detector
+                const auto rows = plan_frame_rows(row_range{0u, n_col}, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr, 1u);
                 const float delta_s = po.det_geo.delta_s * po.det_geo.l_px_row, delta_t = po.det_geo.delta_t * po.det_geo.l_px_col;
                 const auto no_roi = region_of_interest{};
                 auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
                 std::uint32_t frames = 0;
                 auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
                 if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file, on whole frames
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, 0u, n_col), "lag_begin()");
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
                 for(bool more = true; more;)
                 {
                     std::uint32_t filled = 0;
                     for(; filled < batch; ++filled)
                     {
-                        infos[filled] = source.next_raw(h_buf[filled], n_row, n_col, 0u, n_col);
+                        infos[filled] = source.next_raw(slots.host(filled), n_row, n_col, rows.src.first, rows.src.count);
                         const auto& p = infos[filled];
                         if(!p.valid())
                         {
@@ -2092,18 +2003,14 @@ namespace paris
                     {
                         // The group goes through the stages once per basis, but the sequence's state must see every frame once: the
                         // counts are corrected once, in time order, and the pinned frames (a slot holds 4 bytes per pixel) are replaced
-                        // by the corrected counts as f32, which every basis then uploads.
+                        // by the corrected counts as f32, which every basis then uploads (chain.upload: lag already applied).
+                        for(std::uint32_t f = 0; f < filled; ++f)
+                            rt(paris_hip_upload_projection_raw(ctx, slots.frame(f), slots.pitch, slots.host(f), n_row * his::pixel_size(infos[f].pixel), n_row,
+                                                               n_col, infos[f].pixel), "load()");
+                        rt(paris_hip_lag_correct_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, 0u, n_col), "lag correction");
                         for(std::uint32_t f = 0; f < filled; ++f)
                         {
-                            auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * f);
-                            rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * his::pixel_size(infos[f].pixel), n_row, n_col,
-                                                               infos[f].pixel), "load()");
-                        }
-                        rt(paris_hip_lag_correct_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "lag correction");
-                        for(std::uint32_t f = 0; f < filled; ++f)
-                        {
-                            rt(paris_hip_memcpy_projection_d2h(ctx, h_buf[f], n_row * sizeof(float), reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_all) + d_stride * f),
-                                                               d_pitch, n_row, n_col), "copy_d2h()");
+                            rt(paris_hip_memcpy_projection_d2h(ctx, slots.host(f), n_row * sizeof(float), slots.frame(f), slots.pitch, n_row, n_col), "copy_d2h()");
                             infos[f].pixel = his::pixel_f32;
                         }
                         rt(paris_hip_ctx_synchronize(ctx), "synchronize");
@@ -2111,42 +2018,15 @@ namespace paris
                     for(std::uint32_t k = 0; k < degree; ++k)
                     {
                         for(std::uint32_t f = 0; f < filled; ++f)
-                        {
-                            auto* d_frame = reinterpret_cast<float*>(reinterpret_cast<char*>(d_all) + d_stride * f);
-                            const auto px = his::pixel_size(infos[f].pixel);
-                            if(po.lag) // the unfused route: the corrected counts, then the dark / flat correction as a pass of its own
-                            {
-                                rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, infos[f].pixel), "load()");
-                                rt(paris_hip_flat_field_rows(ctx, d_frame, d_pitch, 0u, 1u, n_row, n_col, 0u, n_col), "flat field");
-                            }
-                            else if(po.flat)
-                                rt(paris_hip_upload_projection_raw_corrected(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, 0u, n_col,
-                                                                             infos[f].pixel), "load()");
-                            else
-                                rt(paris_hip_upload_projection_raw(ctx, d_frame, d_pitch, h_buf[f], n_row * px, n_row, n_col, infos[f].pixel), "load()");
-                        }
-                        if(po.air)
-                            rt(paris_hip_air_normalize_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "air normalisation");
-                        if(repair)
-                            rt(paris_hip_defect_repair_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "defect repair");
-                        if(po.zingers)
-                            rt(paris_hip_zinger_filter_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "zinger filter");
-                        if(po.ring_c)
-                            rt(paris_hip_ring_correct_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "ring correction");
+                            chain.upload(f, infos[f].pixel, rows, true);
                         auto unit = paris_hip_beam_hardening{};
                         unit.degree = k + 1u;
                         unit.c[k] = 1.f;
-                        rt(paris_hip_beam_hardening_rows_with(ctx, &unit, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col), "beam hardening");
-                        if(po.offset_detector)
-                            rt(paris_hip_offset_detector_weight_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo),
-                               "offset-detector weight()");
-                        if(po.short_scan)
-                            rt(paris_hip_short_scan_weight_rows(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo, &po.scan,
-                                                                angles.data()), "short-scan weight()");
-                        rt(paris_hip_stage_weight_filter_batch(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, 0u, n_col, &po.det_geo, nullptr, 0u, 0u),
-                           "weight() + filter()");
-                        rt(paris_hip_backproject_batch(ctx, d_all, d_pitch, d_stride, filled, n_row, n_col, d_slab[k], vg.dim_x, vg.dim_y, slices, z_first,
-                                                       &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
+                        chain.clean(0u, filled, true, rows);
+                        chain.linearise(0u, filled, true, rows, &unit);
+                        chain.finish(0u, filled, true, rows, angles.data());
+                        rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, filled, n_row, n_col, fit.d_slab[k], vg.dim_x, vg.dim_y, slices,
+                                                       z_first, &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
                         rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the device frames are free for the next basis or group
                     }
                     frames += filled;
@@ -2157,26 +2037,20 @@ namespace paris
                     throw stage_runtime_error{"--fit-beam-hardening: the input holds no projection"};
                 const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
                 auto stats = paris_hip_volume_statistics{};
-                rt(paris_hip_volume_stats(ctx, d_slab[0], voxels, 0.f, 0.f, 0u, nullptr, &stats), "volume_stats()");
+                rt(paris_hip_volume_stats(ctx, fit.d_slab[0], voxels, 0.f, 0.f, 0u, nullptr, &stats), "volume_stats()");
                 auto hist = std::vector<std::uint64_t>(PARIS_HIP_BH_HISTOGRAM_BINS);
-                if(paris_hip_volume_stats(ctx, d_slab[0], voxels, stats.min, stats.max, PARIS_HIP_BH_HISTOGRAM_BINS, hist.data(), &stats) != PARIS_HIP_SUCCESS
+                if(paris_hip_volume_stats(ctx, fit.d_slab[0], voxels, stats.min, stats.max, PARIS_HIP_BH_HISTOGRAM_BINS, hist.data(), &stats) != PARIS_HIP_SUCCESS
                    || paris_hip_bh_threshold_from_histogram(hist.data(), PARIS_HIP_BH_HISTOGRAM_BINS, stats.min, stats.max, &r.bh_threshold) != PARIS_HIP_SUCCESS)
                     throw stage_runtime_error{"--fit-beam-hardening: the reconstruction of the scan has no range of values to take a threshold from"};
-                rt(paris_hip_bh_classify(ctx, d_slab[0], vg.dim_x, vg.dim_y, slices, r.bh_threshold, po.bh_margin, d_labels), "bh_classify()");
+                rt(paris_hip_bh_classify(ctx, fit.d_slab[0], vg.dim_x, vg.dim_y, slices, r.bh_threshold, po.bh_margin, fit.d_labels), "bh_classify()");
                 double gram[(PARIS_HIP_BH_DEGREE_MAX + 1) * (PARIS_HIP_BH_DEGREE_MAX + 2) / 2];
-                rt(paris_hip_bh_gram(ctx, d_slab, degree, d_labels, voxels, gram, &r.bh_counts), "bh_gram()");
+                rt(paris_hip_bh_gram(ctx, fit.d_slab, degree, fit.d_labels, voxels, gram, &r.bh_counts), "bh_gram()");
                 rt(paris_hip_bh_solve(gram, degree, &r.bh_counts, 0u, &r.bh_fit), "--fit-beam-hardening: bh_solve()");
                 r.bh_fitted = true;
                 r.bh_frames = frames;
                 r.bh_slice_first = z_first;
                 r.bh_slices = slices;
-            }
-            catch(...)
-            {
-                cleanup();
-                throw;
-            }
-            cleanup();
+            } // (the buffers and the ctx are gone: the time below includes that)
             r.bh_prepass_s = since(t_start);
         }
 

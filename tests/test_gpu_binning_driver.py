@@ -95,6 +95,16 @@ def test_bin_equals_the_driver_on_host_binned_inputs(tmp_path, scan, option, bin
         assert line and line == [l for l in plain.splitlines() if l.startswith("defect map on")]
 
 
+def test_bin_frame_by_frame(tmp_path, scan):
+    """--batch 1: every frame is binned, corrected and repaired on its own, behind its upload, against the reference of the test above,
+    which the driver makes group by group"""
+    prebinned(tmp_path / "binned", scan, 2, 2)
+    text, got = drive(scan[0], tmp_path / "bin", ["--bin", "2", "--slabs", 2, "--batch", 1])
+    _, want = drive(tmp_path / "binned", tmp_path / "pre", ["--slabs", 2])
+    assert "binning on: 2 x 2 bins" in text
+    assert np.abs(want).max() > 0 and np.array_equal(bits(got), bits(want))
+
+
 def test_the_later_passes_run_on_binned_frames(tmp_path, scan):
     """--zingers and --rings (whose pre-pass reads the scan once more) see binned frames: the same volume and the same counts as on
     host-binned inputs"""

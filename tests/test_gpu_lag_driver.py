@@ -114,6 +114,22 @@ def test_lag_on_binned_counts(tmp_path, scan):
     assert np.abs(want).max() > 0 and np.array_equal(bits(got), bits(want))
 
 
+@pytest.mark.parametrize("binned", [False, True])
+def test_lag_frame_by_frame(tmp_path, scan, binned):
+    """--batch 1: every frame goes through the chain on its own, behind its upload -- the lag route alone and the one behind --bin --,
+    against the references of the two tests above, which the driver makes group by group"""
+    src, frames, dark, flat = scan
+    if binned:
+        counts = np.stack([BR.bin_frame(f.astype(np.float32), 2, 2, None) for f in frames])
+        corrected_set(tmp_path / "fixed", counts, BR.bin_frame(dark, 2, 2, None), BR.bin_frame(flat, 2, 2, None), BR.binned_geometry(GEO, 2, 2))
+    else:
+        corrected_set(tmp_path / "fixed", frames, dark, flat, GEO)
+    text, got = drive(src, tmp_path / "lag", ["--lag", OPTION, "--slabs", 2, "--batch", 1] + (["--bin", "2"] if binned else []))
+    _, want = drive(tmp_path / "fixed", tmp_path / "plain", ["--slabs", 2])
+    assert "lag correction on" in text and ("binning on" in text) == binned
+    assert np.abs(want).max() > 0 and np.array_equal(bits(got), bits(want))
+
+
 def test_the_pre_passes_open_sequences_of_their_own(tmp_path, scan):
     """--rings reads the scan once more before the reconstruction, --fit-beam-hardening once again: each pass corrects the lag from
     frame 0, so the volume and the reports are those of the run on the corrected frames"""

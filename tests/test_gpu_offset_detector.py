@@ -373,7 +373,7 @@ def test_driver_and_cpp_mirror_against_the_python_mirror(tmp_path, oracle):
     want_off = mirror_volume(fr, False)
     assert H.rel_rms(want, want_off, 1.0) > 0.1                # the weight made a difference
     for k, extra in enumerate((["--slabs", 1], ["--slabs", 3], ["--slabs", 3, "--no-row-band"], ["--slabs", 1, "--batch", 1],
-                               ["--slabs", 3, "--batch", 5, "--no-read-ahead"])):
+                               ["--slabs", 3, "--batch", 5, "--no-read-ahead"], ["--slabs", 3, "--batch", 1, "--no-read-ahead"])):
         P.run(["--geometry", geo, "--input", d, "--output", tmp_path / ("o%d" % k), "--offset-detector"] + extra)
         _, vol = F.ddbvf_read(str(tmp_path / ("o%d" % k) / "vol.ddbvf"))
         assert np.array_equal(bits(vol), bits(want)), extra
