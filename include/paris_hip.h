@@ -44,6 +44,8 @@ extern "C" {
 #define PARIS_HIP_ERROR_BH_TOO_FEW_VOXELS 10004 /* fewer object or air voxels than the caller's minimum */
 #define PARIS_HIP_ERROR_BH_NOT_POSITIVE 10005   /* a Cholesky pivot of the normal equations is not positive */
 #define PARIS_HIP_ERROR_BH_NOT_FINITE 10006     /* a coefficient is not a finite float */
+/* what paris_hip_metal_collect may return beside those */
+#define PARIS_HIP_ERROR_METAL_TOO_MANY_VOXELS 10007 /* the threshold marks more voxels than the caller's cap */
 
 /* ctx flags */
 #define PARIS_HIP_CTX_DEFAULT 0u
@@ -1224,6 +1226,91 @@ int paris_hip_lag_correct_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, siz
                                uint32_t dim_y, uint32_t row_first, uint32_t row_count);
 /* The open sequence's frame counter (0 without one). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL argument. */
 int paris_hip_lag_frames(paris_hip_ctx* ctx, uint64_t* frames);
+/* Extension (no reference counterpart): metal artefact reduction by linear interpolation (LI-MAR; Kalender et al. 1987; DESIGN.md
+ * section 4.21). Metal drives its rays to the detector's floor; the ramp filter spreads that non-linearity as streaks. The remedy:
+ * reconstruct once, take the metal voxels out of the volume (1), forward-project their mask and mark where it casts a shadow -- the
+ * metal TRACE (2) --, replace the trace's pixels of every frame by linear interpolation along the row before the row filter (3),
+ * reconstruct again and put the metal voxels back (4). Each of the four has ONE definition; the host function and the device give
+ * the same bits.
+ * (1) collect: every voxel with v > threshold (a NaN compares false), in ascending linear index (z * dim_y + y) * dim_x + x, with its
+ *     value. With binarize != 0 the volume then becomes the mask: 1.0f where a voxel was reported, 0.0f elsewhere. More than max_n
+ *     hits: nothing is written, neither the lists nor the volume, *n still holds the count, PARIS_HIP_ERROR_METAL_TOO_MANY_VOXELS.
+ * (2) pack: pixel (x, y) of a frame is in the trace when any pixel (x', y') of that frame with |x' - x| <= grow and |y' - y| <= grow,
+ *     the window clipped to the frame, has t > min_path (a NaN compares false); grow in 0 .. PARIS_HIP_METAL_GROW_MAX. Layout:
+ *     words = (dim_x + 63) / 64 uint64_t per row, pixel x is bit x & 63 of word x >> 6, rows in order, frame f from word
+ *     f * dim_y * words; the bits at and beyond dim_x are 0.
+ * (3) inpaint: in every row of the band, for every maximal run [a, b] of set bits, with pL = p[a - 1] and pR = p[b + 1] as stored:
+ *       interior run:  t = (float)(x - (a - 1)) / (float)(b - a + 2)  (one fp32 division);  p[x] = fmaf(t, pR - pL, pL)
+ *       a = 0:  p[x] = pR;    b = dim_x - 1:  p[x] = pL;    both: the row is left as it is.
+ *     Anchors that are not finite propagate by this arithmetic (which payload a resulting NaN carries is left open). Pixels outside
+ *     the trace are not written. Counted: the pixels
+ *     replaced, the runs replaced, and the rows left because the trace covers them whole.
+ * (4) reinsert: every listed voxel whose index falls into a slab gets its listed value; nothing else is written.
+ * Order. The inpainting runs on line integrals on the ideal detector -- after the detector roll, before the redundancy and cosine
+ * weights. */
+#define PARIS_HIP_METAL_GROW_MAX 4
+#define PARIS_HIP_METAL_MIN_VOXELS_CAP 1024
+typedef struct paris_hip_metal_counts {
+    uint64_t replaced;  /* pixels replaced */
+    uint64_t runs;      /* runs replaced */
+    uint64_t rows_left; /* rows left as they were because the trace covers them whole */
+} paris_hip_metal_counts;
+/* Host only, no ctx and no device: the checks every entry point below shares, and the cap on the list a threshold may mark --
+ * *max_voxels (may be NULL) = max(PARIS_HIP_METAL_MIN_VOXELS_CAP, dim_x * dim_y * dim_z / 32): a threshold that marks more is a wrong
+ * threshold, not metal. PARIS_HIP_ERROR_INVALID_ARGUMENT for a zero dimension, a threshold that is not finite, grow >
+ * PARIS_HIP_METAL_GROW_MAX, or a min_path that is negative or not finite. */
+int paris_hip_metal_check(uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, float threshold, uint32_t grow, float min_path,
+                          uint64_t* max_voxels);
+/* Host only: (1) on a host volume. index and value receive up to max_n entries (either may be NULL when max_n == 0).
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL v or n, a zero dimension or a threshold that is not finite. */
+int paris_hip_metal_collect_host(float* v, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, float threshold, uint64_t max_n,
+                                 uint64_t* index, float* value, uint64_t* n, int binarize);
+/* (1) on a device volume, synchronous; what is deferred runs first. h_index and h_value are host arrays. The scratch -- a count per
+ * 4096 voxels, their exclusive scan and the lists -- lives in device memory the call allocates and frees. A binarized volume is
+ * treated as paris_hip_volume_mark_dirty treats a range. Errors as the host function's. */
+int paris_hip_metal_collect(paris_hip_ctx* ctx, float* d_v, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, float threshold, uint64_t max_n,
+                            uint64_t* h_index, float* h_value, uint64_t* n, int binarize);
+/* Host only: (2) on n_frames dense frames of dim_x x dim_y floats. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL pointer with work to do,
+ * grow > PARIS_HIP_METAL_GROW_MAX, or a min_path that is negative or not finite. */
+int paris_hip_metal_trace_pack_host(const float* t, uint32_t n_frames, uint32_t dim_x, uint32_t dim_y, float min_path, uint32_t grow,
+                                    uint64_t* bits);
+/* (2) on device frames frame_stride bytes apart with rows pitch bytes apart, synchronous: h_bits, a host array, receives
+ * n_frames * dim_y * words words. A held-back weighting runs first, and a frame of the pending by-reference group has that group
+ * launched first. The packed words pass through device memory the call allocates and frees. Errors as the host function's, or for
+ * a pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_metal_trace_pack(paris_hip_ctx* ctx, const float* d_t, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                               uint32_t dim_y, float min_path, uint32_t grow, uint64_t* h_bits);
+/* Host only: (3) on the rows [row_first, row_first + row_count) of one dense dim_x x dim_y frame, with the dim_y * words words of its
+ * trace; adds to *counts (may be NULL). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL p or bits with work to do or a band outside the
+ * frame. */
+int paris_hip_metal_inpaint_host(float* p, const uint64_t* bits, uint32_t dim_x, uint32_t dim_y, uint32_t row_first, uint32_t row_count,
+                                 paris_hip_metal_counts* counts);
+/* The traces of all n_views views of a scan on dim_x x dim_y frames, in the layout of (2), as a setting of the ctx: 64 bytes of
+ * counters, then n_views * dim_y * words words on the device, which count towards paris_hip_projection_reserve_bytes while set;
+ * paris_hip_ctx_destroy frees them. Replaces an earlier setting and its counts safely: work already queued keeps the old one.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL h_bits or a zero n_views or dimension. Without a setting nothing else changes. */
+int paris_hip_set_metal_trace(paris_hip_ctx* ctx, const uint64_t* h_bits, uint32_t n_views, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_metal_trace(paris_hip_ctx* ctx);
+/* (3) in place on float frames, asynchronous: the band's rows of n_frames frames frame_stride bytes apart, d_p the first frame's row
+ * 0; frame f is inpainted with the trace of view h_view[f] (a host array, read before the call returns). A row without a set bit
+ * costs the read of its words. The pass reads no row outside the band. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when
+ * dim_x / dim_y differ from the setting's, for a NULL h_view or an h_view[f] >= n_views, or for a band, pitch or stride
+ * paris_hip_flat_field_rows would refuse. */
+int paris_hip_metal_inpaint_rows(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                 uint32_t dim_y, uint32_t row_first, uint32_t row_count, const uint32_t* h_view);
+/* The counts since paris_hip_set_metal_trace or the last reset; waits for the work queued on the ctx stream that still adds to them
+ * and reads them; reset != 0 zeroes them afterwards. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting or for a NULL out. */
+int paris_hip_metal_stats(paris_hip_ctx* ctx, paris_hip_metal_counts* out, int reset);
+/* The list of (1) as a setting of the ctx: n indices, strictly ascending, and their values, copied to the device (12 bytes per
+ * voxel, counted towards paris_hip_projection_reserve_bytes while set) and, the indices, kept on the host. n == 0 is a setting
+ * without memory. PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL array with n != 0 or indices that do not ascend strictly. */
+int paris_hip_set_metal_voxels(paris_hip_ctx* ctx, const uint64_t* h_index, const float* h_value, uint64_t n);
+int paris_hip_clear_metal_voxels(paris_hip_ctx* ctx);
+/* (4), asynchronous: d_v holds slices [v_offset, v_offset + v_dim_z) of a grid of dim_x x dim_y voxels per slice; the slab's part of
+ * the list is found by bisection on the host. What is deferred into a volume runs first, as for paris_hip_volume_stats; a slab
+ * written into is treated as paris_hip_volume_mark_dirty treats a range. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, for a
+ * NULL d_v or a zero dim_x or dim_y. */
+int paris_hip_metal_reinsert(paris_hip_ctx* ctx, float* d_v, uint32_t dim_x, uint32_t dim_y, uint32_t v_dim_z, uint32_t v_offset);
 /* Extension (no reference counterpart): row extension for laterally truncated projections -- the object is wider than the detector,
  * "interior" or region-of-interest tomography. The row filter zero-pads every row, as the reference does;
  * a truncated row then steps from its edge value to 0 and the ramp answers with a bright rim and cupping. With a setting the filter

@@ -183,6 +183,18 @@ class LagModel(C.Structure):
     _fields_ = [("terms", C.c_uint32), ("b", C.c_float * LAG_TERMS_MAX), ("a", C.c_float * LAG_TERMS_MAX), ("start", C.c_int)]
 
 
+# what paris_hip_metal_collect refuses
+ERROR_METAL_TOO_MANY_VOXELS = 10007
+METAL_GROW_MAX = 4  # PARIS_HIP_METAL_GROW_MAX
+METAL_MIN_VOXELS_CAP = 1024  # PARIS_HIP_METAL_MIN_VOXELS_CAP
+METAL_COUNTER_BYTES = 64  # what the counters at the head of a metal trace setting occupy on the device
+
+
+class MetalCounts(C.Structure):
+    """paris_hip_metal_counts: what paris_hip_metal_stats reports (extension)"""
+    _fields_ = [("replaced", C.c_uint64), ("runs", C.c_uint64), ("rows_left", C.c_uint64)]
+
+
 class RowExtension(C.Structure):
     """paris_hip_row_extension: the row extension for truncated projections (extension)"""
     _fields_ = [("edge_pixels", C.c_uint32), ("taper_pixels", C.c_uint32)]
@@ -319,6 +331,19 @@ SIGNATURES = {
     "paris_hip_lag_end": (C.c_int, [_vp]),
     "paris_hip_lag_correct_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_lag_frames": (C.c_int, [_vp, _P(C.c_uint64)]),
+    "paris_hip_metal_check": (C.c_int, [_u32, _u32, _u32, _f, _u32, _f, _P(C.c_uint64)]),
+    "paris_hip_metal_collect_host": (C.c_int, [_vp, _u32, _u32, _u32, _f, C.c_uint64, _vp, _vp, _P(C.c_uint64), C.c_int]),
+    "paris_hip_metal_collect": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _f, C.c_uint64, _vp, _vp, _P(C.c_uint64), C.c_int]),
+    "paris_hip_metal_trace_pack_host": (C.c_int, [_vp, _u32, _u32, _u32, _f, _u32, _vp]),
+    "paris_hip_metal_trace_pack": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _f, _u32, _vp]),
+    "paris_hip_metal_inpaint_host": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _P(MetalCounts)]),
+    "paris_hip_set_metal_trace": (C.c_int, [_vp, _vp, _u32, _u32, _u32]),
+    "paris_hip_clear_metal_trace": (C.c_int, [_vp]),
+    "paris_hip_metal_inpaint_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "paris_hip_metal_stats": (C.c_int, [_vp, _P(MetalCounts), C.c_int]),
+    "paris_hip_set_metal_voxels": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "paris_hip_clear_metal_voxels": (C.c_int, [_vp]),
+    "paris_hip_metal_reinsert": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32]),
     "paris_hip_row_extension_check": (C.c_int, [_P(RowExtension), _u32]),
     "paris_hip_row_extension_response": (C.c_int, [_P(RowExtension), _u32, _f, _vp]),
     "paris_hip_set_row_extension": (C.c_int, [_vp, _P(RowExtension)]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BeamHardening, BhCounts, BhFit, LagModel, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -27,7 +27,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "BeamHardening", "BhCounts", "BhFit", "Labels", "BeamHardeningFit", "beam_hardening_check", "beam_hardening_host",
            "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve", "DetectorRoll", "RollSearch", "RollResult",
            "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs",
-           "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host"]
+           "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host", "MetalCounts", "MetalTrace", "metal_check",
+           "metal_collect_host", "metal_trace_pack_host", "metal_inpaint_host", "metal_words"]
 
 
 class Projection:
@@ -409,6 +410,86 @@ def lag_correct_host(terms, frames, dark=None, start="steady", state=None, start
                                                  st.ctypes.data if st.size else None, C.byref(flag), n_pixels, n_frames),
           "paris_hip_lag_correct_host")
     return f, st, bool(flag.value)
+
+
+def metal_words(dim_x):
+    """the uint64 words a packed trace holds per row of dim_x pixels"""
+    return (dim_x + 63) // 64
+
+
+def metal_check(dim_x, dim_y, dim_z, threshold, grow=0, min_path=0.0):
+    """Host only, no device (paris_hip_metal_check): raises ParisHipError for a zero dimension, a threshold that is not finite, grow > 4
+    or a min_path that is negative or not finite; returns the cap on the voxels a threshold may mark -- 1/32 of the grid, 1024 at
+    least."""
+    cap = C.c_uint64(0)
+    check(_lib.load().paris_hip_metal_check(dim_x, dim_y, dim_z, threshold, grow, min_path, C.byref(cap)), "paris_hip_metal_check")
+    return int(cap.value)
+
+
+def metal_collect_host(v, threshold, max_n=None, binarize=False):
+    """Host only, no device (paris_hip_metal_collect_host): (index uint64[n], value float32[n], mask) of the voxels of the 3-D array v
+    (dim_z, dim_y, dim_x; taken as float32) above threshold, in ascending linear index; mask is the binarized copy of v with
+    binarize, else None. v is not written. max_n None: the cap of metal_check(). More than max_n hits raise ParisHipError with the
+    status ERROR_METAL_TOO_MANY_VOXELS and the count as .n."""
+    a = np.array(v, np.float32, order="C")
+    if a.ndim != 3:
+        raise ValueError("metal_collect_host: the volume must be a 3-D array (dim_z, dim_y, dim_x)")
+    dz, dy, dx = a.shape
+    cap = metal_check(dx, dy, dz, threshold) if max_n is None else int(max_n)
+    room = min(cap, a.size)
+    index, value, n = np.empty(room, np.uint64), np.empty(room, np.float32), C.c_uint64(0)
+    status = _lib.load().paris_hip_metal_collect_host(a.ctypes.data, dx, dy, dz, threshold, room, index.ctypes.data if room else None,
+                                                      value.ctypes.data if room else None, C.byref(n), 1 if binarize else 0)
+    if status == _lib.SUCCESS and n.value > cap:
+        status = _lib.ERROR_METAL_TOO_MANY_VOXELS
+    _metal_collect_check(status, n.value, "paris_hip_metal_collect_host")
+    return index[:n.value].copy(), value[:n.value].copy(), (a if binarize else None)
+
+
+def _metal_collect_check(status, n, what):
+    if status == _lib.ERROR_METAL_TOO_MANY_VOXELS:
+        e = ParisHipError(status, what)
+        e.n = int(n)
+        raise e
+    check(status, what)
+
+
+def metal_trace_pack_host(t, min_path, grow=0):
+    """Host only, no device (paris_hip_metal_trace_pack_host): the packed trace uint64[(n_frames, dim_y, words)] of the frames t
+    (n_frames, dim_y, dim_x; a 2-D array is one frame), taken as float32: a pixel is in it when any pixel of its frame at most grow
+    away in x and in y is above min_path."""
+    a = np.ascontiguousarray(t, np.float32)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("metal_trace_pack_host: the frames must be a 2-D or 3-D array")
+    n, dy, dx = a.shape
+    bits = np.zeros((n, dy, metal_words(dx)), np.uint64)
+    check(_lib.load().paris_hip_metal_trace_pack_host(a.ctypes.data if a.size else None, n, dx, dy, min_path, grow,
+                                                      bits.ctypes.data if bits.size else None), "paris_hip_metal_trace_pack_host")
+    return bits
+
+
+def metal_inpaint_host(p, bits, row_first=0, row_count=None):
+    """Host only, no device (paris_hip_metal_inpaint_host): (the inpainted copy of the 2-D float32 frame p, MetalCounts) for the
+    trace bits uint64[(dim_y, words)] and the rows [row_first, row_first + row_count) -- None: to the last row."""
+    a = np.array(p, np.float32, order="C")
+    b = np.ascontiguousarray(bits, np.uint64)
+    if a.ndim != 2 or b.shape != (a.shape[0], metal_words(a.shape[1])):
+        raise ValueError("metal_inpaint_host: the trace does not belong to this frame")
+    count = a.shape[0] - row_first if row_count is None else row_count
+    st = MetalCounts()
+    check(_lib.load().paris_hip_metal_inpaint_host(a.ctypes.data if a.size else None, b.ctypes.data if b.size else None, a.shape[1], a.shape[0],
+                                                   row_first, count, C.byref(st)), "paris_hip_metal_inpaint_host")
+    return a, st
+
+
+class MetalTrace:
+    """What Backend.reduce_metal returns: index / value -- the metal voxels of the first reconstruction, as metal_collect_host lists
+    them --, bits -- the packed traces uint64[(n_views, dim_y, words)] --, trace_pixels -- the set bits --, threshold, grow, min_path."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
 
 
 def bh_threshold_from_histogram(hist, h_lo, h_hi):
@@ -1151,6 +1232,132 @@ class Backend:
         n = C.c_uint64(0)
         check(self._L.paris_hip_lag_frames(self._ctx, C.byref(n)), "paris_hip_lag_frames")
         return int(n.value)
+
+    # ---- metal artefact reduction ---------------------------------------------------
+    metal_check = staticmethod(metal_check)
+    metal_collect_host = staticmethod(metal_collect_host)
+    metal_trace_pack_host = staticmethod(metal_trace_pack_host)
+    metal_inpaint_host = staticmethod(metal_inpaint_host)
+
+    def metal_collect(self, v, threshold, max_n=None, binarize=False):
+        """paris_hip_metal_collect of the device volume v: (index uint64[n], value float32[n]) of the voxels above threshold in
+        ascending linear index -- bit for bit metal_collect_host(). binarize: v then holds 1.0 where a voxel was listed and 0.0
+        elsewhere. max_n None: the cap of metal_check(). More than max_n hits raise ParisHipError with the status
+        ERROR_METAL_TOO_MANY_VOXELS and the count as .n; v is then as it was. Runs what is deferred first and waits."""
+        cap = metal_check(v.dim_x, v.dim_y, v.dim_z, threshold) if max_n is None else int(max_n)
+        room = min(cap, v.dim_x * v.dim_y * v.dim_z)
+        index, value, n = np.empty(room, np.uint64), np.empty(room, np.float32), C.c_uint64(0)
+        status = self._L.paris_hip_metal_collect(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z, threshold, room,
+                                                 index.ctypes.data if room else None, value.ctypes.data if room else None, C.byref(n),
+                                                 1 if binarize else 0)
+        _metal_collect_check(status, n.value, "paris_hip_metal_collect")
+        return index[:n.value].copy(), value[:n.value].copy()
+
+    def metal_trace_pack(self, p, min_path, grow=0, frame_stride=0, n_frames=1):
+        """paris_hip_metal_trace_pack of n_frames device frames frame_stride bytes apart starting at p: the packed trace
+        uint64[(n_frames, dim_y, words)] -- bit for bit metal_trace_pack_host(). Waits for the result."""
+        bits = np.zeros((n_frames, p.dim_y, metal_words(p.dim_x)), np.uint64)
+        check(self._L.paris_hip_metal_trace_pack(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, min_path, grow,
+                                                 bits.ctypes.data if bits.size else None), "paris_hip_metal_trace_pack")
+        return bits
+
+    def set_metal_trace(self, bits, dim_x):
+        """paris_hip_set_metal_trace: bits uint64[(n_views, dim_y, words)] are the packed traces of every view of a scan on frames of
+        dim_x x dim_y pixels; metal_inpaint() reads them on the device. Replaces an earlier setting and its counts safely."""
+        b = np.ascontiguousarray(bits, np.uint64)
+        if b.ndim != 3 or b.shape[2] != metal_words(dim_x):
+            raise ValueError("set_metal_trace: bits must be (n_views, dim_y, words) for rows of dim_x pixels")
+        check(self._L.paris_hip_set_metal_trace(self._ctx, b.ctypes.data if b.size else None, b.shape[0], dim_x, b.shape[1]),
+              "paris_hip_set_metal_trace")
+
+    def clear_metal_trace(self):
+        """paris_hip_clear_metal_trace: no trace from here on; metal_inpaint() refuses"""
+        check(self._L.paris_hip_clear_metal_trace(self._ctx), "paris_hip_clear_metal_trace")
+
+    def metal_inpaint(self, p, view=None, row_first=0, row_count=None, frame_stride=0, n_frames=1):
+        """The inpainting of set_metal_trace() in place on float frames (paris_hip_metal_inpaint_rows): in rows [row_first, row_first +
+        row_count) of n_frames frames frame_stride bytes apart starting at p every run of the trace is replaced by the linear
+        interpolation between the pixels beside it. view: the trace of each frame -- a number or a sequence; None: p.idx. Call it on
+        line integrals after the detector roll, before every weight."""
+        count = p.dim_y - row_first if row_count is None else row_count
+        views = np.atleast_1d(np.asarray(p.idx if view is None else view, np.int64))
+        if views.ndim != 1 or len(views) != n_frames or (views < 0).any() or (views > 0xffffffff).any():
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_metal_inpaint_rows")
+        h = views.astype(np.uint32)
+        check(self._L.paris_hip_metal_inpaint_rows(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y, row_first, count,
+                                                   h.ctypes.data if n_frames else None), "paris_hip_metal_inpaint_rows")
+
+    def metal_stats(self, reset=False):
+        """The MetalCounts since set_metal_trace() or the last reset (paris_hip_metal_stats): replaced, runs, rows_left. Waits for the
+        ctx stream."""
+        st = MetalCounts()
+        check(self._L.paris_hip_metal_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_metal_stats")
+        return st
+
+    def set_metal_voxels(self, index, value):
+        """paris_hip_set_metal_voxels: the list of metal_collect() -- strictly ascending indices and their values -- for
+        metal_reinsert()"""
+        i, x = np.ascontiguousarray(index, np.uint64), np.ascontiguousarray(value, np.float32)
+        if i.ndim != 1 or i.shape != x.shape:
+            raise ValueError("set_metal_voxels: index and value must be 1-D arrays of one length")
+        check(self._L.paris_hip_set_metal_voxels(self._ctx, i.ctypes.data if i.size else None, x.ctypes.data if x.size else None, i.size),
+              "paris_hip_set_metal_voxels")
+
+    def clear_metal_voxels(self):
+        """paris_hip_clear_metal_voxels: no list from here on; metal_reinsert() refuses"""
+        check(self._L.paris_hip_clear_metal_voxels(self._ctx), "paris_hip_clear_metal_voxels")
+
+    def metal_reinsert(self, v, v_offset=0, dim_x=None, dim_y=None):
+        """paris_hip_metal_reinsert: the listed voxels that fall into the device slab v -- slices [v_offset, v_offset + v.dim_z) of a
+        grid with v.dim_x x v.dim_y voxels per slice -- get their listed values. Runs what is deferred first; does not wait."""
+        check(self._L.paris_hip_metal_reinsert(self._ctx, v.ptr, v.dim_x if dim_x is None else dim_x, v.dim_y if dim_y is None else dim_y,
+                                               v.dim_z, v_offset), "paris_hip_metal_reinsert")
+
+    def reduce_metal(self, frames, det_geo, threshold, grow=1, min_path=None, prepare=None, vol_geo=None, enable_angles=False, angles=None):
+        """Linear-interpolation metal artefact reduction, the part before the second reconstruction. frames: the scan's line
+        integrals, one 2-D float32 array (n_col, n_row) per view, in view order. They are reconstructed once -- upload,
+        prepare(backend, projection) if given (the redundancy weights of a short or offset scan), weight, filter, backprojection --
+        into the whole grid vol_geo (None: the natural volume of det_geo); the voxels above threshold (in the volume's own units) are
+        collected and the volume binarized; the mask is forward-projected view by view and each projection packed with min_path (mm;
+        None: half the smallest voxel edge) and grow; the traces are installed with set_metal_trace() and the list with
+        set_metal_voxels(). Returns a MetalTrace. The caller's loop then calls metal_inpaint(p, view) before weight() and
+        metal_reinsert() on the finished volume. Every device buffer made here is freed before the call returns; raises
+        ParisHipError where the library refuses."""
+        vg = vol_geo if vol_geo is not None else calculate_volume_geometry(det_geo)
+        path = 0.5 * min(vg.l_vx_x, vg.l_vx_y, vg.l_vx_z) if min_path is None else min_path
+        metal_check(vg.dim_x, vg.dim_y, vg.dim_z, threshold, grow, path)
+        vol, d_p = self.make_volume_device(vg.dim_x, vg.dim_y, vg.dim_z), None
+        try:
+            self.memset_volume(vol)
+            n_views = 0
+            for i, frame in enumerate(frames):
+                f = np.ascontiguousarray(frame, np.float32)
+                d_p = load(self, Projection(f, det_geo.n_row, det_geo.n_col, idx=i, phi=0.0 if angles is None else float(angles[i])))
+                if prepare is not None:
+                    prepare(self, d_p)
+                weight(self, d_p, det_geo)
+                filter(self, d_p, det_geo)
+                backproject(self, d_p, vol, 0, det_geo, vg, enable_angles, False, None)
+                self.free(d_p)
+                d_p = None
+                n_views += 1
+            index, value = self.metal_collect(vol, threshold, binarize=True)
+            bits = np.zeros((n_views, det_geo.n_col, metal_words(det_geo.n_row)), np.uint64)
+            d_p = self.make_projection_device(det_geo.n_row, det_geo.n_col)
+            for i in range(n_views):
+                d_p.idx, d_p.phi = i, 0.0 if angles is None else float(angles[i])
+                forward_project(self, vol, 0, d_p, det_geo, vg, enable_angles)
+                bits[i] = self.metal_trace_pack(d_p, path, grow)[0]
+            self.set_metal_trace(bits, det_geo.n_row)
+            self.set_metal_voxels(index, value)
+            pixels = int(sum(bin(int(w)).count("1") for w in bits.ravel()[np.flatnonzero(bits.ravel())]))
+            return MetalTrace(index=index, value=value, bits=bits, trace_pixels=pixels, threshold=threshold, grow=grow, min_path=path)
+        finally:
+            self.flush()
+            self.synchronize()
+            if d_p is not None:
+                self.free(d_p)
+            self.free(vol)
 
     def make_labels_device(self, dim_x, dim_y, dim_z):
         """one byte per voxel of a slab, uninitialised; free() takes it"""

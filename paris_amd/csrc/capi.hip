@@ -119,6 +119,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_beam_hardening();
             paris_hip_warm_detector_roll();
             paris_hip_warm_lag();
+            paris_hip_warm_metal();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes
@@ -1530,6 +1531,7 @@ extern "C" const char* paris_hip_strerror(int status)
         case PARIS_HIP_ERROR_BH_TOO_FEW_VOXELS: return "paris_hip: beam-hardening fit: too few object or air voxels were labelled";
         case PARIS_HIP_ERROR_BH_NOT_POSITIVE: return "paris_hip: beam-hardening fit: the normal equations are not positive definite";
         case PARIS_HIP_ERROR_BH_NOT_FINITE: return "paris_hip: beam-hardening fit: a coefficient is not finite";
+        case PARIS_HIP_ERROR_METAL_TOO_MANY_VOXELS: return "paris_hip: metal: the threshold marks more voxels than the cap";
         default: return hipGetErrorString(static_cast<hipError_t>(status));
     }
 }

@@ -239,6 +239,22 @@ struct paris_hip_ctx
             uint64_t frames = 0;
         } seq;
     } lag;
+    // Metal trace (paris_hip_set_metal_trace): PARIS_HIP_METAL_COUNTER_BYTES of counters -- replaced, runs,
+    // rows_left, 64-bit each, zeroed at install --, then the packed traces of all views.
+    struct metal_trace_t
+    {
+        bool set = false;
+        paris_hip_device_buffer mem;
+        uint32_t n_views = 0, dim_x = 0, dim_y = 0, words = 0;
+    } metal_trace;
+    // Metal voxels (paris_hip_set_metal_voxels): n 64-bit indices, ascending, then their n values; the indices on the host as well,
+    // for the bisection per slab. An empty list has no buffer (mem.d == nullptr while set).
+    struct metal_voxels_t
+    {
+        bool set = false;
+        paris_hip_device_buffer mem;
+        std::vector<uint64_t> index;
+    } metal_voxels;
     // Row extension (paris_hip_set_row_extension): the rule, and the responses c made so far, one buffer per (dim_x, tau bits, W) --
     // the second stream reads them too, behind a join.
     struct row_extension_t
@@ -262,7 +278,7 @@ struct paris_hip_ctx
     void each_setting(F&& f)
     {
         f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
-        f(row_extension), f(volume_window);
+        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels);
     }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
@@ -560,6 +576,7 @@ void paris_hip_warm_air_region();
 void paris_hip_warm_beam_hardening();
 void paris_hip_warm_detector_roll();
 void paris_hip_warm_lag();
+void paris_hip_warm_metal();
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the
@@ -634,6 +651,9 @@ inline paris_hip_roll_layout paris_hip_roll_layout_of(uint32_t n_row, uint32_t n
     l.bytes = l.total_of + pad(static_cast<size_t>(count) * 24u);
     return l;
 }
+
+// what the counters at the head of paris_hip_ctx::metal_trace_t::mem occupy (metal.hip)
+constexpr size_t PARIS_HIP_METAL_COUNTER_BYTES = 64u;
 
 // Where the pieces of an air region's one allocation lie (air_region.hip); air_rule.cpp reports the total. The counters: four 64-bit
 // counts (frames, normalised, too_few, above_limit), then the smallest and the largest value as ordered 32-bit keys, padded to 64 bytes.

@@ -11,6 +11,7 @@
 //             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]
 //             [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]
 //             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
+//             [--metal THR[:GROW[:MIN_PATH]]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -91,6 +92,7 @@ int main(int argc, char** argv)
                             "          [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]\n"
                             "          [--detector-roll DEG | --find-roll LO:HI[:STEP] [--roll-only]]\n"
                             "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
+                            "          [--metal THR[:GROW[:MIN_PATH]]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -158,7 +160,14 @@ int main(int argc, char** argv)
                             "files, after the upload (and --bin) and before the dark / flat correction; each pass over the scan starts from frame 0.\n"
                             "--lag-start steady (the default): the beam was on and the first view had been seen for a long time; rest: the detector\n"
                             "had seen nothing. Needs --flat (the frames must be counts); not with --quality above 1 (the skipped frames still fed\n"
-                            "the detector's memory).\n");
+                            "the detector's memory).\n"
+                            "--metal: metal (a screw, a pin, a filling) drives its rays to the detector's floor and the ramp filter spreads the\n"
+                            "error as streaks. A pre-pass on the first device, after every other pre-pass, reconstructs the whole volume once,\n"
+                            "takes the voxels above THR [the volume's own units] out of it, forward-projects their mask and marks every pixel\n"
+                            "whose ray crosses more than MIN_PATH mm of it [default: half the smallest voxel edge], widened by GROW pixels [0 .. 4,\n"
+                            "default 1]. In the reconstruction those pixels of every frame are replaced by linear interpolation along the row,\n"
+                            "after the roll and before the weights, and every slab gets its metal voxels back. The pre-pass needs the whole\n"
+                            "volume on one device. Not with --roi.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -200,6 +209,7 @@ int main(int argc, char** argv)
             else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
             else if(k == "--lag") paris::detail::parse_lag(val(), po);
             else if(k == "--lag-start") paris::detail::parse_lag_start(val(), po);
+            else if(k == "--metal") paris::detail::parse_metal(val(), po);
             else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
             else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
@@ -320,6 +330,13 @@ int main(int argc, char** argv)
                 std::printf("%s%.9g", k == 0u ? " " : ":", static_cast<double>(r.bh.c[k]));
             std::printf("\n");
         }
+        if(r.metal)
+            std::printf("metal reduction on: %llu voxel(s) above %.9g collected, grow %u, min_path %.9g mm, %llu trace pixel(s) over all views, "
+                        "%u frame(s) in the pre-pass (%.3f s), %llu pixel(s) replaced in %llu run(s) and %llu row(s) left in the main pass\n",
+                        static_cast<unsigned long long>(r.metal_voxels), static_cast<double>(r.metal_threshold), r.metal_grow,
+                        static_cast<double>(r.metal_min_path), static_cast<unsigned long long>(r.metal_trace_pixels), r.metal_frames, r.metal_prepass_s,
+                        static_cast<unsigned long long>(r.metal_counts.replaced), static_cast<unsigned long long>(r.metal_counts.runs),
+                        static_cast<unsigned long long>(r.metal_counts.rows_left));
         if(r.voxel_type != 0)
             std::printf("%llu voxel(s) written as %s over [%.9g, %.9g]: %llu below, %llu above, %llu not finite\n",
                         static_cast<unsigned long long>(r.voxels.voxels), r.voxel_type == PARIS_HIP_VOXEL_U8 ? "u8" : "u16", static_cast<double>(r.voxel_lo),

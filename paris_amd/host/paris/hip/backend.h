@@ -133,6 +133,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
                 std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
                 std::set<const paris_hip_ctx*> detector_rolls; // set_detector_roll(), per device of this thread
+                std::set<const paris_hip_ctx*> metal_traces;   // set_metal_trace(), per device of this thread
             };
 
             inline auto state() -> thread_state&
@@ -619,6 +620,57 @@ namespace paris
         inline auto lag_end() -> void
         {
             detail::runtime_check(paris_hip_lag_end(current_ctx()), "lag_end()");
+        }
+
+        // Extension (no reference counterpart): metal artefact reduction by linear interpolation. bits holds
+        // the packed traces of all n_views views of the scan on n_row x n_col frames (paris_hip_metal_trace_pack's layout). Until
+        // clear_metal_trace(), paris::weight() replaces the trace's pixels of every frame -- the trace of view p.idx -- by linear
+        // interpolation along the row, after the detector roll and before the redundancy and cosine weights
+        // (paris_hip_metal_inpaint_rows). Off unless called.
+        inline auto set_metal_trace(const std::uint64_t* bits, std::uint32_t n_views, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_set_metal_trace(current_ctx(), bits, n_views, n_row, n_col), "set_metal_trace()");
+            detail::state().metal_traces.insert(current_ctx());
+        }
+
+        inline auto clear_metal_trace() -> void
+        {
+            detail::runtime_check(paris_hip_clear_metal_trace(current_ctx()), "clear_metal_trace()");
+            detail::state().metal_traces.erase(current_ctx());
+        }
+
+        namespace detail
+        {
+            inline auto has_metal_trace(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().metal_traces;
+                return s.find(ctx) != s.end();
+            }
+        }
+
+        // the rows [row_first, row_first + row_count) of one n_row x n_col frame of line integrals at d_p, with the trace of `view`
+        inline auto metal_inpaint(float* d_p, std::size_t pitch, std::uint32_t n_row, std::uint32_t n_col, std::uint32_t row_first, std::uint32_t row_count,
+                                  std::uint32_t view) -> void
+        {
+            detail::runtime_check(paris_hip_metal_inpaint_rows(current_ctx(), d_p, pitch, 0u, 1u, n_row, n_col, row_first, row_count, &view), "metal_inpaint()");
+        }
+
+        // the metal voxels of the first reconstruction (paris_hip_metal_collect's list: n strictly ascending indices and their values),
+        // which metal_reinsert() puts back into a finished slab: slices [v_offset, v_offset + v_dim_z) of a grid of dim_x x dim_y
+        // voxels per slice
+        inline auto set_metal_voxels(const std::uint64_t* index, const float* value, std::uint64_t n) -> void
+        {
+            detail::runtime_check(paris_hip_set_metal_voxels(current_ctx(), index, value, n), "set_metal_voxels()");
+        }
+
+        inline auto clear_metal_voxels() -> void
+        {
+            detail::runtime_check(paris_hip_clear_metal_voxels(current_ctx()), "clear_metal_voxels()");
+        }
+
+        inline auto metal_reinsert(float* d_v, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t v_dim_z, std::uint32_t v_offset) -> void
+        {
+            detail::runtime_check(paris_hip_metal_reinsert(current_ctx(), d_v, dim_x, dim_y, v_dim_z, v_offset), "metal_reinsert()");
         }
 
         // ---- buffers ------------------------------------------------------------------------------------------

@@ -176,6 +176,19 @@ namespace paris
         // binning) and the dark / flat correction, which then runs as a pass of its own, and closes the sequence after the last frame
         bool lag = false, lag_start_given = false;
         paris_hip_lag_model lag_model{0u, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, PARIS_HIP_LAG_START_STEADY};
+        // metal artefact reduction by linear interpolation (extension): --metal THR[:GROW[:MIN_PATH]] -- THR in
+        // the volume's own units, GROW pixels the trace is widened by (default 1), MIN_PATH [mm] of metal a ray must cross (default:
+        // half the smallest voxel edge) -- checked by run() before any device work (detail::check_metal). run() then reconstructs the
+        // scan once on the first device (detail::metal_prepass, after every other pre-pass, with their results in force), collects
+        // the voxels above THR, forward-projects their mask and packs the traces. Every device ctx gets the traces and the list; each
+        // frame is inpainted after the roll and before the redundancy weights, and each slab gets its metal voxels back at its end
+        bool metal = false;
+        float metal_threshold = 0.f, metal_min_path = -1.f;     // min_path < 0: not given; run() resolves it from the voxel size
+        std::uint32_t metal_grow = 1;
+        std::uint32_t metal_views = 0;                          // filled by run(): the views the traces cover
+        std::shared_ptr<const std::vector<std::uint64_t>> metal_bits, metal_index; // filled by run(): the packed traces; the list's indices
+        std::shared_ptr<const std::vector<float>> metal_value;  // filled by run(): the list's values
+        std::size_t metal_bytes = 0;                            // filled by run(): what both settings occupy on a device
         // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
         // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
         // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
@@ -310,6 +323,7 @@ namespace paris
         bool air_region = false; // --air-region: the setting was made; its counts over this device's tasks:
         paris_hip_air_counts air{};
         bool row_extension = false; // --extend-rows: the setting was made on this device's ctx
+        paris_hip_metal_counts metal{}; // --metal: the inpainting's counts over this device's tasks
         paris_hip_volume_counts voxels{}; // --voxel-type: the counts of this device's drain ctx
         std::vector<std::string> skipped;
     };
@@ -419,6 +433,11 @@ namespace paris
                 rt(paris_hip_set_row_extension(ctx, &setting), "set_row_extension()");
                 rep.row_extension = true;
             }
+            if(po.metal_bits) // (the metal pre-pass itself runs before there are any)
+            {
+                rt(paris_hip_set_metal_trace(ctx, po.metal_bits->data(), po.metal_views, po.det_geo.n_row, po.det_geo.n_col), "set_metal_trace()");
+                rt(paris_hip_set_metal_voxels(ctx, po.metal_index->data(), po.metal_value->data(), po.metal_index->size()), "set_metal_voxels()");
+            }
             rt(paris_hip_set_filter_window(ctx, po.window), "filter window");
         }
 
@@ -449,7 +468,7 @@ namespace paris
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
             // with --lag, the state of a whole-detector sequence at most
             const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
-            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -638,7 +657,9 @@ namespace paris
             // then :102-103 in one launch: the weight rides along in the row filter's load, and with half frames the filtered band is
             // stored as IEEE half straight into them. One frame goes through the entry point for a frame, a group -- of one frame
             // too -- through the one for a batch.
-            void finish(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles) const
+            // With --metal the trace's pixels are inpainted between the two, on the ideal detector the roll writes (views: the trace
+            // of each frame).
+            void finish(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles, const std::uint32_t* views = nullptr) const
             {
                 const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
                 const auto stride = grouped ? slots.stride : 0u;
@@ -647,6 +668,8 @@ namespace paris
                 if(po.roll)
                     rt(paris_hip_detector_roll_rows(ctx, slots.frame(first), slots.pitch, stride, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count),
                        "detector roll");
+                if(po.metal_bits)
+                    rt(paris_hip_metal_inpaint_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count, views), "metal inpainting");
                 if(po.offset_detector)
                     rt(paris_hip_offset_detector_weight_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, out.first, out.count, &po.det_geo),
                        "offset-detector weight()");
@@ -661,11 +684,11 @@ namespace paris
                                                           slots.half_pitch), "weight() + filter()");
             }
 
-            void run(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles) const
+            void run(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const float* angles, const std::uint32_t* views = nullptr) const
             {
                 clean(first, n, grouped, rows);
                 linearise(first, n, grouped, rows);
-                finish(first, n, grouped, rows, angles);
+                finish(first, n, grouped, rows, angles, views);
             }
         };
     }
@@ -1093,6 +1116,7 @@ namespace paris
             auto feed = std::unique_ptr<frame_feed>{};
             auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch);
             auto angles = std::vector<float>(batch); // --short-scan: each frame's angle [deg], resolved as paris_hip_stage_angle does
+            auto views = std::vector<std::uint32_t>(batch); // --metal: each frame's trace, its index in the scan after the quality stride
             const float delta_s = t.det_geo.delta_s * t.det_geo.l_px_row, delta_t = t.det_geo.delta_t * t.det_geo.l_px_col; // src/backprojection.cpp:49-50
             // frames of up to 1024 x 1024 are weighted and filtered group by group (one launch for up to `batch` frames when the
             // group is flushed) instead of frame by frame behind each upload: their launches are mostly latency
@@ -1102,7 +1126,7 @@ namespace paris
                     return;
                 const auto t1 = clock::now();
                 if(filter_by_group && rows.band.count != 0) // the chain for the group: one call per pass
-                    chain.run(group * batch, filled, true, rows, angles.data());
+                    chain.run(group * batch, filled, true, rows, angles.data(), views.data());
                 if(po.f16)
                     rt(paris_hip_backproject_batch_f16(ctx, slots.half(group * batch), slots.half_pitch, slots.half_stride, filled, n_row, n_col, d_v,
                                                        t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset, &t.det_geo, &t.vol_geo, t.enable_roi, &t.roi,
@@ -1154,9 +1178,10 @@ namespace paris
                     chain.upload(slot, p.pixel, rows);
                     rep.h2d_bytes += static_cast<std::uint64_t>(rows.src.count) * sn_row * his::pixel_size(p.pixel);
                     angles[filled] = t.enable_angles ? p.phi : static_cast<float>(p.idx) * t.det_geo.delta_phi; // src/backprojection.cpp:52-57
+                    views[filled] = p.idx / std::max<std::uint32_t>(1u, t.quality);
                     // (small frames: the whole group by one call per pass when it is flushed -- a launch per 512^2 frame is mostly latency)
                     if(!filter_by_group)
-                        chain.run(slot, 1u, false, rows, &angles[filled]);
+                        chain.run(slot, 1u, false, rows, &angles[filled], &views[filled]);
                 }
                 rt(paris_hip_stage_angle(&t.det_geo, p.idx, t.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle"); // src/backprojection.cpp:52-63
                 rep.enqueue_s += since(t0);
@@ -1175,6 +1200,8 @@ namespace paris
             for(const auto& s : (shared ? cur.skipped_files() : own->skipped_files())) // the shared source's list: run_report
                 rep.skipped.push_back(s);
 
+            if(po.metal_index) // the slab's last backprojection is queued: its metal voxels go back, ahead of the fence the drain waits for
+                rt(paris_hip_metal_reinsert(ctx, d_v, t.subvol_geo.dim_x, t.subvol_geo.dim_y, dim_z, offset), "metal reinsertion");
             // src/sink.cpp:76-82: the slab is complete behind this fence; the drain thread takes it from there
             rt(paris_hip_fence_record(ctx, slab.done[b]), "fence record");
             auto j = volume_drain::job{};
@@ -1195,6 +1222,8 @@ namespace paris
             rt(paris_hip_zinger_stats(ctx, &rep.zingers, 0), "zinger stats");
         if(po.air)
             rt(paris_hip_air_stats(ctx, &rep.air, 0), "air stats");
+        if(po.metal_bits)
+            rt(paris_hip_metal_stats(ctx, &rep.metal, 0), "metal stats");
         rep.drain_s = drain.drain_seconds();
         rep.save_s = drain.save_seconds();
         rep.voxels = drain.voxel_counts();
@@ -1238,6 +1267,12 @@ namespace paris
         float bh_threshold = 0.f;
         std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
         double bh_prepass_s = 0;
+        bool metal = false;                             // --metal: the pre-pass ran; what it found, and the main pass's counts over all devices
+        float metal_threshold = 0.f, metal_min_path = 0.f;
+        std::uint32_t metal_grow = 0, metal_frames = 0;
+        std::uint64_t metal_voxels = 0, metal_trace_pixels = 0;
+        paris_hip_metal_counts metal_counts{};
+        double metal_prepass_s = 0;
         bool detector_roll = false;                     // --detector-roll / --find-roll: every frame was resampled by roll_deg;
         float roll_deg = 0.f;                           // with the search: the estimate and its costs' summary, the frames of its
         bool roll_search = false;                       // pre-pass, the candidates, and how long the pre-pass took (reading the
@@ -2054,6 +2089,202 @@ namespace paris
             r.bh_prepass_s = since(t_start);
         }
 
+        // --metal THR[:GROW[:MIN_PATH]] as typed; refuses anything but one to three numbers (the ranges: check_metal)
+        inline auto parse_metal(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: cannot read '" + v + "'"}; };
+            auto field = std::vector<std::string>{};
+            for(std::size_t at = 0;;)
+            {
+                const auto colon = v.find(':', at);
+                field.push_back(v.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
+                if(colon == std::string::npos)
+                    break;
+                at = colon + 1u;
+            }
+            if(field.size() > 3u)
+                throw bad();
+            const auto number = [&bad](const std::string& t) -> float {
+                if(t.empty())
+                    throw bad();
+                char* end = nullptr;
+                const float x = std::strtof(t.c_str(), &end);
+                if(end == nullptr || *end != '\0')
+                    throw bad();
+                return x;
+            };
+            po.metal_threshold = number(field[0]);
+            if(field.size() > 1u)
+            {
+                const float g = number(field[1]);
+                if(!(g >= 0.f) || g != std::floor(g) || g > 1e6f)
+                    throw bad();
+                po.metal_grow = static_cast<std::uint32_t>(g);
+            }
+            if(field.size() > 2u)
+            {
+                po.metal_min_path = number(field[2]);
+                if(!(po.metal_min_path >= 0.f)) // (a negative or NaN MIN_PATH must not pass for "not given")
+                    throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: MIN_PATH must be finite and not negative (got " + field[2] + ")"};
+            }
+            po.metal = true;
+        }
+
+        // --metal: checked here, before any device work. The metal outside a region of interest still casts a trace, and the list is
+        // indexed in the whole grid: --roi is refused with it.
+        inline auto check_metal(const program_options& po) -> void
+        {
+            if(!po.metal)
+                return;
+            if(po.enable_roi)
+                throw stage_construction_error{"--metal cannot be combined with --roi: metal outside the region still casts a trace"};
+            if(!std::isfinite(po.metal_threshold))
+                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: THR must be finite"};
+            if(po.metal_grow > PARIS_HIP_METAL_GROW_MAX)
+                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: GROW must lie in 0 .. " + std::to_string(PARIS_HIP_METAL_GROW_MAX) + " (got "
+                                               + std::to_string(po.metal_grow) + ")"};
+            if(po.metal_min_path >= 0.f && !std::isfinite(po.metal_min_path))
+                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: MIN_PATH must be finite and not negative"};
+            if(po.axis_only || po.roll_only)
+                throw stage_construction_error{"--metal cannot be combined with --axis-only or --roll-only: nothing would be reconstructed"};
+        }
+
+        // --metal: the pre-pass, after every other pre-pass, with their results in force (po holds the ring correction, the axis, the
+        // polynomial and the roll by now). Every projection the run uses is read once on the first device, whole, in groups of
+        // po.batch frames, and goes through the main loop's whole frame chain and the backprojection into ONE buffer that holds the
+        // whole grid; each frame's sine and cosine are kept. Then the voxels above the threshold are collected and the volume
+        // binarized, the mask is forward-projected group by group into the slots' frames, and each group packed to the host
+        // (DESIGN.md section 4.21). Everything allocated here is freed before it returns: run() plans the slabs afterwards.
+        inline auto metal_prepass(program_options& po, run_report& r) -> void
+        {
+            const auto t_start = clock::now();
+            const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+            const auto& vg = r.vol_geo;
+            const std::uint32_t batch = slot_shape(po).first;
+            const bool binning = po.binning();
+            const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
+            const std::uint32_t words = (n_row + 63u) / 64u;
+            const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * vg.dim_z;
+            std::uint64_t cap = 0;
+            if(paris_hip_metal_check(vg.dim_x, vg.dim_y, vg.dim_z, po.metal_threshold, po.metal_grow, po.metal_min_path, &cap) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--metal: the library refuses the setting"};
+            {
+                std::size_t free_b = 0, total_b = 0;
+                rt(paris_hip_device_memory(0, &free_b, &total_b), "device memory");
+                const auto need = voxels * sizeof(float) + driver_bytes(po);
+                if(need > free_b)
+                    throw stage_construction_error{"--metal: the pre-pass needs the whole volume and its frame slots on one device, " + std::to_string(need)
+                                                   + " bytes, and " + std::to_string(free_b) + " are free: try --bin"};
+            }
+            auto bits = std::make_shared<std::vector<std::uint64_t>>();
+            auto index = std::make_shared<std::vector<std::uint64_t>>();
+            auto value = std::make_shared<std::vector<float>>();
+            std::uint32_t frames = 0, n_views = 0;
+            {
+                const device_ctx ctx{0};
+                struct whole_volume
+                {
+                    paris_hip_ctx* ctx;
+                    float* d_v;
+                    ~whole_volume() { paris_hip_free(ctx, d_v); }
+                } vol{ctx, nullptr};
+                auto rep = device_report{};
+                set_frame_chain(ctx, po, rep);
+                set_chain_back(ctx, po, rep); // (no trace and no list yet)
+                const frame_slots slots{ctx, po, batch, 0u, po.roll, false};
+                const frame_chain chain{ctx, po, slots, rep.defect_map};
+                rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, vg.dim_z, &vol.d_v), "make_volume()");
+                // whole frames: every range of the plan is the detector
+                const auto roll = paris_hip_detector_roll{po.roll_deg};
+                const auto rows = plan_frame_rows(row_range{0u, n_col}, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr,
+                                                  binning ? po.bin_y : 1u, po.roll ? &roll : nullptr, &po.det_geo);
+                const float delta_s = po.det_geo.delta_s * po.det_geo.l_px_row, delta_t = po.det_geo.delta_t * po.det_geo.l_px_col;
+                const auto no_roi = region_of_interest{};
+                auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
+                auto all_sin = std::vector<float>{}, all_cos = std::vector<float>{}; // per view, for the forward projection
+                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
+                const std::uint32_t stride = std::max<std::uint32_t>(1u, po.quality);
+                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file, on whole frames
+                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
+                for(bool more = true; more;)
+                {
+                    std::uint32_t filled = 0;
+                    for(; filled < batch; ++filled)
+                    {
+                        const auto p = source.next_raw(slots.host(filled), sn_row, sn_col, rows.src.first, rows.src.count);
+                        if(!p.valid())
+                        {
+                            more = false;
+                            break;
+                        }
+                        if(p.dim_x != sn_row || p.dim_y != sn_col)
+                            throw stage_runtime_error{"projection size does not match the detector geometry"};
+                        chain.upload(filled, p.pixel, rows);
+                        angles[filled] = po.enable_angles ? p.phi : static_cast<float>(p.idx) * po.det_geo.delta_phi;
+                        rt(paris_hip_stage_angle(&po.det_geo, p.idx, po.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle");
+                        const std::uint32_t view = p.idx / stride;
+                        if(view >= all_sin.size())
+                        {
+                            all_sin.resize(view + 1u, 0.f);
+                            all_cos.resize(view + 1u, 1.f);
+                        }
+                        all_sin[view] = sines[filled];
+                        all_cos[view] = cosines[filled];
+                    }
+                    if(filled == 0)
+                        break;
+                    chain.run(0u, filled, true, rows, angles.data());
+                    rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, filled, n_row, n_col, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, 0u,
+                                                   &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
+                    rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the pinned and the device frames are free for the next group
+                    frames += filled;
+                }
+                if(po.lag)
+                    rt(paris_hip_lag_end(ctx), "lag_end()");
+                if(frames == 0u)
+                    throw stage_runtime_error{"--metal: the input holds no projection"};
+                n_views = static_cast<std::uint32_t>(all_sin.size());
+                // the list: counted first, so that the host arrays hold what is there and not what the cap allows
+                std::uint64_t n = 0;
+                const int counted = paris_hip_metal_collect(ctx, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, po.metal_threshold, 0u, nullptr, nullptr, &n, 0);
+                if(counted != PARIS_HIP_SUCCESS && counted != PARIS_HIP_ERROR_METAL_TOO_MANY_VOXELS)
+                    rt(counted, "metal_collect()");
+                if(n > cap)
+                    throw stage_runtime_error{"--metal: " + std::to_string(n) + " voxel(s) lie above the threshold, more than 1/32 of the grid ("
+                                              + std::to_string(cap) + "): that is a wrong threshold, not metal"};
+                index->resize(n);
+                value->resize(n);
+                rt(paris_hip_metal_collect(ctx, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, po.metal_threshold, n, index->data(), value->data(), &n, 1),
+                   "metal_collect()");
+                // the mask's projections, in groups of the slots, packed to the host
+                bits->assign(static_cast<std::size_t>(n_views) * n_col * words, 0u);
+                for(std::uint32_t v0 = 0; v0 < n_views; v0 += batch)
+                {
+                    const std::uint32_t nv = std::min(batch, n_views - v0);
+                    rt(paris_hip_forward_project(ctx, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, 0u, &po.det_geo, &vg, slots.frame(0u), slots.pitch, slots.stride, nv,
+                                                 n_row, n_col, all_sin.data() + v0, all_cos.data() + v0, delta_s, delta_t, 0), "forward_project()");
+                    rt(paris_hip_metal_trace_pack(ctx, slots.frame(0u), slots.pitch, slots.stride, nv, n_row, n_col, po.metal_min_path, po.metal_grow,
+                                                  bits->data() + static_cast<std::size_t>(v0) * n_col * words), "metal_trace_pack()");
+                }
+            } // (the buffers and the ctx are gone: the time below includes that)
+            std::uint64_t pixels = 0;
+            for(const auto w : *bits)
+                pixels += static_cast<std::uint64_t>(__builtin_popcountll(w));
+            po.metal_views = n_views;
+            po.metal_bytes = 64u + bits->size() * sizeof(std::uint64_t) + index->size() * (sizeof(std::uint64_t) + sizeof(float));
+            r.metal = true;
+            r.metal_threshold = po.metal_threshold;
+            r.metal_grow = po.metal_grow;
+            r.metal_min_path = po.metal_min_path;
+            r.metal_frames = frames;
+            r.metal_voxels = index->size();
+            r.metal_trace_pixels = pixels;
+            po.metal_bits = std::move(bits);
+            po.metal_index = std::move(index);
+            po.metal_value = std::move(value);
+            r.metal_prepass_s = since(t_start);
+        }
+
         // --find-axis LO:HI[:STEP] as typed; refuses anything but two or three numbers
         inline auto parse_find_axis(const std::string& v, program_options& po) -> void
         {
@@ -2285,6 +2516,7 @@ namespace paris
         detail::check_axis(po);
         detail::check_beam_hardening(po);
         detail::check_roll(po);
+        detail::check_metal(po);
         // --find-roll: the estimate becomes the run's roll (an estimate of exactly 0 is no roll)
         const auto adopt_roll = [&] {
             po.roll_deg = r.roll.eta_deg;
@@ -2353,6 +2585,12 @@ namespace paris
         }
         r.beam_hardening = po.beam_hardening;
         r.bh = po.bh;
+        if(po.metal) // after every other pre-pass, whose results it uses; its volume is gone before the run's slabs are planned
+        {
+            if(po.metal_min_path < 0.f) // not given: half the smallest voxel edge
+                po.metal_min_path = 0.5f * std::min(r.vol_geo.l_vx_x, std::min(r.vol_geo.l_vx_y, r.vol_geo.l_vx_z));
+            detail::metal_prepass(po, r);
+        }
         r.detector_roll = po.roll;
         r.roll_deg = po.roll_deg;
         r.lag = po.lag;
@@ -2454,6 +2692,9 @@ namespace paris
             r.zingers.frames += d.zingers.frames;
             r.zingers.replaced += d.zingers.replaced;
             r.zingers.saturated_frames += d.zingers.saturated_frames;
+            r.metal_counts.replaced += d.metal.replaced;
+            r.metal_counts.runs += d.metal.runs;
+            r.metal_counts.rows_left += d.metal.rows_left;
             r.voxels.voxels += d.voxels.voxels;
             r.voxels.below += d.voxels.below;
             r.voxels.above += d.voxels.above;

@@ -98,6 +98,9 @@ namespace paris
                                                                         rolled.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y, 0u, p.dim_y), "weight()");
             std::swap(p.buf, rolled.buf);
         }
+        // then with a metal trace (backend::set_metal_trace) the inpainting of the trace of view p.idx, on the detector the roll wrote
+        if(backend::detail::has_metal_trace(backend::current_ctx()))
+            backend::metal_inpaint(p.buf.get(), p.buf.pitch(), p.dim_x, p.dim_y, 0u, p.dim_y, p.idx);
         if(backend::detail::has_offset_detector(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_stage_offset_detector_weight(backend::current_ctx(), p.buf.get(), p.buf.pitch(), p.dim_x,
                                                                                   p.dim_y, &det_geo), "weight()");
