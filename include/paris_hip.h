@@ -1493,6 +1493,73 @@ int paris_hip_volume_quantize_counts(paris_hip_ctx* ctx, paris_hip_volume_counts
 int paris_hip_volume_stats(paris_hip_ctx* ctx, const float* d_v, uint64_t n_voxels, float h_lo, float h_hi, uint32_t n_bins,
                            uint64_t* hist, paris_hip_volume_statistics* out);
 
+/* Extension (no reference counterpart): single-distance phase retrieval after Paganin et al. (2002) -- at magnification a micro-focus
+ * scan shows propagation fringes at material edges, which the ramp filter amplifies. For one material with a known delta / beta the
+ * remedy is a low-pass on the TRANSMISSION image: the library's only pass that filters a frame in two dimensions (phase.hip,
+ * phase_rule.cpp).
+ * Setting paris_hip_phase_retrieval { float alpha_mm2; float t_min; uint32_t margin; }: alpha_mm2 finite and > 0, 0 < t_min <= 1,
+ *   1 <= margin <= PARIS_HIP_PHASE_MARGIN_MAX.
+ * Input: whole frames of line integrals p, dim_x x dim_y floats (both >= 1) with the pixel pitches l_x = l_px_row, l_y = l_px_col (finite,
+ *   > 0). In place.
+ * Rule, per frame:
+ *   1. T = expf(-p). A pixel whose p or T is not finite enters as T = 1 and is LEFT AS STORED in the output.
+ *   2. N_x is the smallest power of two >= max(8, dim_x + 2 margin), N_y likewise from dim_y. Either above PARIS_HIP_PHASE_SIZE_MAX:
+ *      PARIS_HIP_ERROR_UNSUPPORTED.
+ *   3. Extension by edge replication with a circular wrap: padded column x >= dim_x reads column dim_x - 1 while
+ *      x - dim_x < (N_x - dim_x + 1) / 2 (integer division) and column 0 beyond; rows likewise, applied to the extended rows.
+ *   4. T' = IFFT2(FFT2(T_ext) H), H(k_x, k_y) = 1 / (1 + a_x[k_x] + a_y[k_y]) -- in fp32 (1 + a_x) + a_y and one IEEE division --,
+ *      a_x[k] = alpha f^2 with f = k / (N_x l_x) for k <= N_x / 2 and (k - N_x) / (N_x l_x) above, a_y from N_y and l_y. Both tables
+ *      are made in double on the host, rounded once to float and uploaded. H is real and even in both axes.
+ *   5. p' = -logf(fmaxf(T', t_min)) on the first dim_x x dim_y samples; T' carries the division by N_x N_y, an exact scaling.
+ * The answer for a frame does not depend on which other frames share the call, bit for bit: realness is exploited WITHIN the frame
+ * (rows 2r and 2r + 1 packed as a + ib, split into their Hermitian half-spectra of N_x / 2 + 1 columns, merged before the inverse
+ * row pass). Only the dim_y distinct rows are transformed; the column pass reads the padded rows through the row map.
+ * Scratch: frames_per_launch * dim_y * (N_x / 2 + 1) complex floats, frames_per_launch = max(1, min(16, 64 MiB / the bytes of one
+ * frame's spectra)); with the twiddles of both lengths (N_x / 2 + N_y / 2 complex floats) and the two tables in front of it, it is a
+ * ctx-owned setting that paris_hip_projection_reserve_bytes counts.
+ * Order: after the ring correction (a ring offset is a per-pixel gain in transmission, removed before a low-pass smears it), before
+ * the beam-hardening polynomial, which acts on the retrieved line integral.
+ * Limits: powers of two only; no band-wise form (a 2-D filter has no row band); one material, one distance. */
+#define PARIS_HIP_PHASE_MARGIN_MAX 1024
+#define PARIS_HIP_PHASE_SIZE_MAX 8192
+typedef struct paris_hip_phase_retrieval {
+    float alpha_mm2; /* pi lambda (delta / beta) z_eff at the detector plane [mm^2]; finite, > 0 */
+    float t_min;     /* floor of the retrieved transmission; in (0, 1] */
+    uint32_t margin; /* padding per side [px]: 1 .. PARIS_HIP_PHASE_MARGIN_MAX */
+} paris_hip_phase_retrieval;
+/* Host only, no ctx and no device: alpha = pi lambda (delta / beta) d_od (d_so + d_od) / d_so with lambda = 1.2398419843e-6 mm keV /
+ * energy_kev, in double from |d_so| and |d_od| (as d_sd is formed), rounded once. (The effective defocus is d_od / M, and the
+ * detector-plane frequencies are M times smaller than the object's: together the factor M.) PARIS_HIP_ERROR_INVALID_ARGUMENT for a
+ * NULL pointer, a delta_over_beta or energy that is not finite and > 0, a d_so or d_od of 0 or not finite, or an alpha that does not
+ * round to a finite float > 0. */
+int paris_hip_phase_alpha(const paris_detector_geometry* det_geo, double delta_over_beta, double energy_kev, float* alpha_mm2);
+/* Host only: max(8, ceil(6 sqrt(alpha) / (2 pi min(l_x, l_y)))), capped at PARIS_HIP_PHASE_MARGIN_MAX -- six decay lengths
+ * sqrt(alpha) / 2 pi of the filter's kernel, in pixels. 0 for arguments that are not finite and > 0. */
+uint32_t paris_hip_phase_default_margin(float alpha_mm2, float l_x, float l_y);
+/* Host only: validates the setting for dim_x x dim_y frames of these pitches and returns the padded sizes and the bytes of scratch
+ * the device needs (each pointer may be NULL). PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a field out of range, a zero
+ * dimension or a pitch that is not finite and > 0; PARIS_HIP_ERROR_UNSUPPORTED for a padded size above PARIS_HIP_PHASE_SIZE_MAX
+ * (n_x and n_y are still returned). */
+int paris_hip_phase_retrieval_check(const paris_hip_phase_retrieval* setting, uint32_t dim_x, uint32_t dim_y, float l_x, float l_y,
+                                    uint32_t* n_x, uint32_t* n_y, size_t* scratch_bytes);
+/* Host only: the rule in DOUBLE on one dense frame, src to dst (which may be the same array), rounded to float at the store -- exp, a
+ * double radix-2 transform of its own, log; the special pixels are judged as the rule says, on the fp32 expf. The C statement of the
+ * model, not a mirror of the device's bits: the device agrees with it within FFT rounding. Refusals as the check, or
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL src or dst. */
+int paris_hip_phase_retrieval_host(const paris_hip_phase_retrieval* setting, float l_x, float l_y, const float* src, float* dst,
+                                   uint32_t dim_x, uint32_t dim_y);
+/* paris_hip_set_phase_retrieval runs the check and installs twiddles, tables and scratch for dim_x x dim_y frames in memory the ctx
+ * owns. It replaces an earlier setting safely: work already queued keeps the old one. Without a setting nothing else changes. */
+int paris_hip_set_phase_retrieval(paris_hip_ctx* ctx, const paris_hip_phase_retrieval* setting, uint32_t dim_x, uint32_t dim_y, float l_x,
+                                  float l_y);
+int paris_hip_clear_phase_retrieval(paris_hip_ctx* ctx);
+/* In place on whole float frames, asynchronous: n_frames frames frame_stride bytes apart, d_p the first frame's row 0, rows pitch
+ * bytes apart. Every row is the pass's band: a pending by-reference group and a held-back weighting run first. Calls of more than
+ * frames_per_launch frames loop. PARIS_HIP_ERROR_INVALID_ARGUMENT without a setting, when dim_x / dim_y differ from the setting's, or
+ * for a pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_phase_retrieval_frames(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                     uint32_t dim_y);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 const char* paris_hip_strerror(int status);
 /* library version "major.minor.patch" */

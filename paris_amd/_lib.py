@@ -173,6 +173,15 @@ class BhFit(C.Structure):
     _fields_ = [("setting", BeamHardening), ("level", C.c_double), ("residual_before", C.c_double), ("residual_after", C.c_double)]
 
 
+PHASE_MARGIN_MAX = 1024  # PARIS_HIP_PHASE_MARGIN_MAX
+PHASE_SIZE_MAX = 8192  # PARIS_HIP_PHASE_SIZE_MAX
+
+
+class PhaseRetrieval(C.Structure):
+    """paris_hip_phase_retrieval: Paganin's single-distance filter on the transmission image (extension)"""
+    _fields_ = [("alpha_mm2", C.c_float), ("t_min", C.c_float), ("margin", C.c_uint32)]
+
+
 LAG_TERMS_MAX = 4  # PARIS_HIP_LAG_TERMS_MAX
 LAG_START_REST = 0  # PARIS_HIP_LAG_START_REST
 LAG_START_STEADY = 1  # PARIS_HIP_LAG_START_STEADY
@@ -311,6 +320,14 @@ SIGNATURES = {
     "paris_hip_air_normalize_rows": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _u32]),
     "paris_hip_air_measure": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _vp, _vp]),
     "paris_hip_air_stats": (C.c_int, [_vp, _P(AirCounts), C.c_int]),
+    "paris_hip_phase_alpha": (C.c_int, [_P(DetectorGeometry), C.c_double, C.c_double, _P(C.c_float)]),
+    "paris_hip_phase_default_margin": (C.c_uint32, [C.c_float, C.c_float, C.c_float]),
+    "paris_hip_phase_retrieval_check": (C.c_int, [_P(PhaseRetrieval), _u32, _u32, C.c_float, C.c_float, _P(C.c_uint32), _P(C.c_uint32),
+                                                  _P(C.c_size_t)]),
+    "paris_hip_phase_retrieval_host": (C.c_int, [_P(PhaseRetrieval), C.c_float, C.c_float, _vp, _vp, _u32, _u32]),
+    "paris_hip_set_phase_retrieval": (C.c_int, [_vp, _P(PhaseRetrieval), _u32, _u32, C.c_float, C.c_float]),
+    "paris_hip_clear_phase_retrieval": (C.c_int, [_vp]),
+    "paris_hip_phase_retrieval_frames": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32]),
     "paris_hip_beam_hardening_check": (C.c_int, [_P(BeamHardening)]),
     "paris_hip_beam_hardening_host": (C.c_int, [_P(BeamHardening), _vp, _vp, C.c_uint64]),
     "paris_hip_set_beam_hardening": (C.c_int, [_vp, _P(BeamHardening), _u32, _u32]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -28,7 +28,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve", "DetectorRoll", "RollSearch", "RollResult",
            "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs",
            "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host", "MetalCounts", "MetalTrace", "metal_check",
-           "metal_collect_host", "metal_trace_pack_host", "metal_inpaint_host", "metal_words"]
+           "metal_collect_host", "metal_trace_pack_host", "metal_inpaint_host", "metal_words", "PhaseRetrieval", "phase_alpha",
+           "phase_default_margin", "phase_retrieval_check", "phase_retrieval_host"]
 
 
 class Projection:
@@ -353,6 +354,44 @@ def beam_hardening_host(c, frame):
     s = _bh_setting(c)
     check(_lib.load().paris_hip_beam_hardening_host(C.byref(s), f.ctypes.data if f.size else None, out.ctypes.data if f.size else None,
                                                     f.size), "paris_hip_beam_hardening_host")
+    return out
+
+
+def phase_alpha(det_geo, delta_over_beta, energy_kev):
+    """Host only, no device (paris_hip_phase_alpha): alpha = pi lambda (delta / beta) d_od (d_so + d_od) / d_so in mm^2 at the detector
+    plane, lambda = 1.2398419843e-6 mm keV / energy_kev, in double and rounded once to float."""
+    a = C.c_float()
+    check(_lib.load().paris_hip_phase_alpha(C.byref(det_geo), delta_over_beta, energy_kev, C.byref(a)), "paris_hip_phase_alpha")
+    return a.value
+
+
+def phase_default_margin(alpha_mm2, l_x, l_y):
+    """Host only (paris_hip_phase_default_margin): max(8, ceil(6 sqrt(alpha) / (2 pi min(l_x, l_y)))) pixels, at most 1024; 0 for
+    arguments that are not finite and positive."""
+    return _lib.load().paris_hip_phase_default_margin(alpha_mm2, l_x, l_y)
+
+
+def phase_retrieval_check(alpha_mm2, t_min, margin, dim_x, dim_y, l_x, l_y):
+    """Host only (paris_hip_phase_retrieval_check): raises ParisHipError for a setting the library refuses -- a padded size above 8192
+    is ERROR_UNSUPPORTED --, else returns (n_x, n_y, scratch_bytes)."""
+    s = PhaseRetrieval(alpha_mm2, t_min, margin)
+    nx, ny, b = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(_lib.load().paris_hip_phase_retrieval_check(C.byref(s), dim_x, dim_y, l_x, l_y, C.byref(nx), C.byref(ny), C.byref(b)),
+          "paris_hip_phase_retrieval_check")
+    return nx.value, ny.value, b.value
+
+
+def phase_retrieval_host(alpha_mm2, t_min, margin, l_x, l_y, frame):
+    """Host only (paris_hip_phase_retrieval_host): the phase-retrieval rule in double on one frame of line integrals, a 2-D array
+    (dim_y, dim_x) taken as float32, rounded to float32 at the store. Returns a new array."""
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.ndim != 2:
+        raise ValueError("phase_retrieval_host: the frame must be a 2-D array (dim_y, dim_x)")
+    out = np.empty_like(f)
+    s = PhaseRetrieval(alpha_mm2, t_min, margin)
+    check(_lib.load().paris_hip_phase_retrieval_host(C.byref(s), l_x, l_y, f.ctypes.data if f.size else None,
+                                                     out.ctypes.data if f.size else None, f.shape[1], f.shape[0]),
+          "paris_hip_phase_retrieval_host")
     return out
 
 
@@ -1160,6 +1199,30 @@ class Backend:
         st = AirCounts()
         check(self._L.paris_hip_air_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_air_stats")
         return st
+
+    # ---- phase retrieval -----------------------------------------------------------
+    phase_alpha = staticmethod(phase_alpha)
+    phase_default_margin = staticmethod(phase_default_margin)
+    phase_retrieval_check = staticmethod(phase_retrieval_check)
+    phase_retrieval_host = staticmethod(phase_retrieval_host)
+
+    def set_phase_retrieval(self, alpha_mm2, t_min, margin, dim_x, dim_y, l_x, l_y):
+        """paris_hip_set_phase_retrieval for dim_x x dim_y frames with pixel pitches l_x, l_y: phase_retrieval() then low-passes the
+        transmission of whole frames with 1 / (1 + alpha f^2). Twiddles, tables and scratch live on the device and count towards
+        projection_reserve_bytes. Replaces an earlier setting; work already queued keeps the old one."""
+        s = PhaseRetrieval(alpha_mm2, t_min, margin)
+        check(self._L.paris_hip_set_phase_retrieval(self._ctx, C.byref(s), dim_x, dim_y, l_x, l_y), "paris_hip_set_phase_retrieval")
+
+    def clear_phase_retrieval(self):
+        """paris_hip_clear_phase_retrieval: no phase retrieval from here on"""
+        check(self._L.paris_hip_clear_phase_retrieval(self._ctx), "paris_hip_clear_phase_retrieval")
+
+    def phase_retrieval(self, p, frame_stride=0, n_frames=1):
+        """The rule of set_phase_retrieval() in place on whole float frames of line integrals (paris_hip_phase_retrieval_frames):
+        the n_frames frames frame_stride bytes apart starting at p. Call it after the ring correction and before the beam-hardening
+        polynomial. A frame's result does not depend on the other frames of the call."""
+        check(self._L.paris_hip_phase_retrieval_frames(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y),
+              "paris_hip_phase_retrieval_frames")
 
     # ---- beam hardening (DESIGN.md section 4.17) ------------------------------------------------------------
     beam_hardening_check = staticmethod(beam_hardening_check)

@@ -255,6 +255,16 @@ struct paris_hip_ctx
         paris_hip_device_buffer mem;
         std::vector<uint64_t> index;
     } metal_voxels;
+    // Phase retrieval (paris_hip_set_phase_retrieval): in this order the twiddles of N_x (N_x / 2 complex
+    // floats) and of N_y, the tables a_x (N_x floats) and a_y, and the scratch -- `frames` frames of dim_y x (N_x / 2 + 1) complex floats.
+    struct phase_t
+    {
+        bool set = false;
+        paris_hip_phase_retrieval rule{};
+        paris_hip_device_buffer mem;
+        uint32_t dim_x = 0, dim_y = 0, n_x = 0, n_y = 0;
+        uint32_t frames = 0; // frames one round of launches serves
+    } phase;
     // Row extension (paris_hip_set_row_extension): the rule, and the responses c made so far, one buffer per (dim_x, tau bits, W) --
     // the second stream reads them too, behind a join.
     struct row_extension_t
@@ -278,7 +288,7 @@ struct paris_hip_ctx
     void each_setting(F&& f)
     {
         f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
-        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels);
+        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase);
     }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
@@ -577,6 +587,10 @@ void paris_hip_warm_beam_hardening();
 void paris_hip_warm_detector_roll();
 void paris_hip_warm_lag();
 void paris_hip_warm_metal();
+void paris_hip_warm_phase();
+// phase_rule.cpp: a[k] = alpha f^2 of n bins at this pitch, in double and rounded once; the extension's source sample of padded sample s
+void paris_hip_phase_table(float alpha, uint32_t n, float pitch, float* a);
+uint32_t paris_hip_phase_source(uint32_t s, uint32_t dim, uint32_t n);
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the

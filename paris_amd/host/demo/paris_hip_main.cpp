@@ -11,7 +11,7 @@
 //             [--find-axis LO:HI[:STEP] [--axis-rows R] [--axis-only]] [--air-region X0:Y0:W:H[:LIMIT]]
 //             [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]
 //             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
-//             [--metal THR[:GROW[:MIN_PATH]]]
+//             [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -92,7 +92,7 @@ int main(int argc, char** argv)
                             "          [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]\n"
                             "          [--detector-roll DEG | --find-roll LO:HI[:STEP] [--roll-only]]\n"
                             "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
-                            "          [--metal THR[:GROW[:MIN_PATH]]]\n"
+                            "          [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -205,6 +205,9 @@ int main(int argc, char** argv)
             else if(k == "--find-roll") paris::detail::parse_find_roll(val(), po);
             else if(k == "--roll-only") po.roll_only = true;
             else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
+            else if(k == "--phase") paris::detail::parse_phase(val(), po, true);
+            else if(k == "--phase-alpha") paris::detail::parse_phase(val(), po, false);
+            else if(k == "--phase-floor") paris::detail::parse_phase_floor(val(), po);
             else if(k == "--beam-hardening") paris::detail::parse_beam_hardening(val(), po);
             else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
             else if(k == "--lag") paris::detail::parse_lag(val(), po);
@@ -317,6 +320,14 @@ int main(int argc, char** argv)
         }
         if(r.detector_roll)
             std::printf("detector roll on: %.9g deg\n", static_cast<double>(r.roll_deg));
+        if(r.phase)
+        {
+            const double length = std::sqrt(static_cast<double>(r.phase_setting.alpha_mm2)) / (2.0 * 3.14159265358979323846);
+            std::printf("phase retrieval on: alpha %.9g mm^2, kernel length %.4g x %.4g px, margin %u, floor %.9g, padded %u x %u, %llu scratch byte(s) per "
+                        "device, whole frames (planned as --no-row-band)\n", static_cast<double>(r.phase_setting.alpha_mm2),
+                        length / static_cast<double>(r.phase_l_x), length / static_cast<double>(r.phase_l_y), r.phase_setting.margin,
+                        static_cast<double>(r.phase_setting.t_min), r.phase_nx, r.phase_ny, static_cast<unsigned long long>(r.phase_scratch));
+        }
         if(r.beam_hardening)
         {
             if(r.bh_fitted)

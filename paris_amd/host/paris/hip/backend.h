@@ -132,6 +132,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> ring_corrections; // set_ring_correction(), per device of this thread
                 std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
                 std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
+                std::set<const paris_hip_ctx*> phase_retrievals; // set_phase_retrieval(), per device of this thread
                 std::set<const paris_hip_ctx*> detector_rolls; // set_detector_roll(), per device of this thread
                 std::set<const paris_hip_ctx*> metal_traces;   // set_metal_trace(), per device of this thread
             };
@@ -322,6 +323,40 @@ namespace paris
             inline auto has_air_region(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().air_regions;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): at magnification the frames of this thread's current device (n_row x n_col pixels with
+        // the pitches l_px_row, l_px_col) show propagation fringes. Until clear_phase_retrieval(),
+        // paris::weight() low-passes the transmission of every frame with 1 / (1 + alpha f^2) -- Paganin's single-distance filter --
+        // after the ring correction and before the beam-hardening polynomial (paris_hip_phase_retrieval_frames).
+        inline auto set_phase_retrieval(float alpha_mm2, float t_min, std::uint32_t margin, std::uint32_t n_row, std::uint32_t n_col, float l_px_row,
+                                        float l_px_col) -> void
+        {
+            const auto setting = paris_hip_phase_retrieval{alpha_mm2, t_min, margin};
+            detail::runtime_check(paris_hip_set_phase_retrieval(current_ctx(), &setting, n_row, n_col, l_px_row, l_px_col), "set_phase_retrieval()");
+            detail::state().phase_retrievals.insert(current_ctx());
+        }
+
+        inline auto clear_phase_retrieval() -> void
+        {
+            detail::runtime_check(paris_hip_clear_phase_retrieval(current_ctx()), "clear_phase_retrieval()");
+            detail::state().phase_retrievals.erase(current_ctx());
+        }
+
+        // the pass itself, on n_frames whole frames frame_stride bytes apart
+        inline auto phase_retrieval(float* d_p, std::size_t pitch, std::size_t frame_stride, std::uint32_t n_frames, std::uint32_t n_row,
+                                    std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_phase_retrieval_frames(current_ctx(), d_p, pitch, frame_stride, n_frames, n_row, n_col), "phase_retrieval()");
+        }
+
+        namespace detail
+        {
+            inline auto has_phase_retrieval(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().phase_retrievals;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

@@ -151,6 +151,17 @@ namespace paris
         bool beam_hardening = false, fit_beam_hardening = false;
         paris_hip_beam_hardening bh{};                          // as given, or filled by run() with the fitted coefficients
         std::uint32_t bh_slices = 32, bh_margin = 2;            // the fit's slab -- the central slices of the volume -- and its margin
+        // single-distance phase retrieval (extension): --phase DELTA_BETA:ENERGY_KEV[:MARGIN] gives the material
+        // and the energy, --phase-alpha MM2[:MARGIN] the filter's alpha at the detector plane itself; --phase-floor T the floor of the
+        // retrieved transmission (default: the flat field's t_min, else 1e-6). Checked by run() before any device work, for the binned
+        // detector with --bin (detail::check_phase). Every device ctx gets the setting, and each frame is filtered -- as a whole: the run
+        // is planned without the row band -- after the ring correction and before the beam-hardening polynomial
+        bool phase = false, phase_material = false, phase_floor_given = false;
+        double phase_delta_beta = 0.0, phase_energy = 0.0;
+        std::uint32_t phase_margin = 0;                         // 0: not given; run() takes paris_hip_phase_default_margin
+        paris_hip_phase_retrieval phase_setting{};              // alpha as given; the rest filled by run()
+        std::uint32_t phase_nx = 0, phase_ny = 0;               // filled by run(): the padded size
+        std::size_t phase_scratch = 0, phase_bytes = 0;         // filled by run(): the scratch, and what the setting occupies on a device
         // correction of the detector's in-plane rotation (extension): --detector-roll DEG gives the angle,
         // --find-roll LO:HI[:STEP] [--roll-only] has run() find it from the scan mean of the ring profile pre-pass (detail::prepass,
         // after the axis search, whose delta_s it uses): both checked by run() before any device work (detail::check_roll). Every
@@ -420,6 +431,9 @@ namespace paris
         {
             if(po.ring_c)
                 rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
+            if(po.phase)
+                rt(paris_hip_set_phase_retrieval(ctx, &po.phase_setting, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col),
+                   "set_phase_retrieval()");
             if(po.beam_hardening)
                 rt(paris_hip_set_beam_hardening(ctx, &po.bh, po.det_geo.n_row, po.det_geo.n_col), "set_beam_hardening()");
             if(po.roll)
@@ -468,7 +482,7 @@ namespace paris
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
             // with --lag, the state of a whole-detector sequence at most
             const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
-            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -638,7 +652,8 @@ namespace paris
                     rt(paris_hip_zinger_filter_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "zinger filter");
             }
 
-            // the detector's stationary offsets, then the polynomial of the line integral: the run's, or `unit` in its place
+            // the detector's stationary offsets, the phase retrieval -- a 2-D filter of whole frames: the run has no row band --, then
+            // the polynomial of the line integral: the run's, or `unit` in its place
             void linearise(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const paris_hip_beam_hardening* unit = nullptr) const
             {
                 const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
@@ -646,6 +661,12 @@ namespace paris
                 auto* d = slots.frame(first);
                 if(po.ring_c)
                     rt(paris_hip_ring_correct_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "ring correction");
+                if(po.phase)
+                {
+                    if(rows.band.first != 0u || rows.band.count != n_col)
+                        throw stage_runtime_error{"phase retrieval: the plan gave a row band to a pass that filters whole frames"};
+                    rt(paris_hip_phase_retrieval_frames(ctx, d, slots.pitch, stride, n, n_row, n_col), "phase retrieval");
+                }
                 if(unit != nullptr)
                     rt(paris_hip_beam_hardening_rows_with(ctx, unit, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "beam hardening");
                 else if(po.beam_hardening)
@@ -1267,6 +1288,11 @@ namespace paris
         float bh_threshold = 0.f;
         std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
         double bh_prepass_s = 0;
+        bool phase = false;                             // --phase / --phase-alpha: every frame went through this setting at these
+        paris_hip_phase_retrieval phase_setting{};      // pitches; the padded size and the scratch a device keeps for it
+        float phase_l_x = 0.f, phase_l_y = 0.f;
+        std::uint32_t phase_nx = 0, phase_ny = 0;
+        std::size_t phase_scratch = 0;
         bool metal = false;                             // --metal: the pre-pass ran; what it found, and the main pass's counts over all devices
         float metal_threshold = 0.f, metal_min_path = 0.f;
         std::uint32_t metal_grow = 0, metal_frames = 0;
@@ -1901,6 +1927,82 @@ namespace paris
             }
         }
 
+        // --phase DELTA_BETA:ENERGY_KEV[:MARGIN] (material = true) or --phase-alpha MM2[:MARGIN] as typed; refuses anything but the numbers
+        // and an unsigned margin
+        inline auto parse_phase(const std::string& v, program_options& po, bool material) -> void
+        {
+            const auto name = std::string{material ? "--phase DELTA_BETA:ENERGY_KEV[:MARGIN]" : "--phase-alpha MM2[:MARGIN]"};
+            const auto field = colon_fields(v);
+            const auto numbers = material ? std::size_t{2} : std::size_t{1};
+            if(field.size() < numbers || field.size() > numbers + 1u)
+                throw stage_construction_error{name + ": cannot read '" + v + "'"};
+            double value[2] = {0.0, 0.0};
+            for(std::size_t k = 0; k < numbers; ++k)
+            {
+                char* end = nullptr;
+                value[k] = std::strtod(field[k].c_str(), &end);
+                if(field[k].empty() || end == nullptr || *end != '\0')
+                    throw stage_construction_error{name + ": cannot read '" + v + "'"};
+            }
+            po.phase_margin = 0u;
+            if(field.size() > numbers)
+            {
+                const auto& m = field[numbers];
+                if(m.empty() || m.size() > 9u || m.find_first_not_of("0123456789") != std::string::npos)
+                    throw stage_construction_error{name + ": cannot read '" + v + "'"};
+                po.phase_margin = static_cast<std::uint32_t>(std::stoul(m));
+                if(po.phase_margin == 0u)
+                    throw stage_construction_error{name + ": MARGIN must lie in 1 .. " + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX)};
+            }
+            if(po.phase)
+                throw stage_construction_error{"--phase and --phase-alpha cannot be combined: give the material or the filter's alpha"};
+            po.phase = true;
+            po.phase_material = material;
+            po.phase_delta_beta = value[0];
+            po.phase_energy = value[1];
+            po.phase_setting.alpha_mm2 = material ? 0.f : static_cast<float>(value[0]);
+        }
+
+        inline auto parse_phase_floor(const std::string& v, program_options& po) -> void
+        {
+            char* end = nullptr;
+            po.phase_setting.t_min = std::strtof(v.c_str(), &end);
+            if(v.empty() || end == nullptr || *end != '\0')
+                throw stage_construction_error{"--phase-floor T: cannot read '" + v + "'"};
+            po.phase_floor_given = true;
+        }
+
+        // --phase / --phase-alpha: resolved and checked here for the detector the reconstruction sees (the binned one with --bin),
+        // before any device work. A 2-D filter has no row band: the run is planned as --no-row-band plans it.
+        inline auto check_phase(program_options& po) -> void
+        {
+            if(po.phase_floor_given && !po.phase)
+                throw stage_construction_error{"--phase-floor needs --phase or --phase-alpha"};
+            if(!po.phase)
+                return;
+            auto& s = po.phase_setting;
+            if(po.phase_material && paris_hip_phase_alpha(&po.det_geo, po.phase_delta_beta, po.phase_energy, &s.alpha_mm2) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--phase DELTA_BETA:ENERGY_KEV[:MARGIN]: both must be finite and greater than 0, and give a finite alpha"};
+            if(!(std::isfinite(s.alpha_mm2) && s.alpha_mm2 > 0.f))
+                throw stage_construction_error{"--phase-alpha MM2[:MARGIN]: MM2 must be finite and greater than 0"};
+            if(!po.phase_floor_given)
+                s.t_min = po.flat_path.empty() ? 1e-6f : po.t_min;
+            if(!(s.t_min > 0.f && s.t_min <= 1.f))
+                throw stage_construction_error{"--phase-floor T: T must lie in (0, 1]"};
+            s.margin = po.phase_margin != 0u ? po.phase_margin : paris_hip_phase_default_margin(s.alpha_mm2, po.det_geo.l_px_row, po.det_geo.l_px_col);
+            const int rc = paris_hip_phase_retrieval_check(&s, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col, &po.phase_nx,
+                                                           &po.phase_ny, &po.phase_scratch);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--phase: the padded size " + std::to_string(po.phase_nx) + " x " + std::to_string(po.phase_ny) + " of a "
+                                               + std::to_string(po.det_geo.n_row) + " x " + std::to_string(po.det_geo.n_col) + " frame with a margin of "
+                                               + std::to_string(s.margin) + " exceeds " + std::to_string(PARIS_HIP_PHASE_SIZE_MAX)};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--phase: MARGIN must lie in 1 .. " + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX) + " and the detector's pixel pitches must be positive (got a margin of "
+                                               + std::to_string(s.margin) + ")"};
+            po.phase_bytes = po.phase_scratch + 8u * (std::size_t{po.phase_nx} + po.phase_ny); // twiddles and tables in front of the scratch
+            po.row_band = false;
+        }
+
         // --beam-hardening C1:C2[:C3[:C4]] as typed; refuses anything but two to four numbers
         inline auto parse_beam_hardening(const std::string& v, program_options& po) -> void
         {
@@ -2514,6 +2616,7 @@ namespace paris
         detail::check_rings(po);
         detail::check_voxels(po);
         detail::check_axis(po);
+        detail::check_phase(po);
         detail::check_beam_hardening(po);
         detail::check_roll(po);
         detail::check_metal(po);
@@ -2591,6 +2694,13 @@ namespace paris
                 po.metal_min_path = 0.5f * std::min(r.vol_geo.l_vx_x, std::min(r.vol_geo.l_vx_y, r.vol_geo.l_vx_z));
             detail::metal_prepass(po, r);
         }
+        r.phase = po.phase;
+        r.phase_setting = po.phase_setting;
+        r.phase_l_x = po.det_geo.l_px_row;
+        r.phase_l_y = po.det_geo.l_px_col;
+        r.phase_nx = po.phase_nx;
+        r.phase_ny = po.phase_ny;
+        r.phase_scratch = po.phase_scratch;
         r.detector_roll = po.roll;
         r.roll_deg = po.roll_deg;
         r.lag = po.lag;

@@ -84,6 +84,10 @@ namespace paris
         if(backend::detail::has_ring_correction(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_ring_correct_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                        p.dim_y, 0u, p.dim_y), "weight()");
+        // then with a phase-retrieval setting (backend::set_phase_retrieval) the low-pass of the transmission image: a ring offset is a
+        // per-pixel gain in transmission and must be gone before a 2-D filter smears it; the polynomial acts on the retrieved integral
+        if(backend::detail::has_phase_retrieval(backend::current_ctx()))
+            backend::phase_retrieval(p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y);
         // then with a beam-hardening setting (backend::set_beam_hardening) the polynomial of the line integral: the last step that is
         // not linear in it, so before every weight
         if(backend::detail::has_beam_hardening(backend::current_ctx()))
