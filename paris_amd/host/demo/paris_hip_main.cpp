@@ -193,28 +193,8 @@ int main(int argc, char** argv)
             else if(k == "--min-transmission") po.t_min = std::stof(val());
             else if(k == "--defects") po.defects_path = val();
             else if(k == "--defects-from-flat") po.defects_from_flat = true;
-            else if(k == "--zingers") paris::detail::parse_zingers(val(), po);
-            else if(k == "--zinger-polarity") paris::detail::parse_zinger_polarity(val(), po);
-            else if(k == "--extend-rows") paris::detail::parse_extend_rows(val(), po);
-            else if(k == "--rings") paris::detail::parse_rings(val(), po);
-            else if(k == "--bin") paris::detail::parse_bin(val(), po);
-            else if(k == "--find-axis") paris::detail::parse_find_axis(val(), po);
-            else if(k == "--axis-rows") paris::detail::parse_axis_rows(val(), po);
             else if(k == "--axis-only") po.axis_only = true;
-            else if(k == "--detector-roll") paris::detail::parse_detector_roll(val(), po);
-            else if(k == "--find-roll") paris::detail::parse_find_roll(val(), po);
             else if(k == "--roll-only") po.roll_only = true;
-            else if(k == "--air-region") paris::detail::parse_air_region(val(), po);
-            else if(k == "--phase") paris::detail::parse_phase(val(), po, true);
-            else if(k == "--phase-alpha") paris::detail::parse_phase(val(), po, false);
-            else if(k == "--phase-floor") paris::detail::parse_phase_floor(val(), po);
-            else if(k == "--beam-hardening") paris::detail::parse_beam_hardening(val(), po);
-            else if(k == "--fit-beam-hardening") paris::detail::parse_fit_beam_hardening(val(), po);
-            else if(k == "--lag") paris::detail::parse_lag(val(), po);
-            else if(k == "--lag-start") paris::detail::parse_lag_start(val(), po);
-            else if(k == "--metal") paris::detail::parse_metal(val(), po);
-            else if(k == "--voxel-type") paris::detail::parse_voxel_type(val(), po);
-            else if(k == "--voxel-range") paris::detail::parse_voxel_range(val(), po);
             else if(k == "--no-row-band") po.row_band = false;
             else if(k == "--window")
             {
@@ -229,6 +209,7 @@ int main(int argc, char** argv)
             else if(k == "--no-read-ahead") po.read_ahead = false;
             else if(k == "--pipeline-slabs") po.pipeline_slabs = std::stoi(val());
             else if(k == "--drain-chunk-kib") po.drain_chunk_bytes = static_cast<std::size_t>(std::stoull(val())) << 10;
+            else if(const auto parse = paris::detail::find_option_parser(k)) parse(val(), po); // the options paris/options.h reads
             else throw paris::stage_construction_error{"unknown option " + k};
         }
         if(geometry.empty())

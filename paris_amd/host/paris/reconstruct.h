@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "frame_rows.h"
+#include "options.h"
 #include "sink.h"
 #include "source.h"
 #include "types.h"
@@ -49,170 +50,6 @@ namespace paris
     static_assert(his::pixel_u8 == PARIS_HIP_PIXEL_U8 && his::pixel_u16 == PARIS_HIP_PIXEL_U16 && his::pixel_u32 == PARIS_HIP_PIXEL_U32
                       && his::pixel_f32 == PARIS_HIP_PIXEL_F32,
                   "his::pixel_type names the pixel types of paris_hip_upload_projection_raw");
-
-    // --voxel-type / --voxel-range as given (program_options, below); what a drain thread needs to know about the output
-    struct voxel_output
-    {
-        int type = 0;             // 0: float voxels into the DDBVF; PARIS_HIP_VOXEL_U8 / _U16
-        bool range_given = false; // --voxel-range was given
-        bool automatic = false;   // ... as auto
-        float lo = 0.f, hi = 0.f;
-        double p_lo = 0.1, p_hi = 99.9;
-    };
-
-    // src/program_options.h:34-50 (the parts the hot path needs)
-    struct program_options
-    {
-        detector_geometry det_geo{};
-        bool enable_io = false;
-        std::string input_path, output_path, prefix = "vol";
-        bool enable_roi = false;
-        region_of_interest roi{};
-        bool enable_angles = false;
-        std::string angle_path;
-        std::uint16_t quality = 1;
-        int slabs = 0;     // 0: memory driven (reference behaviour); > 0: fixed slab count
-        int devices = 0;   // 0: all
-        int slots = 4;     // pinned upload buffers per device
-        bool f16 = false;  // store filtered projections as IEEE half before backprojection (BASELINE config 5)
-        int batch = 32;    // projections per fused backprojection launch, up to 64 (1: one launch per projection, as the reference)
-        // pinned staging per buffer for the volume's way to the file: small, because pinning costs more than it saves (two
-        // 256 MiB buffers added 0.4 s to a 1.3 s reconstruction; 16 MiB chunks still run the copy at full rate)
-        std::size_t drain_chunk_bytes = std::size_t{16} << 20;
-        int window = PARIS_HIP_WINDOW_RAMP; // filter window (extension: PARIS_HIP_WINDOW_SHEPP_LOGAN; the reference has the ramp only)
-        bool row_band = true; // f4: per slab, upload / weight / filter only the detector rows the slab can read
-        // several devices: 1 = the device threads of a pass share one read-once frame source (source.h: shared_frames), 0 = each reads
-        // the files through a stream of its own (only its slab's detector rows when row_band is on), -1 = decided by how many
-        // detector rows the slabs of a pass need between them (run())
-        int share_frames = -1;
-        bool read_ahead = true;  // frames are read and converted by a feed thread per device, ahead of the device thread
-        bool two_volumes = true; // a device with several slabs to do keeps two volume buffers when memory allows (drain thread, below)
-        // memory-driven split that gives every device one slab of at least 1 GiB: cut each into this many (0: leave it), so that all
-        // but the last of a device's slabs go to the file while the next one is reconstructed
-        int pipeline_slabs = 4;
-        // Parker redundancy weighting of a short scan (extension): [start, start + range] is derived by run() from the first and last
-        // angle of the frames the run uses, before any device work (detail::derive_short_scan)
-        bool short_scan = false;
-        paris_short_scan scan{};
-        // redundancy weighting of an offset-detector (half-fan) full circle (extension): run() checks the detector's overlap and that
-        // the frames cover the circle, before any device work (detail::check_offset_detector)
-        bool offset_detector = false;
-        // dark / flat correction of intensity frames to line integrals (extension): --flat / --dark name HIS files whose frames are
-        // averaged into one reference frame each by run(), before any device work (detail::load_flat_field); every device ctx gets
-        // them and uploads frames through the corrected upload (detail::frame_chain::upload)
-        std::string flat_path, dark_path;
-        float t_min = 1e-5f;
-        std::shared_ptr<const his::mean> flat, dark; // filled by run(); dark may stay empty (a zero dark)
-        // repair of defective detector pixels (extension): --defects names a file of n_col x n_row raw bytes
-        // (nonzero = defective), read by run() before any device work (detail::load_defects); --defects-from-flat ORs in the pixels
-        // the flat-field setting finds dead (paris_hip_flat_field_dead_pixels; needs --flat). Every device ctx gets the map, and each
-        // frame is repaired after the dark / flat correction and before the weights
-        std::string defects_path;
-        bool defects_from_flat = false;
-        std::shared_ptr<const std::vector<std::uint8_t>> defect_mask; // filled by run() from --defects
-        std::size_t defect_bytes = 0; // filled by run(): what the plan of --defects occupies on a device
-        // removal of per-frame outlier pixels (extension): --zingers ABS[:REL] and --zinger-polarity
-        // bright|dark|both (default: dark with --flat, where a hit's high count is a deep negative line integral, else bright), checked
-        // by run() before any device work (detail::check_zingers). Every device ctx gets the setting, and each frame is filtered after
-        // the defect repair and before the weights
-        bool zingers = false;
-        float zinger_abs = 0.f, zinger_rel = 0.f;
-        int zinger_polarity = 2;      // +1 bright, -1 dark, 0 both; 2: the default, resolved by run()
-        std::size_t zinger_bytes = 0; // filled by run(): what the setting occupies on a device
-        // normalisation of every frame to an air region (extension): --air-region X0:Y0:W:H[:LIMIT], a rectangle
-        // of the frame the reconstruction sees (the binned frame with --bin) that sees only air in every view, checked by run()
-        // before any device work (detail::check_air_region). Every device ctx gets the setting, with the defect map's mask if there
-        // is one, and each frame has the rectangle's mean line integral subtracted directly after the correction
-        bool air = false;
-        paris_hip_air_region air_region{};
-        std::size_t air_bytes = 0; // filled by run(): what the setting occupies on a device
-        // removal of ring artefacts (extension): --rings H[:FLOOR[:LIMIT]], checked by run() before any device
-        // work (detail::check_rings). run() then reads the scan once on the first device (detail::ring_prepass): every frame goes
-        // through the chain the reconstruction uses -- correction, repair, zinger filter -- into the profile, and the rule's correction
-        // frame is kept here. Every device ctx gets it, and each frame is corrected after the zinger filter and before the weights
-        bool rings = false;
-        std::uint32_t ring_half_width = 0;
-        float ring_floor = 0.f, ring_limit = 0.f;
-        std::size_t ring_bytes = 0;                             // filled by run(): what the correction frame occupies on a device
-        std::shared_ptr<const std::vector<float>> ring_c;       // filled by run(): the correction frame
-        // the rotation axis from the scan itself (extension): --find-axis LO:HI[:STEP] [--axis-rows R]
-        // [--axis-only], checked by run() before any device work (detail::check_axis). run() then reads the scan once on the first
-        // device (detail::prepass, the ring filter's pre-pass: with --rings each group of frames feeds both), scores the candidates
-        // and replaces det_geo.delta_s by the estimate before anything is derived from it
-        bool find_axis = false, axis_only = false;
-        float axis_lo = 0.f, axis_hi = 0.f, axis_step = 0.25f;
-        std::uint32_t axis_rows = 2;
-        bool axis_rows_given = false;
-        std::uint32_t axis_count = 0, axis_frames = 0;          // filled by run(): the candidates, and the frames of the circle
-        // beam-hardening correction (extension): --beam-hardening C1:C2[:C3[:C4]] gives the polynomial of the
-        // line integral, --fit-beam-hardening N[:SLICES[:MARGIN]] has run() fit it from the scan itself (detail::bh_prepass, after the
-        // ring pre-pass and the axis search): both checked by run() before any device work (detail::check_beam_hardening). Every
-        // device ctx gets the setting, and each frame is corrected after the ring correction and before every weight
-        bool beam_hardening = false, fit_beam_hardening = false;
-        paris_hip_beam_hardening bh{};                          // as given, or filled by run() with the fitted coefficients
-        std::uint32_t bh_slices = 32, bh_margin = 2;            // the fit's slab -- the central slices of the volume -- and its margin
-        // single-distance phase retrieval (extension): --phase DELTA_BETA:ENERGY_KEV[:MARGIN] gives the material
-        // and the energy, --phase-alpha MM2[:MARGIN] the filter's alpha at the detector plane itself; --phase-floor T the floor of the
-        // retrieved transmission (default: the flat field's t_min, else 1e-6). Checked by run() before any device work, for the binned
-        // detector with --bin (detail::check_phase). Every device ctx gets the setting, and each frame is filtered -- as a whole: the run
-        // is planned without the row band -- after the ring correction and before the beam-hardening polynomial
-        bool phase = false, phase_material = false, phase_floor_given = false;
-        double phase_delta_beta = 0.0, phase_energy = 0.0;
-        std::uint32_t phase_margin = 0;                         // 0: not given; run() takes paris_hip_phase_default_margin
-        paris_hip_phase_retrieval phase_setting{};              // alpha as given; the rest filled by run()
-        std::uint32_t phase_nx = 0, phase_ny = 0;               // filled by run(): the padded size
-        std::size_t phase_scratch = 0, phase_bytes = 0;         // filled by run(): the scratch, and what the setting occupies on a device
-        // correction of the detector's in-plane rotation (extension): --detector-roll DEG gives the angle,
-        // --find-roll LO:HI[:STEP] [--roll-only] has run() find it from the scan mean of the ring profile pre-pass (detail::prepass,
-        // after the axis search, whose delta_s it uses): both checked by run() before any device work (detail::check_roll). Every
-        // device ctx gets the setting, and each frame is resampled into a second buffer of its slot after the beam-hardening
-        // correction and before every weight; everything after reads that buffer
-        bool roll = false, find_roll = false, roll_only = false;
-        float roll_deg = 0.f;                                   // as given, or filled by run() with the estimate
-        float roll_lo = 0.f, roll_hi = 0.f, roll_step = 0.25f;
-        std::uint32_t roll_count = 0;                           // filled by run(): the candidates
-        // detector binning (extension): --bin BX[:BY], each 1, 2, 4 or 8; 1 x 1 is no binning. run() checks the
-        // setting before any device work and replaces det_geo by the binned geometry (detail::apply_binning), so that everything
-        // derived from it follows; the dark and flat means and the defect mask are binned on the host, the frames on the device, each
-        // between its raw upload into a full-width slot and the correction
-        std::uint32_t bin_x = 1, bin_y = 1;
-        std::uint32_t src_row = 0, src_col = 0;                         // filled by run() with binning: the source detector (0: no binning)
-        std::shared_ptr<const std::vector<std::uint8_t>> bin_mask;      // filled by run(): the bad source pixels left out of their bins (may be empty)
-        bool binning() const { return src_row != 0; }
-        // correction of the detector's lag (extension): --lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] gives the weights and
-        // decay rates per frame of the panel's impulse response, --lag-start rest|steady how a pass over the scan starts (steady: the
-        // beam was on before the first frame, the default), checked by run() before any device work (detail::check_lag): it needs
-        // --flat, because the frames must be counts, and every frame of the scan (no --quality above 1). Every device ctx gets the
-        // setting; each pass over the scan opens a sequence for the rows it uploads, corrects every frame between its raw upload (and
-        // binning) and the dark / flat correction, which then runs as a pass of its own, and closes the sequence after the last frame
-        bool lag = false, lag_start_given = false;
-        paris_hip_lag_model lag_model{0u, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, PARIS_HIP_LAG_START_STEADY};
-        // metal artefact reduction by linear interpolation (extension): --metal THR[:GROW[:MIN_PATH]] -- THR in
-        // the volume's own units, GROW pixels the trace is widened by (default 1), MIN_PATH [mm] of metal a ray must cross (default:
-        // half the smallest voxel edge) -- checked by run() before any device work (detail::check_metal). run() then reconstructs the
-        // scan once on the first device (detail::metal_prepass, after every other pre-pass, with their results in force), collects
-        // the voxels above THR, forward-projects their mask and packs the traces. Every device ctx gets the traces and the list; each
-        // frame is inpainted after the roll and before the redundancy weights, and each slab gets its metal voxels back at its end
-        bool metal = false;
-        float metal_threshold = 0.f, metal_min_path = -1.f;     // min_path < 0: not given; run() resolves it from the voxel size
-        std::uint32_t metal_grow = 1;
-        std::uint32_t metal_views = 0;                          // filled by run(): the views the traces cover
-        std::shared_ptr<const std::vector<std::uint64_t>> metal_bits, metal_index; // filled by run(): the packed traces; the list's indices
-        std::shared_ptr<const std::vector<float>> metal_value;  // filled by run(): the list's values
-        std::size_t metal_bytes = 0;                            // filled by run(): what both settings occupy on a device
-        // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
-        // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
-        // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
-        bool extend_rows = false;
-        std::uint32_t extend_taper = 0, extend_edge = 4;
-        std::size_t extend_bytes = 0; // filled by run(): the response vector a device keeps while set
-        // voxels written as 8- or 16-bit integers over a grey window (extension): --voxel-type u8|u16 with
-        // --voxel-range LO:HI or auto[:P_LO:P_HI], checked by run() before any device work (detail::check_voxels). The drain threads
-        // then quantise each chunk on the device and copy 1 or 2 bytes per voxel down; the file is <name>.raw with <name>.mhd beside
-        // it. auto: the window between two percentiles of the finished volume's histogram -- one slab on one device only.
-        // Without --voxel-type (0) the float DDBVF is written as ever.
-        voxel_output voxels;
-    };
 
     // src/task.h:33-57
     struct task
@@ -597,6 +434,8 @@ namespace paris
         // upload (grouped = false: n = 1 at stride 0) or for n slots from `first` on in one call each (grouped: at the slots' stride).
         // reconstruct() runs all of it either way; the ring / axis / roll pre-pass stops after clean(), the fit pre-pass puts its unit
         // polynomial into linearise(). Every pass runs only where its setting was made, on the rows the plan gives it (frame_rows.h).
+        // The settings themselves are read and checked in options.h; the three pre-passes run the chain from the callbacks of one
+        // walk over the scan (prepass_scope and walk_scan, below), the main loop from its own read-ahead feed (frame_feed).
         struct frame_chain
         {
             paris_hip_ctx* ctx;
@@ -1350,42 +1189,6 @@ namespace paris
             return scan;
         }
 
-        // --offset-detector: refused here, before any device work, together with --short-scan (that combination needs a different
-        // weight), for a detector whose overlap tau = (n_row / 2 - |delta_s|) l_px_row is below 2 pixels, and unless the frames of the
-        // run (after the quality stride) have monotonic angles whose span plus one mean step reaches 360 degrees within half a step
-        inline auto check_offset_detector(const program_options& po) -> void
-        {
-            if(po.short_scan)
-                throw stage_construction_error{"--offset-detector and --short-scan together: a short scan with an offset detector needs a "
-                                               "different weight"};
-            float gamma_tau = 0.f;
-            if(paris_hip_offset_detector_check(&po.det_geo, &gamma_tau) != PARIS_HIP_SUCCESS)
-            {
-                char msg[256];
-                std::snprintf(msg, sizeof msg, "--offset-detector: the overlap tau = (n_row / 2 - |delta_s|) = %.4f pixels (n_row %u, delta_s %.4f); "
-                              "the weight needs at least 2", static_cast<double>(po.det_geo.n_row) / 2.0 - std::abs(static_cast<double>(po.det_geo.delta_s)),
-                              po.det_geo.n_row, static_cast<double>(po.det_geo.delta_s));
-                throw stage_construction_error{msg};
-            }
-            const auto a = frame_angles(po.input_path, po.enable_angles, po.angle_path, po.quality, po.det_geo.delta_phi);
-            if(a.size() < 2u)
-                throw stage_construction_error{"--offset-detector needs at least two projections"};
-            const bool up = a[1] > a[0];
-            for(std::size_t i = 1; i < a.size(); ++i)
-                if(up ? !(a[i] > a[i - 1]) : !(a[i] < a[i - 1]))
-                    throw stage_construction_error{"--offset-detector: the projection angles are not monotonic (frame " + std::to_string(i) + ": "
-                                                   + std::to_string(a[i]) + " degrees after " + std::to_string(a[i - 1]) + ")"};
-            const double span = std::abs(static_cast<double>(a.back()) - static_cast<double>(a.front()));
-            const double step = span / static_cast<double>(a.size() - 1u);
-            if(360.0 - (span + step) > step / 2.0)
-            {
-                char msg[256];
-                std::snprintf(msg, sizeof msg, "--offset-detector: the projections cover %.4f degrees (%.4f plus one step of %.4f), an offset "
-                              "detector needs a full circle of 360", span + step, span, step);
-                throw stage_construction_error{msg};
-            }
-        }
-
         // --flat / --dark: each file's frames averaged into one reference frame (his::mean_frame), refused here -- before any device
         // work -- when the file cannot be read or holds no frames, when its frames are not the detector's size, when it lies inside
         // --input (it would be read as a projection too), or when t_min is outside (0, 1]
@@ -1463,19 +1266,6 @@ namespace paris
 
     namespace detail
     {
-        // --bin BX[:BY] as typed; BY defaults to BX
-        inline auto parse_bin(const std::string& v, program_options& po) -> void
-        {
-            const auto factor = [&v](const std::string& t) -> std::uint32_t {
-                if(t != "1" && t != "2" && t != "4" && t != "8")
-                    throw stage_construction_error{"--bin BX[:BY]: each factor is 1, 2, 4 or 8 (got '" + v + "')"};
-                return static_cast<std::uint32_t>(t[0] - '0');
-            };
-            const auto colon = v.find(':');
-            po.bin_x = factor(v.substr(0, colon));
-            po.bin_y = colon == std::string::npos ? po.bin_x : factor(v.substr(colon + 1u));
-        }
-
         // --bin: checked here, before any device work; 1 x 1 changes nothing. Otherwise the dark and flat means and the defect mask are
         // binned on the host by the rule the device applies to the frames (paris_hip_bin_frame_host, paris_hip_bin_mask), the dead
         // pixels of the SOURCE references (--defects-from-flat: paris_hip_set_flat_field's rule on D and F) join the source mask first,
@@ -1544,318 +1334,135 @@ namespace paris
             r.binned_col = b_col;
         }
 
-        // --zingers / --zinger-polarity: the default polarity is resolved and the setting checked here, before any device work
-        inline auto check_zingers(program_options& po) -> void
+        // What every pre-pass keeps on the first device while it reads the scan: a ctx, the chain's settings up to the zinger filter
+        // (set_frame_chain) -- with `whole`, those behind it as well (set_chain_back) and, with a roll, the slots' second frames --, one
+        // group of slots, the chain, and the row plan of `band`. A pre-pass declares its own device buffers after the scope, so that
+        // they are freed before the slots and the ctx; everything is gone when the scope ends, before run() plans the slabs.
+        struct prepass_scope
         {
-            if(!po.zingers)
+            prepass_scope(const program_options& po, bool whole, row_range band)
+            : rep{settings(ctx, po, whole)}, slots{ctx, po, slot_shape(po).first, 0u, whole && po.roll, false}, chain{ctx, po, slots, rep.defect_map}
             {
-                if(po.zinger_polarity != 2)
-                    throw stage_construction_error{"--zinger-polarity needs --zingers"};
-                return;
+                const auto roll = paris_hip_detector_roll{po.roll_deg};
+                rows = plan_frame_rows(band, po.det_geo.n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr,
+                                       po.binning() ? po.bin_y : 1u, whole && po.roll ? &roll : nullptr, &po.det_geo);
             }
-            if(po.zinger_polarity == 2)
-                po.zinger_polarity = po.flat_path.empty() ? 1 : -1;
-            const auto setting = paris_hip_zinger_filter{po.zinger_abs, po.zinger_rel, po.zinger_polarity, 0u};
-            const int rc = paris_hip_zinger_filter_check(&setting, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.zinger_bytes);
-            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
-                throw stage_construction_error{"--zingers: the detector has more than 2^32 - 1 pixels"};
-            if(rc != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--zingers ABS[:REL]: the thresholds must be finite, not negative and not both zero (got "
-                                               + std::to_string(po.zinger_abs) + ":" + std::to_string(po.zinger_rel) + ")"};
-        }
 
-        // --voxel-type u8|u16 as typed
-        inline auto parse_voxel_type(const std::string& v, program_options& po) -> void
-        {
-            if(v == "u8") po.voxels.type = PARIS_HIP_VOXEL_U8;
-            else if(v == "u16") po.voxels.type = PARIS_HIP_VOXEL_U16;
-            else throw stage_construction_error{"--voxel-type u8|u16: unknown type " + v};
-        }
+            const device_ctx ctx{0};
+            const device_report rep;
+            const frame_slots slots;
+            const frame_chain chain;
+            frame_rows rows;
 
-        // --voxel-range LO:HI or auto[:P_LO:P_HI] as typed; refuses anything else
-        inline auto parse_voxel_range(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&]() -> stage_construction_error {
-                return stage_construction_error{"--voxel-range LO:HI | auto[:P_LO:P_HI]: cannot read '" + v + "'"};
-            };
-            auto parts = std::vector<std::string>{};
-            for(std::size_t at = 0;;)
+        private:
+            static auto settings(paris_hip_ctx* ctx, const program_options& po, bool whole) -> device_report
             {
-                const auto colon = v.find(':', at);
-                parts.push_back(v.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
-                if(colon == std::string::npos)
+                auto rep = device_report{};
+                set_frame_chain(ctx, po, rep);
+                if(whole)
+                    set_chain_back(ctx, po, rep);
+                return rep;
+            }
+        };
+
+        // a group of frames the walk has read into slots 0 .. count - 1: `first` frames came before it; each frame's metadata; and,
+        // where the pre-pass asked for them, each frame's angle [deg] with its sine and cosine (paris_hip_stage_angle)
+        struct scan_group
+        {
+            std::uint32_t first, count;
+            frame_info* infos;
+            const float *angles, *sines, *cosines;
+        };
+
+        // One pass over the scan for a pre-pass, in groups of po.batch frames as the main loop groups them: every projection the run
+        // uses is read as stored, at the source size, over the plan's source rows, into the scope's pinned slots. each_frame(slot, info)
+        // is called for every frame read, each_group(scan_group) for every group; the walk then synchronizes, so that the group's
+        // pinned buffers and device frames are free again. With --lag the walk is a sequence of its own, from frame 0 of the file, for
+        // the rows the plan uploads. Returns the number of frames. (The main loop's feed, frame_feed, reads ahead on a thread of its
+        // own and is not this.)
+        template<class Frame, class Group>
+        inline auto walk_scan(const prepass_scope& s, const program_options& po, bool with_angles, Frame&& each_frame, Group&& each_group) -> std::uint32_t
+        {
+            const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
+            const auto sn_row = po.binning() ? po.src_row : n_row, sn_col = po.binning() ? po.src_col : n_col;
+            const std::uint32_t batch = slot_shape(po).first;
+            auto infos = std::vector<frame_info>(batch);
+            auto angles = std::vector<float>(batch), sines = std::vector<float>(batch), cosines = std::vector<float>(batch);
+            auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
+            if(po.lag)
+                rt(paris_hip_lag_begin(s.ctx, n_row, n_col, s.rows.up.first, s.rows.up.count), "lag_begin()");
+            std::uint32_t frames = 0;
+            for(bool more = true; more;)
+            {
+                std::uint32_t filled = 0;
+                for(; filled < batch; ++filled)
+                {
+                    auto& p = infos[filled];
+                    p = source.next_raw(s.slots.host(filled), sn_row, sn_col, s.rows.src.first, s.rows.src.count);
+                    if(!p.valid())
+                    {
+                        more = false;
+                        break;
+                    }
+                    if(p.dim_x != sn_row || p.dim_y != sn_col)
+                        throw stage_runtime_error{"projection size does not match the detector geometry"};
+                    if(with_angles)
+                    {
+                        angles[filled] = po.enable_angles ? p.phi : static_cast<float>(p.idx) * po.det_geo.delta_phi;
+                        rt(paris_hip_stage_angle(&po.det_geo, p.idx, po.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle");
+                    }
+                    each_frame(filled, p);
+                }
+                if(filled == 0)
                     break;
-                at = colon + 1u;
+                each_group(scan_group{frames, filled, infos.data(), angles.data(), sines.data(), cosines.data()});
+                rt(paris_hip_ctx_synchronize(s.ctx), "synchronize");
+                frames += filled;
             }
-            const auto number = [&](const std::string& t) -> double {
-                if(t.empty())
-                    throw bad();
-                char* end = nullptr;
-                const double x = std::strtod(t.c_str(), &end);
-                if(end == t.c_str() || *end != '\0')
-                    throw bad();
-                return x;
-            };
-            if(parts.front() == "auto")
-            {
-                if(parts.size() != 1u && parts.size() != 3u)
-                    throw bad();
-                po.voxels.automatic = true;
-                if(parts.size() == 3u)
-                {
-                    po.voxels.p_lo = number(parts[1]);
-                    po.voxels.p_hi = number(parts[2]);
-                }
-            }
-            else
-            {
-                if(parts.size() != 2u)
-                    throw bad();
-                po.voxels.automatic = false;
-                po.voxels.lo = static_cast<float>(number(parts[0]));
-                po.voxels.hi = static_cast<float>(number(parts[1]));
-            }
-            po.voxels.range_given = true;
+            if(po.lag)
+                rt(paris_hip_lag_end(s.ctx), "lag_end()");
+            return frames;
         }
 
-        // --voxel-type / --voxel-range: both or neither, a window the library accepts, and auto only where one drain thread sees the
-        // whole volume -- here, before any device work and before the output directory is made
-        inline auto check_voxels(const program_options& po) -> void
-        {
-            if(po.voxels.type == 0 && !po.voxels.range_given)
-                return;
-            if(po.voxels.type == 0)
-                throw stage_construction_error{"--voxel-range needs --voxel-type u8|u16"};
-            if(!po.voxels.range_given)
-                throw stage_construction_error{"--voxel-type needs --voxel-range LO:HI | auto[:P_LO:P_HI]"};
-            if(po.voxels.automatic)
-            {
-                if(!(po.voxels.p_lo >= 0.0) || !(po.voxels.p_lo < po.voxels.p_hi) || !(po.voxels.p_hi <= 100.0))
-                    throw stage_construction_error{"--voxel-range auto:P_LO:P_HI: the percentiles must satisfy 0 <= P_LO < P_HI <= 100"};
-                if(po.slabs != 1)
-                    throw stage_construction_error{"--voxel-range auto needs the whole volume in one slab on one device: give --slabs 1 (and --devices 1)"};
-                return;
-            }
-            const auto window = paris_hip_volume_window{po.voxels.lo, po.voxels.hi, po.voxels.type};
-            if(paris_hip_volume_window_check(&window) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--voxel-range LO:HI: LO and HI must be finite, with HI > LO by at least 2^-100 (got " + std::to_string(po.voxels.lo)
-                                               + ":" + std::to_string(po.voxels.hi) + ")"};
-        }
-
-        // --air-region X0:Y0:W:H[:LIMIT] as typed; refuses anything but four unsigned integers and an optional number
-        inline auto parse_air_region(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--air-region X0:Y0:W:H[:LIMIT]: cannot read '" + v + "'"}; };
-            auto parts = std::vector<std::string>{};
-            for(std::size_t at = 0;;)
-            {
-                const auto colon = v.find(':', at);
-                parts.push_back(v.substr(at, colon == std::string::npos ? colon : colon - at));
-                if(colon == std::string::npos)
-                    break;
-                at = colon + 1u;
-            }
-            if(parts.size() != 4u && parts.size() != 5u)
-                throw bad();
-            std::uint32_t field[4] = {0, 0, 0, 0};
-            for(int k = 0; k < 4; ++k)
-            {
-                if(parts[k].empty() || parts[k].size() > 9u || parts[k].find_first_not_of("0123456789") != std::string::npos)
-                    throw bad();
-                field[k] = static_cast<std::uint32_t>(std::stoul(parts[k]));
-            }
-            float limit = 0.f;
-            if(parts.size() == 5u)
-            {
-                char* end = nullptr;
-                limit = std::strtof(parts[4].c_str(), &end);
-                if(parts[4].empty() || end == nullptr || *end != '\0')
-                    throw bad();
-            }
-            po.air_region = paris_hip_air_region{field[0], field[1], field[2], field[3], 0u, limit};
-            po.air = true;
-        }
-
-        // --air-region: the rectangle is checked against the detector the reconstruction sees (binned with --bin) here, before any
-        // device work
-        inline auto check_air_region(program_options& po, run_report& r) -> void
-        {
-            if(!po.air)
-                return;
-            r.air_row = po.det_geo.n_row;
-            r.air_col = po.det_geo.n_col;
-            if(paris_hip_air_region_check(&po.air_region, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.air_bytes) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--air-region X0:Y0:W:H[:LIMIT]: W and H at least 1, the rectangle inside the " + std::to_string(po.det_geo.n_row)
-                                               + " x " + std::to_string(po.det_geo.n_col) + " frame, at most 2^20 pixels, LIMIT finite and not negative (got "
-                                               + std::to_string(po.air_region.x0) + ":" + std::to_string(po.air_region.y0) + ":"
-                                               + std::to_string(po.air_region.width) + ":" + std::to_string(po.air_region.height) + ":"
-                                               + std::to_string(po.air_region.limit_abs) + ")"};
-        }
-
-        // --zingers ABS[:REL] as typed; refuses anything that is not one or two numbers
-        inline auto parse_zingers(const std::string& v, program_options& po) -> void
-        {
-            const auto number = [&v](const std::string& t) -> float {
-                std::size_t used = 0;
-                float x = 0.f;
-                try
-                {
-                    x = std::stof(t, &used);
-                }
-                catch(const std::exception&)
-                {
-                    used = 0;
-                }
-                if(t.empty() || used != t.size())
-                    throw stage_construction_error{"--zingers ABS[:REL]: cannot read '" + v + "'"};
-                return x;
-            };
-            const auto colon = v.find(':');
-            po.zinger_abs = number(v.substr(0, colon));
-            po.zinger_rel = colon == std::string::npos ? 0.f : number(v.substr(colon + 1u));
-            po.zingers = true;
-        }
-
-        // --extend-rows W[:M] as typed; refuses anything that is not one or two unsigned integers
-        inline auto parse_extend_rows(const std::string& v, program_options& po) -> void
-        {
-            const auto number = [&v](const std::string& t) -> std::uint32_t {
-                if(t.empty() || t.size() > 9u || t.find_first_not_of("0123456789") != std::string::npos)
-                    throw stage_construction_error{"--extend-rows W[:M]: cannot read '" + v + "'"};
-                return static_cast<std::uint32_t>(std::stoul(t));
-            };
-            const auto colon = v.find(':');
-            po.extend_taper = number(v.substr(0, colon));
-            po.extend_edge = colon == std::string::npos ? 4u : number(v.substr(colon + 1u));
-            po.extend_rows = true;
-        }
-
-        // --extend-rows: the setting is checked for this detector here, before any device work
-        inline auto check_extend_rows(program_options& po) -> void
-        {
-            if(!po.extend_rows)
-                return;
-            const auto setting = paris_hip_row_extension{po.extend_edge, po.extend_taper};
-            if(paris_hip_row_extension_check(&setting, po.det_geo.n_row) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--extend-rows W[:M]: W must lie in 1 .. 16384 and M must be 1, 2, 4 or 8 and at most n_row (got "
-                                               + std::to_string(po.extend_taper) + ":" + std::to_string(po.extend_edge) + ")"};
-            po.extend_bytes = std::size_t{po.det_geo.n_row} * sizeof(float);
-        }
-
-        // --rings H[:FLOOR[:LIMIT]] as typed; refuses anything that is not an unsigned integer and up to two numbers
-        inline auto parse_rings(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: cannot read '" + v + "'"}; };
-            const auto number = [&bad](const std::string& t) -> float {
-                std::size_t used = 0;
-                float x = 0.f;
-                try
-                {
-                    x = std::stof(t, &used);
-                }
-                catch(const std::exception&)
-                {
-                    used = 0;
-                }
-                if(t.empty() || used != t.size())
-                    throw bad();
-                return x;
-            };
-            const auto first = v.find(':');
-            const auto second = first == std::string::npos ? first : v.find(':', first + 1u);
-            const auto h = v.substr(0, first);
-            if(h.empty() || h.size() > 9u || h.find_first_not_of("0123456789") != std::string::npos
-               || (second != std::string::npos && v.find(':', second + 1u) != std::string::npos))
-                throw bad();
-            po.ring_half_width = static_cast<std::uint32_t>(std::stoul(h));
-            po.ring_floor = first == std::string::npos ? 0.f : number(v.substr(first + 1u, second == std::string::npos ? second : second - first - 1u));
-            po.ring_limit = second == std::string::npos ? 0.f : number(v.substr(second + 1u));
-            po.rings = true;
-        }
-
-        // --rings: the setting is checked for this detector here, before any device work
-        inline auto check_rings(program_options& po) -> void
-        {
-            if(!po.rings)
-                return;
-            const auto setting = paris_hip_ring_filter{po.ring_half_width, po.ring_floor, po.ring_limit};
-            const int rc = paris_hip_ring_filter_check(&setting, po.det_geo.n_row, po.det_geo.n_col, nullptr, &po.ring_bytes);
-            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
-                throw stage_construction_error{"--rings: the detector has more than 2^32 - 1 pixels"};
-            if(rc != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: H must lie in 1 .. 32, FLOOR must be finite and not negative, LIMIT 0 (none) or "
-                                               "finite and above FLOOR (got " + std::to_string(po.ring_half_width) + ":" + std::to_string(po.ring_floor)
-                                               + ":" + std::to_string(po.ring_limit) + ")"};
-        }
-
-        // --rings and --find-axis: the pre-pass. Every projection the run uses is read once on the first device and goes through the
-        // chain the reconstruction uses, as far as the zinger filter (frame_chain: upload() and clean()), into the ring
-        // profile (rings), into the axis search's sinogram (axis), or into both: a group of po.batch frames per call as the main loop
-        // groups them. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by the row
-        // plan as a slab's band is. Then the ring rule makes the correction frame,
-        // which is kept in po, and the search gives its estimate, which is kept in r. Everything allocated here is freed before it
-        // returns: run() plans the slabs afterwards.
+        // --rings and --find-axis: the pre-pass. Every projection the run uses goes through the chain the reconstruction uses, as far
+        // as the zinger filter (frame_chain: upload() and clean()), into the ring profile (rings), into the axis search's sinogram
+        // (axis), or into both. With rings the frames are read whole; for the axis alone only the search's band of rows, widened by
+        // the row plan as a slab's band is. Then the ring rule makes the correction frame, which is kept in po, and the search gives
+        // its estimate, which is kept in r.
         inline auto prepass(program_options& po, run_report& r, bool rings, bool axis, bool roll = false) -> void
         {
             const bool profile = rings || roll; // --find-roll scores the scan mean, which the ring profile makes
             const auto t_start = clock::now();
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
             const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
-            const std::uint32_t batch = slot_shape(po).first;
-            // --bin: the profile is taken on binned frames; the source frames go through the slots' full-width frames
-            const bool binning = po.binning();
-            const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
             {
-                const device_ctx ctx{0};
-                auto rep = device_report{};
-                set_frame_chain(ctx, po, rep);
-                const frame_slots slots{ctx, po, batch, 0u, false, false};
-                const frame_chain chain{ctx, po, slots, rep.defect_map};
-                // the rows of every frame that are filtered and consumed: all of them, or the search's band; the plan widens them
+                // the rows of every frame that are filtered and consumed: all of them, or the search's band; the plan widens them.
+                // (--bin: the profile is taken on binned frames; the source frames go through the slots' full-width frames)
                 auto band = row_range{0u, n_col};
                 if(axis && !profile)
                 {
                     rt(paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, &band.first, nullptr), "axis_search_check()");
                     band.count = po.axis_rows;
                 }
-                const auto rows = plan_frame_rows(band, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr, binning ? po.bin_y : 1u);
+                const prepass_scope s{po, false, band};
+                const auto& ctx = s.ctx;
                 if(profile)
                     rt(paris_hip_ring_profile_begin(ctx, n_row, n_col), "ring_profile_begin()");
                 if(axis)
                     rt(paris_hip_axis_search_begin(ctx, &search, &po.det_geo, po.axis_frames), "axis_search_begin()");
-                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
-                std::uint32_t frames = 0;
-                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
-                for(bool more = true; more;)
-                {
-                    std::uint32_t filled = 0;
-                    for(; filled < batch; ++filled)
-                    {
-                        const auto p = source.next_raw(slots.host(filled), sn_row, sn_col, rows.src.first, rows.src.count);
-                        if(!p.valid())
-                        {
-                            more = false;
-                            break;
-                        }
-                        if(p.dim_x != sn_row || p.dim_y != sn_col)
-                            throw stage_runtime_error{"projection size does not match the detector geometry"};
-                        chain.upload(filled, p.pixel, rows);
-                    }
-                    if(filled == 0)
-                        break;
-                    if(axis && filled > po.axis_frames - frames)
-                        throw stage_runtime_error{"--find-axis: the input holds more frames than were counted"};
-                    chain.clean(0u, filled, true, rows);
-                    if(profile)
-                        rt(paris_hip_ring_profile_add_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, 0u, n_col), "ring_profile_add_rows()");
-                    if(axis)
-                        rt(paris_hip_axis_search_add_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, frames), "axis_search_add_rows()");
-                    rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the group's pinned buffers and device frames are free again
-                    frames += filled;
-                }
-                if(po.lag)
-                    rt(paris_hip_lag_end(ctx), "lag_end()");
+                const auto frames = walk_scan(
+                    s, po, false, [&](std::uint32_t slot, const frame_info& p) { s.chain.upload(slot, p.pixel, s.rows); },
+                    [&](const scan_group& g) {
+                        if(axis && g.count > po.axis_frames - g.first)
+                            throw stage_runtime_error{"--find-axis: the input holds more frames than were counted"};
+                        s.chain.clean(0u, g.count, true, s.rows);
+                        if(profile)
+                            rt(paris_hip_ring_profile_add_rows(ctx, s.slots.frame(0u), s.slots.pitch, s.slots.stride, g.count, n_row, n_col, 0u, n_col),
+                               "ring_profile_add_rows()");
+                        if(axis)
+                            rt(paris_hip_axis_search_add_rows(ctx, s.slots.frame(0u), s.slots.pitch, s.slots.stride, g.count, n_row, n_col, g.first),
+                               "axis_search_add_rows()");
+                    });
                 if(po.air)
                     rt(paris_hip_air_stats(ctx, &r.air_prepass, 0), "air stats");
                 auto mean = std::vector<float>(roll ? static_cast<std::size_t>(n_row) * n_col : 0u); // --find-roll: the scan mean
@@ -1912,175 +1519,23 @@ namespace paris
                 r.axis_prepass_s = since(t_start);
         }
 
-        // the fields of a colon-separated option value; an empty field stays in as an empty string
-        inline auto colon_fields(const std::string& v) -> std::vector<std::string>
-        {
-            auto out = std::vector<std::string>{};
-            std::size_t at = 0;
-            for(;;)
-            {
-                const auto next = v.find(':', at);
-                out.push_back(v.substr(at, next == std::string::npos ? next : next - at));
-                if(next == std::string::npos)
-                    return out;
-                at = next + 1u;
-            }
-        }
-
-        // --phase DELTA_BETA:ENERGY_KEV[:MARGIN] (material = true) or --phase-alpha MM2[:MARGIN] as typed; refuses anything but the numbers
-        // and an unsigned margin
-        inline auto parse_phase(const std::string& v, program_options& po, bool material) -> void
-        {
-            const auto name = std::string{material ? "--phase DELTA_BETA:ENERGY_KEV[:MARGIN]" : "--phase-alpha MM2[:MARGIN]"};
-            const auto field = colon_fields(v);
-            const auto numbers = material ? std::size_t{2} : std::size_t{1};
-            if(field.size() < numbers || field.size() > numbers + 1u)
-                throw stage_construction_error{name + ": cannot read '" + v + "'"};
-            double value[2] = {0.0, 0.0};
-            for(std::size_t k = 0; k < numbers; ++k)
-            {
-                char* end = nullptr;
-                value[k] = std::strtod(field[k].c_str(), &end);
-                if(field[k].empty() || end == nullptr || *end != '\0')
-                    throw stage_construction_error{name + ": cannot read '" + v + "'"};
-            }
-            po.phase_margin = 0u;
-            if(field.size() > numbers)
-            {
-                const auto& m = field[numbers];
-                if(m.empty() || m.size() > 9u || m.find_first_not_of("0123456789") != std::string::npos)
-                    throw stage_construction_error{name + ": cannot read '" + v + "'"};
-                po.phase_margin = static_cast<std::uint32_t>(std::stoul(m));
-                if(po.phase_margin == 0u)
-                    throw stage_construction_error{name + ": MARGIN must lie in 1 .. " + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX)};
-            }
-            if(po.phase)
-                throw stage_construction_error{"--phase and --phase-alpha cannot be combined: give the material or the filter's alpha"};
-            po.phase = true;
-            po.phase_material = material;
-            po.phase_delta_beta = value[0];
-            po.phase_energy = value[1];
-            po.phase_setting.alpha_mm2 = material ? 0.f : static_cast<float>(value[0]);
-        }
-
-        inline auto parse_phase_floor(const std::string& v, program_options& po) -> void
-        {
-            char* end = nullptr;
-            po.phase_setting.t_min = std::strtof(v.c_str(), &end);
-            if(v.empty() || end == nullptr || *end != '\0')
-                throw stage_construction_error{"--phase-floor T: cannot read '" + v + "'"};
-            po.phase_floor_given = true;
-        }
-
-        // --phase / --phase-alpha: resolved and checked here for the detector the reconstruction sees (the binned one with --bin),
-        // before any device work. A 2-D filter has no row band: the run is planned as --no-row-band plans it.
-        inline auto check_phase(program_options& po) -> void
-        {
-            if(po.phase_floor_given && !po.phase)
-                throw stage_construction_error{"--phase-floor needs --phase or --phase-alpha"};
-            if(!po.phase)
-                return;
-            auto& s = po.phase_setting;
-            if(po.phase_material && paris_hip_phase_alpha(&po.det_geo, po.phase_delta_beta, po.phase_energy, &s.alpha_mm2) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--phase DELTA_BETA:ENERGY_KEV[:MARGIN]: both must be finite and greater than 0, and give a finite alpha"};
-            if(!(std::isfinite(s.alpha_mm2) && s.alpha_mm2 > 0.f))
-                throw stage_construction_error{"--phase-alpha MM2[:MARGIN]: MM2 must be finite and greater than 0"};
-            if(!po.phase_floor_given)
-                s.t_min = po.flat_path.empty() ? 1e-6f : po.t_min;
-            if(!(s.t_min > 0.f && s.t_min <= 1.f))
-                throw stage_construction_error{"--phase-floor T: T must lie in (0, 1]"};
-            s.margin = po.phase_margin != 0u ? po.phase_margin : paris_hip_phase_default_margin(s.alpha_mm2, po.det_geo.l_px_row, po.det_geo.l_px_col);
-            const int rc = paris_hip_phase_retrieval_check(&s, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col, &po.phase_nx,
-                                                           &po.phase_ny, &po.phase_scratch);
-            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
-                throw stage_construction_error{"--phase: the padded size " + std::to_string(po.phase_nx) + " x " + std::to_string(po.phase_ny) + " of a "
-                                               + std::to_string(po.det_geo.n_row) + " x " + std::to_string(po.det_geo.n_col) + " frame with a margin of "
-                                               + std::to_string(s.margin) + " exceeds " + std::to_string(PARIS_HIP_PHASE_SIZE_MAX)};
-            if(rc != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--phase: MARGIN must lie in 1 .. " + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX) + " and the detector's pixel pitches must be positive (got a margin of "
-                                               + std::to_string(s.margin) + ")"};
-            po.phase_bytes = po.phase_scratch + 8u * (std::size_t{po.phase_nx} + po.phase_ny); // twiddles and tables in front of the scratch
-            po.row_band = false;
-        }
-
-        // --beam-hardening C1:C2[:C3[:C4]] as typed; refuses anything but two to four numbers
-        inline auto parse_beam_hardening(const std::string& v, program_options& po) -> void
-        {
-            const auto field = colon_fields(v);
-            if(field.size() < 2u || field.size() > PARIS_HIP_BH_DEGREE_MAX)
-                throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: cannot read '" + v + "'"};
-            po.bh = paris_hip_beam_hardening{};
-            po.bh.degree = static_cast<std::uint32_t>(field.size());
-            for(std::size_t k = 0; k < field.size(); ++k)
-            {
-                char* end = nullptr;
-                po.bh.c[k] = std::strtof(field[k].c_str(), &end);
-                if(field[k].empty() || end == nullptr || *end != '\0')
-                    throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: cannot read '" + v + "'"};
-            }
-            po.beam_hardening = true;
-        }
-
-        // --fit-beam-hardening N[:SLICES[:MARGIN]] as typed; refuses anything but one to three unsigned numbers
-        inline auto parse_fit_beam_hardening(const std::string& v, program_options& po) -> void
-        {
-            const auto field = colon_fields(v);
-            std::uint32_t value[3] = {0u, 32u, 2u};
-            if(field.empty() || field.size() > 3u)
-                throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: cannot read '" + v + "'"};
-            for(std::size_t k = 0; k < field.size(); ++k)
-            {
-                if(field[k].empty() || field[k].size() > 9u || field[k].find_first_not_of("0123456789") != std::string::npos)
-                    throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: cannot read '" + v + "'"};
-                value[k] = static_cast<std::uint32_t>(std::stoul(field[k]));
-            }
-            po.bh = paris_hip_beam_hardening{};
-            po.bh.degree = value[0];
-            po.bh_slices = value[1];
-            po.bh_margin = value[2];
-            po.fit_beam_hardening = true;
-        }
-
-        // --beam-hardening / --fit-beam-hardening: checked here, before any device work. The fit's pre-pass reads whole frames of the
-        // detector the reconstruction sees: it has no full-width slots to bin from, so --bin is refused with it.
-        inline auto check_beam_hardening(const program_options& po) -> void
-        {
-            if(po.beam_hardening && po.fit_beam_hardening)
-                throw stage_construction_error{"--beam-hardening and --fit-beam-hardening cannot be combined: give the coefficients or have them fitted"};
-            if(po.beam_hardening && paris_hip_beam_hardening_check(&po.bh) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--beam-hardening C1:C2[:C3[:C4]]: every coefficient must be finite"};
-            if(!po.fit_beam_hardening)
-                return;
-            if(po.bh.degree < 1u || po.bh.degree > PARIS_HIP_BH_DEGREE_MAX || po.bh_slices < 1u || po.bh_margin > PARIS_HIP_BH_MARGIN_MAX)
-                throw stage_construction_error{"--fit-beam-hardening N[:SLICES[:MARGIN]]: N must lie in 1 .. 4, SLICES must be at least 1 and MARGIN in 0 .. 4 (got "
-                                               + std::to_string(po.bh.degree) + ":" + std::to_string(po.bh_slices) + ":" + std::to_string(po.bh_margin) + ")"};
-            if(po.bh_slices < 2u * po.bh_margin + 1u)
-                throw stage_construction_error{"--fit-beam-hardening: " + std::to_string(po.bh_slices) + " slice(s) hold no voxel with a margin of "
-                                               + std::to_string(po.bh_margin) + " on both sides"};
-            if(po.binning())
-                throw stage_construction_error{"--fit-beam-hardening cannot be combined with --bin: its pre-pass reads the frames at the detector's size"};
-            if(po.axis_only)
-                throw stage_construction_error{"--fit-beam-hardening cannot be combined with --axis-only: nothing would be fitted"};
-        }
-
-        // --fit-beam-hardening: the pre-pass, after the ring pre-pass and the axis search, whose results it uses. Every projection the
-        // run uses is read once on the first device, whole, in groups of po.batch frames as the main loop groups them; each group goes
-        // N times through the main loop's frame stages -- the raw upload (corrected with --flat), the air normalisation, the defect
-        // repair, the zinger filter, the ring correction -- then, the k-th time, through the pass with the unit setting e_k, the
-        // redundancy weights, weight + filter and the backprojection into the k-th basis slab: the central po.bh_slices slices of the
-        // whole volume. (The group is uploaded again for each k from the pinned frames, which are read once: no device copy of it is
-        // kept.) Then threshold, labels, Gram sums and the solve. Everything allocated here is freed before it
-        // returns: run() plans the slabs afterwards.
+        // --fit-beam-hardening: the pre-pass, after the ring pre-pass and the axis search, whose results it uses. Every projection is
+        // read whole; each group goes N times through the main loop's frame stages -- the raw upload (corrected with --flat), the air
+        // normalisation, the defect repair, the zinger filter, the ring correction -- then, the k-th time, through the pass with the
+        // unit setting e_k, the redundancy weights, weight + filter and the backprojection into the k-th basis slab: the central
+        // po.bh_slices slices of the whole volume. (The group is uploaded again for each k from the pinned frames, which are read once:
+        // no device copy of it is kept.) Then threshold, labels, Gram sums and the solve.
         inline auto bh_prepass(const program_options& po, run_report& r) -> void
         {
             const auto t_start = clock::now();
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
             const auto& vg = r.vol_geo;
             const std::uint32_t degree = po.bh.degree, slices = po.bh_slices, z_first = (vg.dim_z - slices) / 2u;
-            const std::uint32_t batch = slot_shape(po).first;
-            auto infos = std::vector<frame_info>(batch);
             {
-                const device_ctx ctx{0};
+                // whole frames: every range of the plan is the detector. (No polynomial and no roll yet: check_beam_hardening, check_roll)
+                const prepass_scope s{po, true, row_range{0u, n_col}};
+                const auto& ctx = s.ctx;
+                const auto& slots = s.slots;
                 struct fit_buffers // the basis slabs and the labels
                 {
                     paris_hip_ctx* ctx;
@@ -2093,11 +1548,6 @@ namespace paris
                         paris_hip_free(ctx, d_labels);
                     }
                 } fit{ctx, {nullptr, nullptr, nullptr, nullptr}, nullptr};
-                auto rep = device_report{};
-                set_frame_chain(ctx, po, rep);
-                set_chain_back(ctx, po, rep); // (no polynomial and no roll yet: check_beam_hardening, check_roll)
-                const frame_slots slots{ctx, po, batch, 0u, false, false};
-                const frame_chain chain{ctx, po, slots, rep.defect_map};
                 for(std::uint32_t k = 0; k < degree; ++k)
                     rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, slices, &fit.d_slab[k]), "make_volume()");
                 {
@@ -2108,68 +1558,41 @@ namespace paris
                     rt(paris_hip_malloc_volume(ctx, static_cast<std::uint32_t>((voxels + 3u) / 4u), 1u, 1u, &words), "make_volume()");
                     fit.d_labels = reinterpret_cast<std::uint8_t*>(words);
                 }
-                // whole frames: every range of the plan is the detector
-                const auto rows = plan_frame_rows(row_range{0u, n_col}, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr, 1u);
                 const float delta_s = po.det_geo.delta_s * po.det_geo.l_px_row, delta_t = po.det_geo.delta_t * po.det_geo.l_px_col;
                 const auto no_roi = region_of_interest{};
-                auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
-                std::uint32_t frames = 0;
-                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
-                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file, on whole frames
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
-                for(bool more = true; more;)
-                {
-                    std::uint32_t filled = 0;
-                    for(; filled < batch; ++filled)
-                    {
-                        infos[filled] = source.next_raw(slots.host(filled), n_row, n_col, rows.src.first, rows.src.count);
-                        const auto& p = infos[filled];
-                        if(!p.valid())
-                        {
-                            more = false;
-                            break;
-                        }
-                        if(p.dim_x != n_row || p.dim_y != n_col)
-                            throw stage_runtime_error{"projection size does not match the detector geometry"};
-                        angles[filled] = po.enable_angles ? p.phi : static_cast<float>(p.idx) * po.det_geo.delta_phi;
-                        rt(paris_hip_stage_angle(&po.det_geo, p.idx, po.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle");
-                    }
-                    if(filled == 0)
-                        break;
+                const auto frames = walk_scan(s, po, true, [](std::uint32_t, const frame_info&) {}, [&](const scan_group& g) {
                     if(po.lag)
                     {
                         // The group goes through the stages once per basis, but the sequence's state must see every frame once: the
                         // counts are corrected once, in time order, and the pinned frames (a slot holds 4 bytes per pixel) are replaced
                         // by the corrected counts as f32, which every basis then uploads (chain.upload: lag already applied).
-                        for(std::uint32_t f = 0; f < filled; ++f)
-                            rt(paris_hip_upload_projection_raw(ctx, slots.frame(f), slots.pitch, slots.host(f), n_row * his::pixel_size(infos[f].pixel), n_row,
-                                                               n_col, infos[f].pixel), "load()");
-                        rt(paris_hip_lag_correct_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, filled, n_row, n_col, 0u, n_col), "lag correction");
-                        for(std::uint32_t f = 0; f < filled; ++f)
+                        for(std::uint32_t f = 0; f < g.count; ++f)
+                            rt(paris_hip_upload_projection_raw(ctx, slots.frame(f), slots.pitch, slots.host(f), n_row * his::pixel_size(g.infos[f].pixel), n_row,
+                                                               n_col, g.infos[f].pixel), "load()");
+                        rt(paris_hip_lag_correct_rows(ctx, slots.frame(0u), slots.pitch, slots.stride, g.count, n_row, n_col, 0u, n_col), "lag correction");
+                        for(std::uint32_t f = 0; f < g.count; ++f)
                         {
                             rt(paris_hip_memcpy_projection_d2h(ctx, slots.host(f), n_row * sizeof(float), slots.frame(f), slots.pitch, n_row, n_col), "copy_d2h()");
-                            infos[f].pixel = his::pixel_f32;
+                            g.infos[f].pixel = his::pixel_f32;
                         }
                         rt(paris_hip_ctx_synchronize(ctx), "synchronize");
                     }
                     for(std::uint32_t k = 0; k < degree; ++k)
                     {
-                        for(std::uint32_t f = 0; f < filled; ++f)
-                            chain.upload(f, infos[f].pixel, rows, true);
+                        for(std::uint32_t f = 0; f < g.count; ++f)
+                            s.chain.upload(f, g.infos[f].pixel, s.rows, true);
                         auto unit = paris_hip_beam_hardening{};
                         unit.degree = k + 1u;
                         unit.c[k] = 1.f;
-                        chain.clean(0u, filled, true, rows);
-                        chain.linearise(0u, filled, true, rows, &unit);
-                        chain.finish(0u, filled, true, rows, angles.data());
-                        rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, filled, n_row, n_col, fit.d_slab[k], vg.dim_x, vg.dim_y, slices,
-                                                       z_first, &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
-                        rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the device frames are free for the next basis or group
+                        s.chain.clean(0u, g.count, true, s.rows);
+                        s.chain.linearise(0u, g.count, true, s.rows, &unit);
+                        s.chain.finish(0u, g.count, true, s.rows, g.angles);
+                        rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, g.count, n_row, n_col, fit.d_slab[k], vg.dim_x, vg.dim_y, slices,
+                                                       z_first, &po.det_geo, &vg, 0, &no_roi, g.sines, g.cosines, delta_s, delta_t), "backproject()");
+                        if(k + 1u < degree) // the device frames are free for the next basis (after the last one the walk synchronizes)
+                            rt(paris_hip_ctx_synchronize(ctx), "synchronize");
                     }
-                    frames += filled;
-                }
-                if(po.lag)
-                    rt(paris_hip_lag_end(ctx), "lag_end()");
+                });
                 if(frames == 0u)
                     throw stage_runtime_error{"--fit-beam-hardening: the input holds no projection"};
                 const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * slices;
@@ -2191,80 +1614,17 @@ namespace paris
             r.bh_prepass_s = since(t_start);
         }
 
-        // --metal THR[:GROW[:MIN_PATH]] as typed; refuses anything but one to three numbers (the ranges: check_metal)
-        inline auto parse_metal(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: cannot read '" + v + "'"}; };
-            auto field = std::vector<std::string>{};
-            for(std::size_t at = 0;;)
-            {
-                const auto colon = v.find(':', at);
-                field.push_back(v.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
-                if(colon == std::string::npos)
-                    break;
-                at = colon + 1u;
-            }
-            if(field.size() > 3u)
-                throw bad();
-            const auto number = [&bad](const std::string& t) -> float {
-                if(t.empty())
-                    throw bad();
-                char* end = nullptr;
-                const float x = std::strtof(t.c_str(), &end);
-                if(end == nullptr || *end != '\0')
-                    throw bad();
-                return x;
-            };
-            po.metal_threshold = number(field[0]);
-            if(field.size() > 1u)
-            {
-                const float g = number(field[1]);
-                if(!(g >= 0.f) || g != std::floor(g) || g > 1e6f)
-                    throw bad();
-                po.metal_grow = static_cast<std::uint32_t>(g);
-            }
-            if(field.size() > 2u)
-            {
-                po.metal_min_path = number(field[2]);
-                if(!(po.metal_min_path >= 0.f)) // (a negative or NaN MIN_PATH must not pass for "not given")
-                    throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: MIN_PATH must be finite and not negative (got " + field[2] + ")"};
-            }
-            po.metal = true;
-        }
-
-        // --metal: checked here, before any device work. The metal outside a region of interest still casts a trace, and the list is
-        // indexed in the whole grid: --roi is refused with it.
-        inline auto check_metal(const program_options& po) -> void
-        {
-            if(!po.metal)
-                return;
-            if(po.enable_roi)
-                throw stage_construction_error{"--metal cannot be combined with --roi: metal outside the region still casts a trace"};
-            if(!std::isfinite(po.metal_threshold))
-                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: THR must be finite"};
-            if(po.metal_grow > PARIS_HIP_METAL_GROW_MAX)
-                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: GROW must lie in 0 .. " + std::to_string(PARIS_HIP_METAL_GROW_MAX) + " (got "
-                                               + std::to_string(po.metal_grow) + ")"};
-            if(po.metal_min_path >= 0.f && !std::isfinite(po.metal_min_path))
-                throw stage_construction_error{"--metal THR[:GROW[:MIN_PATH]]: MIN_PATH must be finite and not negative"};
-            if(po.axis_only || po.roll_only)
-                throw stage_construction_error{"--metal cannot be combined with --axis-only or --roll-only: nothing would be reconstructed"};
-        }
-
         // --metal: the pre-pass, after every other pre-pass, with their results in force (po holds the ring correction, the axis, the
-        // polynomial and the roll by now). Every projection the run uses is read once on the first device, whole, in groups of
-        // po.batch frames, and goes through the main loop's whole frame chain and the backprojection into ONE buffer that holds the
-        // whole grid; each frame's sine and cosine are kept. Then the voxels above the threshold are collected and the volume
-        // binarized, the mask is forward-projected group by group into the slots' frames, and each group packed to the host
-        // (DESIGN.md section 4.21). Everything allocated here is freed before it returns: run() plans the slabs afterwards.
+        // polynomial and the roll by now). Every projection is read whole and goes through the main loop's whole frame chain and the
+        // backprojection into ONE buffer that holds the whole grid; each frame's sine and cosine are kept. Then the voxels above the
+        // threshold are collected and the volume binarized, the mask is forward-projected group by group into the slots' frames, and
+        // each group packed to the host.
         inline auto metal_prepass(program_options& po, run_report& r) -> void
         {
             const auto t_start = clock::now();
             const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
             const auto& vg = r.vol_geo;
             const std::uint32_t batch = slot_shape(po).first;
-            const bool binning = po.binning();
-            const auto sn_row = binning ? po.src_row : n_row, sn_col = binning ? po.src_col : n_col;
             const std::uint32_t words = (n_row + 63u) / 64u;
             const auto voxels = static_cast<std::uint64_t>(vg.dim_x) * vg.dim_y * vg.dim_z;
             std::uint64_t cap = 0;
@@ -2283,66 +1643,39 @@ namespace paris
             auto value = std::make_shared<std::vector<float>>();
             std::uint32_t frames = 0, n_views = 0;
             {
-                const device_ctx ctx{0};
+                // whole frames: every range of the plan is the detector. (No trace and no list yet)
+                const prepass_scope s{po, true, row_range{0u, n_col}};
+                const auto& ctx = s.ctx;
+                const auto& slots = s.slots;
                 struct whole_volume
                 {
                     paris_hip_ctx* ctx;
                     float* d_v;
                     ~whole_volume() { paris_hip_free(ctx, d_v); }
                 } vol{ctx, nullptr};
-                auto rep = device_report{};
-                set_frame_chain(ctx, po, rep);
-                set_chain_back(ctx, po, rep); // (no trace and no list yet)
-                const frame_slots slots{ctx, po, batch, 0u, po.roll, false};
-                const frame_chain chain{ctx, po, slots, rep.defect_map};
                 rt(paris_hip_malloc_volume(ctx, vg.dim_x, vg.dim_y, vg.dim_z, &vol.d_v), "make_volume()");
-                // whole frames: every range of the plan is the detector
-                const auto roll = paris_hip_detector_roll{po.roll_deg};
-                const auto rows = plan_frame_rows(row_range{0u, n_col}, n_col, rep.defects.reach_rows, po.zingers, po.air ? &po.air_region : nullptr,
-                                                  binning ? po.bin_y : 1u, po.roll ? &roll : nullptr, &po.det_geo);
                 const float delta_s = po.det_geo.delta_s * po.det_geo.l_px_row, delta_t = po.det_geo.delta_t * po.det_geo.l_px_col;
                 const auto no_roi = region_of_interest{};
-                auto sines = std::vector<float>(batch), cosines = std::vector<float>(batch), angles = std::vector<float>(batch);
                 auto all_sin = std::vector<float>{}, all_cos = std::vector<float>{}; // per view, for the forward projection
-                auto source = frame_stream{po.input_path, po.enable_angles, po.angle_path, po.quality};
                 const std::uint32_t stride = std::max<std::uint32_t>(1u, po.quality);
-                if(po.lag) // --lag: the pre-pass is a pass over the scan of its own, from frame 0 of the file, on whole frames
-                    rt(paris_hip_lag_begin(ctx, n_row, n_col, rows.up.first, rows.up.count), "lag_begin()");
-                for(bool more = true; more;)
-                {
-                    std::uint32_t filled = 0;
-                    for(; filled < batch; ++filled)
-                    {
-                        const auto p = source.next_raw(slots.host(filled), sn_row, sn_col, rows.src.first, rows.src.count);
-                        if(!p.valid())
+                frames = walk_scan(
+                    s, po, true, [&](std::uint32_t slot, const frame_info& p) { s.chain.upload(slot, p.pixel, s.rows); },
+                    [&](const scan_group& g) {
+                        for(std::uint32_t f = 0; f < g.count; ++f)
                         {
-                            more = false;
-                            break;
+                            const std::uint32_t view = g.infos[f].idx / stride;
+                            if(view >= all_sin.size())
+                            {
+                                all_sin.resize(view + 1u, 0.f);
+                                all_cos.resize(view + 1u, 1.f);
+                            }
+                            all_sin[view] = g.sines[f];
+                            all_cos[view] = g.cosines[f];
                         }
-                        if(p.dim_x != sn_row || p.dim_y != sn_col)
-                            throw stage_runtime_error{"projection size does not match the detector geometry"};
-                        chain.upload(filled, p.pixel, rows);
-                        angles[filled] = po.enable_angles ? p.phi : static_cast<float>(p.idx) * po.det_geo.delta_phi;
-                        rt(paris_hip_stage_angle(&po.det_geo, p.idx, po.enable_angles, p.phi, &sines[filled], &cosines[filled]), "angle");
-                        const std::uint32_t view = p.idx / stride;
-                        if(view >= all_sin.size())
-                        {
-                            all_sin.resize(view + 1u, 0.f);
-                            all_cos.resize(view + 1u, 1.f);
-                        }
-                        all_sin[view] = sines[filled];
-                        all_cos[view] = cosines[filled];
-                    }
-                    if(filled == 0)
-                        break;
-                    chain.run(0u, filled, true, rows, angles.data());
-                    rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, filled, n_row, n_col, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, 0u,
-                                                   &po.det_geo, &vg, 0, &no_roi, sines.data(), cosines.data(), delta_s, delta_t), "backproject()");
-                    rt(paris_hip_ctx_synchronize(ctx), "synchronize"); // the pinned and the device frames are free for the next group
-                    frames += filled;
-                }
-                if(po.lag)
-                    rt(paris_hip_lag_end(ctx), "lag_end()");
+                        s.chain.run(0u, g.count, true, s.rows, g.angles);
+                        rt(paris_hip_backproject_batch(ctx, slots.out(0u), slots.pitch, slots.stride, g.count, n_row, n_col, vol.d_v, vg.dim_x, vg.dim_y, vg.dim_z, 0u,
+                                                       &po.det_geo, &vg, 0, &no_roi, g.sines, g.cosines, delta_s, delta_t), "backproject()");
+                    });
                 if(frames == 0u)
                     throw stage_runtime_error{"--metal: the input holds no projection"};
                 n_views = static_cast<std::uint32_t>(all_sin.size());
@@ -2386,216 +1719,6 @@ namespace paris
             po.metal_value = std::move(value);
             r.metal_prepass_s = since(t_start);
         }
-
-        // --find-axis LO:HI[:STEP] as typed; refuses anything but two or three numbers
-        inline auto parse_find_axis(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--find-axis LO:HI[:STEP]: cannot read '" + v + "'"}; };
-            const auto number = [&bad](const std::string& t) -> float {
-                if(t.empty())
-                    throw bad();
-                char* end = nullptr;
-                const float f = std::strtof(t.c_str(), &end);
-                if(end == nullptr || *end != '\0')
-                    throw bad();
-                return f;
-            };
-            const auto first = v.find(':');
-            if(first == std::string::npos)
-                throw bad();
-            const auto second = v.find(':', first + 1u);
-            if(second != std::string::npos && v.find(':', second + 1u) != std::string::npos)
-                throw bad();
-            po.axis_lo = number(v.substr(0, first));
-            po.axis_hi = number(v.substr(first + 1u, second == std::string::npos ? second : second - first - 1u));
-            po.axis_step = second == std::string::npos ? 0.25f : number(v.substr(second + 1u));
-            po.find_axis = true;
-        }
-
-        inline auto parse_axis_rows(const std::string& v, program_options& po) -> void
-        {
-            if(v.empty() || v.size() > 9u || v.find_first_not_of("0123456789") != std::string::npos)
-                throw stage_construction_error{"--axis-rows R: cannot read '" + v + "'"};
-            po.axis_rows = static_cast<std::uint32_t>(std::stoul(v));
-            po.axis_rows_given = true;
-        }
-
-        // --find-axis: the candidates, the scan and the setting are checked for this detector here, before any device work. The
-        // search needs a full, equidistant circle: it is refused with --short-scan, with an angle file, and for frames (after the
-        // quality stride) whose count times their angle step differs from 360 degrees by more than half a step
-        inline auto check_axis(program_options& po) -> void
-        {
-            if(!po.find_axis)
-            {
-                if(po.axis_only || po.axis_rows_given)
-                    throw stage_construction_error{"--axis-rows and --axis-only need --find-axis"};
-                return;
-            }
-            if(po.short_scan)
-                throw stage_construction_error{"--find-axis needs a full circle: it cannot be combined with --short-scan"};
-            if(po.enable_angles)
-                throw stage_construction_error{"--find-axis needs equidistant projections: it cannot be combined with an angle file (--angles)"};
-            const double span = static_cast<double>(po.axis_hi) - static_cast<double>(po.axis_lo);
-            if(!std::isfinite(po.axis_lo) || !std::isfinite(po.axis_hi) || !std::isfinite(po.axis_step) || !(po.axis_step > 0.f) || !(span >= 0.0)
-               || span / static_cast<double>(po.axis_step) > 1023.0)
-                throw stage_construction_error{"--find-axis LO:HI[:STEP]: LO <= HI and STEP > 0, all finite, and at most 1024 candidates (got "
-                                               + std::to_string(po.axis_lo) + ":" + std::to_string(po.axis_hi) + ":" + std::to_string(po.axis_step) + ")"};
-            po.axis_count = static_cast<std::uint32_t>(std::floor(span / static_cast<double>(po.axis_step) + 0.5)) + 1u;
-            const auto a = frame_angles(po.input_path, false, po.angle_path, po.quality, po.det_geo.delta_phi);
-            const double step = a.size() >= 2u ? static_cast<double>(a[1]) - static_cast<double>(a[0]) : 0.0;
-            if(a.size() < 4u || !(step > 0.0) || std::abs(static_cast<double>(a.size()) * step - 360.0) > 0.5 * step)
-            {
-                char msg[256];
-                std::snprintf(msg, sizeof msg, "--find-axis needs a full circle of at least 4 projections at a positive angle step: %zu projection(s) "
-                              "%.6g degrees apart cover %.6g degrees", a.size(), step, static_cast<double>(a.size()) * step);
-                throw stage_construction_error{msg};
-            }
-            po.axis_frames = static_cast<std::uint32_t>(a.size());
-            const auto search = paris_hip_axis_search{po.axis_lo, po.axis_step, po.axis_count, po.axis_rows, 0u};
-            const int rc = paris_hip_axis_search_check(&search, &po.det_geo, po.axis_frames, nullptr, nullptr);
-            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
-                throw stage_construction_error{"--find-axis: the candidates times the detector's columns, or the sinogram, exceed 2^32 - 1 entries"};
-            if(rc != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--find-axis / --axis-rows: R must lie in 1 .. 64 and within the detector's " + std::to_string(po.det_geo.n_col)
-                                               + " rows, and the geometry needs a positive pixel size and source distance (got R = "
-                                               + std::to_string(po.axis_rows) + ")"};
-        }
-
-        // --detector-roll DEG as typed
-        inline auto parse_detector_roll(const std::string& v, program_options& po) -> void
-        {
-            char* end = nullptr;
-            po.roll_deg = std::strtof(v.c_str(), &end);
-            if(v.empty() || end == nullptr || *end != '\0')
-                throw stage_construction_error{"--detector-roll DEG: cannot read '" + v + "'"};
-            po.roll = true;
-        }
-
-        // --find-roll LO:HI[:STEP] as typed; refuses anything but two or three numbers
-        inline auto parse_find_roll(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--find-roll LO:HI[:STEP]: cannot read '" + v + "'"}; };
-            const auto f = colon_fields(v);
-            if(f.size() < 2u || f.size() > 3u)
-                throw bad();
-            float num[3] = {0.f, 0.f, 0.25f};
-            for(std::size_t k = 0; k < f.size(); ++k)
-            {
-                char* end = nullptr;
-                num[k] = std::strtof(f[k].c_str(), &end);
-                if(f[k].empty() || end == nullptr || *end != '\0')
-                    throw bad();
-            }
-            po.roll_lo = num[0];
-            po.roll_hi = num[1];
-            po.roll_step = num[2];
-            po.find_roll = true;
-        }
-
-        // --detector-roll / --find-roll: the angle, the candidates and the scan are checked for this detector here, before any device
-        // work. The search needs a full, equidistant circle on a centred detector: it is refused with --short-scan, with
-        // --offset-detector, with an angle file, and for frames (after the quality stride) that do not cover 360 degrees
-        inline auto check_roll(program_options& po) -> void
-        {
-            if(po.roll_only && !po.find_roll)
-                throw stage_construction_error{"--roll-only needs --find-roll"};
-            if(po.roll && po.find_roll)
-                throw stage_construction_error{"--detector-roll and --find-roll cannot be combined: give the angle or have it found"};
-            if((po.roll || po.find_roll) && po.fit_beam_hardening)
-                throw stage_construction_error{"--detector-roll / --find-roll cannot be combined with --fit-beam-hardening: its pre-pass does not resample the frames"};
-            if(po.roll)
-            {
-                const auto setting = paris_hip_detector_roll{po.roll_deg};
-                if(paris_hip_detector_roll_check(&setting, &po.det_geo) != PARIS_HIP_SUCCESS)
-                    throw stage_construction_error{"--detector-roll DEG: DEG must be finite, not 0 and at most 10 in size, on a detector of at least 2 x 2 pixels "
-                                                   "with positive pixel sizes (got " + std::to_string(po.roll_deg) + ")"};
-            }
-            if(!po.find_roll)
-                return;
-            if(po.short_scan)
-                throw stage_construction_error{"--find-roll needs a full circle: it cannot be combined with --short-scan"};
-            if(po.offset_detector)
-                throw stage_construction_error{"--find-roll needs a centred detector: it cannot be combined with --offset-detector"};
-            if(po.enable_angles)
-                throw stage_construction_error{"--find-roll needs equidistant projections: it cannot be combined with an angle file (--angles)"};
-            if(po.roll_only && po.axis_only)
-                throw stage_construction_error{"--roll-only cannot be combined with --axis-only: the run would stop before the roll search"};
-            const double span = static_cast<double>(po.roll_hi) - static_cast<double>(po.roll_lo);
-            if(!std::isfinite(po.roll_lo) || !std::isfinite(po.roll_hi) || !std::isfinite(po.roll_step) || !(po.roll_step > 0.f) || !(span >= 0.0)
-               || span / static_cast<double>(po.roll_step) > 255.0)
-                throw stage_construction_error{"--find-roll LO:HI[:STEP]: LO <= HI and STEP > 0, all finite, and at most 256 candidates (got "
-                                               + std::to_string(po.roll_lo) + ":" + std::to_string(po.roll_hi) + ":" + std::to_string(po.roll_step) + ")"};
-            po.roll_count = static_cast<std::uint32_t>(std::floor(span / static_cast<double>(po.roll_step) + 0.5)) + 1u;
-            const auto a = frame_angles(po.input_path, false, po.angle_path, po.quality, po.det_geo.delta_phi);
-            const double step = a.size() >= 2u ? static_cast<double>(a[1]) - static_cast<double>(a[0]) : 0.0;
-            if(a.size() < 4u || !(step > 0.0) || std::abs(static_cast<double>(a.size()) * step - 360.0) > 0.5 * step)
-            {
-                char msg[256];
-                std::snprintf(msg, sizeof msg, "--find-roll needs a full circle of at least 4 projections at a positive angle step: %zu projection(s) "
-                              "%.6g degrees apart cover %.6g degrees", a.size(), step, static_cast<double>(a.size()) * step);
-                throw stage_construction_error{msg};
-            }
-            const auto search = paris_hip_roll_search{po.roll_lo, po.roll_step, po.roll_count, 0u};
-            if(paris_hip_roll_search_check(&search, &po.det_geo, nullptr, nullptr, nullptr) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--find-roll LO:HI[:STEP]: every candidate must lie within 10 degrees of 0 and leave pixels inside the margins "
-                                               "of the detector (got " + std::to_string(po.roll_lo) + ":" + std::to_string(po.roll_hi) + ":"
-                                               + std::to_string(po.roll_step) + ")"};
-        }
-
-        // --lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] as typed; refuses anything but one to four pairs of numbers
-        inline auto parse_lag(const std::string& v, program_options& po) -> void
-        {
-            const auto bad = [&v]() -> stage_construction_error { return stage_construction_error{"--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]]: cannot read '" + v + "'"}; };
-            const auto field = colon_fields(v);
-            if(field.size() < 2u || field.size() % 2u != 0u || field.size() > 2u * PARIS_HIP_LAG_TERMS_MAX)
-                throw bad();
-            po.lag_model.terms = static_cast<std::uint32_t>(field.size() / 2u);
-            for(std::size_t k = 0; k < field.size(); ++k)
-            {
-                char* end = nullptr;
-                const float x = std::strtof(field[k].c_str(), &end);
-                if(field[k].empty() || end == nullptr || *end != '\0')
-                    throw bad();
-                (k % 2u == 0u ? po.lag_model.b : po.lag_model.a)[k / 2u] = x;
-            }
-            po.lag = true;
-        }
-
-        inline auto parse_lag_start(const std::string& v, program_options& po) -> void
-        {
-            if(v == "rest") po.lag_model.start = PARIS_HIP_LAG_START_REST;
-            else if(v == "steady") po.lag_model.start = PARIS_HIP_LAG_START_STEADY;
-            else throw stage_construction_error{"--lag-start rest|steady: unknown start " + v};
-            po.lag_start_given = true;
-        }
-
-        // --lag / --lag-start: checked here, before any device work. The correction works on counts, so it needs --flat; and on every
-        // frame the detector took, so --quality above 1 is refused: the skipped frames still fed the detector's memory.
-        inline auto check_lag(const program_options& po) -> void
-        {
-            if(!po.lag)
-            {
-                if(po.lag_start_given)
-                    throw stage_construction_error{"--lag-start needs --lag"};
-                return;
-            }
-            if(po.flat_path.empty())
-                throw stage_construction_error{"--lag needs --flat: the lag correction works on detector counts, before the dark / flat correction"};
-            if(po.quality > 1u)
-                throw stage_construction_error{"--lag cannot be combined with --quality " + std::to_string(po.quality)
-                                               + ": the skipped frames still fed the detector's memory"};
-            if(paris_hip_lag_model_check(&po.lag_model) != PARIS_HIP_SUCCESS)
-                throw stage_construction_error{"--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]]: every weight B and decay rate per frame A must be finite and above 0, "
-                                               "and b_0 = 1 - sum B / (1 - exp(-A)) must be above 0"};
-        }
-
-        inline auto parse_zinger_polarity(const std::string& v, program_options& po) -> void
-        {
-            if(v == "bright") po.zinger_polarity = 1;
-            else if(v == "dark") po.zinger_polarity = -1;
-            else if(v == "both") po.zinger_polarity = 0;
-            else throw stage_construction_error{"--zinger-polarity bright|dark|both: unknown polarity " + v};
-        }
     }
 
     // src/main.cpp:120-178
@@ -2610,7 +1733,12 @@ namespace paris
         r.dark_frames = po.dark ? po.dark->n_frames : 0u;
         detail::load_defects(po);
         detail::apply_binning(po, r); // from here on po.det_geo is the binned detector
-        detail::check_air_region(po, r);
+        detail::check_air_region(po);
+        if(po.air) // the frame the rectangle was checked against
+        {
+            r.air_row = po.det_geo.n_row;
+            r.air_col = po.det_geo.n_col;
+        }
         detail::check_zingers(po);
         detail::check_extend_rows(po);
         detail::check_rings(po);

@@ -144,6 +144,27 @@ def test_the_pre_passes_open_sequences_of_their_own(tmp_path, scan):
         assert a and a == b, (a, b)
 
 
+def test_the_metal_pre_pass_opens_a_sequence_of_its_own(tmp_path, scan):
+    """--metal reconstructs the scan once more, after the other two pre-passes: with THR taken from the volume of the run without it, so
+    that a few voxels lie above, the volume and the reports are again those of the run on the corrected frames"""
+    src, frames, dark, flat = scan
+    corrected_set(tmp_path / "fixed", frames, dark, flat, GEO)
+    extra = ["--rings", "2:0.01", "--fit-beam-hardening", "2:8:0", "--slabs", 2]
+    _, ref = drive(tmp_path / "fixed", tmp_path / "ref", extra)                     # what the metal pre-pass reconstructs
+    thr = np.sort(ref.ravel())[-(ref.size // 64)]
+    above = int((ref > thr).sum())
+    assert 1 <= above <= ref.size // 32
+    extra += ["--metal", "%.9g" % thr]
+    text, got = drive(src, tmp_path / "lag", ["--lag", OPTION] + extra)
+    plain, want = drive(tmp_path / "fixed", tmp_path / "plain", extra)
+    assert np.array_equal(bits(got), bits(want)) and not np.array_equal(bits(want), bits(ref))
+    for begin in ("ring filter on", "beam hardening on", "metal reduction on"):
+        a, b = ([l.split(" s)")[-1] for l in t.splitlines() if l.startswith(begin)] for t in (text, plain))
+        assert a and a == b, (a, b)
+    for t in (text, plain):
+        assert "metal reduction on: %d voxel(s) above %.9g collected" % (above, thr) in t, t
+
+
 def test_the_cpp_mirror_corrects_as_the_driver_does(tmp_path, scan):
     """PARIS's loop through paris::hip with set_lag_correction(), lag_begin(), lag_correct() and lag_end() (paris_hip_demo --lag), fed
     the counts as f32 and the mean references: the volume of paris.hip --lag, each of its two slabs a sequence of its own"""

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import binning_rule as BR
 import chain_rule as CH
 import fdk_model
 import metal_rule as R
@@ -167,6 +168,36 @@ def test_with_the_roll_and_the_zinger_filter(scan):
     got = volume_of(root, "roll")
     assert "detector roll on" in text and "zinger filter on" in text and int(LINE.search(text).group(5)) == mt.trace_pixels
     assert np.array_equal(bits(got), bits(volume)) and not np.array_equal(bits(volume), bits(plain))
+
+
+def test_with_bin_the_pre_pass_bins_as_the_main_pass_does(tmp_path):
+    """--metal --bin 2 on a source detector of twice the pixels each way, whose 2 x 2 bins make the scene's detector: the pre-pass reads
+    source frames into the full-width slots and bins them as the main pass does, so the volume and the report are those of the driver
+    without --bin on frames, flat and geometry binned on the host by the numpy rule (as tests/test_gpu_binning_driver.py compares --bin)"""
+    rng = np.random.default_rng(37)
+    src_geo = (2 * R.SCENE_DET[0], 2 * R.SCENE_DET[1], 0.5 * R.SCENE_DET[2], 0.5 * R.SCENE_DET[3]) + R.SCENE_DET[4:]
+    assert R.SCENE_DET[4:6] == (0.0, 0.0) and tuple(float(v) for v in BR.binned_geometry(src_geo, 2, 2)) == tuple(float(v) for v in R.SCENE_DET)
+    p = np.repeat(np.repeat(R.scene_frames().astype(np.float64), 2, axis=1), 2, axis=2)
+    counts = np.clip(np.rint(FLAT * np.exp(-p)) + rng.integers(-3, 4, p.shape), 0, 65535).astype(np.uint16)   # bins of unequal pixels
+    flat = (FLAT + rng.integers(-200, 200, counts.shape[1:])).astype(np.uint16)
+    for root, geo, code, ref, frames in (
+            (tmp_path / "src", src_geo, 4, flat, counts),
+            (tmp_path / "binned", BR.binned_geometry(src_geo, 2, 2), 128, BR.bin_frame(flat.astype(np.float32), 2, 2, None),
+             np.stack([BR.bin_frame(f.astype(np.float32), 2, 2, None) for f in counts]))):
+        (root / "ref").mkdir(parents=True)
+        (root / "ref" / "flat.his").write_bytes(F.his_file_bytes(ref[None], code))
+        (root / "counts").mkdir()
+        (root / "counts" / "a.his").write_bytes(F.his_file_bytes(frames[:70], code, 32))
+        (root / "counts" / "b.his").write_bytes(F.his_file_bytes(frames[70:], code, 32))
+        (root / "geo.ini").write_text("\n".join("%s = %s" % (k, v if isinstance(v, int) else "%.9g" % float(v)) for k, v in zip(FF.GEO_KEYS, geo)) + "\n")
+    text = drive(tmp_path / "src", "bin", ["--metal", METAL, "--bin", "2", "--slabs", 2])
+    plain = drive(tmp_path / "binned", "pre", ["--metal", METAL, "--slabs", 2])
+    got, want = volume_of(tmp_path / "src", "bin"), volume_of(tmp_path / "binned", "pre")
+    assert "binning on: 2 x 2 bins, detector 128 x 64 -> 64 x 32" in text and "binning on" not in plain
+    a, b = LINE.search(text), LINE.search(plain)
+    assert a and b and a.groups() == b.groups() and int(a.group(1)) > 100 and int(a.group(5)) > 0 and int(a.group(6)) == R.SCENE_VIEWS, (text, plain)
+    assert got.shape == want.shape == (VG.dim_z, VG.dim_y, VG.dim_x) and np.abs(want).max() > 0
+    assert np.array_equal(bits(got), bits(want))
 
 
 def test_as_u16_voxels_over_an_automatic_window(scan, want):
