@@ -1560,6 +1560,72 @@ int paris_hip_clear_phase_retrieval(paris_hip_ctx* ctx);
 int paris_hip_phase_retrieval_frames(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
                                      uint32_t dim_y);
 
+/* Extension (no reference counterpart): correction of object scatter by kernel superposition after Ohnesorge et al. (1999) and
+ * Sun & Star-Lack (2010), in its stationary form -- scatter is a smooth additive intensity on the detector, which shows as cupping and
+ * as streaks between dense parts and is no function of a pixel's own line integral. A fixed-point iteration solves
+ * T_m = T + (q(T) (*) g) for the primary transmission T: the second client of the library's 2-D transform (scatter.hip,
+ * scatter_rule.cpp, frame_fft2.h).
+ * Setting paris_hip_scatter_correction: amplitude A finite and > 0, alpha in [-2, 2], beta in [0, 4], sigma1_mm and sigma2_mm finite
+ *   and > 0, weight2 finite and >= 0, limit in (0, 1), iterations in 1 .. PARIS_HIP_SCATTER_ITERATIONS_MAX, margin in
+ *   1 .. PARIS_HIP_PHASE_MARGIN_MAX. The padded sizes N_x, N_y and PARIS_HIP_PHASE_SIZE_MAX are as for the phase filter.
+ * Input: whole frames of line integrals p, dim_x x dim_y floats (both >= 1) with the pixel pitches l_x = l_px_row, l_y = l_px_col
+ *   (finite, > 0). In place.
+ * Rule, per frame:
+ *   1. T_m = expf(-p). A pixel enters when p is finite and 0 < T_m < inf. Every other pixel enters as air -- T_m = 1, so a source of 0
+ *      at first: it is iterated as a pixel with p = 0 is -- and is LEFT AS STORED in the output.
+ *   2. T^0 = T_m. For k = 0 .. iterations - 1:
+ *      source      lnT = logf(T^k), L = -lnT; q = A expf(alpha lnT + beta logf(L)) where L > 0, else q = 0 (that is A T^alpha L^beta).
+ *      extension   q is extended to N_x x N_y exactly as step 3 of the phase filter: edge replication with the circular wrap.
+ *      convolution S = IFFT2(FFT2(q_ext) G), G(k_x, k_y) = g1x[k_x] g1y[k_y] + g2x[k_x] g2y[k_y] in fp32 (two products, one sum);
+ *                  g1y[k] = exp(-2 pi^2 sigma1^2 f^2), g1x[k] = that / (1 + w2), g2y[k] = exp(-2 pi^2 sigma2^2 f^2),
+ *                  g2x[k] = w2 that / (1 + w2), f as in step 4 of the phase filter. All four tables are made in double on the host,
+ *                  rounded once to float and uploaded. G(0, 0) = 1: A is the ratio of total scatter to total source. S carries the
+ *                  division by N_x N_y, an exact scaling.
+ *      update      T^(k+1) = fmaxf(T_m - S, (1 - limit) T_m), 1 - limit formed once in fp32. Both terms use the MEASURED T_m, never the
+ *                  previous estimate: the iteration is T = T_m - S(T), and limit bounds the scatter fraction it may remove.
+ *   3. p' = -logf(T^n) on the pixels that entered.
+ * The answer for a frame does not depend on which other frames share the call, bit for bit. The estimate T^k never goes to memory: it
+ * is a function of the unchanged frame p and of S, so one round of frames takes 2 iterations + 1 launches.
+ * Scratch: as the phase filter's, with the same frames_per_launch; with the twiddles of both lengths and the four tables (2 N_x + 2 N_y
+ * floats) in front of it, it is a ctx-owned setting that paris_hip_projection_reserve_bytes counts:
+ * scratch_bytes + 12 (N_x + N_y) bytes.
+ * Order: after the ring correction, before the phase retrieval and the beam-hardening polynomial -- scatter is additive on the measured
+ * intensity and must be gone before a filter or a polynomial acts on what is taken for the primary.
+ * Limits: one stationary, symmetric kernel; no down-sampled estimate; the parameters are given, not fitted. */
+#define PARIS_HIP_SCATTER_ITERATIONS_MAX 16
+typedef struct paris_hip_scatter_correction {
+    float amplitude, alpha, beta; /* A, alpha, beta of the source q = A T^alpha (-ln T)^beta */
+    float sigma1_mm, sigma2_mm;   /* widths of the two Gaussians at the detector plane [mm] */
+    float weight2;                /* weight of the second Gaussian relative to the first; 0: one Gaussian */
+    float limit;                  /* the largest scatter fraction S / T_m the correction removes; in (0, 1) */
+    uint32_t iterations;          /* 1 .. PARIS_HIP_SCATTER_ITERATIONS_MAX */
+    uint32_t margin;              /* padding per side [px]: 1 .. PARIS_HIP_PHASE_MARGIN_MAX */
+} paris_hip_scatter_correction;
+/* Host only: max(8, ceil(3 max(sigma1, sigma2) / min(l_x, l_y))), capped at PARIS_HIP_PHASE_MARGIN_MAX -- three widths of the wider
+ * Gaussian, in pixels. 0 for arguments that are not finite and > 0. */
+uint32_t paris_hip_scatter_default_margin(float sigma1_mm, float sigma2_mm, float l_x, float l_y);
+/* Host only: validates the setting for dim_x x dim_y frames of these pitches and returns the padded sizes and the bytes of scratch
+ * the device needs (each pointer may be NULL). Refusals as paris_hip_phase_retrieval_check: PARIS_HIP_ERROR_INVALID_ARGUMENT for a
+ * NULL setting, a field out of range, a zero dimension or a pitch that is not finite and > 0; PARIS_HIP_ERROR_UNSUPPORTED for a
+ * padded size above PARIS_HIP_PHASE_SIZE_MAX (n_x and n_y are still returned). */
+int paris_hip_scatter_correction_check(const paris_hip_scatter_correction* setting, uint32_t dim_x, uint32_t dim_y, float l_x, float l_y,
+                                       uint32_t* n_x, uint32_t* n_y, size_t* scratch_bytes);
+/* Host only: the rule in DOUBLE on one dense frame, src to dst (which may be the same array), rounded to float at the store; the
+ * special pixels are judged as the rule says, on the fp32 expf. The C statement of the model, not a mirror of the device's bits.
+ * Refusals as the check, or PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL src or dst. */
+int paris_hip_scatter_correction_host(const paris_hip_scatter_correction* setting, float l_x, float l_y, const float* src, float* dst,
+                                      uint32_t dim_x, uint32_t dim_y);
+/* paris_hip_set_scatter_correction runs the check and installs twiddles, tables and scratch for dim_x x dim_y frames in memory the ctx
+ * owns. It replaces an earlier setting safely: work already queued keeps the old one. Without a setting nothing else changes. */
+int paris_hip_set_scatter_correction(paris_hip_ctx* ctx, const paris_hip_scatter_correction* setting, uint32_t dim_x, uint32_t dim_y,
+                                     float l_x, float l_y);
+int paris_hip_clear_scatter_correction(paris_hip_ctx* ctx);
+/* In place on whole float frames, asynchronous: the contract of paris_hip_phase_retrieval_frames -- every row is the pass's band, a
+ * pending by-reference group and a held-back weighting run first, calls of more than frames_per_launch frames loop, and the
+ * refusals are the same. */
+int paris_hip_scatter_correction_frames(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                        uint32_t dim_y);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 const char* paris_hip_strerror(int status);
 /* library version "major.minor.patch" */

@@ -182,6 +182,15 @@ class PhaseRetrieval(C.Structure):
     _fields_ = [("alpha_mm2", C.c_float), ("t_min", C.c_float), ("margin", C.c_uint32)]
 
 
+SCATTER_ITERATIONS_MAX = 16  # PARIS_HIP_SCATTER_ITERATIONS_MAX
+
+
+class ScatterCorrection(C.Structure):
+    """paris_hip_scatter_correction: scatter kernel superposition, iterated (extension)"""
+    _fields_ = [("amplitude", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("sigma1_mm", C.c_float), ("sigma2_mm", C.c_float),
+                ("weight2", C.c_float), ("limit", C.c_float), ("iterations", C.c_uint32), ("margin", C.c_uint32)]
+
+
 LAG_TERMS_MAX = 4  # PARIS_HIP_LAG_TERMS_MAX
 LAG_START_REST = 0  # PARIS_HIP_LAG_START_REST
 LAG_START_STEADY = 1  # PARIS_HIP_LAG_START_STEADY
@@ -328,6 +337,13 @@ SIGNATURES = {
     "paris_hip_set_phase_retrieval": (C.c_int, [_vp, _P(PhaseRetrieval), _u32, _u32, C.c_float, C.c_float]),
     "paris_hip_clear_phase_retrieval": (C.c_int, [_vp]),
     "paris_hip_phase_retrieval_frames": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32]),
+    "paris_hip_scatter_default_margin": (C.c_uint32, [C.c_float, C.c_float, C.c_float, C.c_float]),
+    "paris_hip_scatter_correction_check": (C.c_int, [_P(ScatterCorrection), _u32, _u32, C.c_float, C.c_float, _P(C.c_uint32), _P(C.c_uint32),
+                                                     _P(C.c_size_t)]),
+    "paris_hip_scatter_correction_host": (C.c_int, [_P(ScatterCorrection), C.c_float, C.c_float, _vp, _vp, _u32, _u32]),
+    "paris_hip_set_scatter_correction": (C.c_int, [_vp, _P(ScatterCorrection), _u32, _u32, C.c_float, C.c_float]),
+    "paris_hip_clear_scatter_correction": (C.c_int, [_vp]),
+    "paris_hip_scatter_correction_frames": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32]),
     "paris_hip_beam_hardening_check": (C.c_int, [_P(BeamHardening)]),
     "paris_hip_beam_hardening_host": (C.c_int, [_P(BeamHardening), _vp, _vp, C.c_uint64]),
     "paris_hip_set_beam_hardening": (C.c_int, [_vp, _P(BeamHardening), _u32, _u32]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (ScatterCorrection, PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -29,7 +29,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "detector_roll_check", "detector_roll_host", "detector_roll_source_rows", "roll_search_check", "roll_estimate_from_costs",
            "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host", "MetalCounts", "MetalTrace", "metal_check",
            "metal_collect_host", "metal_trace_pack_host", "metal_inpaint_host", "metal_words", "PhaseRetrieval", "phase_alpha",
-           "phase_default_margin", "phase_retrieval_check", "phase_retrieval_host"]
+           "phase_default_margin", "phase_retrieval_check", "phase_retrieval_host", "ScatterCorrection", "scatter_default_margin",
+           "scatter_correction_check", "scatter_correction_host"]
 
 
 class Projection:
@@ -392,6 +393,36 @@ def phase_retrieval_host(alpha_mm2, t_min, margin, l_x, l_y, frame):
     check(_lib.load().paris_hip_phase_retrieval_host(C.byref(s), l_x, l_y, f.ctypes.data if f.size else None,
                                                      out.ctypes.data if f.size else None, f.shape[1], f.shape[0]),
           "paris_hip_phase_retrieval_host")
+    return out
+
+
+def scatter_default_margin(sigma1_mm, sigma2_mm, l_x, l_y):
+    """Host only (paris_hip_scatter_default_margin): max(8, ceil(3 max(sigma) / min(l))) pixels, at most 1024; 0 for arguments that
+    are not finite and positive."""
+    return _lib.load().paris_hip_scatter_default_margin(sigma1_mm, sigma2_mm, l_x, l_y)
+
+
+def scatter_correction_check(setting, dim_x, dim_y, l_x, l_y):
+    """Host only (paris_hip_scatter_correction_check): setting is a ScatterCorrection (or the nine values of one). Raises ParisHipError
+    for a setting the library refuses -- a padded size above 8192 is ERROR_UNSUPPORTED --, else returns (n_x, n_y, scratch_bytes)."""
+    s = setting if isinstance(setting, ScatterCorrection) else ScatterCorrection(*setting)
+    nx, ny, b = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    check(_lib.load().paris_hip_scatter_correction_check(C.byref(s), dim_x, dim_y, l_x, l_y, C.byref(nx), C.byref(ny), C.byref(b)),
+          "paris_hip_scatter_correction_check")
+    return nx.value, ny.value, b.value
+
+
+def scatter_correction_host(setting, l_x, l_y, frame):
+    """Host only (paris_hip_scatter_correction_host): the scatter rule in double on one frame of line integrals, a 2-D array
+    (dim_y, dim_x) taken as float32, rounded to float32 at the store. Returns a new array."""
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.ndim != 2:
+        raise ValueError("scatter_correction_host: the frame must be a 2-D array (dim_y, dim_x)")
+    out = np.empty_like(f)
+    s = setting if isinstance(setting, ScatterCorrection) else ScatterCorrection(*setting)
+    check(_lib.load().paris_hip_scatter_correction_host(C.byref(s), l_x, l_y, f.ctypes.data if f.size else None,
+                                                        out.ctypes.data if f.size else None, f.shape[1], f.shape[0]),
+          "paris_hip_scatter_correction_host")
     return out
 
 
@@ -1199,6 +1230,30 @@ class Backend:
         st = AirCounts()
         check(self._L.paris_hip_air_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_air_stats")
         return st
+
+    # ---- scatter correction --------------------------------------------------------
+    scatter_default_margin = staticmethod(scatter_default_margin)
+    scatter_correction_check = staticmethod(scatter_correction_check)
+    scatter_correction_host = staticmethod(scatter_correction_host)
+
+    def set_scatter_correction(self, setting, dim_x, dim_y, l_x, l_y):
+        """paris_hip_set_scatter_correction for dim_x x dim_y frames with pixel pitches l_x, l_y; setting is a ScatterCorrection (or
+        the nine values of one): scatter_correction() then solves T_m = T + (q(T) (*) g) for the primary of whole frames. Twiddles,
+        tables and scratch live on the device and count towards projection_reserve_bytes. Replaces an earlier setting; work already
+        queued keeps the old one."""
+        s = setting if isinstance(setting, ScatterCorrection) else ScatterCorrection(*setting)
+        check(self._L.paris_hip_set_scatter_correction(self._ctx, C.byref(s), dim_x, dim_y, l_x, l_y), "paris_hip_set_scatter_correction")
+
+    def clear_scatter_correction(self):
+        """paris_hip_clear_scatter_correction: no scatter correction from here on"""
+        check(self._L.paris_hip_clear_scatter_correction(self._ctx), "paris_hip_clear_scatter_correction")
+
+    def scatter_correction(self, p, frame_stride=0, n_frames=1):
+        """The rule of set_scatter_correction() in place on whole float frames of line integrals (paris_hip_scatter_correction_frames):
+        the n_frames frames frame_stride bytes apart starting at p. Call it after the ring correction and before the phase retrieval.
+        A frame's result does not depend on the other frames of the call."""
+        check(self._L.paris_hip_scatter_correction_frames(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y),
+              "paris_hip_scatter_correction_frames")
 
     # ---- phase retrieval (DESIGN.md section 4.22) -----------------------------------------------------------
     phase_alpha = staticmethod(phase_alpha)

@@ -121,6 +121,7 @@ extern "C" int paris_hip_ctx_create(int device, void* stream, unsigned flags, pa
             paris_hip_warm_lag();
             paris_hip_warm_metal();
             paris_hip_warm_phase();
+            paris_hip_warm_scatter();
             (void)hipGetLastError();
             // the runtime sets up its staging path on the first blocking host-to-device copy (~9 ms), its DMA queue on the first
             // asynchronous one from pinned memory (~7 ms): both paid here, on the counter's 8 bytes

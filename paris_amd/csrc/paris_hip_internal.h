@@ -265,6 +265,16 @@ struct paris_hip_ctx
         uint32_t dim_x = 0, dim_y = 0, n_x = 0, n_y = 0;
         uint32_t frames = 0; // frames one round of launches serves
     } phase;
+    // Scatter correction (paris_hip_set_scatter_correction): in this order the twiddles of N_x and of N_y, the
+    // tables g1x, g2x (N_x floats each), g1y, g2y, and the scratch -- `frames` frames of dim_y x (N_x / 2 + 1) complex floats.
+    struct scatter_t
+    {
+        bool set = false;
+        paris_hip_scatter_correction rule{};
+        paris_hip_device_buffer mem;
+        uint32_t dim_x = 0, dim_y = 0, n_x = 0, n_y = 0;
+        uint32_t frames = 0; // frames one round of launches serves
+    } scatter;
     // Row extension (paris_hip_set_row_extension): the rule, and the responses c made so far, one buffer per (dim_x, tau bits, W) --
     // the second stream reads them too, behind a join.
     struct row_extension_t
@@ -288,7 +298,7 @@ struct paris_hip_ctx
     void each_setting(F&& f)
     {
         f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
-        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase);
+        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase), f(scatter);
     }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
@@ -591,6 +601,10 @@ void paris_hip_warm_phase();
 // phase_rule.cpp: a[k] = alpha f^2 of n bins at this pitch, in double and rounded once; the extension's source sample of padded sample s
 void paris_hip_phase_table(float alpha, uint32_t n, float pitch, float* a);
 uint32_t paris_hip_phase_source(uint32_t s, uint32_t dim, uint32_t n);
+void paris_hip_warm_scatter();
+// scatter_rule.cpp: the four tables of G = g1x g1y + g2x g2y, in double and rounded once; the x tables carry the weights
+void paris_hip_scatter_tables(const paris_hip_scatter_correction* s, uint32_t n_x, uint32_t n_y, float l_x, float l_y, float* g1x, float* g2x,
+                              float* g1y, float* g2y);
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the

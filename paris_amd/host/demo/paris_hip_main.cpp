@@ -12,6 +12,7 @@
 //             [--beam-hardening C1:C2[:C3[:C4]] | --fit-beam-hardening N[:SLICES[:MARGIN]]]
 //             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
 //             [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]
+//             [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -93,6 +94,7 @@ int main(int argc, char** argv)
                             "          [--detector-roll DEG | --find-roll LO:HI[:STEP] [--roll-only]]\n"
                             "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
                             "          [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]\n"
+                            "          [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -301,6 +303,18 @@ int main(int argc, char** argv)
         }
         if(r.detector_roll)
             std::printf("detector roll on: %.9g deg\n", static_cast<double>(r.roll_deg));
+        if(r.scatter)
+        {
+            const auto& s = r.scatter_setting;
+            const double l_x = static_cast<double>(r.scatter_l_x), l_y = static_cast<double>(r.scatter_l_y);
+            std::printf("scatter correction on: A %.9g, alpha %.9g, beta %.9g, sigma %.9g and %.9g mm (%.4g x %.4g and %.4g x %.4g px), weight %.9g, "
+                        "limit %.9g, %u iteration(s), margin %u, padded %u x %u, %u launch(es) per round, %llu scratch byte(s) per device, whole frames "
+                        "(planned as --no-row-band)\n", static_cast<double>(s.amplitude), static_cast<double>(s.alpha), static_cast<double>(s.beta),
+                        static_cast<double>(s.sigma1_mm), static_cast<double>(s.sigma2_mm), static_cast<double>(s.sigma1_mm) / l_x,
+                        static_cast<double>(s.sigma1_mm) / l_y, static_cast<double>(s.sigma2_mm) / l_x, static_cast<double>(s.sigma2_mm) / l_y,
+                        static_cast<double>(s.weight2), static_cast<double>(s.limit), s.iterations, s.margin, r.scatter_nx, r.scatter_ny,
+                        2u * s.iterations + 1u, static_cast<unsigned long long>(r.scatter_scratch));
+        }
         if(r.phase)
         {
             const double length = std::sqrt(static_cast<double>(r.phase_setting.alpha_mm2)) / (2.0 * 3.14159265358979323846);

@@ -30,6 +30,10 @@ namespace
         u("phase", po.phase), u("phase_material", po.phase_material), f("phase_delta_beta", po.phase_delta_beta), f("phase_energy", po.phase_energy);
         u("phase_margin", po.phase_margin), f("phase_alpha", po.phase_setting.alpha_mm2);
         u("phase_floor_given", po.phase_floor_given), f("phase_floor", po.phase_setting.t_min);
+        u("scatter", po.scatter), u("scatter_detail_given", po.scatter_detail_given), f("scatter_amplitude", po.scatter_setting.amplitude);
+        f("scatter_alpha", po.scatter_setting.alpha), f("scatter_beta", po.scatter_setting.beta), f("scatter_sigma1", po.scatter_setting.sigma1_mm);
+        f("scatter_sigma2", po.scatter_setting.sigma2_mm), f("scatter_weight2", po.scatter_setting.weight2), f("scatter_limit", po.scatter_setting.limit);
+        u("scatter_iterations", po.scatter_setting.iterations), u("scatter_margin", po.scatter_setting.margin);
         u("beam_hardening", po.beam_hardening), u("fit_beam_hardening", po.fit_beam_hardening), u("bh_degree", po.bh.degree);
         for(int k = 0; k < 4; ++k)
             f(("bh_c" + std::to_string(k + 1)).c_str(), po.bh.c[k]);

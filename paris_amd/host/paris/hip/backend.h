@@ -133,6 +133,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> air_regions; // set_air_region(), per device of this thread
                 std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
                 std::set<const paris_hip_ctx*> phase_retrievals; // set_phase_retrieval(), per device of this thread
+                std::set<const paris_hip_ctx*> scatter_corrections; // set_scatter_correction(), per device of this thread
                 std::set<const paris_hip_ctx*> detector_rolls; // set_detector_roll(), per device of this thread
                 std::set<const paris_hip_ctx*> metal_traces;   // set_metal_trace(), per device of this thread
             };
@@ -357,6 +358,39 @@ namespace paris
             inline auto has_phase_retrieval(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().phase_retrievals;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): the frames of this thread's current device (n_row x n_col pixels with the pitches l_px_row,
+        // l_px_col) carry object scatter. Until clear_scatter_correction(), paris::weight() solves
+        // T_m = T + (q(T) (*) g) for the primary of every frame -- kernel superposition, iterated -- after the ring correction and before
+        // the phase retrieval (paris_hip_scatter_correction_frames).
+        inline auto set_scatter_correction(const paris_hip_scatter_correction& setting, std::uint32_t n_row, std::uint32_t n_col, float l_px_row,
+                                           float l_px_col) -> void
+        {
+            detail::runtime_check(paris_hip_set_scatter_correction(current_ctx(), &setting, n_row, n_col, l_px_row, l_px_col), "set_scatter_correction()");
+            detail::state().scatter_corrections.insert(current_ctx());
+        }
+
+        inline auto clear_scatter_correction() -> void
+        {
+            detail::runtime_check(paris_hip_clear_scatter_correction(current_ctx()), "clear_scatter_correction()");
+            detail::state().scatter_corrections.erase(current_ctx());
+        }
+
+        // the pass itself, on n_frames whole frames frame_stride bytes apart
+        inline auto scatter_correction(float* d_p, std::size_t pitch, std::size_t frame_stride, std::uint32_t n_frames, std::uint32_t n_row,
+                                       std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_scatter_correction_frames(current_ctx(), d_p, pitch, frame_stride, n_frames, n_row, n_col), "scatter_correction()");
+        }
+
+        namespace detail
+        {
+            inline auto has_scatter_correction(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().scatter_corrections;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

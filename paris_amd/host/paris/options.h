@@ -132,6 +132,15 @@ namespace paris
         paris_hip_phase_retrieval phase_setting{};              // alpha as given; the rest filled by run()
         std::uint32_t phase_nx = 0, phase_ny = 0;               // filled by run(): the padded size
         std::size_t phase_scratch = 0, phase_bytes = 0;         // filled by run(): the scratch, and what the setting occupies on a device
+        // scatter correction (extension): --scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] gives the source and
+        // the kernel (without the last two fields one Gaussian: W2 = 0, SIGMA2 = SIGMA1), --scatter-iterations N, --scatter-limit F and
+        // --scatter-margin M the rest (defaults 4, 0.8 and paris_hip_scatter_default_margin). Checked by run() before any device work,
+        // for the binned detector with --bin (detail::check_scatter). Every device ctx gets the setting, and each frame is corrected -- as
+        // a whole: the run is planned without the row band -- after the ring correction and before the phase retrieval
+        bool scatter = false, scatter_detail_given = false;     // the latter: one of the three options beside --scatter was given
+        paris_hip_scatter_correction scatter_setting{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.8f, 4u, 0u}; // margin 0: not given; run() takes the default
+        std::uint32_t scatter_nx = 0, scatter_ny = 0;           // filled by run(): the padded size
+        std::size_t scatter_scratch = 0, scatter_bytes = 0;     // filled by run(): the scratch, and what the setting occupies on a device
         // correction of the detector's in-plane rotation (extension): --detector-roll DEG gives the angle,
         // --find-roll LO:HI[:STEP] [--roll-only] has run() find it from the scan mean of the ring profile pre-pass (detail::prepass,
         // after the axis search, whose delta_s it uses): both checked by run() before any device work (detail::check_roll). Every
@@ -415,6 +424,73 @@ namespace paris
                 throw stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: H must lie in 1 .. 32, FLOOR must be finite and not negative, LIMIT 0 (none) or "
                                                "finite and above FLOOR (got " + std::to_string(po.ring_half_width) + ":" + std::to_string(po.ring_floor)
                                                + ":" + std::to_string(po.ring_limit) + ")"};
+        }
+
+        // --scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] as typed; refuses anything but four or six numbers
+        inline auto parse_scatter(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = cannot_read("--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2]", v);
+            const auto field = colon_fields(v);
+            if(field.size() != 4u && field.size() != 6u)
+                throw bad;
+            float value[6] = {};
+            for(std::size_t k = 0; k < field.size(); ++k)
+                value[k] = read_number<float>(field[k], bad);
+            auto& s = po.scatter_setting;
+            s.amplitude = value[0], s.alpha = value[1], s.beta = value[2], s.sigma1_mm = value[3];
+            s.sigma2_mm = field.size() == 6u ? value[4] : value[3];
+            s.weight2 = value[5];
+            po.scatter = true;
+        }
+
+        inline auto parse_scatter_iterations(const std::string& v, program_options& po) -> void
+        {
+            po.scatter_setting.iterations = read_unsigned(v, cannot_read("--scatter-iterations N", v));
+            po.scatter_detail_given = true;
+        }
+
+        inline auto parse_scatter_limit(const std::string& v, program_options& po) -> void
+        {
+            po.scatter_setting.limit = read_number<float>(v, cannot_read("--scatter-limit F", v));
+            po.scatter_detail_given = true;
+        }
+
+        inline auto parse_scatter_margin(const std::string& v, program_options& po) -> void
+        {
+            po.scatter_setting.margin = read_unsigned(v, cannot_read("--scatter-margin M", v));
+            if(po.scatter_setting.margin == 0u)
+                throw stage_construction_error{"--scatter-margin M: M must lie in 1 .. " + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX)};
+            po.scatter_detail_given = true;
+        }
+
+        // --scatter: resolved and checked here for the detector the reconstruction sees (the binned one with --bin), before any device
+        // work. The pass has no row band: the run is planned as --no-row-band plans it.
+        inline auto check_scatter(program_options& po) -> void
+        {
+            if(po.scatter_detail_given && !po.scatter)
+                throw stage_construction_error{"--scatter-iterations, --scatter-limit and --scatter-margin need --scatter"};
+            if(!po.scatter)
+                return;
+            auto& s = po.scatter_setting;
+            if(s.iterations < 1u || s.iterations > PARIS_HIP_SCATTER_ITERATIONS_MAX)
+                throw stage_construction_error{"--scatter-iterations N: N must lie in 1 .. " + std::to_string(PARIS_HIP_SCATTER_ITERATIONS_MAX)};
+            if(!(s.limit > 0.f && s.limit < 1.f))
+                throw stage_construction_error{"--scatter-limit F: F must lie in (0, 1)"};
+            if(s.margin == 0u)
+                s.margin = paris_hip_scatter_default_margin(s.sigma1_mm, s.sigma2_mm, po.det_geo.l_px_row, po.det_geo.l_px_col);
+            const int rc = paris_hip_scatter_correction_check(&s, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col,
+                                                              &po.scatter_nx, &po.scatter_ny, &po.scatter_scratch);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--scatter: the padded size " + std::to_string(po.scatter_nx) + " x " + std::to_string(po.scatter_ny) + " of a "
+                                               + std::to_string(po.det_geo.n_row) + " x " + std::to_string(po.det_geo.n_col) + " frame with a margin of "
+                                               + std::to_string(s.margin) + " exceeds " + std::to_string(PARIS_HIP_PHASE_SIZE_MAX)};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2]: A and the widths must be finite and greater than 0, ALPHA "
+                                               "must lie in [-2, 2], BETA in [0, 4], W2 must be finite and not negative, the margin must lie in 1 .. "
+                                               + std::to_string(PARIS_HIP_PHASE_MARGIN_MAX) + " and the detector's pixel pitches must be positive (got a margin of "
+                                               + std::to_string(s.margin) + ")"};
+            po.scatter_bytes = po.scatter_scratch + 12u * (std::size_t{po.scatter_nx} + po.scatter_ny); // twiddles and tables in front of the scratch
+            po.row_band = false;
         }
 
         // --phase DELTA_BETA:ENERGY_KEV[:MARGIN] (material = true) or --phase-alpha MM2[:MARGIN] as typed; refuses anything but the numbers
@@ -810,6 +886,10 @@ namespace paris
                 {"--detector-roll", parse_detector_roll},
                 {"--find-roll", parse_find_roll},
                 {"--air-region", parse_air_region},
+                {"--scatter", parse_scatter},
+                {"--scatter-iterations", parse_scatter_iterations},
+                {"--scatter-limit", parse_scatter_limit},
+                {"--scatter-margin", parse_scatter_margin},
                 {"--phase", [](const std::string& v, program_options& po) { parse_phase(v, po, true); }},
                 {"--phase-alpha", [](const std::string& v, program_options& po) { parse_phase(v, po, false); }},
                 {"--phase-floor", parse_phase_floor},

@@ -268,6 +268,9 @@ namespace paris
         {
             if(po.ring_c)
                 rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
+            if(po.scatter)
+                rt(paris_hip_set_scatter_correction(ctx, &po.scatter_setting, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col),
+                   "set_scatter_correction()");
             if(po.phase)
                 rt(paris_hip_set_phase_retrieval(ctx, &po.phase_setting, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col),
                    "set_phase_retrieval()");
@@ -319,7 +322,7 @@ namespace paris
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
             // with --lag, the state of a whole-detector sequence at most
             const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
-            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes + po.scatter_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -491,8 +494,8 @@ namespace paris
                     rt(paris_hip_zinger_filter_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "zinger filter");
             }
 
-            // the detector's stationary offsets, the phase retrieval -- a 2-D filter of whole frames: the run has no row band --, then
-            // the polynomial of the line integral: the run's, or `unit` in its place
+            // the detector's stationary offsets, the scatter correction and the phase retrieval -- 2-D passes over whole frames: the run
+            // has no row band --, then the polynomial of the line integral: the run's, or `unit` in its place
             void linearise(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const paris_hip_beam_hardening* unit = nullptr) const
             {
                 const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
@@ -500,6 +503,12 @@ namespace paris
                 auto* d = slots.frame(first);
                 if(po.ring_c)
                     rt(paris_hip_ring_correct_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "ring correction");
+                if(po.scatter)
+                {
+                    if(rows.band.first != 0u || rows.band.count != n_col)
+                        throw stage_runtime_error{"scatter correction: the plan gave a row band to a pass that corrects whole frames"};
+                    rt(paris_hip_scatter_correction_frames(ctx, d, slots.pitch, stride, n, n_row, n_col), "scatter correction");
+                }
                 if(po.phase)
                 {
                     if(rows.band.first != 0u || rows.band.count != n_col)
@@ -1127,6 +1136,11 @@ namespace paris
         float bh_threshold = 0.f;
         std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
         double bh_prepass_s = 0;
+        bool scatter = false;                           // --scatter: every frame went through this setting at these pitches; the
+        paris_hip_scatter_correction scatter_setting{}; // padded size and the scratch a device keeps for it
+        float scatter_l_x = 0.f, scatter_l_y = 0.f;
+        std::uint32_t scatter_nx = 0, scatter_ny = 0;
+        std::size_t scatter_scratch = 0;
         bool phase = false;                             // --phase / --phase-alpha: every frame went through this setting at these
         paris_hip_phase_retrieval phase_setting{};      // pitches; the padded size and the scratch a device keeps for it
         float phase_l_x = 0.f, phase_l_y = 0.f;
@@ -1744,6 +1758,7 @@ namespace paris
         detail::check_rings(po);
         detail::check_voxels(po);
         detail::check_axis(po);
+        detail::check_scatter(po);
         detail::check_phase(po);
         detail::check_beam_hardening(po);
         detail::check_roll(po);
@@ -1822,6 +1837,13 @@ namespace paris
                 po.metal_min_path = 0.5f * std::min(r.vol_geo.l_vx_x, std::min(r.vol_geo.l_vx_y, r.vol_geo.l_vx_z));
             detail::metal_prepass(po, r);
         }
+        r.scatter = po.scatter;
+        r.scatter_setting = po.scatter_setting;
+        r.scatter_l_x = po.det_geo.l_px_row;
+        r.scatter_l_y = po.det_geo.l_px_col;
+        r.scatter_nx = po.scatter_nx;
+        r.scatter_ny = po.scatter_ny;
+        r.scatter_scratch = po.scatter_scratch;
         r.phase = po.phase;
         r.phase_setting = po.phase_setting;
         r.phase_l_x = po.det_geo.l_px_row;

@@ -84,6 +84,10 @@ namespace paris
         if(backend::detail::has_ring_correction(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_ring_correct_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                        p.dim_y, 0u, p.dim_y), "weight()");
+        // then with a scatter setting (backend::set_scatter_correction) the kernel superposition: scatter is additive on the measured
+        // intensity and must be gone before a filter or a polynomial acts on what is taken for the primary
+        if(backend::detail::has_scatter_correction(backend::current_ctx()))
+            backend::scatter_correction(p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y);
         // then with a phase-retrieval setting (backend::set_phase_retrieval) the low-pass of the transmission image: a ring offset is a
         // per-pixel gain in transmission and must be gone before a 2-D filter smears it; the polynomial acts on the retrieved integral
         if(backend::detail::has_phase_retrieval(backend::current_ctx()))

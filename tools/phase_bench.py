@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Launches the kernels of the phase retrieval on one GPU, for a kernel trace:
 
-  phase_rows_forward_kernel / phase_columns_kernel / phase_rows_inverse_kernel
+  phase_rows_forward_kernel / frame_fft2_columns_kernel<paganin> / phase_rows_inverse_kernel
                          paris_hip_phase_retrieval_frames on 1 and on 16 frames of 2048^2 f32 line integrals at margin 24 (padded to
                          4096^2; the scratch holds one frame, so 16 frames are 16 rounds of three launches) and of 1024^2 (2048^2; seven
                          frames a round)
@@ -31,7 +31,7 @@ FRAMES = (1, 16)
 MARGIN = 24
 WARM = 3
 ALPHA, T_MIN, PITCH_MM = 0.02, 1e-6, 0.1           # a kernel length of sqrt(alpha) / 2 pi = 0.225 pixels of 0.1 mm
-KERNELS = ("phase_rows_forward_kernel", "phase_columns_kernel", "phase_rows_inverse_kernel")
+KERNELS = ("phase_rows_forward_kernel", "frame_fft2_columns_kernel", "phase_rows_inverse_kernel")
 
 
 def rounds(n, frames):
