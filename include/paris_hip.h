@@ -1493,6 +1493,62 @@ int paris_hip_volume_quantize_counts(paris_hip_ctx* ctx, paris_hip_volume_counts
 int paris_hip_volume_stats(paris_hip_ctx* ctx, const float* d_v, uint64_t n_voxels, float h_lo, float h_hi, uint32_t n_bins,
                            uint64_t* hist, paris_hip_volume_statistics* out);
 
+/* ---- volume denoising (extension, no reference counterpart): edge-preserving 3-D bilateral filter ---------
+ * The library's only neighbourhood operation on a volume (volume_bilateral.hip, bilateral_rule.cpp).
+ * Setting struct paris_hip_volume_bilateral { float sigma_r; float sigma_s; uint32_t radius; } -- the entry point has the same name,
+ *   so the type is always written with its `struct` keyword.
+ *   sigma_r is in the volume's own units.
+ *   sigma_s is in VOXELS, the same along x, y and z: the filter works on the grid, not in millimetres (a grid with unequal voxel edges
+ *   is smoothed by the same number of voxels along each axis).
+ *   radius is r, 1 <= r <= PARIS_HIP_BILATERAL_RADIUS_MAX: the stencil is (2r + 1)^3 taps.
+ * Check (paris_hip_volume_bilateral_check) refuses a NULL setting, a sigma that is not finite or not greater than 0, a radius
+ *   outside 1 .. 3, and a sigma_r for which rscale (below) is not finite or is 0.
+ * Tables, made on the host in double and rounded once to fp32 (paris_hip_volume_bilateral_tables returns them):
+ *   spatial s[dz][dy][dx] = exp(-(dx^2 + dy^2 + dz^2) / (2 sigma_s^2)) for offsets in [-r, r], dx fastest;
+ *   range R[i] = exp(-0.5 ((i + 0.5) * 4 / 1024)^2), PARIS_HIP_BILATERAL_BINS = 1024 entries over [0, 4 sigma_r) sampled at bin centres;
+ *   rscale = (float)(1024 / (4 (double)sigma_r)).
+ *   R departs from the exact Gaussian by at most (2 / 1024) e^-1/2 < 0.0012 in weight inside the cutoff of 4 sigma_r and by at most
+ *   e^-8 beyond it, where a tap gets no weight at all.
+ * Rule for an output voxel c with the value v_c. Its taps n are walked in the order dz, then dy, then dx, each ascending from -r, the
+ *   centre included, with num = den = 0 at the start. Every operation is fp32, rounded once, never contracted:
+ *     a tap outside the source buffer in x, y or z is skipped;
+ *     d = fabsf(v_n - v_c), t = d * rscale;
+ *     the tap contributes only if t < 1024.f -- false for NaN, so neighbours that are not finite drop out;
+ *     w = s[dz][dy][dx] * R[(uint32_t)t], num = num + w * v_n, den = den + w;
+ *   out = num / den with the IEEE division; den > 0 because the centre always contributes.
+ *   A centre that is not finite is written as stored. The device evaluates no transcendental function.
+ * The device gives the bits of paris_hip_volume_bilateral_host, so a volume filtered in chunks of slices equals the volume filtered
+ * whole when every chunk sees its halo of r source slices.
+ * A result CAN be -0: a negative num of a few denormal steps divided by a den above 1 rounds to -0 (and a centre that is not finite
+ * is copied). The destination is therefore treated as paris_hip_volume_mark_dirty treats a range. */
+#define PARIS_HIP_BILATERAL_BINS 1024
+#define PARIS_HIP_BILATERAL_RADIUS_MAX 3
+struct paris_hip_volume_bilateral {
+    float sigma_r;   /* range sigma, the volume's units; finite, > 0 */
+    float sigma_s;   /* spatial sigma, voxels; finite, > 0 */
+    uint32_t radius; /* r: 1 .. PARIS_HIP_BILATERAL_RADIUS_MAX */
+};
+/* Host only, no ctx and no device. */
+int paris_hip_volume_bilateral_check(const struct paris_hip_volume_bilateral* setting);
+/* Host only: spatial receives (2r + 1)^3 floats, range PARIS_HIP_BILATERAL_BINS floats, *rscale the scale. Any of the three may be
+ * NULL. PARIS_HIP_ERROR_INVALID_ARGUMENT for a setting the check refuses. */
+int paris_hip_volume_bilateral_tables(const struct paris_hip_volume_bilateral* setting, float* spatial, float* range, float* rscale);
+/* Host only: the rule on host arrays. src is dim_x x dim_y x src_dim_z floats, x fastest; slices [z_first, z_first + z_count) are
+ * filtered into the z_count slices at dst. Refuses what the device function refuses. */
+int paris_hip_volume_bilateral_host(const float* src, uint32_t dim_x, uint32_t dim_y, uint32_t src_dim_z, uint32_t z_first, uint32_t z_count,
+                                    const struct paris_hip_volume_bilateral* setting, float* dst);
+/* Filters slices [z_first, z_first + z_count) of the source buffer d_src (dim_x x dim_y x src_dim_z floats) into z_count slices at
+ * d_dst, on the ctx stream. What is deferred runs first. A z tap outside [0, src_dim_z) is skipped: where the grid continues beyond
+ * the buffer the caller supplies the halo slices and leaves them out of [z_first, z_first + z_count). The tables of the setting are
+ * uploaded when it differs from the one last used, owned by the ctx (the replaced ones are retired behind queued work), counted in
+ * paris_hip_projection_reserve_bytes and freed by paris_hip_ctx_destroy. The destination is treated as
+ * paris_hip_volume_mark_dirty treats a range (above: -0 can be produced). Aligned or not: the source is read as 16-byte vectors where
+ * its base and dim_x allow, voxel by voxel otherwise.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for NULL pointers, pointers that are not 4-byte aligned, a setting the check refuses, dim_x or
+ * dim_y of 0, z_count == 0, z_first + z_count > src_dim_z, or a destination range that overlaps the source BUFFER. */
+int paris_hip_volume_bilateral(paris_hip_ctx* ctx, const float* d_src, uint32_t dim_x, uint32_t dim_y, uint32_t src_dim_z, uint32_t z_first,
+                               uint32_t z_count, const struct paris_hip_volume_bilateral* setting, float* d_dst);
+
 /* Extension (no reference counterpart): single-distance phase retrieval after Paganin et al. (2002) -- at magnification a micro-focus
  * scan shows propagation fringes at material edges, which the ramp filter amplifies. For one material with a known delta / beta the
  * remedy is a low-pass on the TRANSMISSION image: the library's only pass that filters a frame in two dimensions (phase.hip,

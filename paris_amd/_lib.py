@@ -224,6 +224,16 @@ VOXEL_U16 = 2
 VOLUME_HISTOGRAM_BINS_MAX = 4096  # PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX
 
 
+BILATERAL_BINS = 1024  # PARIS_HIP_BILATERAL_BINS
+BILATERAL_RADIUS_MAX = 3  # PARIS_HIP_BILATERAL_RADIUS_MAX
+
+
+class VolumeBilateral(C.Structure):
+    """struct paris_hip_volume_bilateral: range sigma (the volume's units), spatial sigma (voxels) and radius of the 3-D bilateral
+    filter (extension)"""
+    _fields_ = [("sigma_r", C.c_float), ("sigma_s", C.c_float), ("radius", C.c_uint32)]
+
+
 class VolumeWindow(C.Structure):
     """paris_hip_volume_window: the grey window and integer type a volume is quantised to (extension)"""
     _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("voxel_type", C.c_int)]
@@ -462,6 +472,10 @@ SIGNATURES = {
     "paris_hip_volume_quantize_d2h": (C.c_int, [_vp, _vp, C.c_uint64, _P(VolumeWindow), _vp]),
     "paris_hip_volume_quantize_counts": (C.c_int, [_vp, _P(VolumeCounts), C.c_int]),
     "paris_hip_volume_stats": (C.c_int, [_vp, _vp, C.c_uint64, _f, _f, _u32, _vp, _P(VolumeStatistics)]),
+    "paris_hip_volume_bilateral_check": (C.c_int, [_P(VolumeBilateral)]),
+    "paris_hip_volume_bilateral_tables": (C.c_int, [_P(VolumeBilateral), _vp, _vp, _P(_f)]),
+    "paris_hip_volume_bilateral_host": (C.c_int, [_vp, _u32, _u32, _u32, _u32, _u32, _P(VolumeBilateral), _vp]),
+    "paris_hip_volume_bilateral": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(VolumeBilateral), _vp]),
     "paris_hip_strerror": (C.c_char_p, [C.c_int]),
     "paris_hip_version": (C.c_char_p, []),
     "paris_hip_last_backproject_ms": (C.c_int, [_vp, _P(_f)]),

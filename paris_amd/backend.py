@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (ScatterCorrection, PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (VolumeBilateral, ScatterCorrection, PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -22,7 +22,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "backproject", "forward_project", "short_scan_check", "offset_detector_check", "DefectPlan", "defect_plan",
            "ZingerFilter", "zinger_filter_check", "RowExtension", "row_extension_check", "row_extension_response",
            "RingFilter", "RingStats", "ring_filter_check", "ring_correction_from_mean", "VolumeWindow", "VolumeCounts",
-           "VolumeStatistics", "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
+           "VolumeStatistics", "VolumeBilateral", "volume_bilateral_check", "volume_bilateral_tables", "volume_bilateral_host",
+           "volume_window_check", "volume_window_from_histogram", "Binning", "binning_check",
            "binned_geometry", "bin_frame_host", "bin_mask", "AirRegion", "AirCounts", "air_region_check", "air_value_host",
            "BeamHardening", "BhCounts", "BhFit", "Labels", "BeamHardeningFit", "beam_hardening_check", "beam_hardening_host",
            "bh_threshold_from_histogram", "bh_gram_host", "bh_gram_matrix", "bh_solve", "DetectorRoll", "RollSearch", "RollResult",
@@ -673,6 +674,47 @@ def volume_window_check(lo, hi, dtype):
     check(_lib.load().paris_hip_volume_window_check(C.byref(w)), "paris_hip_volume_window_check")
 
 
+def _volume_bilateral(sigma_r, sigma_s=1.0, radius=None):
+    """the setting; radius None: min(3, ceil(2 sigma_s)), at least 1"""
+    if radius is None:
+        radius = int(min(3, max(1, np.ceil(2.0 * sigma_s)))) if np.isfinite(sigma_s) else 0
+    return VolumeBilateral(sigma_r, sigma_s, radius)
+
+
+def volume_bilateral_check(sigma_r, sigma_s=1.0, radius=None):
+    """Host only, no device (paris_hip_volume_bilateral_check): raises ParisHipError unless both sigmas are finite and > 0, the radius
+    is 1, 2 or 3 and 1024 / (4 sigma_r) is a finite float above 0. Returns the VolumeBilateral."""
+    b = _volume_bilateral(sigma_r, sigma_s, radius)
+    check(_lib.load().paris_hip_volume_bilateral_check(C.byref(b)), "paris_hip_volume_bilateral_check")
+    return b
+
+
+def volume_bilateral_tables(sigma_r, sigma_s=1.0, radius=None):
+    """Host only (paris_hip_volume_bilateral_tables): (spatial float32[2r+1, 2r+1, 2r+1] indexed [dz, dy, dx], range float32[1024],
+    rscale as a Python float that is an exact float32) of the setting."""
+    b = _volume_bilateral(sigma_r, sigma_s, radius)
+    side = 2 * min(int(b.radius), _lib.BILATERAL_RADIUS_MAX) + 1
+    spatial, rng, rscale = np.empty((side, side, side), np.float32), np.empty(_lib.BILATERAL_BINS, np.float32), C.c_float(0)
+    check(_lib.load().paris_hip_volume_bilateral_tables(C.byref(b), spatial.ctypes.data, rng.ctypes.data, C.byref(rscale)),
+          "paris_hip_volume_bilateral_tables")
+    return spatial, rng, float(rscale.value)
+
+
+def volume_bilateral_host(v, sigma_r, sigma_s=1.0, radius=None, z_first=0, z_count=None):
+    """Host only, no device (paris_hip_volume_bilateral_host): slices [z_first, z_first + z_count) of the 3-D array v (dim_z, dim_y,
+    dim_x; taken as float32) filtered by the rule, as a new float32 array of z_count slices. z_count None: all from z_first on."""
+    a = np.ascontiguousarray(v, np.float32)
+    if a.ndim != 3:
+        raise ValueError("volume_bilateral_host: the volume must be a 3-D array")
+    dim_z, dim_y, dim_x = a.shape
+    n = dim_z - z_first if z_count is None else z_count
+    b = _volume_bilateral(sigma_r, sigma_s, radius)
+    out = np.empty((max(int(n), 0), dim_y, dim_x), np.float32)
+    check(_lib.load().paris_hip_volume_bilateral_host(a.ctypes.data if a.size else None, dim_x, dim_y, dim_z, z_first, max(int(n), 0), C.byref(b),
+                                                      out.ctypes.data if out.size else None), "paris_hip_volume_bilateral_host")
+    return out
+
+
 def volume_window_from_histogram(hist, h_lo, h_hi, p_lo=0.1, p_hi=99.9):
     """Host only, no device (paris_hip_volume_window_from_histogram): the window (w_lo, w_hi) between the percentiles p_lo and p_hi
     of a linear histogram over [h_lo, h_hi], as two Python floats that are exact float32 values."""
@@ -863,6 +905,35 @@ class Backend:
         st = VolumeCounts()
         check(self._L.paris_hip_volume_quantize_counts(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_volume_quantize_counts")
         return st
+
+    # ---- volume denoising --------------------------------------------------------
+    volume_bilateral_check = staticmethod(volume_bilateral_check)
+    volume_bilateral_tables = staticmethod(volume_bilateral_tables)
+    volume_bilateral_host = staticmethod(volume_bilateral_host)
+
+    def set_volume_bilateral(self, sigma_r, sigma_s=1.0, radius=None):
+        """The setting volume_bilateral() filters with from here on: sigma_r in the volume's units, sigma_s in voxels, radius 1 .. 3
+        (None: min(3, ceil(2 sigma_s))). Checked on the host (raises ParisHipError); the device tables are made by the first call that
+        uses it. sigma_r None: no setting, volume_bilateral() refuses."""
+        self._bilateral = None if sigma_r is None else volume_bilateral_check(sigma_r, sigma_s, radius)
+
+    def volume_bilateral(self, v, out=None, z_first=0, z_count=None):
+        """paris_hip_volume_bilateral with the setting of set_volume_bilateral(): slices [z_first, z_first + z_count) of the device
+        volume v (z_count None: all from z_first on) filtered into z_count slices at out -- a device Volume, a device address or an
+        object with .ptr, which must not overlap v; None: a new device volume of z_count slices. A z tap outside v is skipped, so a
+        slab of a larger grid is passed with its halo slices and without them in the range. Runs what is deferred first; does not
+        wait. Returns out."""
+        b = getattr(self, "_bilateral", None)
+        if b is None:
+            raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_volume_bilateral")
+        n = v.dim_z - z_first if z_count is None else z_count
+        if out is None:
+            if n <= 0:
+                raise ParisHipError(_lib.ERROR_INVALID_ARGUMENT, "paris_hip_volume_bilateral")
+            out = self.make_volume_device(v.dim_x, v.dim_y, n)
+        check(self._L.paris_hip_volume_bilateral(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z, z_first, max(int(n), 0), C.byref(b),
+                                                 out.ptr if hasattr(out, "ptr") else out), "paris_hip_volume_bilateral")
+        return out
 
     def memset_volume(self, v):
         check(self._L.paris_hip_memset_volume(self._ctx, v.ptr, v.dim_x, v.dim_y, v.dim_z), "paris_hip_memset_volume")

@@ -293,12 +293,21 @@ struct paris_hip_ctx
         paris_hip_device_buffer mem, stage;
         uint64_t voxels = 0;
     } volume_window;
+    // Volume denoising (paris_hip_volume_bilateral), made at the first call with a setting and replaced when a
+    // call brings another: the PARIS_HIP_BILATERAL_BINS floats of the range table, then the (2r + 1)^3 of the spatial table.
+    struct volume_bilateral_t
+    {
+        bool set = false;
+        struct paris_hip_volume_bilateral rule{};
+        float rscale = 0.f;
+        paris_hip_device_buffer mem;
+    } volume_bilateral;
     // every setting above that owns device memory: what paris_hip_ctx_destroy releases and paris_hip_projection_reserve_bytes counts
     template <class F>
     void each_setting(F&& f)
     {
         f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
-        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase), f(scatter);
+        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase), f(scatter), f(volume_bilateral);
     }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
@@ -605,6 +614,10 @@ void paris_hip_warm_scatter();
 // scatter_rule.cpp: the four tables of G = g1x g1y + g2x g2y, in double and rounded once; the x tables carry the weights
 void paris_hip_scatter_tables(const paris_hip_scatter_correction* s, uint32_t n_x, uint32_t n_y, float l_x, float l_y, float* g1x, float* g2x,
                               float* g1y, float* g2y);
+void paris_hip_warm_volume_bilateral();
+// bilateral_rule.cpp: what paris_hip_volume_bilateral and its host rule refuse (the pointers are only compared, never read)
+int paris_hip_volume_bilateral_check_call(const float* src, uint32_t dim_x, uint32_t dim_y, uint32_t src_dim_z, uint32_t z_first, uint32_t z_count,
+                                          const struct paris_hip_volume_bilateral* setting, const float* dst);
 #pragma GCC visibility pop
 
 // widen.hip: enqueues on the ctx stream the in-place widening of rows whose stored pixels (PARIS_HIP_PIXEL_U8 / U16 / U32) sit in the

@@ -13,6 +13,7 @@
 //             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
 //             [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]
 //             [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]
+//             [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -95,6 +96,7 @@ int main(int argc, char** argv)
                             "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
                             "          [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]\n"
                             "          [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]\n"
+                            "          [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -169,7 +171,15 @@ int main(int argc, char** argv)
                             "whose ray crosses more than MIN_PATH mm of it [default: half the smallest voxel edge], widened by GROW pixels [0 .. 4,\n"
                             "default 1]. In the reconstruction those pixels of every frame are replaced by linear interpolation along the row,\n"
                             "after the roll and before the weights, and every slab gets its metal voxels back. The pre-pass needs the whole\n"
-                            "volume on one device. Not with --roi.\n");
+                            "volume on one device. Not with --roi.\n"
+                            "--denoise: the finished volume passes an edge-preserving 3-D bilateral filter on the device before it is written (or\n"
+                            "quantised: --voxel-type and its auto window then see the filtered voxels). A voxel becomes the mean of its\n"
+                            "(2 RADIUS + 1)^3 neighbours weighted by a Gaussian of their distance, SIGMA_S in VOXELS [default 1; the same along x, y\n"
+                            "and z, whatever the voxel edges], times a Gaussian of their difference in value, SIGMA_R in the volume's own units;\n"
+                            "neighbours further than 4 SIGMA_R in value count nothing. RADIUS is 1, 2 or 3 [default min(3, ceil(2 SIGMA_S))].\n"
+                            "Slabs are reconstructed with RADIUS more slices on each side, so the file does not depend on --slabs, --devices or\n"
+                            "--drain-chunk-kib. Runs after the metal reinsertion; with --roi the grid is the region's. Not with --axis-only or\n"
+                            "--roll-only.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -336,6 +346,11 @@ int main(int argc, char** argv)
                 std::printf("%s%.9g", k == 0u ? " " : ":", static_cast<double>(r.bh.c[k]));
             std::printf("\n");
         }
+        if(r.denoise)
+            std::printf("denoising on: 3-D bilateral filter, sigma_r %.9g, sigma_s %.9g voxel(s), radius %u (%u taps), %u halo slice(s) per slab side\n",
+                        static_cast<double>(r.denoise_setting.sigma_r), static_cast<double>(r.denoise_setting.sigma_s), r.denoise_setting.radius,
+                        (2u * r.denoise_setting.radius + 1u) * (2u * r.denoise_setting.radius + 1u) * (2u * r.denoise_setting.radius + 1u),
+                        r.denoise_setting.radius);
         if(r.metal)
             std::printf("metal reduction on: %llu voxel(s) above %.9g collected, grow %u, min_path %.9g mm, %llu trace pixel(s) over all views, "
                         "%u frame(s) in the pre-pass (%.3f s), %llu pixel(s) replaced in %llu run(s) and %llu row(s) left in the main pass\n",

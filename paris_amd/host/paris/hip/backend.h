@@ -742,6 +742,18 @@ namespace paris
             detail::runtime_check(paris_hip_metal_reinsert(current_ctx(), d_v, dim_x, dim_y, v_dim_z, v_offset), "metal_reinsert()");
         }
 
+        // the edge-preserving 3-D bilateral filter: slices [z_first, z_first + z_count) of the device buffer
+        // d_src (dim_x x dim_y x src_dim_z voxels) filtered into z_count slices at d_dst, which must not overlap it, on the calling
+        // thread's current device; sigma_r in the volume's units, sigma_s in voxels, radius 1 .. 3. A z tap outside the buffer is
+        // skipped: a slab of a larger grid is passed with its halo slices and without them in the range
+        inline auto volume_bilateral(const float* d_src, std::uint32_t dim_x, std::uint32_t dim_y, std::uint32_t src_dim_z, std::uint32_t z_first,
+                                     std::uint32_t z_count, float sigma_r, float sigma_s, std::uint32_t radius, float* d_dst) -> void
+        {
+            const struct paris_hip_volume_bilateral setting{sigma_r, sigma_s, radius};
+            detail::runtime_check(paris_hip_volume_bilateral(current_ctx(), d_src, dim_x, dim_y, src_dim_z, z_first, z_count, &setting, d_dst),
+                                  "volume_bilateral()");
+        }
+
         // ---- buffers ------------------------------------------------------------------------------------------
         struct device_free { void operator()(float* p) const noexcept { paris_hip_free(current_ctx(), p); } };
         struct host_free { void operator()(float* p) const noexcept { paris_hip_free_host(current_ctx(), p); } };

@@ -6,6 +6,7 @@
 #ifndef PARIS_AMD_HOST_OPTIONS_H_
 #define PARIS_AMD_HOST_OPTIONS_H_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -179,6 +180,14 @@ namespace paris
         std::shared_ptr<const std::vector<std::uint64_t>> metal_bits, metal_index; // filled by run(): the packed traces; the list's indices
         std::shared_ptr<const std::vector<float>> metal_value;  // filled by run(): the list's values
         std::size_t metal_bytes = 0;                            // filled by run(): what both settings occupy on a device
+        // edge-preserving denoising of the finished volume (extension): --denoise SIGMA_R[:SIGMA_S[:RADIUS]] --
+        // SIGMA_R in the volume's own units, SIGMA_S in voxels (default 1), RADIUS 1 .. 3 (default min(3, ceil(2 SIGMA_S))) -- checked by
+        // run() before any device work (detail::check_denoise). Every slab is then reconstructed with up to RADIUS halo slices on each
+        // side, clamped to the output grid, and the drain thread filters each chunk of whole slices into a scratch before it copies
+        // (or quantises) it down: the file does not depend on slabs, devices or the chunk size
+        bool denoise = false, denoise_radius_given = false;
+        struct paris_hip_volume_bilateral denoise_setting{0.f, 1.f, 0u}; // (`struct`: the entry point has the type's name)
+        std::size_t denoise_bytes = 0; // filled by run(): the halo slices of a slab, the drain ctx's scratch and its tables
         // row extension for laterally truncated projections (extension): --extend-rows W[:M], the taper length
         // and the number of edge pixels averaged (default 4), checked by run() before any device work (detail::check_extend_rows).
         // Every device ctx gets the setting; the row filter then adds the rank-2 update at its store
@@ -656,6 +665,47 @@ namespace paris
                 throw stage_construction_error{"--metal cannot be combined with --axis-only or --roll-only: nothing would be reconstructed"};
         }
 
+        // --denoise SIGMA_R[:SIGMA_S[:RADIUS]] as typed; refuses anything but one or two numbers and an unsigned integer (the ranges:
+        // check_denoise). Without RADIUS it is min(3, ceil(2 SIGMA_S)), at least 1 -- 0 for a SIGMA_S the check refuses anyway.
+        inline auto parse_denoise(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = cannot_read("--denoise SIGMA_R[:SIGMA_S[:RADIUS]]", v);
+            const auto field = colon_fields(v);
+            if(field.size() > 3u)
+                throw bad;
+            auto& s = po.denoise_setting;
+            s.sigma_r = read_number<float>(field[0], bad);
+            s.sigma_s = field.size() > 1u ? read_number<float>(field[1], bad) : 1.f;
+            po.denoise_radius_given = field.size() > 2u;
+            if(po.denoise_radius_given)
+                s.radius = read_unsigned(field[2], bad);
+            else if(std::isfinite(s.sigma_s) && s.sigma_s > 0.f)
+                s.radius = static_cast<std::uint32_t>(std::min(3.0, std::max(1.0, std::ceil(2.0 * static_cast<double>(s.sigma_s)))));
+            else
+                s.radius = 0u;
+            po.denoise = true;
+        }
+
+        // --denoise: checked here, before any device work and before the output directory is made
+        inline auto check_denoise(const program_options& po) -> void
+        {
+            if(!po.denoise)
+                return;
+            const auto usage = std::string{"--denoise SIGMA_R[:SIGMA_S[:RADIUS]]"};
+            const auto& s = po.denoise_setting;
+            if(!std::isfinite(s.sigma_r) || !(s.sigma_r > 0.f))
+                throw stage_construction_error{usage + ": SIGMA_R must be finite and greater than 0"};
+            if(!std::isfinite(s.sigma_s) || !(s.sigma_s > 0.f))
+                throw stage_construction_error{usage + ": SIGMA_S must be finite and greater than 0"};
+            if(s.radius < 1u || s.radius > PARIS_HIP_BILATERAL_RADIUS_MAX)
+                throw stage_construction_error{usage + ": RADIUS must lie in 1 .. " + std::to_string(PARIS_HIP_BILATERAL_RADIUS_MAX) + " (got "
+                                               + std::to_string(s.radius) + ")"};
+            if(paris_hip_volume_bilateral_check(&s) != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{usage + ": SIGMA_R is too small for the range table (1024 / (4 SIGMA_R) is not a finite float)"};
+            if(po.axis_only || po.roll_only)
+                throw stage_construction_error{"--denoise cannot be combined with --axis-only or --roll-only: nothing would be written"};
+        }
+
         // --find-axis LO:HI[:STEP] as typed; refuses anything but two or three numbers
         inline auto parse_find_axis(const std::string& v, program_options& po) -> void
         {
@@ -898,6 +948,7 @@ namespace paris
                 {"--lag", parse_lag},
                 {"--lag-start", parse_lag_start},
                 {"--metal", parse_metal},
+                {"--denoise", parse_denoise},
                 {"--voxel-type", parse_voxel_type},
                 {"--voxel-range", parse_voxel_range},
             };

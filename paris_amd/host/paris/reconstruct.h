@@ -322,7 +322,7 @@ namespace paris
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
             // with --lag, the state of a whole-detector sequence at most
             const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
-            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes + po.scatter_bytes
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes + po.scatter_bytes + po.denoise_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -572,6 +572,9 @@ namespace paris
         // With --voxel-type each chunk is quantised on the device into a scratch of the drain ctx and 1 or 2 bytes per voxel come down
         // (paris_hip_volume_quantize_d2h in the place of the copy); chunks stay whole slices, the two pinned buffers stay. With
         // --voxel-range auto the thread first takes the slab's extremes and histogram on the device and chooses the window.
+        // With --denoise the slab buffer carries halo slices around the slab's own, and each chunk of own slices is first filtered
+        // into a scratch of the drain ctx (paris_hip_volume_bilateral: its taps read the halo and the neighbouring chunks, which stay
+        // as reconstructed); the copy, the quantisation and the statistics then take the chunk from the scratch.
         class volume_drain
         {
         public:
@@ -581,11 +584,16 @@ namespace paris
                 std::uint32_t dim_x = 0, dim_y = 0, dim_z = 0, first = 0; // `first`: global slice of the slab's slice 0
                 paris_hip_fence* ready = nullptr;                          // recorded by the device thread on its own ctx
                 int buffer = 0;                                            // which of the device thread's volume buffers d_v is
+                // --denoise: the buffer holds `halo` more slices in front of slice 0 and buf_z slices in all; d_v is the BUFFER's start
+                std::uint32_t halo = 0, buf_z = 0;
             };
 
-            volume_drain(int device, sink& out, std::size_t chunk_bytes, const voxel_output& voxels)
-            : device_{device}, out_(out), chunk_bytes_{chunk_bytes}, voxels_(voxels)
+            volume_drain(int device, sink& out, std::size_t chunk_bytes, const voxel_output& voxels,
+                         const struct paris_hip_volume_bilateral* denoise = nullptr)
+            : device_{device}, out_(out), chunk_bytes_{chunk_bytes}, voxels_(voxels), denoise_{denoise != nullptr}
             {
+                if(denoise != nullptr)
+                    bilateral_ = *denoise;
                 thread_ = std::thread{[this] { work(); }};
             }
             volume_drain(const volume_drain&) = delete;
@@ -636,6 +644,7 @@ namespace paris
                 char* h_stage[2] = {nullptr, nullptr};
                 paris_hip_fence* stage_fence[2] = {nullptr, nullptr};
                 std::size_t stage_voxels = 0;
+                float* d_filtered = nullptr; // --denoise: a chunk's filtered floats, what is copied down or quantised (stream order: one is enough)
                 const std::size_t voxel_bytes = voxels_.type == 0 ? sizeof(float) : (voxels_.type == PARIS_HIP_VOXEL_U8 ? 1u : 2u);
                 auto window = paris_hip_volume_window{voxels_.lo, voxels_.hi, voxels_.type};
                 try
@@ -659,22 +668,6 @@ namespace paris
                         // src/sink.cpp:76); pinning gigabytes costs more than the reconstruction of a small data set
                         const auto slice_floats = static_cast<std::size_t>(j.dim_x) * j.dim_y;
                         const auto voxels = slice_floats * j.dim_z;
-                        if(voxels_.automatic) // the window from the finished volume: extremes, then 4096 bins over them, then the percentiles
-                        {
-                            auto st = paris_hip_volume_statistics{};
-                            rt(paris_hip_volume_stats(ctx, j.d_v, voxels, 0.f, 0.f, 0u, nullptr, &st), "volume stats");
-                            if(!(st.min < st.max))
-                                throw stage_runtime_error{"--voxel-range auto: the volume holds fewer than two different finite values"};
-                            auto hist = std::vector<std::uint64_t>(PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, 0u);
-                            rt(paris_hip_volume_stats(ctx, j.d_v, voxels, st.min, st.max, PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, hist.data(), &st),
-                               "volume histogram");
-                            rt(paris_hip_volume_window_from_histogram(hist.data(), PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, st.min, st.max, voxels_.p_lo,
-                                                                      voxels_.p_hi, &window.lo, &window.hi), "window from histogram");
-                            if(paris_hip_volume_window_check(&window) != PARIS_HIP_SUCCESS)
-                                throw stage_runtime_error{"--voxel-range auto: the percentiles leave no window (" + std::to_string(window.lo) + " .. "
-                                                          + std::to_string(window.hi) + ")"};
-                            out_.set_window(window.lo, window.hi); // writes the .mhd
-                        }
                         const auto want_voxels = std::max(slice_floats, std::min(voxels, chunk_bytes_ / voxel_bytes) / slice_floats * slice_floats);
                         if(want_voxels > stage_voxels)
                         {
@@ -688,14 +681,67 @@ namespace paris
                                 if(stage_fence[s] == nullptr)
                                     rt(paris_hip_fence_create(ctx, &stage_fence[s]), "fence");
                             }
+                            if(denoise_)
+                            {
+                                rt(paris_hip_free(ctx, d_filtered), "free");
+                                d_filtered = nullptr;
+                                rt(paris_hip_malloc_volume(ctx, j.dim_x, j.dim_y, static_cast<std::uint32_t>(want_voxels / slice_floats), &d_filtered), "make_volume()");
+                            }
                             stage_voxels = want_voxels;
                         }
                         const auto chunk_z = static_cast<std::uint32_t>(stage_voxels / slice_floats);
                         const auto n_chunks = (j.dim_z + chunk_z - 1u) / chunk_z;
+                        // chunk c of the slab's own slices on the device: with --denoise filtered into the scratch first -- the taps reach
+                        // into the halo slices and the neighbouring chunks, which stay as reconstructed --, else where it lies
+                        const auto chunk_on_device = [&](std::uint32_t c) -> const float* {
+                            const auto z0 = c * chunk_z;
+                            const auto nz = std::min(chunk_z, j.dim_z - z0);
+                            if(!denoise_)
+                                return j.d_v + static_cast<std::size_t>(z0) * slice_floats;
+                            rt(paris_hip_volume_bilateral(ctx, j.d_v, j.dim_x, j.dim_y, j.buf_z, j.halo + z0, nz, &bilateral_, d_filtered), "denoise");
+                            return d_filtered;
+                        };
+                        if(voxels_.automatic) // the window from the finished volume: extremes, then 4096 bins over them, then the percentiles
+                        {
+                            // (with --denoise the finished volume is the filtered one, which exists a chunk at a time: every statistic is a
+                            // sum, a minimum or a maximum over the chunks)
+                            auto st = paris_hip_volume_statistics{};
+                            auto hist = std::vector<std::uint64_t>(PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, 0u);
+                            const auto stats = [&](float lo, float hi, std::uint32_t n_bins, const char* what) {
+                                if(!denoise_)
+                                {
+                                    rt(paris_hip_volume_stats(ctx, j.d_v, voxels, lo, hi, n_bins, n_bins != 0u ? hist.data() : nullptr, &st), what);
+                                    return;
+                                }
+                                auto part = std::vector<std::uint64_t>(n_bins, 0u);
+                                for(std::uint32_t c = 0; c < n_chunks; ++c)
+                                {
+                                    auto s = paris_hip_volume_statistics{};
+                                    const auto nz = std::min(chunk_z, j.dim_z - c * chunk_z);
+                                    rt(paris_hip_volume_stats(ctx, chunk_on_device(c), static_cast<std::uint64_t>(slice_floats) * nz, lo, hi, n_bins,
+                                                              n_bins != 0u ? part.data() : nullptr, &s), what);
+                                    st.min = c == 0u ? s.min : std::min(st.min, s.min);
+                                    st.max = c == 0u ? s.max : std::max(st.max, s.max);
+                                    for(std::uint32_t b = 0; b < n_bins; ++b)
+                                        hist[b] = (c == 0u ? 0u : hist[b]) + part[b];
+                                }
+                            };
+                            stats(0.f, 0.f, 0u, "volume stats");
+                            if(!(st.min < st.max))
+                                throw stage_runtime_error{"--voxel-range auto: the volume holds fewer than two different finite values"};
+                            const float lo = st.min, hi = st.max;
+                            stats(lo, hi, PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, "volume histogram");
+                            rt(paris_hip_volume_window_from_histogram(hist.data(), PARIS_HIP_VOLUME_HISTOGRAM_BINS_MAX, lo, hi, voxels_.p_lo,
+                                                                      voxels_.p_hi, &window.lo, &window.hi), "window from histogram");
+                            if(paris_hip_volume_window_check(&window) != PARIS_HIP_SUCCESS)
+                                throw stage_runtime_error{"--voxel-range auto: the percentiles leave no window (" + std::to_string(window.lo) + " .. "
+                                                          + std::to_string(window.hi) + ")"};
+                            out_.set_window(window.lo, window.hi); // writes the .mhd
+                        }
                         const auto copy_down = [&](std::uint32_t c) {
                             const auto z0 = c * chunk_z;
                             const auto nz = std::min(chunk_z, j.dim_z - z0);
-                            const float* d_chunk = j.d_v + static_cast<std::size_t>(z0) * slice_floats;
+                            const float* d_chunk = chunk_on_device(c);
                             if(voxels_.type == 0)
                                 rt(paris_hip_memcpy_volume_d2h(ctx, reinterpret_cast<float*>(h_stage[c % 2u]), d_chunk, j.dim_x, j.dim_y, nz), "copy_d2h()");
                             else
@@ -748,6 +794,7 @@ namespace paris
                     paris_hip_fence_destroy(ctx, stage_fence[s]);
                     paris_hip_free_host(ctx, h_stage[s]);
                 }
+                paris_hip_free(ctx, d_filtered);
                 paris_hip_ctx_destroy(ctx);
             }
 
@@ -755,6 +802,8 @@ namespace paris
             sink& out_;
             std::size_t chunk_bytes_;
             voxel_output voxels_;
+            bool denoise_;
+            struct paris_hip_volume_bilateral bilateral_{};
             paris_hip_volume_counts counts_{};
             std::mutex m_;
             std::condition_variable cv_;
@@ -922,22 +971,29 @@ namespace paris
             rt(paris_hip_fence_create(ctx, &f), "fence");
         // (declared last: its destructor joins the drain thread before anything above is freed -- nothing reads the volumes or the
         // fences after that --, and the ctx is destroyed last of all)
-        volume_drain drain{device, out, po.drain_chunk_bytes, po.voxels};
+        volume_drain drain{device, out, po.drain_chunk_bytes, po.voxels, po.denoise ? &po.denoise_setting : nullptr};
         rep.setup_s = since(t_setup);
         task t{};
         bool two = false, decided = false;
         while(queue.pop(t)) // :89-91
         {
             const bool last = (t.num - t.id) <= 1;                                    // :92
-            const auto dim_z = t.subvol_geo.dim_z + (last ? t.subvol_geo.remainder : 0u); // make_volume: src/make_volume.cpp:32-34
-            const auto offset = t.id * t.subvol_geo.dim_z;                             // :96
+            const auto own_z = t.subvol_geo.dim_z + (last ? t.subvol_geo.remainder : 0u); // make_volume: src/make_volume.cpp:32-34
+            const auto own_offset = t.id * t.subvol_geo.dim_z;                         // :96
+            // --denoise: the slab is reconstructed with up to RADIUS more slices on each side, as far as the output grid goes: the taps
+            // of its own slices read them. Everything below sees the larger slab; the drain thread writes the own slices only
+            const std::uint32_t grid_z = t.num * t.subvol_geo.dim_z + t.subvol_geo.remainder;
+            const std::uint32_t reach = po.denoise ? po.denoise_setting.radius : 0u;
+            const std::uint32_t halo_lo = std::min(reach, own_offset), halo_hi = std::min(reach, grid_z - (own_offset + own_z));
+            const auto dim_z = halo_lo + own_z + halo_hi;
+            const auto offset = own_offset - halo_lo;
             const auto voxels = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * dim_z;
             if(rep.tasks == 1u && !decided) // a second slab for this device: is there room to keep the first while it is written?
             {
                 std::size_t free_b = 0, total_b = 0;
                 rt(paris_hip_device_memory(device, &free_b, &total_b), "device memory");
                 // a slab the size of the largest of the run (the last one carries the remainder) plus slack for the runtime
-                const auto need = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * (t.subvol_geo.dim_z + t.subvol_geo.remainder) * sizeof(float);
+                const auto need = static_cast<std::size_t>(t.subvol_geo.dim_x) * t.subvol_geo.dim_y * (t.subvol_geo.dim_z + t.subvol_geo.remainder + 2u * reach) * sizeof(float);
                 two = po.two_volumes && free_b > need + need / 8u + (std::size_t{256} << 20);
                 decided = true;
                 rep.two_volumes = two;
@@ -1077,8 +1133,10 @@ namespace paris
             j.d_v = d_v;
             j.dim_x = t.subvol_geo.dim_x;
             j.dim_y = t.subvol_geo.dim_y;
-            j.dim_z = dim_z;
-            j.first = offset;
+            j.dim_z = own_z;
+            j.first = own_offset;
+            j.halo = halo_lo;
+            j.buf_z = dim_z;
             j.ready = slab.done[b];
             j.buffer = b;
             drain.submit(j);
@@ -1165,6 +1223,8 @@ namespace paris
         bool lag = false;                               // --lag: every pass over the scan corrected the frames' counts with this model,
         paris_hip_lag_model lag_model{};                // whose instantaneous weight is lag_b0
         double lag_b0 = 0.0;
+        bool denoise = false;                           // --denoise: every voxel written passed the bilateral filter with this setting
+        struct paris_hip_volume_bilateral denoise_setting{};
         int voxel_type = 0;                             // --voxel-type: the voxels were quantised over [voxel_lo, voxel_hi] (with
         float voxel_lo = 0.f, voxel_hi = 0.f;           // --voxel-range auto: the window chosen); the counts of every drain ctx, added
         paris_hip_volume_counts voxels{};
@@ -1763,6 +1823,7 @@ namespace paris
         detail::check_beam_hardening(po);
         detail::check_roll(po);
         detail::check_metal(po);
+        detail::check_denoise(po);
         // --find-roll: the estimate becomes the run's roll (an estimate of exactly 0 is no roll)
         const auto adopt_roll = [&] {
             po.roll_deg = r.roll.eta_deg;
@@ -1801,6 +1862,16 @@ namespace paris
             throw stage_construction_error{"--fit-beam-hardening: the volume has " + std::to_string(r.vol_geo.dim_z) + " slice(s), fewer than the "
                                            + std::to_string(po.bh_slices) + " asked for"};
 
+        r.denoise = po.denoise;
+        r.denoise_setting = po.denoise_setting;
+        if(po.denoise) // beside a slab: its 2 RADIUS halo slices, the drain ctx's scratch of one chunk of floats (a slice at least) and its tables
+        {
+            const auto slice = static_cast<std::size_t>(r.roi_geo.dim_x) * r.roi_geo.dim_y * sizeof(float);
+            const std::size_t voxel_bytes = po.voxels.type == 0 ? sizeof(float) : (po.voxels.type == PARIS_HIP_VOXEL_U8 ? 1u : 2u);
+            const auto side = static_cast<std::size_t>(2u * po.denoise_setting.radius + 1u);
+            po.denoise_bytes = 2u * po.denoise_setting.radius * slice + std::max(slice, po.drain_chunk_bytes / voxel_bytes * sizeof(float))
+                               + sizeof(float) * (PARIS_HIP_BILATERAL_BINS + side * side * side);
+        }
         int n_dev = 0;
         detail::rt(paris_hip_device_count(&n_dev), "get_devices()"); // :145
         if(n_dev == 0)
