@@ -9,6 +9,9 @@
 //                       [--rings half_width floor limit] [--find-axis lo step count rows]
 //                       [--extend-rows W M] [--bin BX BY mask.raw|none] [--air-region x0 y0 width height limit] [--detector-roll deg]
 //                       [--lag steady|rest B1:A1[:B2:A2[:B3:A3[:B4:A4]]]]
+//                       [--beam-hardening C1:C2[:C3[:C4]]] [--scatter A alpha beta sigma1 sigma2 w2 limit iterations margin]
+//                       [--phase-alpha mm2 t_min margin] [--metal-trace bits.raw n_views] [--metal-voxels index.raw value.raw]
+//                       [--denoise sigma_r sigma_s radius] [--clear-after K]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -43,6 +46,24 @@
 // into a buffer of the binned detector (set_binning() before the loops, bin_frame() after paris::load()) and everything downstream runs
 // with binned_geometry(). mask.raw: n_col x n_row bytes at source size, nonzero = left out of its bin. --flat, --defects and the other
 // settings take frames of the BINNED size. Refused together with --rings and --reproject.
+// --beam-hardening: the coefficients c_1 ... c_N of the polynomial, as many as are typed (the library refuses more than four).
+// set_beam_hardening() before the loops, so that paris::weight() linearises each frame after the phase retrieval and before the roll.
+// --scatter: the nine fields of paris_hip_scatter_correction in their order. set_scatter_correction() before the loops, with the
+// binned detector's size and pitches under --bin, so that paris::weight() removes each frame's scatter after the ring correction.
+// --phase-alpha: alpha [mm^2], the floor of the transmission and the margin. set_phase_retrieval() before the loops (binned size and
+// pitches under --bin), so that paris::weight() low-passes each frame's transmission after the scatter correction.
+// --metal-trace: bits.raw holds the packed traces of n_views views, n_views x n_col x words uint64 with words = ceil(n_row / 64)
+// (paris_hip_metal_trace_pack's layout); a file of another size is refused. set_metal_trace() before the loops, so that paris::weight()
+// inpaints each frame with the trace of view p.idx after the roll and before the weights.
+// --metal-voxels: index.raw holds uint64 and value.raw as many float32, the list of paris_hip_metal_collect. set_metal_voxels() before
+// the loops; after each slab's projection loop and before its read-back metal_reinsert() puts the slab's part of the list back.
+// --denoise: sigma_r, sigma_s and the radius of the bilateral filter. Needs --slabs 1: after the loop (and the reinsertion) the volume
+// is filtered into a second device volume by two volume_bilateral() calls, slices [0, h) and [h, dim_z) with h = dim_z / 2, each with
+// the whole volume as its source, and the filtered volume is what is written.
+// --clear-after K: after projection K of each slab's loop the settings of --beam-hardening, --scatter, --phase-alpha, --metal-trace and
+// --metal-voxels are undone with their clear_*() calls, and set again at the top of the next slab: projections 0 .. K of every slab
+// pass through them, the others do not. (With --metal-voxels the list is gone when the slab is finished, so metal_reinsert() refuses.)
+// A setting the library refuses ends the run with status 1 and its message before out.raw is opened.
 // --reproject: the reconstruction is forward-projected at every angle of the scan (backend::forward_project) and the n_proj float32
 // frames are written to frames.raw. One slab's volume is alive at a time: after a slab's projection loop each view is loaded from the
 // host copy of the frames so far, the slab's part is added (the first slab writes) and the view is copied back; slabs go in
@@ -67,6 +88,24 @@ namespace
             s = s * 1664525u + 1013904223u;
             p[i] = static_cast<float>(s >> 8) / 16777216.f;
         }
+    }
+
+    // a whole raw file of T; n != 0: it must hold exactly n of them
+    template <typename T>
+    auto read_raw(const std::string& path, std::size_t n) -> std::vector<T>
+    {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        if(f == nullptr)
+            throw paris::stage_runtime_error{"cannot read " + path};
+        std::fseek(f, 0, SEEK_END);
+        const auto bytes = static_cast<std::size_t>(std::ftell(f));
+        std::fseek(f, 0, SEEK_SET);
+        auto v = std::vector<T>(bytes / sizeof(T));
+        const bool ok = bytes % sizeof(T) == 0 && (n == 0 || v.size() == n) && std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+        std::fclose(f);
+        if(!ok)
+            throw paris::stage_runtime_error{"cannot read " + path + ": " + std::to_string(bytes) + " byte(s), " + std::to_string(n * sizeof(T)) + " expected"};
+        return v;
     }
 }
 
@@ -122,6 +161,19 @@ int main(int argc, char** argv)
         float lag_b[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f}, lag_a[PARIS_HIP_LAG_TERMS_MAX] = {0.f, 0.f, 0.f, 0.f};
         std::uint32_t bin_x = 1, bin_y = 1;
         std::string bin_mask_path;
+        std::uint32_t bh_degree = 0;
+        float bh_c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // as many as are typed: the library judges the degree
+        bool scatter = false;
+        auto scatter_setting = paris_hip_scatter_correction{};
+        bool phase = false;
+        float phase_alpha = 0.f, phase_t_min = 0.f;
+        std::uint32_t phase_margin = 0;
+        std::string trace_path, voxel_index_path, voxel_value_path;
+        std::uint32_t trace_views = 0;
+        bool denoise = false;
+        float denoise_sigma_r = 0.f, denoise_sigma_s = 0.f;
+        std::uint32_t denoise_radius = 0;
+        long clear_after = -1;
         bool vol_given = false;
         int order = -1; // --order N: workgroup -> tile order of the backprojection kernels (A/B; -1 = the library's choice)
         auto roi = paris::region_of_interest{};
@@ -218,6 +270,62 @@ int main(int argc, char** argv)
                 }
                 a += 2;
             }
+            else if(!std::strcmp(argv[a], "--beam-hardening") && a + 1 < argc)
+            {
+                const char* at = argv[++a];
+                for(bh_degree = 0; bh_degree < 8u && *at != '\0';)
+                {
+                    char* end = nullptr;
+                    bh_c[bh_degree] = std::strtof(at, &end);
+                    if(end == at)
+                        break;
+                    ++bh_degree;
+                    at = *end == ':' ? end + 1 : end;
+                }
+            }
+            else if(!std::strcmp(argv[a], "--scatter") && a + 9 < argc)
+            {
+                scatter = true;
+                scatter_setting.amplitude = std::strtof(argv[a + 1], nullptr);
+                scatter_setting.alpha = std::strtof(argv[a + 2], nullptr);
+                scatter_setting.beta = std::strtof(argv[a + 3], nullptr);
+                scatter_setting.sigma1_mm = std::strtof(argv[a + 4], nullptr);
+                scatter_setting.sigma2_mm = std::strtof(argv[a + 5], nullptr);
+                scatter_setting.weight2 = std::strtof(argv[a + 6], nullptr);
+                scatter_setting.limit = std::strtof(argv[a + 7], nullptr);
+                scatter_setting.iterations = static_cast<std::uint32_t>(std::strtoul(argv[a + 8], nullptr, 10));
+                scatter_setting.margin = static_cast<std::uint32_t>(std::strtoul(argv[a + 9], nullptr, 10));
+                a += 9;
+            }
+            else if(!std::strcmp(argv[a], "--phase-alpha") && a + 3 < argc)
+            {
+                phase = true;
+                phase_alpha = std::strtof(argv[a + 1], nullptr);
+                phase_t_min = std::strtof(argv[a + 2], nullptr);
+                phase_margin = static_cast<std::uint32_t>(std::strtoul(argv[a + 3], nullptr, 10));
+                a += 3;
+            }
+            else if(!std::strcmp(argv[a], "--metal-trace") && a + 2 < argc)
+            {
+                trace_path = argv[a + 1];
+                trace_views = static_cast<std::uint32_t>(std::strtoul(argv[a + 2], nullptr, 10));
+                a += 2;
+            }
+            else if(!std::strcmp(argv[a], "--metal-voxels") && a + 2 < argc)
+            {
+                voxel_index_path = argv[a + 1];
+                voxel_value_path = argv[a + 2];
+                a += 2;
+            }
+            else if(!std::strcmp(argv[a], "--denoise") && a + 3 < argc)
+            {
+                denoise = true;
+                denoise_sigma_r = std::strtof(argv[a + 1], nullptr);
+                denoise_sigma_s = std::strtof(argv[a + 2], nullptr);
+                denoise_radius = static_cast<std::uint32_t>(std::strtoul(argv[a + 3], nullptr, 10));
+                a += 3;
+            }
+            else if(!std::strcmp(argv[a], "--clear-after") && a + 1 < argc) clear_after = std::atol(argv[++a]);
             else if(!std::strcmp(argv[a], "--bin") && a + 3 < argc)
             {
                 bin_x = static_cast<std::uint32_t>(std::strtoul(argv[a + 1], nullptr, 10));
@@ -260,6 +368,11 @@ int main(int argc, char** argv)
         if(lag && (rings || find_axis))
         {
             std::fprintf(stderr, "--lag cannot be combined with --rings or --find-axis\n");
+            return 2;
+        }
+        if(denoise && slabs != 1)
+        {
+            std::fprintf(stderr, "--denoise needs --slabs 1: the filter reads the whole volume\n");
             return 2;
         }
         const auto src_det = det; // the detector the frames of in.raw come from
@@ -341,6 +454,38 @@ int main(int argc, char** argv)
             paris::backend::set_detector_roll(roll_deg, det);
         if(lag)
             paris::backend::set_lag_correction(lag_b, lag_a, lag_terms, lag_start);
+        // the settings --clear-after undoes: set here, before out.raw is opened, and again at the top of every slab that follows a clear
+        const auto metal_bits = trace_path.empty() ? std::vector<std::uint64_t>{}
+                                                   : read_raw<std::uint64_t>(trace_path, std::size_t{trace_views} * det.n_col * ((det.n_row + 63u) / 64u));
+        const auto voxel_index = voxel_index_path.empty() ? std::vector<std::uint64_t>{} : read_raw<std::uint64_t>(voxel_index_path, 0u);
+        const auto voxel_value = voxel_value_path.empty() ? std::vector<float>{} : read_raw<float>(voxel_value_path, voxel_index.size());
+        if(!voxel_value_path.empty() && voxel_value.size() != voxel_index.size()) // (an empty list: read_raw's n == 0 checks nothing)
+            throw paris::stage_runtime_error{"cannot read " + voxel_value_path + ": not one value per index"};
+        const auto set_cleared = [&]() {
+            if(bh_degree != 0u)
+                paris::backend::set_beam_hardening(bh_c, bh_degree, det.n_row, det.n_col);
+            if(scatter)
+                paris::backend::set_scatter_correction(scatter_setting, det.n_row, det.n_col, det.l_px_row, det.l_px_col);
+            if(phase)
+                paris::backend::set_phase_retrieval(phase_alpha, phase_t_min, phase_margin, det.n_row, det.n_col, det.l_px_row, det.l_px_col);
+            if(!trace_path.empty())
+                paris::backend::set_metal_trace(metal_bits.data(), trace_views, det.n_row, det.n_col);
+            if(!voxel_index_path.empty())
+                paris::backend::set_metal_voxels(voxel_index.data(), voxel_value.data(), voxel_index.size());
+        };
+        const auto clear_set = [&]() {
+            if(bh_degree != 0u)
+                paris::backend::clear_beam_hardening();
+            if(scatter)
+                paris::backend::clear_scatter_correction();
+            if(phase)
+                paris::backend::clear_phase_retrieval();
+            if(!trace_path.empty())
+                paris::backend::clear_metal_trace();
+            if(!voxel_index_path.empty())
+                paris::backend::clear_metal_voxels();
+        };
+        set_cleared();
         if(order >= 0)
             paris::backend::detail::runtime_check(paris_hip_set_backproject_order(paris::backend::current_ctx(), order, -1), "--order");
 
@@ -415,6 +560,8 @@ int main(int argc, char** argv)
             const bool last = (info.num - id) <= 1;
             auto v = paris::make_volume(info.geo, last);
             const auto offset = static_cast<std::uint32_t>(id) * info.geo.dim_z;
+            if(clear_after >= 0 && id > 0) // the slab before has cleared them
+                set_cleared();
             const auto t_start = std::chrono::steady_clock::now();
             if(lag) // this pass over the scan is a sequence of its own, from frame 0
                 paris::backend::lag_begin(det.n_row, det.n_col, 0u, det.n_col);
@@ -449,6 +596,8 @@ int main(int argc, char** argv)
                 d_p.buf = paris::backend::projection_device_buffer_type{}; // (what the end of the reference's loop body does)
                 const auto c7 = clock::now();
                 p.buf.reset();
+                if(clear_after >= 0 && i == static_cast<std::uint32_t>(clear_after))
+                    clear_set();
                 const auto c8 = clock::now();
                 const clock::time_point c[9] = {c0, c1, c2, c3, c4, c5, c6, c7, c8};
                 for(int k = 0; k < 8; ++k)
@@ -461,6 +610,18 @@ int main(int argc, char** argv)
             paris::backend::synchronize(); // the timed region ends when the GPU has finished, not when the last call returned
             tail_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tail).count();
             loop_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+            auto filtered = paris::backend::volume_device_type{}; // --denoise: what is read back in v's place
+            if(!voxel_index_path.empty()) // the slab's part of the metal voxels, into the finished slab
+                paris::backend::metal_reinsert(v.buf.get(), v.dim_x, v.dim_y, v.dim_z, offset);
+            if(denoise) // one slab: the whole volume, filtered in two ranges of slices that both read all of it
+            {
+                filtered = paris::backend::make_volume_device(v.dim_x, v.dim_y, v.dim_z);
+                const auto h = v.dim_z / 2u;
+                paris::backend::volume_bilateral(v.buf.get(), v.dim_x, v.dim_y, v.dim_z, 0u, h, denoise_sigma_r, denoise_sigma_s, denoise_radius,
+                                                 filtered.buf.get());
+                paris::backend::volume_bilateral(v.buf.get(), v.dim_x, v.dim_y, v.dim_z, h, v.dim_z - h, denoise_sigma_r, denoise_sigma_s, denoise_radius,
+                                                 filtered.buf.get() + std::size_t{h} * v.dim_x * v.dim_y);
+            }
             if(!reproject_path.empty()) // this slab's part of every view, while its volume is alive
             {
                 const float delta_s = det.delta_s * det.l_px_row, delta_t = det.delta_t * det.l_px_col; // src/backprojection.cpp:49-50
@@ -483,7 +644,7 @@ int main(int argc, char** argv)
             if(out == nullptr) // --no-out: a throughput run, the volume is neither read back nor written
                 continue;
             auto h_v = paris::backend::make_volume_host(v.dim_x, v.dim_y, v.dim_z);
-            paris::backend::copy_d2h(v, h_v);
+            paris::backend::copy_d2h(denoise ? filtered : v, h_v);
             const auto n = std::size_t{v.dim_x} * v.dim_y * v.dim_z;
             std::fseek(out, static_cast<long>(std::size_t{v.dim_x} * v.dim_y * offset * sizeof(float)), SEEK_SET);
             if(std::fwrite(h_v.buf.get(), sizeof(float), n, out) != n)

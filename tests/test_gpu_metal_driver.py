@@ -40,24 +40,30 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-@pytest.fixture(scope="module")
-def scan(tmp_path_factory):
-    """the inputs on disk and the line integrals the driver's correction makes of them"""
-    root = tmp_path_factory.mktemp("metal_scan")
+def scene_scan():
+    """(counts, flat, frames): the scene as u16 counts with its flat, and the line integrals the driver's correction makes of them"""
     p = R.scene_frames().astype(np.float64)
     rng = np.random.default_rng(31)
     counts = np.clip(np.rint(FLAT * np.exp(-p)), 0, 65535).astype(np.uint16)
     for k in range(0, len(counts), 7):                                                     # a few zingers, for the run that filters them
         counts[k, rng.integers(0, 32), rng.integers(0, 64)] = 65535
     flat = np.full(counts.shape[1:], FLAT, np.uint16)
+    frames = CH.flat_field(counts.astype(np.float32), np.zeros(flat.shape, np.float32), flat.astype(np.float32), T_MIN)
+    assert frames.max() == np.float32(-math.log(np.float32(T_MIN))) and (frames == frames.max()).sum() > 1000   # the floor clips the metal's rays
+    return counts, flat, frames
+
+
+@pytest.fixture(scope="module")
+def scan(tmp_path_factory):
+    """the inputs on disk and the line integrals the driver's correction makes of them"""
+    root = tmp_path_factory.mktemp("metal_scan")
+    counts, flat, frames = scene_scan()
     (root / "ref").mkdir()
     (root / "ref" / "flat.his").write_bytes(F.his_file_bytes(flat[None], 4))
     (root / "counts").mkdir()
     (root / "counts" / "a.his").write_bytes(F.his_file_bytes(counts[:70], 4, 32))
     (root / "counts" / "b.his").write_bytes(F.his_file_bytes(counts[70:], 4, 32))
     (root / "geo.ini").write_text("\n".join("%s = %s" % (k, v if isinstance(v, int) else "%.9g" % float(v)) for k, v in zip(FF.GEO_KEYS, R.SCENE_DET)) + "\n")
-    frames = CH.flat_field(counts.astype(np.float32), np.zeros(flat.shape, np.float32), flat.astype(np.float32), T_MIN)
-    assert frames.max() == np.float32(-math.log(np.float32(T_MIN))) and (frames == frames.max()).sum() > 1000   # the floor clips the metal's rays
     return root, frames
 
 
@@ -73,9 +79,10 @@ def volume_of(root, out):
     return F.ddbvf_read(str(root / out / "vol.ddbvf"))[1]
 
 
-def python_chain(frames, metal, roll=None, zingers=None):
+def python_chain(frames, metal, roll=None, zingers=None, view=None, reinsert=True, last=None):
     """(volume, MetalTrace or None, MetalCounts or None): the frames through [zinger filter,] [roll,] [the remedy,] weight, filter and
-    backprojection in the Python mirror"""
+    backprojection in the Python mirror. view: the trace frame i is inpainted with, as a function of i (None: its own); reinsert False:
+    the metal voxels are not put back; last: only the frames 0 .. last are inpainted"""
     with B.Backend(0) as be:
         frames = [np.ascontiguousarray(f, np.float32) for f in frames]
         if zingers is not None or roll is not None:
@@ -102,13 +109,13 @@ def python_chain(frames, metal, roll=None, zingers=None):
         be.memset_volume(v)
         for i, f in enumerate(frames):
             d_p = B.load(be, B.Projection(f, DET.n_row, DET.n_col, idx=i))
-            if metal:
-                be.metal_inpaint(d_p)
+            if metal and (last is None or i <= last):
+                be.metal_inpaint(d_p, None if view is None else view(i))
             B.weight(be, d_p, DET)
             B.filter(be, d_p, DET)
             B.backproject(be, d_p, v, 0, DET, VG, False, False, None)
             be.free(d_p)
-        if metal:
+        if metal and reinsert:
             be.metal_reinsert(v)
         h = be.make_volume_host(VG.dim_x, VG.dim_y, VG.dim_z)
         be.copy_d2h(v, h)

@@ -32,13 +32,35 @@ def setting_for(st, limit=0.8, iterations=4, margin=None, typed=TYPED):
     return typed + (limit, iterations, margin)
 
 
-def mirror(s, st, scatter, alpha=None):
+ORDER = ("scatter", "phase", "beam_hardening", "roll")
+
+
+def mirror(s, st, scatter, alpha=None, rings=True, beam_hardening=True, roll=ETA, extend=None, order=ORDER, last=None):
     """the Python mirror's chain on all frames, one call per pass; scatter: the setting or None, alpha: the phase retrieval's or None;
-    then the loop -- roll, weight, filter, backproject -- frame by frame"""
+    then the loop -- roll, weight, filter, backproject -- frame by frame. rings, beam_hardening False, roll None: without that pass;
+    extend (W, M): the row extension in the filter; order: the passes behind the ring correction in another order, which is another
+    rule -- those named behind "roll" run on the resampled frame in the loop; last: scatter, phase and beam_hardening act on the frames
+    0 .. last only"""
     n = len(s.counts)
     det = B.DetectorGeometry(*st.geo)
     vg = B.calculate_volume_geometry(det)
+    assert sorted(order) == sorted(ORDER)
+    passed = n if last is None else last + 1
     with B.Backend(0) as be:
+
+        def run(name, p, **at):
+            if name == "scatter" and scatter is not None:
+                be.set_scatter_correction(scatter, st.dim_x, st.dim_y, det.l_px_row, det.l_px_col)
+                be.scatter_correction(p, **at)
+                be.clear_scatter_correction()
+            if name == "phase" and alpha is not None:
+                be.set_phase_retrieval(alpha, st.t_min, PHASE_MARGIN, st.dim_x, st.dim_y, det.l_px_row, det.l_px_col)
+                be.phase_retrieval(p, **at)
+                be.clear_phase_retrieval()
+            if name == "beam_hardening" and beam_hardening:
+                be.set_beam_hardening(st.bh, st.dim_x, st.dim_y)
+                be.beam_hardening(p, **at)
+
         configure(be, st)
         raw = Frames(be, n, st.src_x, st.src_y)
         dst = Frames(be, n, st.dim_x, st.dim_y) if st.bin > 1 else raw
@@ -51,32 +73,34 @@ def mirror(s, st, scatter, alpha=None):
         be.air_normalize(dst.frame(0), **at)
         be.defect_repair_rows(dst.frame(0), **at)
         be.zinger_filter_rows(dst.frame(0), **at)
-        be.ring_profile_begin(st.dim_x, st.dim_y)
-        be.ring_profile_add_rows(dst.frame(0), **at)
-        c, _, _ = be.ring_profile_finish(*st.rings)
-        be.set_ring_correction(c)
-        be.ring_correct_rows(dst.frame(0), **at)
-        if scatter is not None:
-            be.set_scatter_correction(scatter, st.dim_x, st.dim_y, det.l_px_row, det.l_px_col)
-            be.scatter_correction(dst.frame(0), **at)
-            be.clear_scatter_correction()
-        if alpha is not None:
-            be.set_phase_retrieval(alpha, st.t_min, PHASE_MARGIN, st.dim_x, st.dim_y, det.l_px_row, det.l_px_col)
-            be.phase_retrieval(dst.frame(0), **at)
-            be.clear_phase_retrieval()
-        be.beam_hardening(dst.frame(0), **at)
+        if rings:
+            be.ring_profile_begin(st.dim_x, st.dim_y)
+            be.ring_profile_add_rows(dst.frame(0), **at)
+            c, _, _ = be.ring_profile_finish(*st.rings)
+            be.set_ring_correction(c)
+            be.ring_correct_rows(dst.frame(0), **at)
+        for name in order[:order.index("roll")]:
+            run(name, dst.frame(0), frame_stride=dst.stride, n_frames=passed)
         frames = dst.read()[0].copy()
         clear(be)
         raw.free()
         if dst is not raw:
             dst.free()
-        be.set_detector_roll(ETA, det)
+        if roll is not None:
+            be.set_detector_roll(roll, det)
+        if extend is not None:
+            be.set_row_extension(extend[1], extend[0])
         v = be.make_volume_device(vg.dim_x, vg.dim_y, vg.dim_z)
         for i, fr in enumerate(frames):
             d_p, rolled = be.make_projection_device(det.n_row, det.n_col), be.make_projection_device(det.n_row, det.n_col)
             be.upload_raw(np.ascontiguousarray(fr, np.float32), d_p)
-            be.detector_roll(d_p, rolled)
+            if roll is not None:
+                be.detector_roll(d_p, rolled)
+            else:
+                d_p, rolled = rolled, d_p
             be.free(d_p)
+            for name in order[order.index("roll") + 1:] if i < passed else ():
+                run(name, rolled)
             rolled.idx = i
             B.weight(be, rolled, det)
             B.filter(be, rolled, det)
