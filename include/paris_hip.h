@@ -1682,6 +1682,75 @@ int paris_hip_clear_scatter_correction(paris_hip_ctx* ctx);
 int paris_hip_scatter_correction_frames(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
                                         uint32_t dim_y);
 
+/* Extension (no reference counterpart): suppression of photon-starvation streaks by adaptive filtering of the frames after Hsieh
+ * (1998) and Kachelriess, Watzke & Kalender (2001). Along the longest or densest paths the detector counts a handful of photons; after
+ * -ln the variance of the line integral grows like exp(p), and the ramp filter turns those pixels into streaks across the slice. The
+ * pass smooths a frame only where the line integral is high, and the more the higher it is; every other pixel keeps its bits
+ * (starvation.hip, starvation_rule.cpp).
+ * Setting paris_hip_starvation_filter { float p0; float gain; uint32_t radius; }:
+ *   p0      the line integral above which a pixel is filtered; finite.
+ *   gain    finite and > 0; 1 gives full noise equalisation (below).
+ *   radius  R, 1 <= R <= PARIS_HIP_STARVATION_RADIUS_MAX: the stencil is (2R + 1)^2 taps of the pixel's own frame.
+ * Tables, made once on the host in double and rounded once to fp32 (paris_hip_starvation_filter_tables returns them): there are
+ *   PARIS_HIP_STARVATION_LEVELS = 64 levels, each 1/16 wide in line integral; level k stands for the excess e_k = (k + 0.5) / 16 over p0.
+ *   sigma_k = min(R / 2, gain sqrt(expm1(e_k) / (4 pi))) pixels -- a 2-D Gaussian of width sigma averages about 4 pi sigma^2 pixels, and
+ *             exp(p - p0) pixels are what it takes to bring the variance at p down to the variance at p0.
+ *   g[k][d] = exp(-d^2 / (2 sigma_k^2)) for d = 0 .. R, row k at g + k (R + 1); g[k][0] = 1.
+ * Rule for pixel (x, y) of a frame with the stored value c; every operation is fp32, rounded once, never contracted:
+ *   if !(c > p0) the pixel is NOT WRITTEN: its bits stay, NaN payloads and -0 included.
+ *   t = (c - p0) * 16.f; k = t < 64.f ? (uint32_t)t : 63.
+ *   num = den = 0. Taps are walked with dy ascending from -R and within it dx ascending from -R, the centre included. A tap outside the
+ *   frame is skipped, and so is a tap whose value v is not finite. For every other tap w = g[k][|dy|] * g[k][|dx|],
+ *   num = num + w * v, den = den + w.
+ *   if den == 0 the pixel is not written (a +inf centre none of whose taps counts); else p = num / den, the IEEE division.
+ * Every tap is the value AS STORED BEFORE THE CALL: the result is a pure function of the input frame and depends neither on the other
+ * frames of the call, nor on how the launch is tiled, nor on any sweep order. The pass is not idempotent.
+ * Counts (paris_hip_starvation_stats): frames examined, pixels filtered (c > p0 and den != 0: the pixels that received num / den) and
+ * those of them at level 63, all exact integers equal to the host rule's. A high share at level 63 says that p0 is too low or the
+ * radius too small for the scan.
+ * Device: outputs go to a ctx-owned scratch of PARIS_HIP_STARVATION_FRAMES_MAX frames first and are stored into the frames by a second
+ * kernel, so no window reads a filtered value; calls with more frames loop. Scratch, tables and counters are one ctx-owned setting
+ *  that paris_hip_projection_reserve_bytes counts.
+ * Order: on line integrals, after the ring correction and before the scatter correction.
+ * Limits: 2-D only, no smoothing across views; the level comes from the noisy pixel itself; it works on the grid, not in mm. */
+#define PARIS_HIP_STARVATION_RADIUS_MAX 4
+#define PARIS_HIP_STARVATION_LEVELS 64
+#define PARIS_HIP_STARVATION_FRAMES_MAX 8 /* frames one launch serves: 128 MiB of scratch for 2048 x 2048 frames */
+typedef struct paris_hip_starvation_filter {
+    float p0;        /* filter above this line integral; finite */
+    float gain;      /* scales the width law; finite, > 0; 1: full noise equalisation */
+    uint32_t radius; /* R: 1 .. PARIS_HIP_STARVATION_RADIUS_MAX */
+} paris_hip_starvation_filter;
+/* what paris_hip_starvation_stats reports */
+typedef struct paris_hip_starvation_counts {
+    uint64_t frames;     /* frames examined */
+    uint64_t filtered;   /* pixels that received num / den */
+    uint64_t last_level; /* those of them at level 63 */
+} paris_hip_starvation_counts;
+/* Host only: PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL setting, a p0 or gain that is not finite, gain <= 0, a radius outside
+ * 1 .. PARIS_HIP_STARVATION_RADIUS_MAX or a zero dimension; PARIS_HIP_ERROR_UNSUPPORTED when dim_x * dim_y does not fit 32 bits.
+ * *device_bytes (may be NULL): what the setting occupies on a device. */
+int paris_hip_starvation_filter_check(const paris_hip_starvation_filter* setting, uint32_t dim_x, uint32_t dim_y, size_t* device_bytes);
+/* Host only: sigma receives PARIS_HIP_STARVATION_LEVELS floats, g PARIS_HIP_STARVATION_LEVELS * (R + 1). Either may be NULL.
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a setting the check refuses. */
+int paris_hip_starvation_filter_tables(const paris_hip_starvation_filter* setting, float* sigma, float* g);
+/* Host only: the rule on one dense frame, src to dst (dim_x x dim_y floats each, not overlapping): dst receives src with the filtered
+ * pixels replaced. counts (may be NULL) receives the frame's counts, frames = 1. The device gives these bits. Refusals as the check, or
+ * PARIS_HIP_ERROR_INVALID_ARGUMENT for a NULL src or dst. */
+int paris_hip_starvation_filter_host(const paris_hip_starvation_filter* setting, const float* src, float* dst, uint32_t dim_x, uint32_t dim_y,
+                                     paris_hip_starvation_counts* counts);
+/* paris_hip_set_starvation_filter runs the check and installs counters (zeroed), tables and scratch for dim_x x dim_y frames in memory
+ * the ctx owns. It replaces an earlier setting safely: work already queued keeps the old one. */
+int paris_hip_set_starvation_filter(paris_hip_ctx* ctx, const paris_hip_starvation_filter* setting, uint32_t dim_x, uint32_t dim_y);
+int paris_hip_clear_starvation_filter(paris_hip_ctx* ctx);
+/* In place on whole float frames, asynchronous on the ctx stream: every row is the pass's band, a pending by-reference group and a
+ * held-back weighting run first, calls of more than PARIS_HIP_STARVATION_FRAMES_MAX frames loop. PARIS_HIP_ERROR_INVALID_ARGUMENT
+ * without a setting, for other dimensions than the setting's, or for a pitch or stride paris_hip_flat_field_rows would refuse. */
+int paris_hip_starvation_filter_frames(paris_hip_ctx* ctx, float* d_p, size_t pitch, size_t frame_stride, uint32_t n_frames, uint32_t dim_x,
+                                       uint32_t dim_y);
+/* The counts since the setting was made or last reset; synchronises the ctx stream. reset != 0 zeroes them behind the read. */
+int paris_hip_starvation_stats(paris_hip_ctx* ctx, paris_hip_starvation_counts* out, int reset);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 const char* paris_hip_strerror(int status);
 /* library version "major.minor.patch" */

@@ -191,6 +191,21 @@ class ScatterCorrection(C.Structure):
                 ("weight2", C.c_float), ("limit", C.c_float), ("iterations", C.c_uint32), ("margin", C.c_uint32)]
 
 
+STARVATION_RADIUS_MAX = 4  # PARIS_HIP_STARVATION_RADIUS_MAX
+STARVATION_LEVELS = 64  # PARIS_HIP_STARVATION_LEVELS
+STARVATION_FRAMES_MAX = 8  # PARIS_HIP_STARVATION_FRAMES_MAX
+
+
+class StarvationFilter(C.Structure):
+    """paris_hip_starvation_filter: adaptive frame filter above the line integral p0 (extension)"""
+    _fields_ = [("p0", C.c_float), ("gain", C.c_float), ("radius", C.c_uint32)]
+
+
+class StarvationCounts(C.Structure):
+    """paris_hip_starvation_counts: what paris_hip_starvation_stats reports (extension)"""
+    _fields_ = [("frames", C.c_uint64), ("filtered", C.c_uint64), ("last_level", C.c_uint64)]
+
+
 LAG_TERMS_MAX = 4  # PARIS_HIP_LAG_TERMS_MAX
 LAG_START_REST = 0  # PARIS_HIP_LAG_START_REST
 LAG_START_STEADY = 1  # PARIS_HIP_LAG_START_STEADY
@@ -354,6 +369,13 @@ SIGNATURES = {
     "paris_hip_set_scatter_correction": (C.c_int, [_vp, _P(ScatterCorrection), _u32, _u32, C.c_float, C.c_float]),
     "paris_hip_clear_scatter_correction": (C.c_int, [_vp]),
     "paris_hip_scatter_correction_frames": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32]),
+    "paris_hip_starvation_filter_check": (C.c_int, [_P(StarvationFilter), _u32, _u32, _P(_sz)]),
+    "paris_hip_starvation_filter_tables": (C.c_int, [_P(StarvationFilter), _vp, _vp]),
+    "paris_hip_starvation_filter_host": (C.c_int, [_P(StarvationFilter), _vp, _vp, _u32, _u32, _P(StarvationCounts)]),
+    "paris_hip_set_starvation_filter": (C.c_int, [_vp, _P(StarvationFilter), _u32, _u32]),
+    "paris_hip_clear_starvation_filter": (C.c_int, [_vp]),
+    "paris_hip_starvation_filter_frames": (C.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32]),
+    "paris_hip_starvation_stats": (C.c_int, [_vp, _P(StarvationCounts), C.c_int]),
     "paris_hip_beam_hardening_check": (C.c_int, [_P(BeamHardening)]),
     "paris_hip_beam_hardening_host": (C.c_int, [_P(BeamHardening), _vp, _vp, C.c_uint64]),
     "paris_hip_set_beam_hardening": (C.c_int, [_vp, _P(BeamHardening), _u32, _u32]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (VolumeBilateral, ScatterCorrection, PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
+from ._lib import (StarvationFilter, StarvationCounts, VolumeBilateral, ScatterCorrection, PhaseRetrieval, BeamHardening, BhCounts, BhFit, LagModel, MetalCounts, DetectorRoll, RollSearch, RollResult, AirCounts, AirRegion, AxisEntry, AxisResult, AxisSearch, Binning, DefectStats, DetectorGeometry, ParisHipError, RegionOfInterest, RingFilter, RingStats, RowExtension, ShortScan,
                    SubvolumeGeometry, SubvolumeInfo, VolumeCounts, VolumeGeometry, VolumeStatistics, VolumeWindow, ZingerCounts,
                    ZingerFilter, check)
 
@@ -31,7 +31,8 @@ __all__ = ["DetectorGeometry", "VolumeGeometry", "SubvolumeGeometry", "RegionOfI
            "LagModel", "lag_model_check", "lag_coefficients", "lag_correct_host", "MetalCounts", "MetalTrace", "metal_check",
            "metal_collect_host", "metal_trace_pack_host", "metal_inpaint_host", "metal_words", "PhaseRetrieval", "phase_alpha",
            "phase_default_margin", "phase_retrieval_check", "phase_retrieval_host", "ScatterCorrection", "scatter_default_margin",
-           "scatter_correction_check", "scatter_correction_host"]
+           "scatter_correction_check", "scatter_correction_host", "StarvationFilter", "StarvationCounts", "starvation_filter_check",
+           "starvation_filter_tables", "starvation_filter_host"]
 
 
 class Projection:
@@ -425,6 +426,41 @@ def scatter_correction_host(setting, l_x, l_y, frame):
                                                         out.ctypes.data if f.size else None, f.shape[1], f.shape[0]),
           "paris_hip_scatter_correction_host")
     return out
+
+
+def _starvation_filter(setting):
+    return setting if isinstance(setting, StarvationFilter) else StarvationFilter(*setting)
+
+
+def starvation_filter_check(setting, dim_x, dim_y):
+    """Host only (paris_hip_starvation_filter_check): setting is a StarvationFilter (or its three values p0, gain, radius). Raises
+    ParisHipError for a setting the library refuses -- dim_x * dim_y beyond 32 bits is ERROR_UNSUPPORTED --, else returns the bytes the
+    setting occupies on a device."""
+    s, b = _starvation_filter(setting), C.c_size_t()
+    check(_lib.load().paris_hip_starvation_filter_check(C.byref(s), dim_x, dim_y, C.byref(b)), "paris_hip_starvation_filter_check")
+    return b.value
+
+
+def starvation_filter_tables(setting):
+    """Host only (paris_hip_starvation_filter_tables): (sigma float32[64], g float32[64, radius + 1]) -- the width of every level in
+    pixels and its weights g[k, d] for the distances d = 0 .. radius."""
+    s = _starvation_filter(setting)
+    r = s.radius if 1 <= s.radius <= _lib.STARVATION_RADIUS_MAX else 0
+    sigma, g = np.zeros(_lib.STARVATION_LEVELS, np.float32), np.zeros((_lib.STARVATION_LEVELS, r + 1), np.float32)
+    check(_lib.load().paris_hip_starvation_filter_tables(C.byref(s), sigma.ctypes.data, g.ctypes.data), "paris_hip_starvation_filter_tables")
+    return sigma, g
+
+
+def starvation_filter_host(setting, frame):
+    """Host only (paris_hip_starvation_filter_host): the rule on one frame of line integrals, a 2-D array (dim_y, dim_x) taken as
+    float32. Returns (a new array, the frame's StarvationCounts). The device gives these bits."""
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.ndim != 2:
+        raise ValueError("starvation_filter_host: the frame must be a 2-D array (dim_y, dim_x)")
+    out, counts, s = np.empty_like(f), StarvationCounts(), _starvation_filter(setting)
+    check(_lib.load().paris_hip_starvation_filter_host(C.byref(s), f.ctypes.data if f.size else None, out.ctypes.data if f.size else None,
+                                                       f.shape[1], f.shape[0], C.byref(counts)), "paris_hip_starvation_filter_host")
+    return out, counts
 
 
 _LAG_STARTS = {"rest": _lib.LAG_START_REST, "steady": _lib.LAG_START_STEADY}
@@ -1325,6 +1361,36 @@ class Backend:
         A frame's result does not depend on the other frames of the call."""
         check(self._L.paris_hip_scatter_correction_frames(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y),
               "paris_hip_scatter_correction_frames")
+
+    # ---- starvation filter (DESIGN.md section 4.25) ---------------------------------------------------------
+    starvation_filter_check = staticmethod(starvation_filter_check)
+    starvation_filter_tables = staticmethod(starvation_filter_tables)
+    starvation_filter_host = staticmethod(starvation_filter_host)
+
+    def set_starvation_filter(self, setting, dim_x, dim_y):
+        """paris_hip_set_starvation_filter for dim_x x dim_y frames; setting is a StarvationFilter (or p0, gain, radius):
+        starvation_filter() then smooths whole frames where the line integral lies above p0. Counters, tables and scratch live on the
+        device and count towards projection_reserve_bytes. Replaces an earlier setting; work already queued keeps the old one."""
+        s = _starvation_filter(setting)
+        check(self._L.paris_hip_set_starvation_filter(self._ctx, C.byref(s), dim_x, dim_y), "paris_hip_set_starvation_filter")
+
+    def clear_starvation_filter(self):
+        """paris_hip_clear_starvation_filter: no starvation filter from here on"""
+        check(self._L.paris_hip_clear_starvation_filter(self._ctx), "paris_hip_clear_starvation_filter")
+
+    def starvation_filter(self, p, frame_stride=0, n_frames=1):
+        """The rule of set_starvation_filter() in place on whole float frames of line integrals (paris_hip_starvation_filter_frames):
+        the n_frames frames frame_stride bytes apart starting at p. Call it after the ring correction and before the scatter
+        correction. A frame's result does not depend on the other frames of the call."""
+        check(self._L.paris_hip_starvation_filter_frames(self._ctx, p.ptr, p.pitch, frame_stride, n_frames, p.dim_x, p.dim_y),
+              "paris_hip_starvation_filter_frames")
+
+    def starvation_stats(self, reset=False):
+        """The StarvationCounts since set_starvation_filter() or the last reset (paris_hip_starvation_stats): frames, filtered,
+        last_level. Waits for the ctx stream."""
+        st = StarvationCounts()
+        check(self._L.paris_hip_starvation_stats(self._ctx, C.byref(st), 1 if reset else 0), "paris_hip_starvation_stats")
+        return st
 
     # ---- phase retrieval (DESIGN.md section 4.22) -----------------------------------------------------------
     phase_alpha = staticmethod(phase_alpha)

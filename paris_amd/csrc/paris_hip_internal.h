@@ -302,12 +302,22 @@ struct paris_hip_ctx
         float rscale = 0.f;
         paris_hip_device_buffer mem;
     } volume_bilateral;
+    // Starvation filter (paris_hip_set_starvation_filter): in this order three 64-bit counters (frames,
+    // filtered, last_level; padded to 32 bytes, zeroed at install), the table g -- PARIS_HIP_STARVATION_LEVELS rows of radius + 1 floats,
+    // in room for the largest radius --, and the scratch of PARIS_HIP_STARVATION_FRAMES_MAX dense frames of dim_x x dim_y floats.
+    struct starvation_t
+    {
+        bool set = false;
+        paris_hip_starvation_filter rule{};
+        uint32_t dim_x = 0, dim_y = 0;
+        paris_hip_device_buffer mem;
+    } starvation;
     // every setting above that owns device memory: what paris_hip_ctx_destroy releases and paris_hip_projection_reserve_bytes counts
     template <class F>
     void each_setting(F&& f)
     {
         f(flat_field), f(defect_map), f(zinger), f(ring_profile), f(ring_correction), f(axis), f(binning), f(air), f(lag.seq);
-        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase), f(scatter), f(volume_bilateral);
+        f(row_extension), f(volume_window), f(metal_trace), f(metal_voxels), f(phase), f(scatter), f(volume_bilateral), f(starvation);
     }
     // Buffers of replaced or cleared settings (paris_hip_retire_device_buffer): each behind an event recorded on the compute stream, freed
     // once that event has completed -- at a later set / clear, or at destroy.
@@ -615,6 +625,7 @@ void paris_hip_warm_scatter();
 void paris_hip_scatter_tables(const paris_hip_scatter_correction* s, uint32_t n_x, uint32_t n_y, float l_x, float l_y, float* g1x, float* g2x,
                               float* g1y, float* g2y);
 void paris_hip_warm_volume_bilateral();
+void paris_hip_warm_starvation();
 // bilateral_rule.cpp: what paris_hip_volume_bilateral and its host rule refuse (the pointers are only compared, never read)
 int paris_hip_volume_bilateral_check_call(const float* src, uint32_t dim_x, uint32_t dim_y, uint32_t src_dim_z, uint32_t z_first, uint32_t z_count,
                                           const struct paris_hip_volume_bilateral* setting, const float* dst);
@@ -692,6 +703,11 @@ inline paris_hip_roll_layout paris_hip_roll_layout_of(uint32_t n_row, uint32_t n
     l.bytes = l.total_of + pad(static_cast<size_t>(count) * 24u);
     return l;
 }
+
+// what lies in front of the scratch in paris_hip_ctx::starvation_t::mem (starvation.hip; starvation_rule.cpp reports the total)
+constexpr size_t PARIS_HIP_STARVATION_COUNTER_BYTES = 32u;
+constexpr size_t PARIS_HIP_STARVATION_HEAD_BYTES =
+    PARIS_HIP_STARVATION_COUNTER_BYTES + sizeof(float) * PARIS_HIP_STARVATION_LEVELS * (PARIS_HIP_STARVATION_RADIUS_MAX + 1u);
 
 // what the counters at the head of paris_hip_ctx::metal_trace_t::mem occupy (metal.hip)
 constexpr size_t PARIS_HIP_METAL_COUNTER_BYTES = 64u;

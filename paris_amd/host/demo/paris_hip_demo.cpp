@@ -11,7 +11,7 @@
 //                       [--lag steady|rest B1:A1[:B2:A2[:B3:A3[:B4:A4]]]]
 //                       [--beam-hardening C1:C2[:C3[:C4]]] [--scatter A alpha beta sigma1 sigma2 w2 limit iterations margin]
 //                       [--phase-alpha mm2 t_min margin] [--metal-trace bits.raw n_views] [--metal-voxels index.raw value.raw]
-//                       [--denoise sigma_r sigma_s radius] [--clear-after K]
+//                       [--denoise sigma_r sigma_s radius] [--starvation p0 gain radius] [--clear-after K]
 // in.raw holds n_proj frames of n_col x n_row float32; "lcg" generates the SURVEY.md 8c noise frames.
 // --cycle K: only K distinct lcg frames are held in host memory and projection i is frame i mod K (throughput runs over a whole
 // circle of large frames: 1440 frames of 2048^2 would be 23 GiB); --no-out: the volume is neither read back nor written to out.raw.
@@ -50,6 +50,9 @@
 // set_beam_hardening() before the loops, so that paris::weight() linearises each frame after the phase retrieval and before the roll.
 // --scatter: the nine fields of paris_hip_scatter_correction in their order. set_scatter_correction() before the loops, with the
 // binned detector's size and pitches under --bin, so that paris::weight() removes each frame's scatter after the ring correction.
+// --starvation: the three fields of paris_hip_starvation_filter in their order. set_starvation_filter() before the loops, with the
+// binned detector's size under --bin, so that paris::weight() smooths each frame's starved pixels after the ring correction and before
+// the scatter correction.
 // --phase-alpha: alpha [mm^2], the floor of the transmission and the margin. set_phase_retrieval() before the loops (binned size and
 // pitches under --bin), so that paris::weight() low-passes each frame's transmission after the scatter correction.
 // --metal-trace: bits.raw holds the packed traces of n_views views, n_views x n_col x words uint64 with words = ceil(n_row / 64)
@@ -60,7 +63,7 @@
 // --denoise: sigma_r, sigma_s and the radius of the bilateral filter. Needs --slabs 1: after the loop (and the reinsertion) the volume
 // is filtered into a second device volume by two volume_bilateral() calls, slices [0, h) and [h, dim_z) with h = dim_z / 2, each with
 // the whole volume as its source, and the filtered volume is what is written.
-// --clear-after K: after projection K of each slab's loop the settings of --beam-hardening, --scatter, --phase-alpha, --metal-trace and
+// --clear-after K: after projection K of each slab's loop the settings of --beam-hardening, --starvation, --scatter, --phase-alpha, --metal-trace and
 // --metal-voxels are undone with their clear_*() calls, and set again at the top of the next slab: projections 0 .. K of every slab
 // pass through them, the others do not. (With --metal-voxels the list is gone when the slab is finished, so metal_reinsert() refuses.)
 // A setting the library refuses ends the run with status 1 and its message before out.raw is opened.
@@ -165,6 +168,8 @@ int main(int argc, char** argv)
         float bh_c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // as many as are typed: the library judges the degree
         bool scatter = false;
         auto scatter_setting = paris_hip_scatter_correction{};
+        bool starvation = false;
+        auto starvation_setting = paris_hip_starvation_filter{};
         bool phase = false;
         float phase_alpha = 0.f, phase_t_min = 0.f;
         std::uint32_t phase_margin = 0;
@@ -325,6 +330,14 @@ int main(int argc, char** argv)
                 denoise_radius = static_cast<std::uint32_t>(std::strtoul(argv[a + 3], nullptr, 10));
                 a += 3;
             }
+            else if(!std::strcmp(argv[a], "--starvation") && a + 3 < argc)
+            {
+                starvation = true;
+                starvation_setting.p0 = std::strtof(argv[a + 1], nullptr);
+                starvation_setting.gain = std::strtof(argv[a + 2], nullptr);
+                starvation_setting.radius = static_cast<std::uint32_t>(std::strtoul(argv[a + 3], nullptr, 10));
+                a += 3;
+            }
             else if(!std::strcmp(argv[a], "--clear-after") && a + 1 < argc) clear_after = std::atol(argv[++a]);
             else if(!std::strcmp(argv[a], "--bin") && a + 3 < argc)
             {
@@ -464,6 +477,8 @@ int main(int argc, char** argv)
         const auto set_cleared = [&]() {
             if(bh_degree != 0u)
                 paris::backend::set_beam_hardening(bh_c, bh_degree, det.n_row, det.n_col);
+            if(starvation)
+                paris::backend::set_starvation_filter(starvation_setting, det.n_row, det.n_col);
             if(scatter)
                 paris::backend::set_scatter_correction(scatter_setting, det.n_row, det.n_col, det.l_px_row, det.l_px_col);
             if(phase)
@@ -476,6 +491,8 @@ int main(int argc, char** argv)
         const auto clear_set = [&]() {
             if(bh_degree != 0u)
                 paris::backend::clear_beam_hardening();
+            if(starvation)
+                paris::backend::clear_starvation_filter();
             if(scatter)
                 paris::backend::clear_scatter_correction();
             if(phase)

@@ -13,7 +13,7 @@
 //             [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]
 //             [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]
 //             [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]
-//             [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]]
+//             [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]] [--starvation P0[:GAIN[:RADIUS]]]
 // geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi (:83-91).
 #include <cstdio>
 #include <cstdlib>
@@ -96,7 +96,7 @@ int main(int argc, char** argv)
                             "          [--lag B1:A1[:B2:A2[:B3:A3[:B4:A4]]] [--lag-start rest|steady]]\n"
                             "          [--metal THR[:GROW[:MIN_PATH]]] [--phase DELTA_BETA:ENERGY_KEV[:MARGIN] | --phase-alpha MM2[:MARGIN]] [--phase-floor T]\n"
                             "          [--scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] [--scatter-iterations N] [--scatter-limit F] [--scatter-margin M]]\n"
-                            "          [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]]\n"
+                            "          [--denoise SIGMA_R[:SIGMA_S[:RADIUS]]] [--starvation P0[:GAIN[:RADIUS]]]\n"
                             "geo.ini: key=value lines for n_row n_col l_px_row l_px_col delta_s delta_t d_so d_od delta_phi\n"
                             "Reconstructs the HIS projections of <dir> (sorted by path) into <output>/<name>.ddbvf on all MI355X of the node.\n"
                             "--short-scan: the projections form a short scan from their first to their last angle (at least 180 degrees plus\n"
@@ -179,7 +179,13 @@ int main(int argc, char** argv)
                             "neighbours further than 4 SIGMA_R in value count nothing. RADIUS is 1, 2 or 3 [default min(3, ceil(2 SIGMA_S))].\n"
                             "Slabs are reconstructed with RADIUS more slices on each side, so the file does not depend on --slabs, --devices or\n"
                             "--drain-chunk-kib. Runs after the metal reinsertion; with --roi the grid is the region's. Not with --axis-only or\n"
-                            "--roll-only.\n");
+                            "--roll-only.\n"
+                            "--starvation: along the longest or densest paths the detector counts a handful of photons, and the ramp filter turns\n"
+                            "those noisy pixels into streaks. Every frame is smoothed on the device where its line integral lies above P0, by a 2-D\n"
+                            "Gaussian over (2 RADIUS + 1)^2 pixels [RADIUS 1 .. 4, default 3] whose width grows with the excess over P0 so that the\n"
+                            "noise comes down to that at P0 (GAIN scales the width, default 1; at most RADIUS / 2 pixels); pixels at or below P0 keep\n"
+                            "their bits. After the ring correction, before the scatter correction; whole frames (planned as --no-row-band). Not\n"
+                            "with --axis-only or --roll-only.\n");
                 return 0;
             }
             if(k == "--geometry") geometry = val();
@@ -313,6 +319,17 @@ int main(int argc, char** argv)
         }
         if(r.detector_roll)
             std::printf("detector roll on: %.9g deg\n", static_cast<double>(r.roll_deg));
+        if(r.starvation)
+        {
+            const auto& s = r.starvation_setting;
+            const auto& c = r.starvation_counts;
+            std::printf("starvation filter on: p0 %.9g, gain %.9g, radius %u, %llu pixel(s) filtered of %llu in %llu frame(s) (%.4g %%), %.4g %% of them "
+                        "at the last level, whole frames (planned as --no-row-band)\n", static_cast<double>(s.p0), static_cast<double>(s.gain), s.radius,
+                        static_cast<unsigned long long>(c.filtered), static_cast<unsigned long long>(r.starvation_pixels),
+                        static_cast<unsigned long long>(c.frames),
+                        r.starvation_pixels != 0u ? 100.0 * static_cast<double>(c.filtered) / static_cast<double>(r.starvation_pixels) : 0.0,
+                        c.filtered != 0u ? 100.0 * static_cast<double>(c.last_level) / static_cast<double>(c.filtered) : 0.0);
+        }
         if(r.scatter)
         {
             const auto& s = r.scatter_setting;

@@ -34,6 +34,8 @@ namespace
         f("scatter_alpha", po.scatter_setting.alpha), f("scatter_beta", po.scatter_setting.beta), f("scatter_sigma1", po.scatter_setting.sigma1_mm);
         f("scatter_sigma2", po.scatter_setting.sigma2_mm), f("scatter_weight2", po.scatter_setting.weight2), f("scatter_limit", po.scatter_setting.limit);
         u("scatter_iterations", po.scatter_setting.iterations), u("scatter_margin", po.scatter_setting.margin);
+        u("starvation", po.starvation), f("starvation_p0", po.starvation_setting.p0), f("starvation_gain", po.starvation_setting.gain);
+        u("starvation_radius", po.starvation_setting.radius);
         u("denoise", po.denoise), u("denoise_radius_given", po.denoise_radius_given), f("denoise_sigma_r", po.denoise_setting.sigma_r);
         f("denoise_sigma_s", po.denoise_setting.sigma_s), u("denoise_radius", po.denoise_setting.radius);
         u("beam_hardening", po.beam_hardening), u("fit_beam_hardening", po.fit_beam_hardening), u("bh_degree", po.bh.degree);

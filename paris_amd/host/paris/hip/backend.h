@@ -134,6 +134,7 @@ namespace paris
                 std::set<const paris_hip_ctx*> beam_hardenings; // set_beam_hardening(), per device of this thread
                 std::set<const paris_hip_ctx*> phase_retrievals; // set_phase_retrieval(), per device of this thread
                 std::set<const paris_hip_ctx*> scatter_corrections; // set_scatter_correction(), per device of this thread
+                std::set<const paris_hip_ctx*> starvation_filters;  // set_starvation_filter(), per device of this thread
                 std::set<const paris_hip_ctx*> detector_rolls; // set_detector_roll(), per device of this thread
                 std::set<const paris_hip_ctx*> metal_traces;   // set_metal_trace(), per device of this thread
             };
@@ -391,6 +392,38 @@ namespace paris
             inline auto has_scatter_correction(const paris_hip_ctx* ctx) -> bool
             {
                 const auto& s = state().scatter_corrections;
+                return !s.empty() && s.count(ctx) != 0u;
+            }
+        }
+
+        // Extension (no reference counterpart): along the longest paths the frames of this thread's current device (n_row x n_col pixels)
+        // count a handful of photons. Until clear_starvation_filter(), paris::weight() smooths every frame where
+        // its line integral lies above setting.p0, the more the higher it is, after the ring correction and before the scatter correction
+        // (paris_hip_starvation_filter_frames).
+        inline auto set_starvation_filter(const paris_hip_starvation_filter& setting, std::uint32_t n_row, std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_set_starvation_filter(current_ctx(), &setting, n_row, n_col), "set_starvation_filter()");
+            detail::state().starvation_filters.insert(current_ctx());
+        }
+
+        inline auto clear_starvation_filter() -> void
+        {
+            detail::runtime_check(paris_hip_clear_starvation_filter(current_ctx()), "clear_starvation_filter()");
+            detail::state().starvation_filters.erase(current_ctx());
+        }
+
+        // the pass itself, on n_frames whole frames frame_stride bytes apart
+        inline auto starvation_filter(float* d_p, std::size_t pitch, std::size_t frame_stride, std::uint32_t n_frames, std::uint32_t n_row,
+                                      std::uint32_t n_col) -> void
+        {
+            detail::runtime_check(paris_hip_starvation_filter_frames(current_ctx(), d_p, pitch, frame_stride, n_frames, n_row, n_col), "starvation_filter()");
+        }
+
+        namespace detail
+        {
+            inline auto has_starvation_filter(const paris_hip_ctx* ctx) -> bool
+            {
+                const auto& s = state().starvation_filters;
                 return !s.empty() && s.count(ctx) != 0u;
             }
         }

@@ -142,6 +142,14 @@ namespace paris
         paris_hip_scatter_correction scatter_setting{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.8f, 4u, 0u}; // margin 0: not given; run() takes the default
         std::uint32_t scatter_nx = 0, scatter_ny = 0;           // filled by run(): the padded size
         std::size_t scatter_scratch = 0, scatter_bytes = 0;     // filled by run(): the scratch, and what the setting occupies on a device
+        // suppression of photon-starvation streaks (extension): --starvation P0[:GAIN[:RADIUS]] gives the line
+        // integral above which a pixel is smoothed, the scale of the width law (default 1) and the stencil's radius (default 3). Checked by
+        // run() before any device work, for the binned detector with --bin (detail::check_starvation). Every device ctx gets the setting,
+        // and each frame is filtered -- as a whole: the run is planned without the row band -- after the ring correction and before the
+        // scatter correction
+        bool starvation = false;
+        paris_hip_starvation_filter starvation_setting{0.f, 1.f, 3u};
+        std::size_t starvation_bytes = 0;                       // filled by run(): what the setting occupies on a device
         // correction of the detector's in-plane rotation (extension): --detector-roll DEG gives the angle,
         // --find-roll LO:HI[:STEP] [--roll-only] has run() find it from the scan mean of the ring profile pre-pass (detail::prepass,
         // after the axis search, whose delta_s it uses): both checked by run() before any device work (detail::check_roll). Every
@@ -433,6 +441,39 @@ namespace paris
                 throw stage_construction_error{"--rings H[:FLOOR[:LIMIT]]: H must lie in 1 .. 32, FLOOR must be finite and not negative, LIMIT 0 (none) or "
                                                "finite and above FLOOR (got " + std::to_string(po.ring_half_width) + ":" + std::to_string(po.ring_floor)
                                                + ":" + std::to_string(po.ring_limit) + ")"};
+        }
+
+        // --starvation P0[:GAIN[:RADIUS]] as typed; refuses anything but one or two numbers and an unsigned integer
+        inline auto parse_starvation(const std::string& v, program_options& po) -> void
+        {
+            const auto bad = cannot_read("--starvation P0[:GAIN[:RADIUS]]", v);
+            const auto field = colon_fields(v);
+            if(field.size() > 3u)
+                throw bad;
+            auto& s = po.starvation_setting;
+            s.p0 = read_number<float>(field[0], bad);
+            s.gain = field.size() > 1u ? read_number<float>(field[1], bad) : 1.f;
+            s.radius = field.size() > 2u ? read_unsigned(field[2], bad) : 3u;
+            po.starvation = true;
+        }
+
+        // --starvation: checked here for the detector the reconstruction sees (the binned one with --bin), before any device work. The
+        // pass has no row band: the run is planned as --no-row-band plans it.
+        inline auto check_starvation(program_options& po) -> void
+        {
+            if(!po.starvation)
+                return;
+            const auto& s = po.starvation_setting;
+            const int rc = paris_hip_starvation_filter_check(&s, po.det_geo.n_row, po.det_geo.n_col, &po.starvation_bytes);
+            if(rc == PARIS_HIP_ERROR_UNSUPPORTED)
+                throw stage_construction_error{"--starvation: the detector has more than 2^32 - 1 pixels"};
+            if(rc != PARIS_HIP_SUCCESS)
+                throw stage_construction_error{"--starvation P0[:GAIN[:RADIUS]]: P0 must be finite, GAIN finite and greater than 0 and RADIUS must lie in 1 .. "
+                                               + std::to_string(PARIS_HIP_STARVATION_RADIUS_MAX) + " (got " + std::to_string(s.p0) + ":"
+                                               + std::to_string(s.gain) + ":" + std::to_string(s.radius) + ")"};
+            if(po.axis_only || po.roll_only)
+                throw stage_construction_error{"--starvation cannot be combined with --axis-only or --roll-only: nothing would be reconstructed"};
+            po.row_band = false;
         }
 
         // --scatter A:ALPHA:BETA:SIGMA1_MM[:SIGMA2_MM:W2] as typed; refuses anything but four or six numbers
@@ -936,6 +977,7 @@ namespace paris
                 {"--detector-roll", parse_detector_roll},
                 {"--find-roll", parse_find_roll},
                 {"--air-region", parse_air_region},
+                {"--starvation", parse_starvation},
                 {"--scatter", parse_scatter},
                 {"--scatter-iterations", parse_scatter_iterations},
                 {"--scatter-limit", parse_scatter_limit},

@@ -172,6 +172,7 @@ namespace paris
         paris_hip_air_counts air{};
         bool row_extension = false; // --extend-rows: the setting was made on this device's ctx
         paris_hip_metal_counts metal{}; // --metal: the inpainting's counts over this device's tasks
+        paris_hip_starvation_counts starvation{}; // --starvation: the filter's counts over this device's tasks
         paris_hip_volume_counts voxels{}; // --voxel-type: the counts of this device's drain ctx
         std::vector<std::string> skipped;
     };
@@ -268,6 +269,8 @@ namespace paris
         {
             if(po.ring_c)
                 rt(paris_hip_set_ring_correction(ctx, po.ring_c->data(), po.det_geo.n_row, po.det_geo.n_col), "set_ring_correction()");
+            if(po.starvation)
+                rt(paris_hip_set_starvation_filter(ctx, &po.starvation_setting, po.det_geo.n_row, po.det_geo.n_col), "set_starvation_filter()");
             if(po.scatter)
                 rt(paris_hip_set_scatter_correction(ctx, &po.scatter_setting, po.det_geo.n_row, po.det_geo.n_col, po.det_geo.l_px_row, po.det_geo.l_px_col),
                    "set_scatter_correction()");
@@ -322,7 +325,7 @@ namespace paris
             const auto rolled = po.roll || po.find_roll ? slots * po.det_geo.n_col * row : 0u;
             // with --lag, the state of a whole-detector sequence at most
             const auto lag_state = po.lag ? static_cast<std::size_t>(po.lag_model.terms) * sizeof(float) * po.det_geo.n_row * po.det_geo.n_col : 0u;
-            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes + po.scatter_bytes + po.denoise_bytes
+            return lag_state + rolled + slots * po.det_geo.n_col * (row + (po.f16 ? half_row : 0u)) + 2u * po.drain_chunk_bytes + references + po.defect_bytes + po.zinger_bytes + po.extend_bytes + po.ring_bytes + po.air_bytes + po.metal_bytes + po.phase_bytes + po.scatter_bytes + po.starvation_bytes + po.denoise_bytes
                    + binning + (po.voxels.type != 0 ? po.drain_chunk_bytes + (std::size_t{64} << 10) : 0u);
         }
 
@@ -494,8 +497,8 @@ namespace paris
                     rt(paris_hip_zinger_filter_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "zinger filter");
             }
 
-            // the detector's stationary offsets, the scatter correction and the phase retrieval -- 2-D passes over whole frames: the run
-            // has no row band --, then the polynomial of the line integral: the run's, or `unit` in its place
+            // the detector's stationary offsets, the starvation filter, the scatter correction and the phase retrieval -- 2-D passes over
+            // whole frames: the run has no row band --, then the polynomial of the line integral: the run's, or `unit` in its place
             void linearise(std::uint32_t first, std::uint32_t n, bool grouped, const frame_rows& rows, const paris_hip_beam_hardening* unit = nullptr) const
             {
                 const auto n_row = po.det_geo.n_row, n_col = po.det_geo.n_col;
@@ -503,6 +506,12 @@ namespace paris
                 auto* d = slots.frame(first);
                 if(po.ring_c)
                     rt(paris_hip_ring_correct_rows(ctx, d, slots.pitch, stride, n, n_row, n_col, rows.band.first, rows.band.count), "ring correction");
+                if(po.starvation)
+                {
+                    if(rows.band.first != 0u || rows.band.count != n_col)
+                        throw stage_runtime_error{"starvation filter: the plan gave a row band to a pass that filters whole frames"};
+                    rt(paris_hip_starvation_filter_frames(ctx, d, slots.pitch, stride, n, n_row, n_col), "starvation filter");
+                }
                 if(po.scatter)
                 {
                     if(rows.band.first != 0u || rows.band.count != n_col)
@@ -1151,6 +1160,8 @@ namespace paris
             rt(paris_hip_air_stats(ctx, &rep.air, 0), "air stats");
         if(po.metal_bits)
             rt(paris_hip_metal_stats(ctx, &rep.metal, 0), "metal stats");
+        if(po.starvation)
+            rt(paris_hip_starvation_stats(ctx, &rep.starvation, 0), "starvation stats");
         rep.drain_s = drain.drain_seconds();
         rep.save_s = drain.save_seconds();
         rep.voxels = drain.voxel_counts();
@@ -1194,6 +1205,10 @@ namespace paris
         float bh_threshold = 0.f;
         std::uint32_t bh_frames = 0, bh_slice_first = 0, bh_slices = 0;
         double bh_prepass_s = 0;
+        bool starvation = false;                        // --starvation: every frame went through this setting; its counts over all
+        paris_hip_starvation_filter starvation_setting{}; // devices and slabs (a frame counts once per slab) and the pixels examined
+        paris_hip_starvation_counts starvation_counts{};
+        std::uint64_t starvation_pixels = 0;
         bool scatter = false;                           // --scatter: every frame went through this setting at these pitches; the
         paris_hip_scatter_correction scatter_setting{}; // padded size and the scratch a device keeps for it
         float scatter_l_x = 0.f, scatter_l_y = 0.f;
@@ -1818,6 +1833,7 @@ namespace paris
         detail::check_rings(po);
         detail::check_voxels(po);
         detail::check_axis(po);
+        detail::check_starvation(po);
         detail::check_scatter(po);
         detail::check_phase(po);
         detail::check_beam_hardening(po);
@@ -1908,6 +1924,8 @@ namespace paris
                 po.metal_min_path = 0.5f * std::min(r.vol_geo.l_vx_x, std::min(r.vol_geo.l_vx_y, r.vol_geo.l_vx_z));
             detail::metal_prepass(po, r);
         }
+        r.starvation = po.starvation;
+        r.starvation_setting = po.starvation_setting;
         r.scatter = po.scatter;
         r.scatter_setting = po.scatter_setting;
         r.scatter_l_x = po.det_geo.l_px_row;
@@ -2026,11 +2044,15 @@ namespace paris
             r.metal_counts.replaced += d.metal.replaced;
             r.metal_counts.runs += d.metal.runs;
             r.metal_counts.rows_left += d.metal.rows_left;
+            r.starvation_counts.frames += d.starvation.frames;
+            r.starvation_counts.filtered += d.starvation.filtered;
+            r.starvation_counts.last_level += d.starvation.last_level;
             r.voxels.voxels += d.voxels.voxels;
             r.voxels.below += d.voxels.below;
             r.voxels.above += d.voxels.above;
             r.voxels.not_finite += d.voxels.not_finite;
         }
+        r.starvation_pixels = r.starvation_counts.frames * po.det_geo.n_row * po.det_geo.n_col;
         r.voxel_type = po.voxels.type;
         if(po.voxels.type != 0)
             out.window(r.voxel_lo, r.voxel_hi);

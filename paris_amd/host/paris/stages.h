@@ -84,6 +84,10 @@ namespace paris
         if(backend::detail::has_ring_correction(backend::current_ctx()))
             backend::detail::runtime_check(paris_hip_ring_correct_rows(backend::current_ctx(), p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x,
                                                                        p.dim_y, 0u, p.dim_y), "weight()");
+        // then with a starvation filter (backend::set_starvation_filter) the adaptive smoothing of the starved pixels: a ring offset
+        // would shift a pixel's level, and the scatter estimate's source is steep exactly where the starved pixels are noisy
+        if(backend::detail::has_starvation_filter(backend::current_ctx()))
+            backend::starvation_filter(p.buf.get(), p.buf.pitch(), 0u, 1u, p.dim_x, p.dim_y);
         // then with a scatter setting (backend::set_scatter_correction) the kernel superposition: scatter is additive on the measured
         // intensity and must be gone before a filter or a polynomial acts on what is taken for the primary
         if(backend::detail::has_scatter_correction(backend::current_ctx()))
